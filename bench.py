@@ -10,8 +10,11 @@ One *step* = one frame: every ray of the frame marched through the synthetic uin
 empty-space skipping and early ray termination, from one of 8 fixed orbit cameras (step k uses view k mod 8).  Inputs (volume,
 gradient map, TF texture, distance map, packed sampling image) are resident in HBM before the timed region.
 
-The timed block is EXACTLY K steps between two fences (barrier + synchronize); the block is repeated until at least
---min-seconds have been measured and the MEDIAN block is reported (`repeats`, `ms_per_step_min_max`).
+The timed block is EXACTLY K steps between two fences (barrier + synchronize), and by default it is the only one: K steps are timed.
+Before it, untimed: the W warm-up steps, then the block's own launches repeated for SETTLE_SECONDS (every stream and target it uses).
+`--min-seconds S` repeats the block until at least S seconds have been measured and reports the MEDIAN block (`repeats`,
+`ms_per_step_min_max`).  `--dump-outputs DIR` writes what the last timed step returned to its caller - the RGBA8 frame, as float32 - to
+DIR/rgba8.npy (a fixed, seeded sample of its pixels when the frame exceeds 64 MB as float32); the inputs depend on the arguments only.
 
 N = 1 submits the frames `--frames-per-launch` at a time through vkv_render_batch (default 8: the eight views of one orbit in one
 launch, the frames advance side by side inside one grid; a block's frames are spread evenly over its launches) and alternates
@@ -122,10 +125,6 @@ def self_launch(argv, child_cmd=None):
 if __name__ == "__main__":
     self_launch(sys.argv[1:])
 
-# ROCclr multiplexes HIP streams onto 4 hardware queues by default; frames in flight, the assembly stream and RCCL's own
-# stream need one each or they serialise behind each other (measured: 0.27 -> 0.20 ms per step on the gather path).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -163,6 +162,7 @@ GRID = {1: (1, 1), 2: (2, 1), 4: (2, 2), 8: (4, 2)}
 TILE = 16
 N_VIEWS = 8
 B_OUT = 4  # bytes per ray of the RGBA8 frame
+SETTLE_SECONDS = 0.2  # untimed repeats of the timed block before it is timed
 
 
 def kernel_source_digest():
@@ -253,7 +253,10 @@ def main():
     ap.add_argument("--frames-per-launch", type=int, default=6, help="batch submission: frames per vkv_render_batch launch (1 = one frame per launch; 6 on 4 streams "
                     "measures 1 - 4 % better than 8 on 3 on every workload: profiles/r5_submission_sweep.txt)")
     ap.add_argument("--frames-in-flight", type=int, default=3, help="stream submission: consecutive frames render on this many HIP streams")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the timed block of K steps until this much time has been measured")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the timed block of K steps until this much time has been measured "
+                    "(default 0: one block, K timed steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed blocks, write the frame the last timed step rendered to "
+                    "DIR/rgba8.npy (float32)")
     ap.add_argument("--frame-owner", default="rotate", choices=["rotate", "spread", "rank0"], help="N > 1: rank that assembles a launch's frames: launch l on rank l mod N "
                     "(rotate, default: the inbound xGMI links and the de-interleave of consecutive launches are disjoint), frame j of launch l on rank (l + j) mod N "
                     "(spread: every GPU receives at once; batch submission), or always rank 0")
@@ -349,7 +352,7 @@ def main():
         a2 = copy.copy(args)
         for k, val in over.items():
             setattr(a2, k, val)
-        a2.no_cpu_baseline, a2.no_depth_block = True, True
+        a2.no_cpu_baseline, a2.no_depth_block, a2.dump_outputs = True, True, None
 
         def give_up():
             if rank == 0 and holder is not None:
@@ -792,8 +795,25 @@ def job(args, env):
                 dist.barrier()
         torch.cuda.synchronize()
 
+    def any_rank(flag):
+        """True on every rank when it is true on one (the ranks leave a loop of collectives together)"""
+        if world > 1:
+            t = torch.tensor([1.0 if flag else 0.0], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            flag = t.item() > 0
+        return flag
+
     run(args.warmup, False)
     fence()
+    # untimed, behind the warm-up: the timed block's launches, repeated for at least SETTLE_SECONDS, so that every HIP stream, buffer set and
+    # render target the block uses has been used and the device has settled when the timed block starts (C3, a 20-step block behind a 5-step
+    # warm-up: 0.36 ms per step without this, 0.111 behind one such block, 0.104 behind 0.1 - 0.5 s of them; the median of many blocks is 0.102)
+    t_settle = time.perf_counter()
+    while True:
+        run(args.steps, False)
+        fence()
+        if any_rank(time.perf_counter() - t_settle >= SETTLE_SECONDS):
+            break
     # ---- timed blocks: exactly K steps between two fences, repeated until min_seconds have been measured -----------
     blocks, kernel_ms, kernel_bytes, kernel_frames, enqueue_times = [], [], [], [], []
     total = 0.0
@@ -825,15 +845,15 @@ def job(args, env):
         kernel_bytes += [b for _, _, b, _ in launches]
         kernel_frames += [n for _, _, _, n in launches]
         total += elapsed
-        stop = total >= args.min_seconds or len(blocks) >= 4096
-        if world > 1:
-            t = torch.tensor([1.0 if stop else 0.0], dtype=torch.float64, device="cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            stop = t.item() > 0
-        if stop:
+        if any_rank(total >= args.min_seconds or len(blocks) >= 4096):
             break
     elapsed = float(np.median(blocks))
     kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
+    # the blocks below render into the same buffers: the last timed step's frame is taken now, on the rank that holds it
+    last_fpl = (last_slot[0] + 1) if submit == "batch" else 0
+    last_rank = last_owner[0] if submit == "batch" else ((args.steps - 1) % world if rotate else 0)
+    if getattr(args, "dump_outputs", None) and rank == last_rank:
+        dump_outputs(args.dump_outputs, {"rgba8": last_frame(args.steps, nbuf, last_fpl, bufs, images, gather)})
 
     # ---- the same block with gl_FragDepth written too (not the headline: BASELINE's metric is the colour frame) ------
     depth_ms = None
@@ -841,7 +861,7 @@ def job(args, env):
         with_depth[0] = True
         run(args.warmup, False)
         dblocks, dtotal = [], 0.0
-        while dtotal < min(0.5, args.min_seconds) and len(dblocks) < 1024:
+        while not dblocks or (dtotal < min(0.5, args.min_seconds) and len(dblocks) < 1024):
             fence()
             t0 = time.perf_counter()
             run(args.steps, False)
@@ -889,8 +909,7 @@ def job(args, env):
     vs_total, ds_total, cov_total = float(tot[0].item()), float(tot[1].item()), float(tot[2].item())
 
     if args.verify:
-        verify(ctx, sp, v, views[last_view[0]], params, args.steps, nbuf, (last_slot[0] + 1) if submit == "batch" else 0, (fw, fh), bufs, images, gather, rank,
-               last_owner[0] if submit == "batch" else ((args.steps - 1) % world if rotate else 0))
+        verify(ctx, sp, v, views[last_view[0]], params, args.steps, nbuf, last_fpl, (fw, fh), bufs, images, gather, rank, last_rank)
     if rank != 0:
         if native:
             gather.close()
@@ -1009,12 +1028,35 @@ def verify(ctx, sp, v, view, params, steps, nbuf, fpl, frame, bufs, images, gath
     direct = torch.zeros((fh, fw, 4), dtype=torch.uint8, device="cuda")
     sp.draw(sp.make_params(*view, abi.full_frame_tiles(fw, fh, TILE, TILE)), rgba8=direct)
     torch.cuda.synchronize()
-    slot = (fpl - 1) if fpl else (k % nbuf)  # batch submission: `fpl` carries the last step's output buffer index + 1
-    got = (images[slot] if fpl else images[k % nbuf]) if gather else bufs[slot].view(fh, fw, 4)
+    got = last_frame(steps, nbuf, fpl, bufs, images, gather).view(fh, fw, 4)
     if not torch.equal(got, direct):
         raise SystemExit("verify failed: assembled frame differs from the direct render in %d bytes" % int((got != direct).sum().item()))
     print("verify ok (rank %d): frame of step %d matches the direct render (%d non-zero bytes)" % (rank, k, int((direct != 0).sum().item())),
           file=sys.stderr)
+
+
+def last_frame(steps, nbuf, fpl, bufs, images, gather):
+    """The buffer the last step of a block rendered into, on the rank that assembles that step's frame (batch submission: `fpl` carries the
+    last step's output buffer index + 1, 0 = single-frame submission)."""
+    slot = (fpl - 1) if fpl else ((steps - 1) % nbuf)
+    return images[slot] if gather else bufs[slot]
+
+
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: at most this many bytes of float32 in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every device array as <path>/<name>.npy in float32, its last axis kept (the RGBA channels).  When the arrays exceed
+    DUMP_BYTES together, each keeps a fixed, seeded sample of its rows (all axes but the last flattened), in their original order."""
+    os.makedirs(path, exist_ok=True)
+    host = {name: a.cpu().numpy() for name, a in arrays.items()}
+    total = sum(a.size * 4 for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = rows.shape[0] * DUMP_BYTES // total
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
 
 
 def cpu_quota_cores():

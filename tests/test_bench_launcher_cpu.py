@@ -97,3 +97,29 @@ def test_launch_timeout_kills_the_ranks_it_started(tmp_path):
         except (OSError, IOError):
             alive = False
         assert not alive, "process %d of the timed-out job is still running" % pid
+
+
+def test_dump_outputs_caps_a_large_frame_with_a_fixed_sample(tmp_path):
+    """--dump-outputs writes float32; a frame larger than the cap (7680x4320 RGBA: 530 MB as float32) keeps a seeded sample of its pixels,
+    the same one every time, within 64 MB; a small frame is written whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    small = torch.randint(0, 256, (192, 320, 4), dtype=torch.uint8, generator=g)
+    big = torch.randint(0, 256, (4320, 7680, 4), dtype=torch.uint8, generator=g)
+    bench.dump_outputs(str(tmp_path / "s"), {"rgba8": small})
+    got = np.load(tmp_path / "s" / "rgba8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    samples = []
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), {"rgba8": big})
+        assert os.path.getsize(tmp_path / tag / "rgba8.npy") <= 64 * 10 ** 6
+        samples.append(np.load(tmp_path / tag / "rgba8.npy"))
+    s = samples[0]
+    assert s.dtype == np.float32 and s.ndim == 2 and s.shape[1] == 4 and s.shape[0] > 10 ** 6
+    assert np.array_equal(s, samples[1])
+    rows = big.numpy().reshape(-1, 4)
+    idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], s.shape[0], replace=False))
+    assert np.array_equal(s, rows[idx])

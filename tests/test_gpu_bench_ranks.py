@@ -120,3 +120,30 @@ def test_bench_moving_camera_and_feedback_switch():
         assert d["camera_and_feedback"][key]["ms_per_step"] > 0, d["camera_and_feedback"]
     for key in ("dense", "probe_only"):
         assert "error" not in d["asymptotes"][key], d["asymptotes"]
+
+
+def test_bench_dump_outputs_is_the_frame_of_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: the RGBA8 frame the last timed step rendered, as float32, from exactly --steps timed steps (one block by
+    default).  Steps 11 and 3 both end on view 2 and must dump the same frame (a frame --verify checks against a direct render); step 12 ends
+    on view 3.  Two runs with the same arguments dump the same values."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    frames = {}
+    for tag, steps in (("a", 11), ("b", 11), ("c", 3), ("d", 12)):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "small", "--steps", str(steps), "--warmup", "2", "--verify", "--extras", "off",
+               "--no-cpu-baseline", "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == steps and d["repeats"] == 1 and "verify ok" in r.stderr
+        assert sorted(os.listdir(tmp_path / tag)) == ["rgba8.npy"]
+        frames[tag] = np.load(tmp_path / tag / "rgba8.npy")
+    a = frames["a"]
+    assert a.dtype == np.float32 and a.shape == (192, 320, 4)
+    assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() <= 255 and (a[..., 3] > 0).any()
+    assert np.array_equal(a, frames["b"]) and np.array_equal(a, frames["c"])
+    assert not np.array_equal(a, frames["d"])
