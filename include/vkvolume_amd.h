@@ -345,6 +345,27 @@ int vkv_transfer_function_tables(vkv_ctx *ctx, const uint8_t *d_transfer_functio
                                  uint32_t *d_tables, void *stream);
 int vkv_transfer_function_bits(vkv_ctx *ctx, const uint8_t *d_transfer_function, uint32_t *d_tables, void *stream);
 
+/* CPU + device halves of Volume::update_transfer_function_texture (src/volume_component.cpp:242-278) on the device: the RGBA8 256x256
+ * texture and the vkv_transfer_function_tables() buffer (separable flag set) from the options, in one launch - no host loop, no upload,
+ * no wait.  Every texel equals what vkv_transfer_function_texture writes for the same options (a degenerate intensity window,
+ * intensity_max == intensity_min, gives 0 where the host's product is NaN); every table word equals what vkv_transfer_function_tables
+ * makes of that texture and vkv_transfer_function_uniform(options).  Both pointers 4-byte aligned. */
+int vkv_transfer_function_texture_device(vkv_ctx *ctx, const VkvVolumeOptions *options, uint8_t *d_transfer_function, uint32_t *d_tables,
+                                         void *stream);
+
+/* VolumeRender::update_transfer_function, src/volume_render.cpp:392-445, as ONE enqueue on `stream`: (d_occupied_count != NULL) the
+ * occupied-voxel count of vkv_occupied_voxel_count for the options' uniform (the reference's benchmark-mode submission, :400-416; it is
+ * enqueued first because it stages its own bit table in the stream's scratch block), then the texture + tables of
+ * vkv_transfer_function_texture_device, then the occupancy map and the transform of skipping_type into d_maps, as
+ * vkv_compute_distance_map would build them from that texture (d_gradient == NULL: on-the-fly gradient, as there).  The occupancy pass
+ * takes its bit table from the texture kernel instead of rebuilding it from the texture.  Every argument is checked before anything is
+ * enqueued.  Capture: the call only enqueues kernels and memsets; the stream's scratch block comes out of the arena at its first use without
+ * allocating, so after one direct call (or vkv_prepare_render) on `stream` the update can be captured into a hipGraph, with or without
+ * the frames behind it.  A captured update replays with the options it was captured with: capture again when a slider moves. */
+int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, const uint8_t *d_volume, const uint8_t *d_gradient,
+                                 VkvExtent3D extent, uint8_t *d_transfer_function, uint32_t *d_tables, uint8_t *const d_maps[8],
+                                 uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type, uint64_t *d_occupied_count, void *stream);
+
 /* VolumeRenderSubpass::prepare, src/volume_render_subpass.cpp:95-157 (where the reference builds its pipelines and descriptor layouts).
  * Set-up call: creates, for `count` parameter blocks as a later vkv_render / vkv_render_batch on `stream` will pass them, everything that
  * launch takes from the context: the stream's scratch block, the address tables of the packed image's extent, the tile start order of the

@@ -29,6 +29,10 @@ int vkv_debug_tile_orders(vkv_ctx *ctx, const uint32_t *d_orders, uint32_t frame
  *   what = 4  the dispatch of that quotient for the numerators +0 and -0: they take the IEEE division (the refinement loses the sign of -0 / b) */
 int vkv_debug_check(vkv_ctx *ctx, int32_t what, uint32_t first_bits, uint64_t count, uint64_t *d_mismatches, void *stream);
 
+/* Copies the 2056 words the map update of `stream` left in its scratch block - the 256x256 alpha > 0 bit table and its 8-word column mask
+ * (k_tf_bits + k_tf_columns of vkv_occupancy_map, or the texture kernel of vkv_update_transfer_function) - to d_out, on `stream`. */
+int vkv_debug_tf_scratch(vkv_ctx *ctx, uint32_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

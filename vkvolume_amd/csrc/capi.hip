@@ -23,7 +23,7 @@ namespace vkv
 {
 int launch_gradient_map(vkv_ctx *, const uint8_t *, uint8_t *, VkvExtent3D, const VkvTransferFunctionUniform *, hipStream_t);
 int launch_occupancy_map(vkv_ctx *, const uint8_t *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint8_t *,
-                         VkvExtent3D, hipStream_t);
+                         VkvExtent3D, hipStream_t, bool bits_ready = false);
 int launch_distance_map(vkv_ctx *, uint8_t *, uint8_t *, VkvExtent3D, hipStream_t);
 int launch_distance_map_anisotropic(vkv_ctx *, uint8_t *const[8], uint8_t *, VkvExtent3D, hipStream_t);
 int launch_synth_volume(vkv_ctx *, uint8_t *, VkvExtent3D, uint32_t, uint32_t, hipStream_t);
@@ -37,6 +37,7 @@ int launch_render_batch(vkv_ctx *, const VkvRenderParams *, uint32_t, const floa
 int launch_pack_volume(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, void *, hipStream_t);
 int launch_check_numerics(vkv_ctx *, int, uint32_t, uint64_t, unsigned long long *, hipStream_t);
 int launch_tf_tables(vkv_ctx *, const uint8_t *, const VkvTransferFunctionUniform *, uint32_t *, hipStream_t);
+int launch_tf_build(vkv_ctx *, const VkvTransferFunctionUniform *, uint8_t *, uint32_t *, uint32_t *, hipStream_t);
 int launch_convert_volume(vkv_ctx *, const void *, int, bool, float, float, uint64_t, uint8_t *, hipStream_t);
 int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t);
 
@@ -670,6 +671,20 @@ int vkv_debug_check(vkv_ctx *ctx, int32_t what, uint32_t first_bits, uint64_t co
 	return launch_check_numerics(ctx, what, first_bits, count, reinterpret_cast<unsigned long long *>(d_mismatches), (hipStream_t) stream);
 }
 
+int vkv_debug_tf_scratch(vkv_ctx *ctx, uint32_t *d_out, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_out)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "debug_tf_scratch: null pointer");
+	uint8_t *scratch = stream_scratch(ctx, (hipStream_t) stream);
+	if (!scratch)
+		return VKV_E_UNSUPPORTED;
+	const hipError_t e = hipMemcpyAsync(d_out, scratch + kTfBitsOffset, (2048 + 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t) stream);
+	return e == hipSuccess ? VKV_OK : set_error(ctx, (int) e, "debug_tf_scratch: %s", hipGetErrorString(e));
+}
+
 const char *vkv_last_error(const vkv_ctx *ctx) { return ctx ? ctx->error : "null context"; }
 
 // ---- host helpers ------------------------------------------------------------------------------
@@ -968,6 +983,68 @@ int vkv_transfer_function_tables(vkv_ctx *ctx, const uint8_t *d_tf, const VkvTra
 int vkv_transfer_function_bits(vkv_ctx *ctx, const uint8_t *d_tf, uint32_t *d_tables, void *stream)
 {
 	return vkv_transfer_function_tables(ctx, d_tf, nullptr, d_tables, stream);
+}
+
+int vkv_transfer_function_texture_device(vkv_ctx *ctx, const VkvVolumeOptions *options, uint8_t *d_tf, uint32_t *d_tables, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!options || !d_tf || !d_tables)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "transfer_function_texture_device: null pointer");
+	if (((uintptr_t) d_tf & 3u) != 0 || ((uintptr_t) d_tables & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "transfer_function_texture_device: pointers must be 4-byte aligned");
+	VkvTransferFunctionUniform tf;
+	vkv_transfer_function_uniform(options, &tf);        // the same i_inv / g_inv the host texture is built with
+	return launch_tf_build(ctx, &tf, d_tf, d_tables, nullptr, (hipStream_t) stream);
+}
+
+// src/volume_render.cpp:392-445 as one enqueue: every argument is checked before the first launch
+int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent,
+                                 uint8_t *d_tf, uint32_t *d_tables, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent,
+                                 int32_t skipping_type, uint64_t *d_occupied_count, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!options || !d_volume || !d_tf || !d_tables || !d_maps || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: null pointer or bad extent");
+	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: bad skipping_type %d", (int) skipping_type);
+	if (((uintptr_t) d_tf & 3u) != 0 || ((uintptr_t) d_tables & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: d_transfer_function and d_tables must be 4-byte aligned");
+	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
+	const int  n     = aniso ? 8 : 1;
+	for (int i = 0; i < n; ++i)
+		if (!d_maps[i])
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: map %d is null", i);
+	if (aniso || skipping_type == VKV_SKIP_DISTANCE)
+	{
+		if (!d_swap)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: null swap buffer");
+		for (int i = 0; i < n; ++i)
+			if (d_maps[i] == d_swap)
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: map %d aliases the swap buffer", i);
+	}
+	const hipStream_t s       = (hipStream_t) stream;
+	uint8_t *         scratch = stream_scratch(ctx, s);
+	if (!scratch)
+		return VKV_E_UNSUPPORTED;
+	VkvTransferFunctionUniform tf;
+	vkv_transfer_function_uniform(options, &tf);
+	int rc = VKV_OK;
+	// the count first: it stages its own (analytic) bit table in the same scratch words that k_tf_build fills for the occupancy pass
+	if (d_occupied_count && (rc = launch_occupied_voxel_count(ctx, d_volume, d_gradient, &tf, extent, d_occupied_count, s)) != VKV_OK)
+		return rc;
+	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset), s)) != VKV_OK)
+		return rc;
+	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, &tf, extent, d_maps[n - 1], map_extent, s, true)) != VKV_OK)
+		return rc;
+	if (aniso)
+		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, s);
+	if (skipping_type == VKV_SKIP_DISTANCE)
+		return launch_distance_map(ctx, d_maps[0], d_swap, map_extent, s);
+	return VKV_OK;        // None / Block use the raw 0/255 occupancy map
 }
 
 // argument checks shared by vkv_render and vkv_render_batch

@@ -1497,15 +1497,48 @@ int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, Vkv
 	return check_launch(ctx, "gradient_map");
 }
 
+// 255 (EMPTY) into n bytes: 16-byte stores over the aligned body, single bytes at both ends.  The map fill of vkv_update_transfer_function:
+// replays of a hipGraph that held the fill as a memset node gave maps that differed from replay to replay, while kernel nodes stay ordered
+__global__ void __launch_bounds__(256) k_fill_empty(uint8_t *__restrict__ p, size_t n)
+{
+	const size_t head = min(n, (size_t) ((16u - ((uintptr_t) p & 15u)) & 15u));
+	const size_t body = (n - head) / 16, tail = head + body * 16;
+	const size_t tid = (size_t) blockIdx.x * 256 + threadIdx.x, stride = (size_t) gridDim.x * 256;
+	if (tid < head)
+		p[tid] = 255;
+	uint4 *q = reinterpret_cast<uint4 *>(p + head);
+	for (size_t i = tid; i < body; i += stride)
+		q[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+	if (tid < n - tail)
+		p[tail + tid] = 255;
+}
+
+static int fill_empty(vkv_ctx *ctx, uint8_t *d_map, size_t n, hipStream_t s, bool by_kernel)
+{
+	if (by_kernel)
+	{
+		const size_t blocks = std::min<size_t>(std::max<size_t>(1, (n / 16 + 255) / 256), 4096);
+		hipLaunchKernelGGL(k_fill_empty, dim3((uint32_t) blocks), dim3(256), 0, s, d_map, n);
+		return check_launch(ctx, "occupancy_map: fill");
+	}
+	const hipError_t em = hipMemsetAsync(d_map, 255, n, s);
+	return em == hipSuccess ? VKV_OK : set_error(ctx, (int) em, "occupancy_map: fill: %s", hipGetErrorString(em));
+}
+
+// bits_ready: k_tf_build has already left the bit table and its column mask in the stream's scratch block (vkv_update_transfer_function);
+// d_tf is then not read, and the map is filled by a kernel (k_fill_empty)
 int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
-                         VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s)
+                         VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s, bool bits_ready)
 {
 	uint8_t *scratch = stream_scratch(ctx, s);        // per stream: map updates on different streams do not share the bit table
 	if (!scratch)
 		return VKV_E_UNSUPPORTED;
 	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
-	hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
-	hipLaunchKernelGGL(k_tf_columns, dim3(1), dim3(256), 0, s, d_bits);        // words 2048..2055 of the scratch's table area
+	if (!bits_ready)
+	{
+		hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
+		hipLaunchKernelGGL(k_tf_columns, dim3(1), dim3(256), 0, s, d_bits);        // words 2048..2055 of the scratch's table area
+	}
 	// src/compute_distance_map.cpp:110-113
 	const int bx = (int) ((e.width + me.width - 1) / me.width), by = (int) ((e.height + me.height - 1) / me.height),
 	          bz = (int) ((e.depth + me.depth - 1) / me.depth);
@@ -1521,9 +1554,9 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 	// the workgroup-per-cell-row kernels only visit cells the volume reaches in x, so such a map is filled for them too
 	if ((uint64_t) (mw - 1) * bx >= (uint64_t) W || (uint64_t) (mh - 1) * by >= (uint64_t) H || (uint64_t) (md - 1) * bz >= (uint64_t) D)
 	{
-		const hipError_t em = hipMemsetAsync(d_map, 255, (size_t) me.width * me.height * me.depth, s);
-		if (em != hipSuccess)
-			return set_error(ctx, (int) em, "occupancy_map: fill: %s", hipGetErrorString(em));
+		const int rc = fill_empty(ctx, d_map, (size_t) me.width * me.height * me.depth, s, bits_ready);
+		if (rc != VKV_OK)
+			return rc;
 	}
 	if ((bx == 1 || bx == 2 || bx == 4) && T_occ.occupancy_kernel == 1 && (e.width & 3u) == 0 && (!tf->use_gradient || precomputed) && (((uintptr_t) d_vol | (uintptr_t) d_grad) & 3u) == 0)
 	{
@@ -1571,9 +1604,9 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 		const uint64_t tasks = (uint64_t) spans_x * ((me.height + cyw - 1) / cyw);
 		if ((tasks + 3) / 4 <= 0x7fffffffull && me.depth <= 65535u)
 		{
-			const hipError_t em = hipMemsetAsync(d_map, 255, (size_t) me.width * me.height * me.depth, s);        // EMPTY everywhere; the kernel stores the OCCUPIED cells
-			if (em != hipSuccess)
-				return set_error(ctx, (int) em, "occupancy_map: fill: %s", hipGetErrorString(em));
+			const int rc = fill_empty(ctx, d_map, (size_t) me.width * me.height * me.depth, s, bits_ready);        // EMPTY everywhere; the kernel stores the OCCUPIED cells
+			if (rc != VKV_OK)
+				return rc;
 			const dim3 wgrid((uint32_t) ((tasks + 3) / 4), me.depth);
 #define VKV_OCC_WAVES(G, R, C) hipLaunchKernelGGL((k_occupancy_map_waves<G, R, C>), wgrid, dim3(256), 0, s, d_vol, d_grad, d_bits, d_map, W, H, D, mw, mh, bx, by, bz, spans_x, cyw)
 #define VKV_OCC_WAVES_G(G)                                                                                                                             \
@@ -1945,6 +1978,73 @@ int launch_tf_tables(vkv_ctx *ctx, const uint8_t *d_tf, const VkvTransferFunctio
 	                   has_tf ? tf->gradient_min : 0.0f, has_tf ? tf->gradient_range_inv : 0.0f, has_tf ? (int) (tf->use_gradient != 0) : 0);
 	hipLaunchKernelGGL(k_tf_tables, dim3(8), dim3(256), 0, s, d_tf, d_tables, has_tf);
 	return check_launch(ctx, "transfer_function_tables");
+}
+
+// The whole transfer function of the reference (src/volume_component.cpp:242-278) from the uniform's fields, without a host loop or an
+// upload: the RGBA8 texture, the integrator's tables (what k_tf_tables_init + k_tf_tables make of that texture) and, when `bits` is given,
+// the occupancy pass's bit table + column mask (what k_tf_bits + k_tf_columns leave in the stream's scratch block).  One workgroup per
+// gradient row, one lane per intensity column: one dword store per texel, the row's alpha > 0 bits out of one ballot per wave.
+// The texel is the host's expression (vkv_transfer_function_texture): comparison clamps as std::max / std::min write them, (a_i * a_g) * 255
+// as two multiplies, truncation.  A NaN product - intensity_max == intensity_min gives one at the column where i / 255 == intensity_min -
+// stores 0, the byte (uint8) NaN gives on x86-64.  The separable flag holds by construction.
+__device__ __forceinline__ float tf_axis_alpha(uint32_t i, float lo, float inv)
+{
+	const float x = (float) i / 255.0f;
+	float       a = (x - lo) * inv;
+	a = (a < 0.0f) ? 0.0f : a, a = (1.0f < a) ? 1.0f : a;        // std::max / std::min as the host writes them
+	return a;
+}
+__device__ __forceinline__ uint32_t tf_texel_alpha(float ai, float ag)
+{
+	const float p = (ai * ag) * 255.0f;        // in [0, 255] or NaN: the host's clamp to [0, 255] changes nothing else
+	return p == p ? (uint32_t) p : 0u;
+}
+
+__global__ void __launch_bounds__(256) k_tf_build(uint32_t *__restrict__ tex, uint32_t *__restrict__ tables, uint32_t *__restrict__ bits, float imin,
+                                                  float iinv, float gmin, float ginv, int use_gradient)
+{
+	__shared__ float s_max[4];
+	const uint32_t   i  = threadIdx.x, g = blockIdx.x;        // intensity column, gradient row
+	const float      ai = tf_axis_alpha(i, imin, iinv);
+	const float      ag = use_gradient ? tf_axis_alpha(g, gmin, ginv) : 1.0f;
+	const uint32_t   b  = tf_texel_alpha(ai, ag);
+	tex[g * 256u + i]   = b * 0x01010101u;
+	const unsigned long long m = __builtin_amdgcn_ballot_w64(b != 0u);
+	if ((i & 63u) == 0u)
+	{
+		const uint32_t w = g * 8u + (i >> 5);
+		tables[w] = (uint32_t) m, tables[w + 1u] = (uint32_t) (m >> 32);
+		if (bits)
+			bits[w] = (uint32_t) m, bits[w + 1u] = (uint32_t) (m >> 32);
+	}
+	if (g != 0u)
+		return;
+	// workgroup 0: the separable tables (lane i also holds row i's a_g), the flag words and the column mask.  Column i has an occupied texel iff
+	// (uint8) (a_i[i] * max_g a_g * 255) > 0: the product is monotone in a_g >= 0, and a row whose a_g is NaN has none (it counts as 0)
+	const float agi = use_gradient ? tf_axis_alpha(i, gmin, ginv) : 1.0f;
+	tables[kTfAiWord + i] = __float_as_uint(ai);
+	tables[kTfAgWord + i] = __float_as_uint(agi);
+	if (i < 4u)
+		tables[kTfFlagWord + i] = i == 0u ? kTfFlagSeparable : 0u;
+	if (!bits)
+		return;
+	float mx = agi == agi ? agi : 0.0f;
+	for (int o = 32; o > 0; o >>= 1)
+		mx = g_max(mx, __shfl_xor(mx, o));
+	if ((i & 63u) == 0u)
+		s_max[i >> 6] = mx;
+	__syncthreads();
+	mx = g_max(g_max(s_max[0], s_max[1]), g_max(s_max[2], s_max[3]));
+	const unsigned long long c = __builtin_amdgcn_ballot_w64(tf_texel_alpha(ai, mx) != 0u);
+	if ((i & 63u) == 0u)
+		bits[2048u + (i >> 5)] = (uint32_t) c, bits[2048u + (i >> 5) + 1u] = (uint32_t) (c >> 32);
+}
+
+int launch_tf_build(vkv_ctx *ctx, const VkvTransferFunctionUniform *tf, uint8_t *d_tf, uint32_t *d_tables, uint32_t *d_bits, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_tf_build, dim3(256), dim3(256), 0, s, reinterpret_cast<uint32_t *>(d_tf), d_tables, d_bits, tf->intensity_min,
+	                   tf->intensity_range_inv, tf->gradient_min, tf->gradient_range_inv, (int) (tf->use_gradient != 0));
+	return check_launch(ctx, "transfer_function_texture_device");
 }
 
 // --- synthetic volume: host builds the shell table (same definition as DESIGN.md "Synthetic inputs") ---

@@ -13,6 +13,10 @@
 //                 [--virtual-ranks=N --dump-assembled=file]   the multi-GPU decomposition on one GPU: rank r of N renders
 //                                  VolumeRenderSubpass::rank_schedule(r, N) - its share of the tiles of the frame's screen rectangle - into a compact
 //                                  buffer, vkv_scatter_tiles assembles the N buffers (what the frame's owner does behind ncclGather)
+//                 [--tf-drag=N --tf-path=host|device]   N transfer-function slider moves after the first frame: each shifts intensity_min by
+//                                  a small step, updates the texture and the maps and renders one frame; prints ms per move from device events
+//                                  (two warm-up moves untimed).  host = the blocking update (CPU texture, upload, wait, tables, occupancy +
+//                                  transform); device = Volume::update_transfer_function, one enqueue with no host wait
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -52,6 +56,8 @@ struct Args
 	int         ert              = -1;        // --ert[=0|1]: -1 = the mode's own setting (benchmark mode: off)
 	int         virtual_ranks    = 0;         // --virtual-ranks=N: this GPU plays N ranks in turn, --dump-assembled gets their assembled frame
 	std::string dump_assembled;
+	int         tf_drag = 0;              // --tf-drag=N: slider moves
+	std::string tf_path = "device";        // --tf-path=host|device
 };
 
 bool flag(const char *arg, const char *name, std::string &value)
@@ -107,6 +113,13 @@ Args parse(int argc, char **argv)
 		else if (flag(s, "--ert", v)) a.ert = v.empty() ? 1 : std::stoi(v);
 		else if (flag(s, "--virtual-ranks", v)) a.virtual_ranks = std::stoi(v);
 		else if (flag(s, "--dump-assembled", v)) a.dump_assembled = v;
+		else if (flag(s, "--tf-drag", v)) a.tf_drag = std::max(0, std::stoi(v));
+		else if (flag(s, "--tf-path", v))
+		{
+			if (v != "host" && v != "device")
+				throw std::runtime_error("--tf-path=host|device");
+			a.tf_path = v;
+		}
 		else if (s[0] != '-') a.dataset = s;
 		else throw std::runtime_error(std::string("unknown flag ") + s);
 	}
@@ -298,6 +311,43 @@ int main(int argc, char **argv)
 		subpass.prepare_targets({target});
 		subpass.draw(target);        // warm-up (and the frame the dumps below read)
 		(void) hipStreamSynchronize(stream);
+		if (args.tf_drag > 0)
+		{        // slider moves (src/volume_render.cpp:392-445 per move), each followed by one frame into the same target
+			const bool  device_path = args.tf_path == "device";
+			const int   warmup      = 2;
+			const float step        = 0.005f;
+			hipEvent_t  ev0 = nullptr, ev1 = nullptr;
+			if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)
+				throw std::runtime_error("hipEventCreate failed");
+			std::chrono::steady_clock::time_point t0;
+			for (int k = 1; k <= warmup + args.tf_drag; ++k)
+			{
+				if (k == warmup + 1)
+				{
+					(void) hipStreamSynchronize(stream);
+					t0 = std::chrono::steady_clock::now();
+					(void) hipEventRecord(ev0, stream);
+				}
+				volume.options.intensity_min = args.imin + step * (float) k;
+				if (device_path)
+					volume.update_transfer_function(dc, static_cast<int32_t>(render_options.skipping_type));
+				else
+				{
+					volume.update_transfer_function_texture(dc);
+					compute_distance_map.compute(volume, volume.get_transfer_function_uniform(), render_options.skipping_type);
+				}
+				subpass.draw(target);
+			}
+			(void) hipEventRecord(ev1, stream);
+			(void) hipEventSynchronize(ev1);
+			const double wall = ms_since(t0);
+			float        ms   = 0.0f;
+			(void) hipEventElapsedTime(&ms, ev0, ev1);
+			std::printf("tf-drag %s: %d moves, %g ms per move (device events), %g ms per move (wall)\n", args.tf_path.c_str(), args.tf_drag,
+			            ms / args.tf_drag, wall / args.tf_drag);
+			(void) hipEventDestroy(ev0);
+			(void) hipEventDestroy(ev1);
+		}
 		{
 			// Benchmark frames go round-robin over a few HIP streams, each with its own colour target - what the reference gets from
 			// its per-swap-chain-image command buffers: the long tail of one frame overlaps the start of the next.

@@ -155,6 +155,28 @@ void Volume::update_transfer_function_texture(DeviceContext &dc)
 	vkv_check(dc, vkv_transfer_function_tables(dc.ctx, transfer_function.data, &tf, transfer_function_bits, dc.stream), "TF tables");
 }
 
+void Volume::update_transfer_function_on_device(DeviceContext &dc)
+{
+	const VkvVolumeOptions o{options.sampling_factor, options.voxel_alpha_factor, options.use_precomputed_gradient ? 1u : 0u,
+	                         options.intensity_min,   options.intensity_max,      options.gradient_min, options.gradient_max};
+	vkv_check(dc, vkv_transfer_function_texture_device(dc.ctx, &o, transfer_function.data, transfer_function_bits, dc.stream), "TF texture");
+}
+
+void Volume::update_transfer_function(DeviceContext &dc, int32_t skipping_type, uint64_t *d_occupied_count)
+{
+	const VkvVolumeOptions o{options.sampling_factor, options.voxel_alpha_factor, options.use_precomputed_gradient ? 1u : 0u,
+	                         options.intensity_min,   options.intensity_max,      options.gradient_min, options.gradient_max};
+	set_number_of_distance_maps(dc, skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 8 : 1);
+	uint8_t *maps[8] = {nullptr};
+	for (size_t i = 0; i < distance_maps.size() && i < 8; ++i)
+		maps[i] = distance_maps[i].data;
+	vkv_check(dc,
+	          vkv_update_transfer_function(dc.ctx, &o, volume.data, options.use_precomputed_gradient ? gradient.data : nullptr, volume.extent,
+	                                       transfer_function.data, transfer_function_bits, maps, distance_map_swap.data, distance_map_swap.extent,
+	                                       skipping_type, d_occupied_count, dc.stream),
+	          "TF update");
+}
+
 void Volume::pack(DeviceContext &dc)
 {
 	const size_t need = vkv_packed_volume_bytes(volume.extent);

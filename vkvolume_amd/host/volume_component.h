@@ -67,6 +67,12 @@ class Volume
 
 	TransferFunctionUniform get_transfer_function_uniform();                 // src/volume_component.cpp:226-240
 	void                    update_transfer_function_texture(DeviceContext &dc);        // src/volume_component.cpp:242-278
+	// the same texture + tables built on the device (vkv_transfer_function_texture_device): no host loop, no upload, no wait
+	void update_transfer_function_on_device(DeviceContext &dc);
+	// VolumeRender::update_transfer_function (src/volume_render.cpp:392-445) as one enqueue (vkv_update_transfer_function): texture + tables,
+	// occupancy and the transform of skipping_type (a VkvSkippingType) into the distance maps (grown as ComputeDistanceMap::compute grows them);
+	// d_occupied_count != nullptr also receives the occupied-voxel count
+	void update_transfer_function(DeviceContext &dc, int32_t skipping_type, uint64_t *d_occupied_count = nullptr);
 
 	// vkb::sg::Node stand-in: the node's world matrix (benchmark mode rescales it, src/volume_render.cpp:224-238)
 	vkv::mat4 node_transform;

@@ -20,9 +20,10 @@ EXPORTS = [
     "vkv_occupied_voxel_count", "vkv_load_header", "vkv_load_data", "vkv_convert_volume", "vkv_gather_tiles", "vkv_assemble_frame",
     "vkv_assemble_frames", "vkv_get_tuning", "vkv_set_tuning", "vkv_prepare_render", "vkv_register_target", "vkv_forget_target",
     "vkv_release_stream", "vkv_trim", "vkv_release_captured", "vkv_screen_tile_rect",
+    "vkv_transfer_function_texture_device", "vkv_update_transfer_function",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
-DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check"]
+DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
 
 
 class VkvError(RuntimeError):
@@ -89,6 +90,9 @@ def load():
     L.vkv_transfer_function_bits.argtypes = [vp, vp, vp, vp]
     L.vkv_transfer_function_tables.argtypes = [vp, vp, P(abi.TransferFunctionUniform), vp, vp]
     L.vkv_occupied_voxel_count.argtypes = [vp, vp, vp, P(abi.TransferFunctionUniform), abi.Extent3D, vp, vp]
+    L.vkv_transfer_function_texture_device.argtypes = [vp, P(abi.VolumeOptions), vp, vp, vp]
+    L.vkv_update_transfer_function.argtypes = [vp, P(abi.VolumeOptions), vp, vp, abi.Extent3D, vp, vp, P(vp), vp, abi.Extent3D, i32, vp, vp]
+    L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
     L.vkv_load_data.argtypes = [C.c_char_p, P(abi.VolumeHeader), vp, C.c_size_t]
@@ -232,6 +236,27 @@ class Context:
 
     def transfer_function_tables(self, d_tf, tf, d_tables, stream=0):
         self.check(self._lib.vkv_transfer_function_tables(self.handle, d_tf, None if tf is None else C.byref(tf), d_tables, stream))
+
+    def transfer_function_texture_device(self, options, d_tf, d_tables, stream=0):
+        """vkv_transfer_function_texture_device: the TF texture + the integrator's tables from `options`, on the device (no host loop, no wait)"""
+        self.check(self._lib.vkv_transfer_function_texture_device(self.handle, C.byref(options), d_tf, d_tables, stream))
+
+    def update_transfer_function(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
+                                 d_count=None, stream=0):
+        """vkv_update_transfer_function: [count,] texture + tables, occupancy and the transform of skipping_type, as one enqueue"""
+        self.check(self.update_transfer_function_rc(options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
+                                                    d_count, stream))
+
+    def update_transfer_function_rc(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
+                                    d_count=None, stream=0):
+        """Like update_transfer_function() but returns the status code (error-path tests); d_maps None passes a NULL array."""
+        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
+        return self._lib.vkv_update_transfer_function(self.handle, None if options is None else C.byref(options), d_volume, d_gradient, extent, d_tf,
+                                                      d_tables, arr, d_swap, map_extent, skipping_type, d_count, stream)
+
+    def debug_tf_scratch(self, d_out, stream=0):
+        """vkv_debug_tf_scratch: the bit table + column mask (2056 words) in `stream`'s scratch block, copied to d_out"""
+        self.check(self._lib.vkv_debug_tf_scratch(self.handle, d_out, stream))
 
     def occupied_voxel_count(self, d_volume, d_gradient, tf, extent, d_count, stream=0):
         self.check(self._lib.vkv_occupied_voxel_count(self.handle, d_volume, d_gradient, C.byref(tf), extent, d_count, stream))

@@ -92,6 +92,21 @@ class Volume:
         self.ctx.transfer_function_tables(_ptr(self.transfer_function), self.get_transfer_function_uniform(), _ptr(self.transfer_function_bits),
                                           _stream())
 
+    def update_transfer_function_on_device(self):
+        """update_transfer_function_texture() without the host: texture + tables built on the device on the current stream, no wait.
+        Same state afterwards (VolumeRenderSubpass picks it up)."""
+        self.ctx.transfer_function_texture_device(self.options, _ptr(self.transfer_function), _ptr(self.transfer_function_bits), _stream())
+
+    def update_transfer_function(self, skipping_type, d_count=None):
+        """VolumeRender::update_transfer_function (src/volume_render.cpp:392-445) as one enqueue on the current stream: texture + tables,
+        the occupancy map and the transform of `skipping_type` (grows the map list like ComputeDistanceMap.compute); `d_count`: a device
+        int64 tensor that receives the occupied-voxel count."""
+        self.set_number_of_distance_maps(8 if skipping_type == abi.SKIP_ANISOTROPIC_DISTANCE else 1)
+        grad = self.gradient if self.options.use_precomputed_gradient else None
+        self.ctx.update_transfer_function(self.options, _ptr(self.volume), _ptr(grad), self.extent, _ptr(self.transfer_function),
+                                          _ptr(self.transfer_function_bits), [_ptr(m) for m in self.distance_maps], _ptr(self.distance_map_swap),
+                                          self.map_extent, skipping_type, _ptr(d_count), _stream())
+
     def pack(self):
         """(Re)build the bricked sampling image from the linear volume (+ gradient map).  Call after the gradient map
         is computed — the counterpart of the driver's swizzle into an optimally tiled VkImage.  The packed image is a COPY:
