@@ -366,6 +366,38 @@ int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, 
                                  VkvExtent3D extent, uint8_t *d_transfer_function, uint32_t *d_tables, uint8_t *const d_maps[8],
                                  uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type, uint64_t *d_occupied_count, void *stream);
 
+/* A box of voxels: [x0, x0 + width) x [y0, y0 + height) x [z0, z0 + depth). */
+typedef struct VkvBox
+{
+	uint32_t x0, y0, z0, width, height, depth;
+} VkvBox;
+
+/* New voxels for a box of the volume, and every derived buffer rebuilt where the box reaches it - as ONE enqueue on `stream`:
+ *   1. the width * height * depth raw elements of `type` at d_src (x fastest; a raw z-slab of a .header file is one) are converted as
+ *      vkv_convert_volume converts them (endianness, normalisation to [range_min, range_max], truncating) into their place in d_volume;
+ *   2. (d_gradient != NULL) the gradient of the box grown by one voxel per side, clamped to the volume (a voxel's gradient reads its +-1
+ *      neighbours);
+ *   3. (d_packed != NULL) every brick of the vkv_pack_volume image whose 5^3 texels read a changed volume or gradient byte (the clamped
+ *      apron bricks on the volume's faces included), from d_volume and d_gradient (NULL: gradient channel 0, as there);
+ *   4. (d_maps != NULL) the occupancy cells that meet the grown box, OCCUPIED or EMPTY, into the map that holds the occupancy, with the bit
+ *      table of d_transfer_function staged in the stream's scratch block (d_gradient == NULL: the on-the-fly gradient, as in
+ *      vkv_compute_distance_map).  `skipping_type` names what d_maps hold: NONE / BLOCK raw occupancy in d_maps[0], DISTANCE the Chebyshev
+ *      map in d_maps[0], ANISOTROPIC the eight octant maps; a distance is 0 exactly where the cell is occupied, so the map holding the
+ *      occupancy input (d_maps[0], d_maps[7] for ANISOTROPIC) is first turned back into occupancy;
+ *   5. the whole-map transform of skipping_type, as vkv_compute_distance_map runs it.
+ * PRECONDITION: before the call d_gradient, d_packed and d_maps hold what vkv_gradient_map, vkv_pack_volume and vkv_compute_distance_map
+ * (with this tf, d_transfer_function, extent, map_extent and skipping_type) make of d_volume.  Then after the call they hold, byte for byte,
+ * what those entry points make of the updated volume.
+ * The box must lie inside `extent` and not be empty; 16-bit sources must be 2-byte aligned; d_packed 256-byte aligned; with d_maps the
+ * maps the skipping type uses and d_transfer_function must be non-NULL, and DISTANCE / ANISOTROPIC need a d_swap that aliases no map.
+ * Every argument is checked before anything is enqueued: a rejected call writes nothing.  Capture: the call enqueues kernels only (no
+ * memset or copy nodes, no allocation, no host wait), so after one direct call (or vkv_prepare_render) on `stream` the update can be
+ * captured into a hipGraph; it replays with the source pointer and box it was captured with. */
+int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int32_t big_endian, float range_min, float range_max, const VkvBox *box,
+                             uint8_t *d_volume, uint8_t *d_gradient, void *d_packed, VkvExtent3D extent, const uint8_t *d_transfer_function,
+                             const VkvTransferFunctionUniform *tf, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent,
+                             int32_t skipping_type, void *stream);
+
 /* VolumeRenderSubpass::prepare, src/volume_render_subpass.cpp:95-157 (where the reference builds its pipelines and descriptor layouts).
  * Set-up call: creates, for `count` parameter blocks as a later vkv_render / vkv_render_batch on `stream` will pass them, everything that
  * launch takes from the context: the stream's scratch block, the address tables of the packed image's extent, the tile start order of the

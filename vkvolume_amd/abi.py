@@ -33,6 +33,15 @@ class Extent3D(C.Structure):
         return self.width * self.height * self.depth
 
 
+class Box(C.Structure):
+    """VkvBox: voxels [x0, x0 + width) x [y0, y0 + height) x [z0, z0 + depth)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("z0", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32)]
+
+    def __init__(self, x0=0, y0=0, z0=0, width=0, height=0, depth=0):
+        super().__init__(int(x0), int(y0), int(z0), int(width), int(height), int(depth))
+
+
 class TransferFunctionUniform(C.Structure):
     """VkvTransferFunctionUniform (src/transfer_function.h:20-32)"""
     _fields_ = [("sampling_factor", C.c_float), ("voxel_alpha_factor", C.c_float),

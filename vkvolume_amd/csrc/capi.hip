@@ -40,6 +40,8 @@ int launch_tf_tables(vkv_ctx *, const uint8_t *, const VkvTransferFunctionUnifor
 int launch_tf_build(vkv_ctx *, const VkvTransferFunctionUniform *, uint8_t *, uint32_t *, uint32_t *, hipStream_t);
 int launch_convert_volume(vkv_ctx *, const void *, int, bool, float, float, uint64_t, uint8_t *, hipStream_t);
 int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t);
+int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float, const VkvBox &, uint8_t *, uint8_t *, void *, VkvExtent3D, const uint8_t *,
+                                const VkvTransferFunctionUniform *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
 
 int set_error(vkv_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -1045,6 +1047,53 @@ int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, 
 	if (skipping_type == VKV_SKIP_DISTANCE)
 		return launch_distance_map(ctx, d_maps[0], d_swap, map_extent, s);
 	return VKV_OK;        // None / Block use the raw 0/255 occupancy map
+}
+
+// every argument is checked before the first launch (launch_update_volume_region checks the launches' size limits the same way)
+int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int32_t big_endian, float range_min, float range_max, const VkvBox *box,
+                             uint8_t *d_volume, uint8_t *d_gradient, void *d_packed, VkvExtent3D extent, const uint8_t *d_tf,
+                             const VkvTransferFunctionUniform *tf, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type,
+                             void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_src || !box || !d_volume || !tf || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null pointer or zero extent");
+	const VkvBox b = *box;
+	if (b.width == 0 || b.height == 0 || b.depth == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: empty box");
+	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
+		                 b.height, b.depth);
+	if (type < VKV_VOXEL_UINT8 || type > VKV_VOXEL_INT16)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: unsupported image data type %d", (int) type);
+	if ((type == VKV_VOXEL_UINT16 || type == VKV_VOXEL_INT16) && (((uintptr_t) d_src) & 1u))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: 16-bit input must be 2-byte aligned");
+	if (d_packed && ((uintptr_t) d_packed & 255u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: d_packed must be 256-byte aligned");
+	if (d_maps)
+	{
+		if (!d_tf || !map_extent_ok(extent, map_extent))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null transfer function or bad map extent");
+		if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: bad skipping_type %d", (int) skipping_type);
+		const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
+		const int  n     = aniso ? 8 : 1;
+		for (int i = 0; i < n; ++i)
+			if (!d_maps[i])
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: map %d is null", i);
+		if (aniso || skipping_type == VKV_SKIP_DISTANCE)
+		{
+			if (!d_swap)
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null swap buffer");
+			for (int i = 0; i < n; ++i)
+				if (d_maps[i] == d_swap)
+					return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: map %d aliases the swap buffer", i);
+		}
+	}
+	return launch_update_volume_region(ctx, d_src, type, big_endian != 0, range_min, range_max, b, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
+	                                   d_swap, map_extent, skipping_type, (hipStream_t) stream);
 }
 
 // argument checks shared by vkv_render and vkv_render_batch

@@ -18,15 +18,14 @@ using namespace vkv;
 // The four taps sit on the (±1,±1,±1) tetrahedron, i.e. in four different (y,z) rows; L1/L2 absorb the
 // 4x re-read (each byte is requested by the 4 voxels diagonal to it).
 __global__ void __launch_bounds__(256) k_gradient_map(const uint8_t *__restrict__ vol, uint8_t *__restrict__ grad, int W, int H, int D,
-                                                      int use_gradient, float modifier, uint32_t blocks_x, uint32_t nblocks)
+                                                      int use_gradient, float modifier, uint32_t blocks_x, int x0, int y0, int z0, int x1, int y1)
 {
 	// grid.x = column blocks x 4-row groups of one z slice, grid.y = z (keeps every grid dimension x block size below 2^32
-	// for 2048^3 and larger volumes)
-	(void) nblocks;
+	// for 2048^3 and larger volumes); the grid covers the box [x0, x1) x [y0, y1) x [z0, z0 + grid.y) (the whole volume, or a region update's)
 	const uint32_t bx = blockIdx.x % blocks_x;
-	const int      x  = (int) (bx * 64 + (threadIdx.x & 63));
-	const int      y  = (int) ((blockIdx.x / blocks_x) * 4 + (threadIdx.x >> 6)), z = (int) blockIdx.y;
-	if (x >= W || y >= H)
+	const int      x  = x0 + (int) (bx * 64 + (threadIdx.x & 63));
+	const int      y  = y0 + (int) ((blockIdx.x / blocks_x) * 4 + (threadIdx.x >> 6)), z = z0 + (int) blockIdx.y;
+	if (x >= x1 || y >= y1)
 		return;
 	float g = 1.0f;        // get_gradient_compute.glsl:6-7
 	if (use_gradient)
@@ -142,16 +141,18 @@ __device__ __forceinline__ void store_u8_uniform_base(uint8_t *base, uint32_t of
 template <bool ALIGNED>
 __global__ void __launch_bounds__(256) k_gradient_map_tiled(const uint8_t *__restrict__ vol, uint8_t *__restrict__ grad, int W, int H, int D,
                                                             float modifier, uint32_t tiles_x, uint32_t tiles_y, uint32_t tiles_z, uint32_t seg,
-                                                            uint32_t n_wgs)
+                                                            uint32_t n_wgs, uint32_t tx0, uint32_t ty0, uint32_t tz0)
 {
+	// the launch covers tiles_x x tiles_y tiles from tile (tx0, ty0) and the z tiles tz0 .. tiles_z - 1 (0, 0, 0 and all tiles for the whole
+	// volume; a region update passes the tiles its box touches: whole tiles are recomputed, the bytes outside the box come out as they were)
 	constexpr int kRows = (kGradTileZ + 2) * (kGradTileY + 2), kCols = kGradPitch / 4, kIter = (kRows * kCols + 255) / 256;
 	__shared__ __align__(16) uint16_t s_tile[kRows * kGradPitch];
 	__shared__ float                  s_unorm[256];        // b / 255 (IEEE division, once per workgroup): a tap costs one LDS read, not four VALU
 	s_unorm[threadIdx.x] = unorm8(threadIdx.x);
 	const uint32_t t  = xcd_remap(blockIdx.x, n_wgs);
-	const int      x0 = (int) (t % tiles_x) * kGradTileX;
-	const int      y0 = (int) ((t / tiles_x) % tiles_y) * kGradTileY;
-	const uint32_t k0 = (t / (tiles_x * tiles_y)) * seg, k1 = min(k0 + seg, tiles_z);
+	const int      x0 = (int) (tx0 + t % tiles_x) * kGradTileX;
+	const int      y0 = (int) (ty0 + (t / tiles_x) % tiles_y) * kGradTileY;
+	const uint32_t k0 = tz0 + (t / (tiles_x * tiles_y)) * seg, k1 = min(k0 + seg, tiles_z);
 	const int      wd = (W + 3) >> 2;        // dword columns of a row (round 6: the last one partial when W % 4 != 0; rows then start at any alignment)
 	const float    quarter_modifier = 0.25f * modifier;
 	// per-thread staging slots (100 rows x 18 dwords, 8 per thread): row / column of the tile are the same for every tile of the march,
@@ -540,7 +541,8 @@ __global__ void __launch_bounds__(256) k_occupancy_map_waves(const uint8_t *__re
 template <int GRAD>
 __global__ void __launch_bounds__(256) k_occupancy_map(const uint8_t *__restrict__ vol, const uint8_t *__restrict__ grad,
                                                        const uint32_t *__restrict__ tf_bits, uint8_t *__restrict__ map, int W, int H, int D,
-                                                       int mw, int mh, int md, int bx, int by, int bz, float modifier, uint32_t blocks_x)
+                                                       int mw, int mh, int md, int bx, int by, int bz, float modifier, uint32_t blocks_x,
+                                                       int cx0, int cy0, int cz0, int cx1)
 {
 	__shared__ uint32_t s_bits[2048];
 	__shared__ uint32_t s_cell[256];
@@ -549,11 +551,13 @@ __global__ void __launch_bounds__(256) k_occupancy_map(const uint8_t *__restrict
 	s_cell[threadIdx.x] = 0;
 	__syncthreads();
 
+	// the grid covers the cells [cx0, cx1) of the cell rows cy0 .. and slices cz0 .. (the whole map, or the cells of a region update: every
+	// cell is written, OCCUPIED or EMPTY)
 	const uint32_t bxi = blockIdx.x % blocks_x;
-	const int      cy = (int) (blockIdx.x / blocks_x), cz = (int) blockIdx.y;        // grid = (x blocks * cell rows, cell slices)
+	const int      cy = cy0 + (int) (blockIdx.x / blocks_x), cz = cz0 + (int) blockIdx.y;        // grid = (x blocks * cell rows, cell slices)
 	// the block covers cells [c0, c0 + cells_per_block) of this cell row
 	const int cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
-	const int c0              = (int) bxi * cells_per_block;
+	const int c0              = cx0 + (int) bxi * cells_per_block;
 	const int x0              = c0 * bx;
 	const int span            = cells_per_block * bx;        // voxels handled per pass (<= 256 unless bx > 256)
 	const int y_end = min((cy + 1) * by, H), z_end = min((cz + 1) * bz, D);
@@ -585,7 +589,7 @@ __global__ void __launch_bounds__(256) k_occupancy_map(const uint8_t *__restrict
 	}
 	__syncthreads();
 	const int c = c0 + (int) threadIdx.x;
-	if ((int) threadIdx.x < cells_per_block && c < mw)
+	if ((int) threadIdx.x < cells_per_block && c < cx1)
 		map[vidx(c, cy, cz, mw, mh)] = s_cell[threadIdx.x] ? 0 : 255;        // OCCUPIED = 0, EMPTY = 255
 }
 
@@ -937,22 +941,23 @@ __global__ void __launch_bounds__(256) k_dm_x_wave(const uint8_t *src, uint8_t *
 // Packed sampling layout (see vkv_device.hpp): one 128-thread half-block per brick, thread = one of the 5^3 texels
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_pack_volume(const uint8_t *__restrict__ vol, const uint8_t *__restrict__ grad, uint8_t *__restrict__ packed,
-                                                     int W, int H, int D, PackedDims pd, uint32_t n_bricks)
+                                                     int W, int H, int D, PackedDims pd, int ox, int oy, int oz, int nbx, int nby, int nbz)
 {
 	// a workgroup packs 2 bricks that are neighbours in x; consecutive workgroups walk a 4 x 4 x 4 group of brick pairs
 	// (8 x 4 x 4 bricks = 32 x 16 x 16 voxels) before moving on, so the overlapping 5^3 neighbourhoods are re-read from L1 / L2
-	// and not from HBM (the first version walked whole brick rows and fetched every byte ~5x)
-	(void) n_bricks;
-	const uint32_t gx = (uint32_t) (pd.bx + 7) / 8, gy = (uint32_t) (pd.by + 3) / 4;        // groups per axis
+	// and not from HBM (the first version walked whole brick rows and fetched every byte ~5x).  The launch packs the nbx x nby x nbz
+	// bricks from brick (ox, oy, oz): all of them, or a region update's
+	const uint32_t gx = (uint32_t) (nbx + 7) / 8, gy = (uint32_t) (nby + 3) / 4;        // groups per axis
 	// workgroup ids are dealt round-robin to the 8 XCDs: XCD (id & 7) takes groups id&7, id&7 + 8, ... so a group stays in one L2;
 	// grid.y = group layer in z (keeps grid.x * 256 below 2^32 for 2048^3)
 	const uint32_t grp = ((blockIdx.x >> 3) >> 6) * 8u + (blockIdx.x & 7u), in = (blockIdx.x >> 3) & 63u;
-	const int      bx = (int) ((grp % gx) * 8 + (in & 3u) * 2 + (threadIdx.x >> 7));
-	const int      by = (int) ((grp / gx) * 4 + ((in >> 2) & 3u));
-	const int      bz = (int) (blockIdx.y * 4 + (in >> 4));
+	const int      lbx = (int) ((grp % gx) * 8 + (in & 3u) * 2 + (threadIdx.x >> 7));
+	const int      lby = (int) ((grp / gx) * 4 + ((in >> 2) & 3u));
+	const int      lbz = (int) (blockIdx.y * 4 + (in >> 4));
 	const int      t  = threadIdx.x & 127;
-	if (bx >= pd.bx || by >= pd.by || bz >= pd.bz || grp >= gx * gy)
+	if (lbx >= nbx || lby >= nby || lbz >= nbz || grp >= gx * gy)
 		return;
+	const int bx = ox + lbx, by = oy + lby, bz = oz + lbz;
 	uint16_t *dst = reinterpret_cast<uint16_t *>(packed + packed_brick_offset(bx, by, bz, pd.mx, pd.my));
 	if (t >= 125)
 	{
@@ -1206,15 +1211,17 @@ __global__ void __launch_bounds__(THREADS) k_dm_rmq(const DmPasses passes, uint3
 // barrier (8 x 2 x 2: 2 x 3 - not enough outstanding bytes per CU to cover the HBM latency) and the apron re-read drops from 1.42 to 1.27.
 template <int BY, int BZ, int PITCH, bool ALIGNED>        // ALIGNED: W % 4 == 0 and dword-aligned buffers (plain dword loads); else row_dword
 __global__ void __launch_bounds__(256) k_pack_volume_tiled(const uint8_t *__restrict__ vol, const uint8_t *__restrict__ grad, uint8_t *__restrict__ packed,
-                                                           int W, int H, int D, PackedDims pd, uint32_t groups_x)
+                                                           int W, int H, int D, PackedDims pd, uint32_t groups_x, uint32_t gx0, uint32_t gy0, uint32_t gz0)
 {
+	// the grid covers groups_x x (grid.x / groups_x) x grid.y groups of 8 x BY x BZ bricks from group (gx0, gy0, gz0): all of them, or the
+	// groups a region update touches (whole groups are re-packed; the bricks outside its footprint come out as they were)
 	// tile: rows (jz, jy) of (v | g << 8) texels; staged dword column c (voxels 4 * (bx0 - 1 + c) ..) sits at texels 4c .. 4c + 3, so the
 	// padded tile column jx (voxel x = 4 * bx0 - 1 + jx) is texel jx + 3; 36 texels staged, 33 used
 	constexpr int kTX = PITCH, kRY = 4 * BY + 1, kRZ = 4 * BZ + 1, kRows = kRY * kRZ;
 	__shared__ __align__(8) uint16_t s_tile[kRows * kTX];
 	// x-neighbouring workgroups stage parts of the same 128-byte lines: consecutive groups go to one XCD (own L2)
 	const uint32_t bid = xcd_remap(blockIdx.x, gridDim.x);
-	const int      bx0 = (int) (bid % groups_x) * 8, by0 = (int) (bid / groups_x) * BY, bz0 = (int) blockIdx.y * BZ;
+	const int      bx0 = (int) (gx0 + bid % groups_x) * 8, by0 = (int) (gy0 + bid / groups_x) * BY, bz0 = (int) (gz0 + blockIdx.y) * BZ;
 	const int wd  = (W + 3) >> 2;        // dword columns of a row; the last one partial when W % 4 != 0 (its texels x >= W are fixed up below)
 	// ---- stage: row = (jz, jy) of the padded tile, 9 dwords per row starting one dword left of the tile; a lane's (row, column) advance by
 	// constants from one of its loads to the next (256 = 28 * 9 + 4), so the divisions are done once
@@ -1418,6 +1425,24 @@ __global__ void __launch_bounds__(256) k_convert_volume(const T *__restrict__ ra
 			out[i] = normalise_voxel<T>(raw[i], swap, lo, hi);
 }
 
+// The same conversion for a box of the volume (vkv_update_volume_region): raw holds bw x bh x (rows / bh) elements, x fastest; element
+// (x, y, z) goes to voxel (x0 + x, y0 + y, z0 + z).  A workgroup converts 256 elements of a row (`chunks_x` of them per row), grid-stride
+// over the rows.
+template <typename T>
+__global__ void __launch_bounds__(256) k_convert_box(const T *__restrict__ raw, uint8_t *__restrict__ out, int W, int H, int x0, int y0, int z0, int bw,
+                                                     int bh, unsigned long long rows, uint32_t chunks_x, bool swap, float lo, float hi)
+{
+	for (unsigned long long b = blockIdx.x; b < rows * chunks_x; b += gridDim.x)
+	{
+		const unsigned long long row = b / chunks_x;
+		const int                x   = (int) (b - row * chunks_x) * 256 + (int) threadIdx.x;
+		if (x >= bw)
+			continue;
+		const int y = (int) (row % (unsigned) bh), z = (int) (row / (unsigned) bh);
+		out[vidx(x0 + x, y0 + y, z0 + z, W, H)] = normalise_voxel<T>(raw[row * (unsigned) bw + (unsigned) x], swap, lo, hi);
+	}
+}
+
 // ---------------------------------------------------------------------------------------------
 // Multi-GPU: de-interleave gathered compact tile buffers into the final image(s) (one thread per pixel, or per four RGBA8 pixels).
 // blockIdx.z = frame of the launch; each frame has its own image, source ([rank][tiles], `stride` tiles between two ranks' buffers) and
@@ -1462,10 +1487,12 @@ __global__ void __launch_bounds__(256) k_scatter_tiles_frames(const ScatterFrame
 namespace vkv
 {
 
-int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, VkvExtent3D e, const VkvTransferFunctionUniform *tf, hipStream_t s)
+// the gradient of the voxels of the box [b.x0, b.x0 + b.width) x ... (inside e); launch_gradient_map: the whole volume
+int launch_gradient_map_box(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, VkvExtent3D e, const VkvBox &b, const VkvTransferFunctionUniform *tf,
+                            hipStream_t s)
 {
-	const uint32_t blocks_x = (e.width + 63) / 64;
-	if (e.depth > 65535u || (uint64_t) blocks_x * ((e.height + 3) / 4) > 0xffffffull)
+	const uint32_t blocks_x = (b.width + 63) / 64;
+	if (e.depth > 65535u || (uint64_t) blocks_x * ((b.height + 3) / 4) > 0xffffffull)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "gradient_map: volume too large for one launch");
 	// the tiled kernel folds the three factors 0.25 into the modifier: exact unless 0.25 * modifier is denormal (or the modifier no number)
 	const float m_abs    = std::fabs(tf->grad_magnitude_modifier);
@@ -1473,8 +1500,10 @@ int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, Vkv
 	// round 6: any width >= 4 and any alignment of the volume (the staging loads need none: row_dword / load_u32_any)
 	if (tf->use_gradient && m_normal && e.width >= 4 && (uint64_t) e.width * e.height * (kGradTileZ + 2) <= 0xffffffffull)
 	{
-		const uint64_t tx = (e.width + kGradTileX - 1) / kGradTileX, ty = (e.height + kGradTileY - 1) / kGradTileY,
-		               tz = (e.depth + kGradTileZ - 1) / kGradTileZ;
+		// the tiles the box touches: [t0, t1) per axis
+		const uint32_t tx0 = b.x0 / kGradTileX, ty0 = b.y0 / kGradTileY, tz0 = b.z0 / kGradTileZ;
+		const uint64_t tx = (b.x0 + b.width + kGradTileX - 1) / kGradTileX - tx0, ty = (b.y0 + b.height + kGradTileY - 1) / kGradTileY - ty0,
+		               tz1 = (b.z0 + b.depth + kGradTileZ - 1) / kGradTileZ, tz = tz1 - tz0;
 		// kGradSegment tiles per workgroup, fewer when the volume would not give every CU its eight workgroups otherwise
 		const uint64_t want = (uint64_t) 8 * (uint64_t) std::max(1, ctx->cu_count);
 		uint32_t       seg  = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(kGradSegment, tx * ty * tz / want));
@@ -1485,16 +1514,22 @@ int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, Vkv
 		{
 			if ((e.width & 3u) == 0 && (((uintptr_t) d_vol) & 3u) == 0)
 				hipLaunchKernelGGL(k_gradient_map_tiled<true>, dim3((uint32_t) n_wgs), dim3(256), 0, s, d_vol, d_grad, (int) e.width, (int) e.height, (int) e.depth,
-				                   tf->grad_magnitude_modifier, (uint32_t) tx, (uint32_t) ty, (uint32_t) tz, seg, (uint32_t) n_wgs);
+				                   tf->grad_magnitude_modifier, (uint32_t) tx, (uint32_t) ty, (uint32_t) tz1, seg, (uint32_t) n_wgs, tx0, ty0, tz0);
 			else
 				hipLaunchKernelGGL(k_gradient_map_tiled<false>, dim3((uint32_t) n_wgs), dim3(256), 0, s, d_vol, d_grad, (int) e.width, (int) e.height, (int) e.depth,
-				                   tf->grad_magnitude_modifier, (uint32_t) tx, (uint32_t) ty, (uint32_t) tz, seg, (uint32_t) n_wgs);
+				                   tf->grad_magnitude_modifier, (uint32_t) tx, (uint32_t) ty, (uint32_t) tz1, seg, (uint32_t) n_wgs, tx0, ty0, tz0);
 			return check_launch(ctx, "gradient_map");
 		}
 	}
-	hipLaunchKernelGGL(k_gradient_map, dim3(blocks_x * ((e.height + 3) / 4), e.depth), dim3(256), 0, s, d_vol, d_grad, (int) e.width, (int) e.height,
-	                   (int) e.depth, (int) (tf->use_gradient != 0), tf->grad_magnitude_modifier, blocks_x, 0u);
+	hipLaunchKernelGGL(k_gradient_map, dim3(blocks_x * ((b.height + 3) / 4), b.depth), dim3(256), 0, s, d_vol, d_grad, (int) e.width, (int) e.height,
+	                   (int) e.depth, (int) (tf->use_gradient != 0), tf->grad_magnitude_modifier, blocks_x, (int) b.x0, (int) b.y0, (int) b.z0,
+	                   (int) (b.x0 + b.width), (int) (b.y0 + b.height));
 	return check_launch(ctx, "gradient_map");
+}
+
+int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, VkvExtent3D e, const VkvTransferFunctionUniform *tf, hipStream_t s)
+{
+	return launch_gradient_map_box(ctx, d_vol, d_grad, e, VkvBox{0, 0, 0, e.width, e.height, e.depth}, tf, s);
 }
 
 // 255 (EMPTY) into n bytes: 16-byte stores over the aligned body, single bytes at both ends.  The map fill of vkv_update_transfer_function:
@@ -1511,6 +1546,27 @@ __global__ void __launch_bounds__(256) k_fill_empty(uint8_t *__restrict__ p, siz
 		q[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
 	if (tid < n - tail)
 		p[tail + tid] = 255;
+}
+
+// A distance map (or an octant map) back into the occupancy it was made from: every transform keeps the zero set (a cell is its own
+// candidate at distance 0, any other is at least 1 away), so byte v -> v == 0 ? OCCUPIED (0) : EMPTY (255).  Same layout as k_fill_empty.
+__global__ void __launch_bounds__(256) k_occupancy_of_distance(uint8_t *__restrict__ p, size_t n)
+{
+	const size_t head = min(n, (size_t) ((16u - ((uintptr_t) p & 15u)) & 15u));
+	const size_t body = (n - head) / 16, tail = head + body * 16;
+	const size_t tid = (size_t) blockIdx.x * 256 + threadIdx.x, stride = (size_t) gridDim.x * 256;
+	if (tid < head)
+		p[tid] = p[tid] ? 255 : 0;
+	// bit 7 of ((b & 0x7f) + 0x7f) | b is set exactly for the non-zero bytes b (no carries between bytes)
+	auto nonzero = [](uint32_t w) { return ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u) >> 7; };
+	uint4 *q = reinterpret_cast<uint4 *>(p + head);
+	for (size_t i = tid; i < body; i += stride)
+	{
+		const uint4 v = q[i];
+		q[i]          = make_uint4(nonzero(v.x) * 255u, nonzero(v.y) * 255u, nonzero(v.z) * 255u, nonzero(v.w) * 255u);
+	}
+	if (tid < n - tail)
+		p[tail + tid] = p[tail + tid] ? 255 : 0;
 }
 
 static int fill_empty(vkv_ctx *ctx, uint8_t *d_map, size_t n, hipStream_t s, bool by_kernel)
@@ -1638,13 +1694,13 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 	}
 	if (!tf->use_gradient)
 		hipLaunchKernelGGL(k_occupancy_map<0>, grid, dim3(256), 0, s, d_vol, d_grad, d_bits, d_map, W, H, D, mw, mh, md, bx, by,
-		                   bz, tf->grad_magnitude_modifier, blocks_x);
+		                   bz, tf->grad_magnitude_modifier, blocks_x, 0, 0, 0, mw);
 	else if (d_grad)
 		hipLaunchKernelGGL(k_occupancy_map<1>, grid, dim3(256), 0, s, d_vol, d_grad, d_bits, d_map, W, H, D, mw, mh, md, bx, by,
-		                   bz, tf->grad_magnitude_modifier, blocks_x);
+		                   bz, tf->grad_magnitude_modifier, blocks_x, 0, 0, 0, mw);
 	else
 		hipLaunchKernelGGL(k_occupancy_map<2>, grid, dim3(256), 0, s, d_vol, d_grad, d_bits, d_map, W, H, D, mw, mh, md, bx, by,
-		                   bz, tf->grad_magnitude_modifier, blocks_x);
+		                   bz, tf->grad_magnitude_modifier, blocks_x, 0, 0, 0, mw);
 	return check_launch(ctx, "occupancy_map");
 }
 
@@ -1887,15 +1943,18 @@ int launch_check_numerics(vkv_ctx *ctx, int what, uint32_t first_bits, uint64_t 
 	return check_launch(ctx, "check_numerics");
 }
 
-int launch_pack_volume(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, void *d_packed, hipStream_t s)
+// the bricks [b0, b1) per axis (packed_dims' brick grid); launch_pack_volume: all of them
+int launch_pack_volume_bricks(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, const int b0[3], const int b1[3], void *d_packed,
+                              hipStream_t s)
 {
 	const PackedDims pd = packed_dims((int) e.width, (int) e.height, (int) e.depth);
-	if (e.width >= 4)        // round 6: any width and alignment (row_dword: the staging loads need no alignment, an odd row's last column is shifted in)
+	if (e.width >= 4)        // round 6: any width and alignment (row_dword: the staging loads need none, an odd row's last column is shifted in)
 	{
 		const int tile_env = tuning_of(ctx).pack_tile;        // A/B switch: 2 or 4
 		const bool     big = tile_env ? tile_env == 4 : (pd.by >= 16 && pd.bz >= 16);
 		const uint32_t t   = big ? 4u : 2u;
-		const uint32_t gx = (uint32_t) (pd.bx + 7) / 8, gy = ((uint32_t) pd.by + t - 1) / t, gz = ((uint32_t) pd.bz + t - 1) / t;
+		const uint32_t gx0 = (uint32_t) b0[0] / 8, gy0 = (uint32_t) b0[1] / t, gz0 = (uint32_t) b0[2] / t;        // groups of 8 x t x t bricks touched
+		const uint32_t gx = ((uint32_t) b1[0] + 7) / 8 - gx0, gy = ((uint32_t) b1[1] + t - 1) / t - gy0, gz = ((uint32_t) b1[2] + t - 1) / t - gz0;
 		if ((uint64_t) gx * gy <= 0xffffffull && gz <= 65535u && (uint64_t) pd.mx * pd.my * pd.mz * 512 <= 0xffffffffull)
 		{
 			// row pitch 40 texels; 38 (19 banks, odd: no bank conflicts, 70 % of the LDS cycles otherwise) measured the same 1.34 ms: the
@@ -1903,7 +1962,7 @@ int launch_pack_volume(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad
 			const bool aligned = (e.width & 3u) == 0 && ((((uintptr_t) d_vol) | ((uintptr_t) d_grad)) & 3u) == 0;
 #define VKV_PACK(T, A)                                                                                                                              \
 	hipLaunchKernelGGL((k_pack_volume_tiled<T, T, 40, A>), dim3(gx * gy, gz), dim3(256), 0, s, d_vol, d_grad, (uint8_t *) d_packed, (int) e.width,     \
-	                   (int) e.height, (int) e.depth, pd, gx)
+	                   (int) e.height, (int) e.depth, pd, gx, gx0, gy0, gz0)
 			if (big)
 			{
 				if (aligned) VKV_PACK(4, true); else VKV_PACK(4, false);
@@ -1920,12 +1979,20 @@ int launch_pack_volume(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad
 	if (nb > 0xffffffull || pd.bz > 65535 || (uint64_t) pd.mx * pd.my * pd.mz * 512 > 0xffffffffull)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "pack_volume: volume too large");
 	// macro-brick padding (bricks that exist only because of the 8x8x8 grouping) is never addressed by the sampler
-	const uint64_t groups = (uint64_t) ((pd.bx + 7) / 8) * ((pd.by + 3) / 4);        // per layer of 4 bricks in z
-	if ((groups + 8) * 64 * 256 > 0xffffffffull || (pd.bz + 3) / 4 > 65535)
+	const int      nbx = b1[0] - b0[0], nby = b1[1] - b0[1], nbz = b1[2] - b0[2];
+	const uint64_t groups = (uint64_t) ((nbx + 7) / 8) * ((nby + 3) / 4);        // per layer of 4 bricks in z
+	if ((groups + 8) * 64 * 256 > 0xffffffffull || (nbz + 3) / 4 > 65535)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "pack_volume: volume too large");
-	hipLaunchKernelGGL(k_pack_volume, dim3((uint32_t) (((groups + 7) / 8) * 8 * 64), (uint32_t) ((pd.bz + 3) / 4)), dim3(256), 0, s, d_vol, d_grad, (uint8_t *) d_packed, (int) e.width, (int) e.height,
-	                   (int) e.depth, pd, (uint32_t) nb);
+	hipLaunchKernelGGL(k_pack_volume, dim3((uint32_t) (((groups + 7) / 8) * 8 * 64), (uint32_t) ((nbz + 3) / 4)), dim3(256), 0, s, d_vol, d_grad, (uint8_t *) d_packed, (int) e.width, (int) e.height,
+	                   (int) e.depth, pd, b0[0], b0[1], b0[2], nbx, nby, nbz);
 	return check_launch(ctx, "pack_volume");
+}
+
+int launch_pack_volume(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, void *d_packed, hipStream_t s)
+{
+	const PackedDims pd = packed_dims((int) e.width, (int) e.height, (int) e.depth);
+	const int        b0[3] = {0, 0, 0}, b1[3] = {pd.bx, pd.by, pd.bz};
+	return launch_pack_volume_bricks(ctx, d_vol, d_grad, e, b0, b1, d_packed, s);
 }
 
 // Separable alpha tables of the reference's transfer function (src/volume_component.cpp:246-261) from the uniform's fields, and
@@ -2102,11 +2169,16 @@ int launch_synth_volume(vkv_ctx *ctx, uint8_t *d_vol, VkvExtent3D e, uint32_t ki
 	return check_launch(ctx, "synth_volume");
 }
 
+// 16-bit elements of a file in this byte order need a swap (the device shares the host's byte order)
+static bool swap_for(bool big_endian)
+{
+	const uint16_t probe = 1;
+	return big_endian == (*reinterpret_cast<const uint8_t *>(&probe) == 1);
+}
+
 int launch_convert_volume(vkv_ctx *ctx, const void *d_raw, int type, bool big_endian, float lo, float hi, uint64_t n, uint8_t *d_out, hipStream_t s)
 {
-	const uint16_t probe          = 1;
-	const bool     host_is_little = *reinterpret_cast<const uint8_t *>(&probe) == 1;        // the device shares the host's byte order
-	const bool     swap           = big_endian == host_is_little;
+	const bool     swap           = swap_for(big_endian);
 	const int      per            = (type == VKV_VOXEL_UINT16 || type == VKV_VOXEL_INT16) ? 8 : 16;
 	const uint64_t blocks         = (n + (uint64_t) per * 256 - 1) / ((uint64_t) per * 256);
 	if (blocks == 0)
@@ -2146,6 +2218,126 @@ int launch_scatter_tiles_frames(vkv_ctx *ctx, uint32_t n, void *const *images, c
 	else
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "scatter_tiles: bytes_per_pixel must be 4 or 16");
 	return check_launch(ctx, "scatter_tiles");
+}
+
+
+// vkv_update_volume_region (include/vkvolume_amd.h), after the entry point's argument checks.  The size limits of every launch below are
+// checked before the first one, so a call this rejects writes nothing.
+int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool big_endian, float lo, float hi, const VkvBox &box, uint8_t *d_vol,
+                                uint8_t *d_grad, void *d_packed, VkvExtent3D e, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
+                                uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D me, int skipping_type, hipStream_t s)
+{
+	const uint32_t ext[3] = {e.width, e.height, e.depth}, org[3] = {box.x0, box.y0, box.z0}, size[3] = {box.width, box.height, box.depth};
+	// the box grown by one voxel per side and clamped to the volume: where the gradient can change (a voxel's gradient reads its +-1
+	// neighbours), and with it the packed bricks and the occupancy cells
+	uint32_t g0[3], g1[3];
+	for (int a = 0; a < 3; ++a)
+		g0[a] = org[a] > 0 ? org[a] - 1 : 0, g1[a] = std::min(org[a] + size[a] + 1, ext[a]);        // (org + size <= ext was checked in 64 bits)
+	const VkvBox     grown = {g0[0], g0[1], g0[2], g1[0] - g0[0], g1[1] - g0[1], g1[2] - g0[2]};
+	const PackedDims pd    = packed_dims((int) e.width, (int) e.height, (int) e.depth);
+	// ---- limits (those of the whole-volume launchers: any volume they build can be updated)
+	if (e.depth > 65535u || (uint64_t) ((e.width + 63) / 64) * ((e.height + 3) / 4) > 0xffffffull)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: volume too large for one launch");
+	if (d_packed && ((uint64_t) pd.mx * pd.my * pd.mz * 512 > 0xffffffffull || (uint64_t) pd.bx * pd.by > 0xffffffull))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: pack_volume: volume too large");
+	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE, transform = aniso || skipping_type == VKV_SKIP_DISTANCE;
+	int        blk[3] = {1, 1, 1};
+	uint32_t   c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
+	uint8_t *  scratch = nullptr;
+	if (d_maps)
+	{
+		if (transform && me.width > 2048)
+			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map rows longer than 2048 cells (LDS strip limit of the x pass)");
+		const uint32_t mext[3] = {me.width, me.height, me.depth};
+		for (int a = 0; a < 3; ++a)        // src/compute_distance_map.cpp:110-113; the cells that meet the grown box
+			blk[a] = (int) ((ext[a] + mext[a] - 1) / mext[a]), c0[a] = g0[a] / (uint32_t) blk[a], c1[a] = (g1[a] - 1) / (uint32_t) blk[a] + 1;
+		const int cpb = 256 / blk[0] > 0 ? 256 / blk[0] : 1;
+		if ((uint64_t) ((me.width + cpb - 1) / cpb) * me.height > 0xffffffull || me.depth > 65535u)
+			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map too large for one launch");
+		if (!(scratch = stream_scratch(ctx, s)))
+			return VKV_E_UNSUPPORTED;
+	}
+	// ---- 1. convert the source box into the volume
+	{
+		const bool               swap = swap_for(big_endian);
+		const unsigned long long rows = (unsigned long long) box.height * box.depth;
+		const uint32_t chunks_x       = (box.width + 255) / 256;
+		const uint32_t blocks         = (uint32_t) std::min<unsigned long long>(rows * chunks_x, 1ull << 20);
+		const int      W = (int) e.width, H = (int) e.height, x0 = (int) box.x0, y0 = (int) box.y0, z0 = (int) box.z0, bw = (int) box.width, bh = (int) box.height;
+#define VKV_CONVERT_BOX(T) hipLaunchKernelGGL(k_convert_box<T>, dim3(blocks), dim3(256), 0, s, (const T *) d_src, d_vol, W, H, x0, y0, z0, bw, bh, rows, chunks_x, swap, lo, hi)
+		switch (type)
+		{
+			case VKV_VOXEL_UINT8: VKV_CONVERT_BOX(uint8_t); break;
+			case VKV_VOXEL_INT8: VKV_CONVERT_BOX(int8_t); break;
+			case VKV_VOXEL_UINT16: VKV_CONVERT_BOX(uint16_t); break;
+			default: VKV_CONVERT_BOX(int16_t); break;        // VKV_VOXEL_INT16 (the type was checked)
+		}
+#undef VKV_CONVERT_BOX
+		const int rc = check_launch(ctx, "update_volume_region: convert");
+		if (rc != VKV_OK)
+			return rc;
+	}
+	// ---- 2. gradient of the grown box; 3. the bricks whose texels read a changed byte
+	int rc = VKV_OK;
+	if (d_grad && (rc = launch_gradient_map_box(ctx, d_vol, d_grad, e, grown, tf, s)) != VKV_OK)
+		return rc;
+	if (d_packed)
+	{
+		// brick b reads voxels 4b - 1 .. 4b + 3 (clamped): the bricks [g0 / 4, (g1 - 1 + 1) / 4] per axis, and up to the last brick when the grown box
+		// reaches the volume's far face (the apron bricks there read only the clamped last voxel)
+		const int nb[3] = {pd.bx, pd.by, pd.bz};
+		int       b0[3], b1[3];
+		for (int a = 0; a < 3; ++a)
+			b0[a] = (int) (g0[a] / 4), b1[a] = g1[a] == ext[a] ? nb[a] : std::min(nb[a], (int) (g1[a] / 4) + 1);
+		if ((rc = launch_pack_volume_bricks(ctx, d_vol, d_grad, e, b0, b1, d_packed, s)) != VKV_OK)
+			return rc;
+	}
+	if (!d_maps)
+		return VKV_OK;
+	// ---- 4. occupancy of the cells that meet the grown box, from the bit table of the texture (staged in the stream's scratch block)
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
+	hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
+	hipLaunchKernelGGL(k_tf_columns, dim3(1), dim3(256), 0, s, d_bits);
+	if ((rc = check_launch(ctx, "update_volume_region: bit table")) != VKV_OK)
+		return rc;
+	uint8_t *occ = d_maps[aniso ? 7 : 0];
+	if (c0[0] == 0 && c0[1] == 0 && c0[2] == 0 && c1[0] == me.width && c1[1] == me.height && c1[2] == me.depth)
+	{        // every cell: the whole-map pass writes them all (its EMPTY fill is a kernel here)
+		if ((rc = launch_occupancy_map(ctx, d_vol, d_grad, d_tf, tf, e, occ, me, s, true)) != VKV_OK)
+			return rc;
+	}
+	else
+	{
+		const size_t n_cells = (size_t) me.width * me.height * me.depth;
+		if (transform)
+		{
+			const size_t blocks = std::min<size_t>(std::max<size_t>(1, (n_cells / 16 + 255) / 256), 4096);
+			hipLaunchKernelGGL(k_occupancy_of_distance, dim3((uint32_t) blocks), dim3(256), 0, s, occ, n_cells);
+		}
+		const int      cpb      = 256 / blk[0] > 0 ? 256 / blk[0] : 1;
+		const uint32_t blocks_x = (c1[0] - c0[0] + cpb - 1) / cpb;
+		const dim3     grid(blocks_x * (c1[1] - c0[1]), c1[2] - c0[2]);
+		const int      G = !tf->use_gradient ? 0 : (d_grad ? 1 : 2);
+#define VKV_OCC_BOX(G_)                                                                                                                                  \
+	hipLaunchKernelGGL(k_occupancy_map<G_>, grid, dim3(256), 0, s, d_vol, d_grad, d_bits, occ, (int) e.width, (int) e.height, (int) e.depth, (int) me.width, \
+	                   (int) me.height, (int) me.depth, blk[0], blk[1], blk[2], tf->grad_magnitude_modifier, blocks_x, (int) c0[0], (int) c0[1], (int) c0[2],    \
+	                   (int) c1[0])
+		if (G == 0)
+			VKV_OCC_BOX(0);
+		else if (G == 1)
+			VKV_OCC_BOX(1);
+		else
+			VKV_OCC_BOX(2);
+#undef VKV_OCC_BOX
+		if ((rc = check_launch(ctx, "update_volume_region: occupancy")) != VKV_OK)
+			return rc;
+	}
+	// ---- 5. the whole-map transform
+	if (aniso)
+		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, me, s);
+	if (skipping_type == VKV_SKIP_DISTANCE)
+		return launch_distance_map(ctx, d_maps[0], d_swap, me, s);
+	return VKV_OK;
 }
 
 }        // namespace vkv

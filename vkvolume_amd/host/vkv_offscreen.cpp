@@ -17,6 +17,9 @@
 //                                  a small step, updates the texture and the maps and renders one frame; prints ms per move from device events
 //                                  (two warm-up moves untimed).  host = the blocking update (CPU texture, upload, wait, tables, occupancy +
 //                                  transform); device = Volume::update_transfer_function, one enqueue with no host wait
+//                 [--stream-slabs=N]   progressive loading: the volume starts all zero (its maps built as for any volume), then arrives in N
+//                                  z-slabs - read from the raw file, or cut from the synthetic volume generated into a staging buffer - each
+//                                  written with Volume::update_region and followed by one frame; --dump-rgba8 writes the last frame
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -33,6 +36,7 @@
 #include "compute_distance_map.h"
 #include "compute_gradient_map.h"
 #include "compute_occupied_voxel_count.h"
+#include "load_volume.h"
 #include "volume_render_subpass.h"
 
 namespace
@@ -58,6 +62,7 @@ struct Args
 	std::string dump_assembled;
 	int         tf_drag = 0;              // --tf-drag=N: slider moves
 	std::string tf_path = "device";        // --tf-path=host|device
+	uint32_t    stream_slabs = 0;          // --stream-slabs=N: z-slabs of a progressive load
 };
 
 bool flag(const char *arg, const char *name, std::string &value)
@@ -120,6 +125,7 @@ Args parse(int argc, char **argv)
 				throw std::runtime_error("--tf-path=host|device");
 			a.tf_path = v;
 		}
+		else if (flag(s, "--stream-slabs", v)) a.stream_slabs = (uint32_t) std::stoul(v);
 		else if (s[0] != '-') a.dataset = s;
 		else throw std::runtime_error(std::string("unknown flag ") + s);
 	}
@@ -187,7 +193,43 @@ int main(int argc, char **argv)
 		volume.options.gradient_min             = args.gmin;
 		volume.options.gradient_max             = args.gmax;
 		volume.options.use_precomputed_gradient = !args.gradient_test;
-		if (!args.synthetic.empty())
+		// --stream-slabs: the raw source of the slabs (the synthetic volume's bytes, or the file's header: the slabs are read when they are written)
+		std::vector<uint8_t> slab_source;
+		LoadVolume::Header   slab_header;
+		int                  slab_type = VKV_VOXEL_UINT8;
+		if (args.stream_slabs > 0)
+		{
+			if (!args.synthetic.empty())
+			{
+				unsigned w = 0, h = 0, d = 0, kind = 1, seed = 0xC0FFEE03u;
+				if (std::sscanf(args.synthetic.c_str(), "%ux%ux%u:%u:%u", &w, &h, &d, &kind, &seed) < 3)
+					throw std::runtime_error("--synthetic=WxHxD[:kind[:seed]]");
+				slab_header.extent = VkvExtent3D{w, h, d};
+				slab_header.normalisation_range[0] = 0.0f, slab_header.normalisation_range[1] = 255.0f;        // uint8 voxels as they are
+				const size_t n       = (size_t) w * h * d;
+				uint8_t *    staging = device_alloc<uint8_t>(n);
+				const int    rc      = vkv_synth_volume(ctx, staging, slab_header.extent, kind, seed, stream);
+				slab_source.resize(n);
+				const bool ok = rc == VKV_OK && hipMemcpyAsync(slab_source.data(), staging, n, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+				                hipStreamSynchronize(stream) == hipSuccess;
+				(void) hipFree(staging);
+				if (!ok)
+					throw std::runtime_error("synthetic volume for --stream-slabs failed");
+				volume.set_image_transform(vkv::scale(vkv::vec3{(float) w, (float) h, (float) d}));
+			}
+			else if (!args.dataset.empty())
+			{
+				slab_header = LoadVolume::load_header(args.dataset + ".header");
+				slab_type   = LoadVolume::voxel_type(slab_header);
+				volume.set_image_transform(slab_header.image_transform);
+			}
+			else
+				throw std::runtime_error("give a volume file or --synthetic=WxHxD");
+			const VkvExtent3D    e = slab_header.extent;
+			std::vector<uint8_t> zeros((size_t) e.width * e.height * e.depth, 0);
+			volume.load_from_memory(dc, zeros.data(), e, args.blocksize);
+		}
+		else if (!args.synthetic.empty())
 		{
 			unsigned w = 0, h = 0, d = 0, kind = 1, seed = 0xC0FFEE03u;
 			if (std::sscanf(args.synthetic.c_str(), "%ux%ux%u:%u:%u", &w, &h, &d, &kind, &seed) < 3)
@@ -311,6 +353,42 @@ int main(int argc, char **argv)
 		subpass.prepare_targets({target});
 		subpass.draw(target);        // warm-up (and the frame the dumps below read)
 		(void) hipStreamSynchronize(stream);
+		if (args.stream_slabs > 0)
+		{        // the slabs of a progressive load, each followed by one frame into the same target (the last one is the frame the dumps read)
+			const VkvExtent3D e     = slab_header.extent;
+			const size_t      slice = (size_t) e.width * e.height * ((slab_type == VKV_VOXEL_UINT16 || slab_type == VKV_VOXEL_INT16) ? 2 : 1);
+			const uint32_t    n     = std::min(args.stream_slabs, e.depth);
+			std::ifstream     file;
+			if (slab_source.empty())
+			{
+				file.open(args.dataset, std::ios::binary);
+				if (!file.is_open())
+					throw std::runtime_error("Failed to open data file");
+			}
+			std::vector<uint8_t> buf;
+			const auto           t0 = std::chrono::steady_clock::now();
+			for (uint32_t k = 0; k < n; ++k)
+			{
+				const uint32_t z0 = (uint32_t) ((uint64_t) e.depth * k / n), z1 = (uint32_t) ((uint64_t) e.depth * (k + 1) / n);
+				const uint8_t *src = nullptr;
+				if (slab_source.empty())
+				{
+					buf.resize(slice * (z1 - z0));
+					file.seekg((std::streamoff) (slice * z0));
+					file.read(reinterpret_cast<char *>(buf.data()), (std::streamsize) buf.size());
+					if (!file)
+						throw std::runtime_error("File error");
+					src = buf.data();
+				}
+				else
+					src = slab_source.data() + slice * z0;
+				volume.update_region(dc, VkvBox{0, 0, z0, e.width, e.height, z1 - z0}, src, slab_type, slab_header.endianness == "big",
+				                     slab_header.normalisation_range, static_cast<int32_t>(render_options.skipping_type));
+				subpass.draw(target);
+			}
+			(void) hipStreamSynchronize(stream);
+			std::printf("stream-slabs: %u slabs of %ux%u voxels, %g ms per slab with its frame (wall)\n", n, e.width, e.height, ms_since(t0) / n);
+		}
 		if (args.tf_drag > 0)
 		{        // slider moves (src/volume_render.cpp:392-445 per move), each followed by one frame into the same target
 			const bool  device_path = args.tf_path == "device";

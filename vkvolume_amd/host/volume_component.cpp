@@ -47,6 +47,10 @@ void Volume::release()
 		(void) hipFree(packed);
 	if (transfer_function_bits)
 		(void) hipFree(transfer_function_bits);
+	if (region_staging)
+		(void) hipFree(region_staging);
+	region_staging       = nullptr;
+	region_staging_bytes = 0;
 	packed                 = nullptr;
 	packed_bytes           = 0;
 	transfer_function_bits = nullptr;
@@ -175,6 +179,35 @@ void Volume::update_transfer_function(DeviceContext &dc, int32_t skipping_type, 
 	                                       transfer_function.data, transfer_function_bits, maps, distance_map_swap.data, distance_map_swap.extent,
 	                                       skipping_type, d_occupied_count, dc.stream),
 	          "TF update");
+}
+
+void Volume::update_region(DeviceContext &dc, VkvBox box, const void *host_raw, int32_t type, bool big_endian, const float range[2], int32_t skipping_type)
+{
+	const size_t elem  = (type == VKV_VOXEL_UINT16 || type == VKV_VOXEL_INT16) ? 2 : 1;
+	const size_t bytes = (size_t) box.width * box.height * box.depth * elem;
+	if (bytes > region_staging_bytes)
+	{
+		if (region_staging)
+		{
+			hip_check(hipStreamSynchronize((hipStream_t) dc.stream), "region staging");        // an earlier update may still read it
+			(void) hipFree(region_staging);
+		}
+		region_staging       = device_alloc(bytes);
+		region_staging_bytes = bytes;
+	}
+	// pageable source: the copy has taken the bytes when it returns, the kernels behind it on the stream read the device copy
+	hip_check(hipMemcpyAsync(region_staging, host_raw, bytes, hipMemcpyHostToDevice, (hipStream_t) dc.stream), "region upload");
+	uint8_t *maps[8]  = {nullptr};
+	const size_t need = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 8 : 1;
+	const bool   have = distance_maps.size() >= need;
+	for (size_t i = 0; have && i < need; ++i)
+		maps[i] = distance_maps[i].data;
+	const TransferFunctionUniform tf = get_transfer_function_uniform();
+	vkv_check(dc,
+	          vkv_update_volume_region(dc.ctx, region_staging, type, big_endian ? 1 : 0, range[0], range[1], &box, volume.data,
+	                                   options.use_precomputed_gradient ? gradient.data : nullptr, packed, volume.extent, transfer_function.data, &tf,
+	                                   have ? maps : nullptr, distance_map_swap.data, distance_map_swap.extent, skipping_type, dc.stream),
+	          "volume region update");
 }
 
 void Volume::pack(DeviceContext &dc)

@@ -73,6 +73,11 @@ class Volume
 	// occupancy and the transform of skipping_type (a VkvSkippingType) into the distance maps (grown as ComputeDistanceMap::compute grows them);
 	// d_occupied_count != nullptr also receives the occupied-voxel count
 	void update_transfer_function(DeviceContext &dc, int32_t skipping_type, uint64_t *d_occupied_count = nullptr);
+	// New voxels for a box (vkv_update_volume_region): host_raw holds box.width * height * depth raw elements of `type` (a VkvVoxelType, x
+	// fastest; a z-slab of a raw file), converted like the loader converts a file (byte order, normalisation range[0] .. range[1]); the
+	// gradient, the packed image (if built) and the maps of skipping_type (if built) are rebuilt where the box reaches them, on dc.stream.
+	// The raw bytes are staged in a device buffer the volume keeps (grown as needed); host_raw may be reused when the call returns.
+	void update_region(DeviceContext &dc, VkvBox box, const void *host_raw, int32_t type, bool big_endian, const float range[2], int32_t skipping_type);
 
 	// vkb::sg::Node stand-in: the node's world matrix (benchmark mode rescales it, src/volume_render.cpp:224-238)
 	vkv::mat4 node_transform;
@@ -93,5 +98,7 @@ class Volume
 	void *             packed                 = nullptr;
 	size_t             packed_bytes           = 0;
 	uint32_t *         transfer_function_bits = nullptr;
+	void *             region_staging         = nullptr;        // update_region's device copy of the raw box
+	size_t             region_staging_bytes   = 0;
 	vkv::mat4          image_transform;
 };

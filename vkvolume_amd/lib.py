@@ -20,7 +20,7 @@ EXPORTS = [
     "vkv_occupied_voxel_count", "vkv_load_header", "vkv_load_data", "vkv_convert_volume", "vkv_gather_tiles", "vkv_assemble_frame",
     "vkv_assemble_frames", "vkv_get_tuning", "vkv_set_tuning", "vkv_prepare_render", "vkv_register_target", "vkv_forget_target",
     "vkv_release_stream", "vkv_trim", "vkv_release_captured", "vkv_screen_tile_rect",
-    "vkv_transfer_function_texture_device", "vkv_update_transfer_function",
+    "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -92,6 +92,8 @@ def load():
     L.vkv_occupied_voxel_count.argtypes = [vp, vp, vp, P(abi.TransferFunctionUniform), abi.Extent3D, vp, vp]
     L.vkv_transfer_function_texture_device.argtypes = [vp, P(abi.VolumeOptions), vp, vp, vp]
     L.vkv_update_transfer_function.argtypes = [vp, P(abi.VolumeOptions), vp, vp, abi.Extent3D, vp, vp, P(vp), vp, abi.Extent3D, i32, vp, vp]
+    L.vkv_update_volume_region.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, P(abi.Box), vp, vp, vp, abi.Extent3D, vp,
+                                           P(abi.TransferFunctionUniform), P(vp), vp, abi.Extent3D, i32, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -253,6 +255,21 @@ class Context:
         arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
         return self._lib.vkv_update_transfer_function(self.handle, None if options is None else C.byref(options), d_volume, d_gradient, extent, d_tf,
                                                       d_tables, arr, d_swap, map_extent, skipping_type, d_count, stream)
+
+    def update_volume_region(self, d_src, voxel_type, big_endian, range_min, range_max, box, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
+                             d_swap, map_extent, skipping_type, stream=0):
+        """vkv_update_volume_region: convert a box of raw voxels into the volume and rebuild the gradient, packed bricks, occupancy cells it
+        reaches and the distance transform, as one enqueue; d_gradient / d_packed / d_maps None skip that output"""
+        self.check(self.update_volume_region_rc(d_src, voxel_type, big_endian, range_min, range_max, box, d_volume, d_gradient, d_packed, extent, d_tf,
+                                                tf, d_maps, d_swap, map_extent, skipping_type, stream))
+
+    def update_volume_region_rc(self, d_src, voxel_type, big_endian, range_min, range_max, box, d_volume, d_gradient, d_packed, extent, d_tf, tf,
+                                d_maps, d_swap, map_extent, skipping_type, stream=0):
+        """Like update_volume_region() but returns the status code (error-path tests); box / tf / d_maps None pass NULL."""
+        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
+        return self._lib.vkv_update_volume_region(self.handle, d_src, int(voxel_type), 1 if big_endian else 0, range_min, range_max,
+                                                  None if box is None else C.byref(box), d_volume, d_gradient, d_packed, extent, d_tf,
+                                                  None if tf is None else C.byref(tf), arr, d_swap, map_extent, skipping_type, stream)
 
     def debug_tf_scratch(self, d_out, stream=0):
         """vkv_debug_tf_scratch: the bit table + column mask (2056 words) in `stream`'s scratch block, copied to d_out"""

@@ -107,10 +107,48 @@ class Volume:
                                           _ptr(self.transfer_function_bits), [_ptr(m) for m in self.distance_maps], _ptr(self.distance_map_swap),
                                           self.map_extent, skipping_type, _ptr(d_count), _stream())
 
+    _DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1, np.dtype(np.uint16): 2, np.dtype(np.int16): 3}  # VkvVoxelType
+    _TORCH_DTYPES = {torch.uint8: 0, torch.int8: 1, torch.int16: 3}
+
+    def update_region(self, origin_xyz, voxels_dhw, skipping_type, voxel_type=None, big_endian=False, normalisation_range=None):
+        """Write new voxels into the box at ``origin_xyz`` and rebuild what they reach, as one enqueue on the current stream
+        (vkv_update_volume_region): the gradient map, the packed image (if built), and the occupancy + distance maps of ``skipping_type``
+        (if built; it names what the maps hold, as in ComputeDistanceMap.compute).  ``voxels_dhw``: a (depth, height, width) numpy array
+        (staged through pinned memory) or CUDA tensor of raw elements of ``voxel_type`` (default: from the dtype; a uint16 file's raw bytes
+        come as int16 / uint16 with voxel_type = VKV_VOXEL_UINT16), converted like the loader converts a file: byte order, then
+        ``normalisation_range`` (default (0, 255): uint8 voxels are stored as they are).  Precondition: the derived buffers are up to date
+        (ComputeGradientMap / pack / ComputeDistanceMap with the current options and transfer function texture)."""
+        if torch.is_tensor(voxels_dhw):
+            src = voxels_dhw.to(self.device).contiguous()
+            vt = self._TORCH_DTYPES.get(src.dtype) if voxel_type is None else voxel_type
+        else:
+            arr = np.ascontiguousarray(voxels_dhw)
+            vt = self._DTYPES.get(arr.dtype) if voxel_type is None else voxel_type
+            pinned = torch.from_numpy(arr.view(np.uint8).reshape(-1)).pin_memory()
+            src = torch.empty(pinned.numel(), dtype=torch.uint8, device=self.device)
+            src.copy_(pinned, non_blocking=True)  # (the pinned block is not reused before the copy has run: torch's host allocator)
+        if vt is None:
+            raise ValueError("Volume.update_region: no voxel type for dtype %s (pass voxel_type)" % (voxels_dhw.dtype,))
+        d, h, w = voxels_dhw.shape
+        lo, hi = (0.0, 255.0) if normalisation_range is None else normalisation_range
+        maps = None
+        if self.distance_maps:
+            n = 8 if skipping_type == abi.SKIP_ANISOTROPIC_DISTANCE else 1
+            if len(self.distance_maps) < n:
+                raise RuntimeError("Volume.update_region: the maps of skipping type %d have not been built" % skipping_type)
+            maps = [_ptr(m) for m in self.distance_maps[:n]]
+        grad = self.gradient if self.options.use_precomputed_gradient else None
+        x, y, z = origin_xyz
+        self.ctx.update_volume_region(_ptr(src), vt, big_endian, float(lo), float(hi), abi.Box(x, y, z, w, h, d), _ptr(self.volume), _ptr(grad),
+                                      _ptr(self.packed), self.extent, _ptr(self.transfer_function), self.get_transfer_function_uniform(), maps,
+                                      _ptr(self.distance_map_swap), self.map_extent, skipping_type, _stream())
+        src.record_stream(torch.cuda.current_stream())  # the source stays allocated until the update has read it
+
     def pack(self):
         """(Re)build the bricked sampling image from the linear volume (+ gradient map).  Call after the gradient map
         is computed — the counterpart of the driver's swizzle into an optimally tiled VkImage.  The packed image is a COPY:
-        call pack() again after writing to ``volume`` / ``gradient`` in place (load_* and ComputeGradientMap do it themselves)."""
+        after writing new voxels, use update_region(), which rebuilds only the bricks (and gradient and map cells) the box reaches;
+        after writing to ``volume`` / ``gradient`` in place by other means, call pack() again (load_* and ComputeGradientMap do it themselves)."""
         if self.options.use_precomputed_gradient and not self.gradient_valid:
             raise RuntimeError("Volume.pack: use_precomputed_gradient is set but no gradient map has been computed "
                                "(run ComputeGradientMap.compute first)")
