@@ -398,6 +398,35 @@ int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int3
                              const VkvTransferFunctionUniform *tf, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent,
                              int32_t skipping_type, void *stream);
 
+/* Joint histogram of (gradient byte, intensity byte): 65536 uint64 bins, bin g * 256 + i = the voxels with gradient byte g and intensity
+ * byte i (row = gradient, as in the transfer-function texture).  One bin of a 2048^3 volume can exceed 2^32. */
+#define VKV_HISTOGRAM_BINS 65536
+
+enum VkvHistogramMode
+{
+	VKV_HISTOGRAM_SET      = 0, /* overwrite every bin with the box's counts          */
+	VKV_HISTOGRAM_ADD      = 1, /* add the box's counts to the bins                   */
+	VKV_HISTOGRAM_SUBTRACT = 2, /* subtract them, modulo 2^64 (ADD undoes it exactly) */
+};
+
+/* The histogram of the voxels of `box` (NULL: the whole volume) into d_histogram (VKV_HISTOGRAM_BINS uint64, 8-byte aligned), as `mode`
+ * says.  d_gradient == NULL counts every voxel in gradient row 0: the intensity histogram of a volume without a precomputed gradient.
+ * Every argument is checked before anything is enqueued: a null volume or histogram, a zero extent, an empty box or one not inside
+ * `extent`, an unknown mode or a misaligned d_histogram return VKV_E_INVALID_ARGUMENT and write nothing.  The call only enqueues kernels
+ * (SET clears the bins with a kernel, not a memset node), allocates nothing and does not wait, so after one direct call on `stream` it
+ * can be captured into a hipGraph.
+ * Keeping a histogram current across vkv_update_volume_region: before the update, SUBTRACT over the update's box grown by one voxel per
+ * side and clamped to the volume (the gradient changes there); after it, ADD over the same grown box, on the same stream. */
+int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, const VkvBox *box, int32_t mode,
+                         uint64_t *d_histogram, void *stream);
+
+/* The sum of the bins of d_histogram whose ANALYTIC transfer-function alpha is > 0 (vkv_occupied_voxel_count's rule: bit row g when
+ * tf->use_gradient is set, else 255), STORED to *d_count (8-byte aligned).  Equals vkv_occupied_voxel_count of the same volume and tf when
+ * the histogram was built with the gradient map, or when tf->use_gradient is 0.  Limit: with use_gradient set and no gradient map,
+ * vkv_occupied_voxel_count evaluates an on-the-fly float gradient, which the histogram does not hold.  One small launch; kernels only. */
+int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, const VkvTransferFunctionUniform *tf, uint64_t *d_count,
+                                 void *stream);
+
 /* VolumeRenderSubpass::prepare, src/volume_render_subpass.cpp:95-157 (where the reference builds its pipelines and descriptor layouts).
  * Set-up call: creates, for `count` parameter blocks as a later vkv_render / vkv_render_batch on `stream` will pass them, everything that
  * launch takes from the context: the stream's scratch block, the address tables of the packed image's extent, the tile start order of the

@@ -16,6 +16,8 @@ MAX_BATCH = 32  # VKV_MAX_BATCH
 SKIP_NONE, SKIP_BLOCK, SKIP_DISTANCE, SKIP_ANISOTROPIC_DISTANCE = 0, 1, 2, 3
 VOXEL_TYPES = {"uint8_t": 0, "int8_t": 1, "uint16_t": 2, "int16_t": 3}  # VkvVoxelType by LoadVolume::Header::type
 TEST_NONE, TEST_RAY_ENTRY, TEST_RAY_EXIT, TEST_NUM_TEXTURE_SAMPLES = 0, 1, 2, 3
+HISTOGRAM_BINS = 65536  # VKV_HISTOGRAM_BINS: bin g * 256 + i = voxels with gradient byte g and intensity byte i
+HISTOGRAM_SET, HISTOGRAM_ADD, HISTOGRAM_SUBTRACT = 0, 1, 2  # VkvHistogramMode
 
 
 class Extent3D(C.Structure):

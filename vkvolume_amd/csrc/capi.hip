@@ -42,6 +42,8 @@ int launch_convert_volume(vkv_ctx *, const void *, int, bool, float, float, uint
 int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t);
 int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float, const VkvBox &, uint8_t *, uint8_t *, void *, VkvExtent3D, const uint8_t *,
                                 const VkvTransferFunctionUniform *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
+int launch_volume_histogram(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, const VkvBox &, int, uint64_t *, hipStream_t);
+int launch_histogram_occupied_count(vkv_ctx *, const uint64_t *, const VkvTransferFunctionUniform *, uint64_t *, hipStream_t);
 
 int set_error(vkv_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -1094,6 +1096,40 @@ int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int3
 	}
 	return launch_update_volume_region(ctx, d_src, type, big_endian != 0, range_min, range_max, b, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
 	                                   d_swap, map_extent, skipping_type, (hipStream_t) stream);
+}
+
+// every argument is checked before the first launch
+int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, const VkvBox *box, int32_t mode,
+                         uint64_t *d_histogram, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_volume || !d_histogram || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: null pointer or zero extent");
+	const VkvBox b = box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth};
+	if (b.width == 0 || b.height == 0 || b.depth == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: empty box");
+	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
+		                 b.height, b.depth);
+	if (mode < VKV_HISTOGRAM_SET || mode > VKV_HISTOGRAM_SUBTRACT)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: bad mode %d", (int) mode);
+	if (((uintptr_t) d_histogram & 7u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: d_histogram must be 8-byte aligned");
+	return launch_volume_histogram(ctx, d_volume, d_gradient, extent, b, mode, d_histogram, (hipStream_t) stream);
+}
+
+int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, const VkvTransferFunctionUniform *tf, uint64_t *d_count, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_histogram || !tf || !d_count)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "histogram_occupied_count: null pointer");
+	if ((((uintptr_t) d_histogram) | ((uintptr_t) d_count)) & 7u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "histogram_occupied_count: d_histogram and d_count must be 8-byte aligned");
+	return launch_histogram_occupied_count(ctx, d_histogram, tf, d_count, (hipStream_t) stream);
 }
 
 // argument checks shared by vkv_render and vkv_render_batch

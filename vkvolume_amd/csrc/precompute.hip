@@ -103,21 +103,6 @@ __global__ void __launch_bounds__(256) k_check_numerics(int what, uint32_t first
 		atomicAdd(mismatches, 1ull);
 }
 
-// Four bytes of a voxel row as ONE dword, whatever the row's alignment (round 6: the tiled kernels no longer need W % 4 == 0).  Rows of a volume
-// whose width is no multiple of 4 start at every byte alignment; global loads need none on gfx950 (the integrator's own footprint gathers are
-// 2-byte aligned), the type only tells the compiler not to assume one.
-typedef uint32_t u32_any_align __attribute__((aligned(1)));
-__device__ __forceinline__ uint32_t load_u32_any(const uint8_t *p) { return *reinterpret_cast<const u32_any_align *>(p); }
-// Dword column dc (voxels 4 dc .. 4 dc + 3) of a row of W >= 4 voxels, dc < ceil(W / 4): the last, partial column of an odd width is read as the
-// row's LAST four bytes and shifted down - nothing past the row is touched, the bytes of x >= W come back zero.
-__device__ __forceinline__ uint32_t row_dword(const uint8_t *row, int dc, int W)
-{
-	const int x = 4 * dc;
-	if (x + 4 <= W)
-		return load_u32_any(row + x);
-	return load_u32_any(row + (W - 4)) >> (8 * (x + 4 - W));
-}
-
 constexpr int kGradTileX = 64, kGradTileY = 8, kGradTileZ = 8, kGradPitch = 72;        // pitch = 64 + 4 texels of halo on each side
 constexpr int kGradSegment = 10;                                                       // tiles one workgroup marches over
 
@@ -649,14 +634,6 @@ __global__ void __launch_bounds__(256) k_occupancy_map_dword(const uint8_t *__re
 // ---------------------------------------------------------------------------------------------
 // Occupied-voxel count (shaders/occupied_voxel_count.comp + occupied_voxel_count_reduce.comp)
 // ---------------------------------------------------------------------------------------------
-// analytic get_color (transfer_function.glsl:41-43) > 0
-__device__ __forceinline__ bool analytic_occupied(float intensity, float gradient, float imin, float iinv, float gmin, float ginv)
-{
-	const float ai = g_clamp((intensity - imin) * iinv, 0.0f, 1.0f);
-	const float ag = g_clamp((gradient - gmin) * ginv, 0.0f, 1.0f);
-	return ai * ag > 0.0f;
-}
-
 // The statistic's alpha is again a pure function of the (gradient byte, intensity byte) pair when the gradient comes
 // from the R8_UNORM map: reduce the analytic TF to the same 8 KiB bit table the occupancy pass uses.
 __global__ void __launch_bounds__(256) k_tf_bits_analytic(uint32_t *__restrict__ bits, float imin, float iinv, float gmin, float ginv)

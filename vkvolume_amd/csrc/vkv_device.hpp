@@ -97,6 +97,29 @@ __device__ __forceinline__ float recip_exact(float d)
 // R8_UNORM store: round to nearest even.
 __device__ __forceinline__ uint8_t store_unorm8(float g) { return (uint8_t) __builtin_rintf(g * 255.0f); }
 
+// Four bytes of a voxel row as ONE dword, whatever the row's alignment (round 6: the tiled kernels no longer need W % 4 == 0).  Rows of a volume
+// whose width is no multiple of 4 start at every byte alignment; global loads need none on gfx950 (the integrator's own footprint gathers are
+// 2-byte aligned), the type only tells the compiler not to assume one.
+typedef uint32_t u32_any_align __attribute__((aligned(1)));
+__device__ __forceinline__ uint32_t load_u32_any(const uint8_t *p) { return *reinterpret_cast<const u32_any_align *>(p); }
+// Dword column dc (voxels 4 dc .. 4 dc + 3) of a row of W >= 4 voxels, dc < ceil(W / 4): the last, partial column of an odd width is read as the
+// row's LAST four bytes and shifted down - nothing past the row is touched, the bytes of x >= W come back zero.
+__device__ __forceinline__ uint32_t row_dword(const uint8_t *row, int dc, int W)
+{
+	const int x = 4 * dc;
+	if (x + 4 <= W)
+		return load_u32_any(row + x);
+	return load_u32_any(row + (W - 4)) >> (8 * (x + 4 - W));
+}
+
+// analytic get_color (transfer_function.glsl:41-43) > 0
+__device__ __forceinline__ bool analytic_occupied(float intensity, float gradient, float imin, float iinv, float gmin, float ginv)
+{
+	const float ai = g_clamp((intensity - imin) * iinv, 0.0f, 1.0f);
+	const float ag = g_clamp((gradient - gmin) * ginv, 0.0f, 1.0f);
+	return ai * ag > 0.0f;
+}
+
 // XCD-aware block remap: hardware deals consecutive block ids round-robin over the 8 XCDs, so give each XCD a
 // contiguous range of logical ids (neighbouring screen tiles / slabs then share one L2).
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nb)

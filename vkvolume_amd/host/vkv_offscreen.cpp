@@ -20,6 +20,9 @@
 //                 [--stream-slabs=N]   progressive loading: the volume starts all zero (its maps built as for any volume), then arrives in N
 //                                  z-slabs - read from the raw file, or cut from the synthetic volume generated into a staging buffer - each
 //                                  written with Volume::update_region and followed by one frame; --dump-rgba8 writes the last frame
+//                 [--histogram=file]   after the gradient map: the joint (gradient byte, intensity byte) histogram of the volume (Volume::histogram),
+//                                  written as 65536 little-endian uint64 bins (bin g * 256 + i), and the line "Occupied voxels (histogram): X%"
+//                                  (vkv_histogram_occupied_count of the options' transfer function; in benchmark mode next to "Occupied voxels")
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -63,6 +66,7 @@ struct Args
 	int         tf_drag = 0;              // --tf-drag=N: slider moves
 	std::string tf_path = "device";        // --tf-path=host|device
 	uint32_t    stream_slabs = 0;          // --stream-slabs=N: z-slabs of a progressive load
+	std::string histogram;                 // --histogram=file: the volume's joint histogram
 };
 
 bool flag(const char *arg, const char *name, std::string &value)
@@ -126,6 +130,7 @@ Args parse(int argc, char **argv)
 			a.tf_path = v;
 		}
 		else if (flag(s, "--stream-slabs", v)) a.stream_slabs = (uint32_t) std::stoul(v);
+		else if (flag(s, "--histogram", v)) a.histogram = v;
 		else if (s[0] != '-') a.dataset = s;
 		else throw std::runtime_error(std::string("unknown flag ") + s);
 	}
@@ -260,6 +265,32 @@ int main(int argc, char **argv)
 			std::printf("Updated gradient map in %gms\n", ms_since(t0));
 		}
 
+		// --histogram: the joint histogram of the loaded volume and its occupied-voxel count (printed below, next to the existing one)
+		std::string histogram_line;
+		if (!args.histogram.empty())
+		{
+			uint64_t *d_hist = device_alloc<uint64_t>(VKV_HISTOGRAM_BINS + 1), *d_count = d_hist + VKV_HISTOGRAM_BINS;
+			volume.histogram(dc, d_hist);
+			const auto tf = volume.get_transfer_function_uniform();
+			if (vkv_histogram_occupied_count(ctx, d_hist, &tf, d_count, stream) != VKV_OK)
+				throw std::runtime_error(std::string("histogram count: ") + vkv_last_error(ctx));
+			std::vector<uint64_t> bins(VKV_HISTOGRAM_BINS + 1);
+			const bool ok = hipMemcpyAsync(bins.data(), d_hist, bins.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+			                hipStreamSynchronize(stream) == hipSuccess;
+			(void) hipFree(d_hist);
+			if (!ok)
+				throw std::runtime_error("histogram download failed");
+			std::ofstream f(args.histogram, std::ios::binary);        // the bins as they are in memory: little-endian on the host
+			f.write(reinterpret_cast<const char *>(bins.data()), VKV_HISTOGRAM_BINS * sizeof(uint64_t));
+			if (!f)
+				throw std::runtime_error("cannot write " + args.histogram);
+			const auto & e        = volume.get_volume().extent;
+			const size_t n_voxels = (size_t) e.width * e.height * e.depth;
+			char         line[128];
+			std::snprintf(line, sizeof(line), "Occupied voxels (histogram): %g%%\n", 100.0f * (float) bins[VKV_HISTOGRAM_BINS] / (float) n_voxels);
+			histogram_line = line;
+		}
+
 		// update_transfer_function (src/volume_render.cpp:392-445)
 		{
 			const auto tf = volume.get_transfer_function_uniform();
@@ -273,6 +304,8 @@ int main(int argc, char **argv)
 				const auto &   e          = volume.get_volume().extent;
 				const size_t   n_voxels   = (size_t) e.width * e.height * e.depth;
 				std::printf("Occupied voxels: %g%% in %gms\n", 100.0f * (float) n_occupied / (float) n_voxels, ms_since(t0));
+				std::fputs(histogram_line.c_str(), stdout);
+				histogram_line.clear();
 				compute_distance_map.compute(volume, tf, render_options.skipping_type);        // untimed first run (see above)
 				(void) hipStreamSynchronize(stream);
 				const int  runs = 5;
@@ -290,6 +323,8 @@ int main(int argc, char **argv)
 				compute_distance_map.compute(volume, tf, render_options.skipping_type);
 			}
 		}
+
+		std::fputs(histogram_line.c_str(), stdout);        // (not benchmark mode)
 
 		// node scale: longest physical edge -> 100 units (src/volume_render.cpp:224-238)
 		{

@@ -210,6 +210,14 @@ void Volume::update_region(DeviceContext &dc, VkvBox box, const void *host_raw, 
 	          "volume region update");
 }
 
+void Volume::histogram(DeviceContext &dc, uint64_t *d_histogram, const VkvBox *box, int32_t mode)
+{
+	vkv_check(dc,
+	          vkv_volume_histogram(dc.ctx, volume.data, options.use_precomputed_gradient ? gradient.data : nullptr, volume.extent, box, mode, d_histogram,
+	                               dc.stream),
+	          "volume histogram");
+}
+
 void Volume::pack(DeviceContext &dc)
 {
 	const size_t need = vkv_packed_volume_bytes(volume.extent);

@@ -78,6 +78,10 @@ class Volume
 	// gradient, the packed image (if built) and the maps of skipping_type (if built) are rebuilt where the box reaches them, on dc.stream.
 	// The raw bytes are staged in a device buffer the volume keeps (grown as needed); host_raw may be reused when the call returns.
 	void update_region(DeviceContext &dc, VkvBox box, const void *host_raw, int32_t type, bool big_endian, const float range[2], int32_t skipping_type);
+	// Joint (gradient byte, intensity byte) histogram of `box` (nullptr: the whole volume) into the VKV_HISTOGRAM_BINS uint64 bins at
+	// d_histogram, set / added / subtracted as `mode` (a VkvHistogramMode) says (vkv_volume_histogram), on dc.stream; the gradient map is used
+	// when options.use_precomputed_gradient is set, else every voxel counts in gradient row 0
+	void histogram(DeviceContext &dc, uint64_t *d_histogram, const VkvBox *box = nullptr, int32_t mode = VKV_HISTOGRAM_SET);
 
 	// vkb::sg::Node stand-in: the node's world matrix (benchmark mode rescales it, src/volume_render.cpp:224-238)
 	vkv::mat4 node_transform;

@@ -21,6 +21,7 @@ EXPORTS = [
     "vkv_assemble_frames", "vkv_get_tuning", "vkv_set_tuning", "vkv_prepare_render", "vkv_register_target", "vkv_forget_target",
     "vkv_release_stream", "vkv_trim", "vkv_release_captured", "vkv_screen_tile_rect",
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
+    "vkv_volume_histogram", "vkv_histogram_occupied_count",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -94,6 +95,8 @@ def load():
     L.vkv_update_transfer_function.argtypes = [vp, P(abi.VolumeOptions), vp, vp, abi.Extent3D, vp, vp, P(vp), vp, abi.Extent3D, i32, vp, vp]
     L.vkv_update_volume_region.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, P(abi.Box), vp, vp, vp, abi.Extent3D, vp,
                                            P(abi.TransferFunctionUniform), P(vp), vp, abi.Extent3D, i32, vp]
+    L.vkv_volume_histogram.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), i32, vp, vp]
+    L.vkv_histogram_occupied_count.argtypes = [vp, vp, P(abi.TransferFunctionUniform), vp, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -270,6 +273,23 @@ class Context:
         return self._lib.vkv_update_volume_region(self.handle, d_src, int(voxel_type), 1 if big_endian else 0, range_min, range_max,
                                                   None if box is None else C.byref(box), d_volume, d_gradient, d_packed, extent, d_tf,
                                                   None if tf is None else C.byref(tf), arr, d_swap, map_extent, skipping_type, stream)
+
+    def volume_histogram(self, d_volume, d_gradient, extent, box, mode, d_histogram, stream=0):
+        """vkv_volume_histogram: the (gradient byte, intensity byte) histogram of `box` (None: the whole volume) into the 65536 uint64 bins
+        at d_histogram, set, added or subtracted as `mode` says; d_gradient None counts every voxel in gradient row 0"""
+        self.check(self.volume_histogram_rc(d_volume, d_gradient, extent, box, mode, d_histogram, stream))
+
+    def volume_histogram_rc(self, d_volume, d_gradient, extent, box, mode, d_histogram, stream=0):
+        """Like volume_histogram() but returns the status code (error-path tests)."""
+        return self._lib.vkv_volume_histogram(self.handle, d_volume, d_gradient, extent, None if box is None else C.byref(box), int(mode),
+                                              d_histogram, stream)
+
+    def histogram_occupied_count(self, d_histogram, tf, d_count, stream=0):
+        """vkv_histogram_occupied_count: the bins whose analytic transfer-function alpha is > 0, summed into *d_count (stored, not added)"""
+        self.check(self.histogram_occupied_count_rc(d_histogram, tf, d_count, stream))
+
+    def histogram_occupied_count_rc(self, d_histogram, tf, d_count, stream=0):
+        return self._lib.vkv_histogram_occupied_count(self.handle, d_histogram, None if tf is None else C.byref(tf), d_count, stream)
 
     def debug_tf_scratch(self, d_out, stream=0):
         """vkv_debug_tf_scratch: the bit table + column mask (2056 words) in `stream`'s scratch block, copied to d_out"""

@@ -144,6 +144,40 @@ class Volume:
                                       _ptr(self.distance_map_swap), self.map_extent, skipping_type, _stream())
         src.record_stream(torch.cuda.current_stream())  # the source stays allocated until the update has read it
 
+    _HISTOGRAM_MODES = (abi.HISTOGRAM_SET, abi.HISTOGRAM_ADD, abi.HISTOGRAM_SUBTRACT)
+
+    def histogram(self, out=None, box=None, mode=abi.HISTOGRAM_SET):
+        """Joint histogram of (gradient byte, intensity byte) on the current stream (vkv_volume_histogram): a (256, 256) int64 CUDA tensor
+        of the uint64 bins, row = gradient byte, column = intensity byte (as the transfer-function texture).  Uses the gradient map when
+        use_precomputed_gradient is set, else counts every voxel in row 0.  ``out``: a contiguous (256, 256) int64 tensor on this volume's
+        device to write into (required for ADD / SUBTRACT); ``box``: an abi.Box, or ((x0, y0, z0), (width, height, depth)); None: the
+        whole volume.  SUBTRACT wraps modulo 2^64, so a histogram kept with SUBTRACT / ADD across update_region() stays exact."""
+        if mode not in self._HISTOGRAM_MODES:
+            raise ValueError("Volume.histogram: unknown mode %r" % (mode,))
+        if out is None:
+            if mode != abi.HISTOGRAM_SET:
+                raise ValueError("Volume.histogram: ADD and SUBTRACT need `out`")
+            out = torch.empty((256, 256), dtype=torch.int64, device=self.device)
+        elif out.dtype != torch.int64 or tuple(out.shape) != (256, 256) or not out.is_contiguous() or out.device != self.volume.device:
+            raise ValueError("Volume.histogram: `out` must be a contiguous (256, 256) int64 tensor on %s" % (self.volume.device,))
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        grad = self.gradient if self.options.use_precomputed_gradient else None
+        self.ctx.volume_histogram(_ptr(self.volume), _ptr(grad), self.extent, box, mode, _ptr(out), _stream())
+        return out
+
+    def occupied_count_from_histogram(self, hist, d_count):
+        """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
+        ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
+        with the gradient map or use_gradient is 0."""
+        if hist.dtype != torch.int64 or hist.numel() != abi.HISTOGRAM_BINS or not hist.is_contiguous():
+            raise ValueError("Volume.occupied_count_from_histogram: `hist` must be a contiguous int64 tensor of %d bins" % abi.HISTOGRAM_BINS)
+        if d_count.dtype != torch.int64 or d_count.numel() < 1:
+            raise ValueError("Volume.occupied_count_from_histogram: `d_count` must be an int64 tensor")
+        self.ctx.histogram_occupied_count(_ptr(hist), self.get_transfer_function_uniform(), _ptr(d_count), _stream())
+        return d_count
+
     def pack(self):
         """(Re)build the bricked sampling image from the linear volume (+ gradient map).  Call after the gradient map
         is computed — the counterpart of the driver's swizzle into an optimally tiled VkImage.  The packed image is a COPY:
