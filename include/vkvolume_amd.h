@@ -416,7 +416,8 @@ enum VkvHistogramMode
  * (SET clears the bins with a kernel, not a memset node), allocates nothing and does not wait, so after one direct call on `stream` it
  * can be captured into a hipGraph.
  * Keeping a histogram current across vkv_update_volume_region: before the update, SUBTRACT over the update's box grown by one voxel per
- * side and clamped to the volume (the gradient changes there); after it, ADD over the same grown box, on the same stream. */
+ * side and clamped to the volume (the gradient changes there); after it, ADD over the same grown box, on the same stream.  A cell summary
+ * (vkv_cell_summary below) is kept current the same way: rebuild it over that grown box after the update. */
 int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, const VkvBox *box, int32_t mode,
                          uint64_t *d_histogram, void *stream);
 
@@ -426,6 +427,49 @@ int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d
  * vkv_occupied_voxel_count evaluates an on-the-fly float gradient, which the histogram does not hold.  One small launch; kernels only. */
 int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, const VkvTransferFunctionUniform *tf, uint64_t *d_count,
                                  void *stream);
+
+/* Per-cell summaries: a transfer-function change decides most occupancy cells without reading a voxel (DESIGN.md §5 "Cell summaries").
+ * Each cell of the occupancy map (block = ceil(extent / map_extent) per axis, voxels clipped to the volume) has 16 bytes, in map order (x fastest):
+ *   bytes 0, 1   i_lo, i_hi: min / max intensity byte of the cell's voxels
+ *   bytes 2, 3   g_lo, g_hi: min / max gradient byte (a summary built without a gradient map records 255 for every voxel)
+ *   byte 4       g_at_i_hi: the largest gradient byte among the voxels whose intensity is i_hi
+ *   byte 5       i_at_g_hi: the largest intensity byte among the voxels whose gradient is g_hi
+ *   byte 6       flags: bit 0 = the cell holds at least one voxel (cells past the volume are all zero)
+ *   byte 7       0
+ *   bytes 8..15  mask (uint64, little-endian): bit (g >> 5) * 8 + (i >> 5) is set if some voxel has gradient byte g and intensity byte i.
+ * Every field is a min, a max or an OR: a rebuild is byte-comparable. */
+#define VKV_CELL_SUMMARY_BYTES 16
+
+/* The summaries of every cell (box == NULL), or of every cell that meets `box`, into d_summary (16-byte aligned, map_extent cells x
+ * VKV_CELL_SUMMARY_BYTES); a cell is rebuilt whole, from all of its voxels.  d_gradient == NULL records gradient byte 255 for every voxel.
+ * Every argument is checked before anything is enqueued: a rejected call writes nothing.  Kernels only: no memset, no allocation, no
+ * host wait, so after one direct call on `stream` it can be captured into a hipGraph.
+ * Keeping a summary current across vkv_update_volume_region: after the update, call vkv_cell_summary over the update's box grown by one voxel
+ * per side and clamped to the volume (the gradient changes there), on the same stream. */
+int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
+                     void *d_summary, void *stream);
+
+/* The occupancy map of vkv_occupancy_map with the same arguments, byte for byte, decided per cell from d_summary where the rule is certain
+ * and from the cell's voxels where it is not.  d_unresolved (optional, 8-byte aligned) receives the number of cells evaluated from their
+ * voxels, stored rather than accumulated.
+ * PRECONDITION: d_summary was built by vkv_cell_summary from the current d_volume and d_gradient, with the same extent and map_extent and the
+ * same NULL-ness of d_gradient.  A summary built with a gradient map serves both tf->use_gradient values.  tf->use_gradient with
+ * d_gradient == NULL (the on-the-fly float gradient, which no summary byte can hold) returns VKV_E_UNSUPPORTED.
+ * The call stages the bit table and a 64 KiB table of row-range ORs / ANDs in the stream's scratch block; checks, capture and "writes
+ * nothing when rejected" as vkv_cell_summary. */
+int vkv_occupancy_map_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_volume, const uint8_t *d_gradient,
+                                   const uint8_t *d_transfer_function, const VkvTransferFunctionUniform *tf, VkvExtent3D extent, uint8_t *d_map,
+                                   VkvExtent3D map_extent, uint64_t *d_unresolved, void *stream);
+
+/* vkv_update_transfer_function with the occupancy map from d_summary (as vkv_occupancy_map_from_summary, same precondition and limits) and,
+ * when d_occupied_count is given, the count from d_histogram (vkv_histogram_occupied_count; d_histogram is then required, and must have been
+ * built with the gradient map whenever d_gradient is given): a counted slider move reads no voxel of a resolved cell.  Texture, tables, maps and
+ * count equal those of vkv_update_transfer_function byte for byte.  d_unresolved as in vkv_occupancy_map_from_summary.  Every argument is
+ * checked before anything is enqueued; kernels only, so after one direct call on `stream` it can be captured into a hipGraph. */
+int vkv_update_transfer_function_from_summary(vkv_ctx *ctx, const VkvVolumeOptions *options, const uint8_t *d_volume, const uint8_t *d_gradient,
+                                              VkvExtent3D extent, uint8_t *d_transfer_function, uint32_t *d_tables, uint8_t *const d_maps[8],
+                                              uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type, uint64_t *d_occupied_count,
+                                              const void *d_summary, const uint64_t *d_histogram, uint64_t *d_unresolved, void *stream);
 
 /* VolumeRenderSubpass::prepare, src/volume_render_subpass.cpp:95-157 (where the reference builds its pipelines and descriptor layouts).
  * Set-up call: creates, for `count` parameter blocks as a later vkv_render / vkv_render_batch on `stream` will pass them, everything that

@@ -18,6 +18,7 @@ VOXEL_TYPES = {"uint8_t": 0, "int8_t": 1, "uint16_t": 2, "int16_t": 3}  # VkvVox
 TEST_NONE, TEST_RAY_ENTRY, TEST_RAY_EXIT, TEST_NUM_TEXTURE_SAMPLES = 0, 1, 2, 3
 HISTOGRAM_BINS = 65536  # VKV_HISTOGRAM_BINS: bin g * 256 + i = voxels with gradient byte g and intensity byte i
 HISTOGRAM_SET, HISTOGRAM_ADD, HISTOGRAM_SUBTRACT = 0, 1, 2  # VkvHistogramMode
+CELL_SUMMARY_BYTES = 16  # VKV_CELL_SUMMARY_BYTES: one occupancy cell's summary (vkv_cell_summary)
 
 
 class Extent3D(C.Structure):

@@ -44,6 +44,11 @@ int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float
                                 const VkvTransferFunctionUniform *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
 int launch_volume_histogram(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, const VkvBox &, int, uint64_t *, hipStream_t);
 int launch_histogram_occupied_count(vkv_ctx *, const uint64_t *, const VkvTransferFunctionUniform *, uint64_t *, hipStream_t);
+int launch_tf_bits(vkv_ctx *, const uint8_t *, uint32_t *, hipStream_t);
+bool cells_launch_ok(VkvExtent3D, VkvExtent3D);
+int launch_cell_summary(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, VkvExtent3D, const VkvBox *, void *, hipStream_t);
+int launch_occupancy_from_summary(vkv_ctx *, const void *, const uint8_t *, const uint8_t *, bool, const uint32_t *, VkvExtent3D, uint8_t *, VkvExtent3D,
+                                  uint64_t *, hipStream_t);
 
 int set_error(vkv_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -1130,6 +1135,124 @@ int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, cons
 	if ((((uintptr_t) d_histogram) | ((uintptr_t) d_count)) & 7u)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "histogram_occupied_count: d_histogram and d_count must be 8-byte aligned");
 	return launch_histogram_occupied_count(ctx, d_histogram, tf, d_count, (hipStream_t) stream);
+}
+
+// every argument is checked before the first launch
+int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
+                     void *d_summary, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_volume || !d_summary || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: null pointer or bad extent");
+	if (((uintptr_t) d_summary & 15u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: d_summary must be 16-byte aligned");
+	if (box)
+	{
+		const VkvBox b = *box;
+		if (b.width == 0 || b.height == 0 || b.depth == 0)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: empty box");
+		if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
+			                 b.height, b.depth);
+	}
+	if (!cells_launch_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "cell_summary: map too large for one launch");
+	return launch_cell_summary(ctx, d_volume, d_gradient, extent, map_extent, box, d_summary, (hipStream_t) stream);
+}
+
+// the checks the two summary-based map calls share (after their own null checks)
+static int check_from_summary(vkv_ctx *ctx, const char *what, const void *d_summary, const uint8_t *d_gradient, int32_t use_gradient, VkvExtent3D extent,
+                              VkvExtent3D map_extent, const uint64_t *d_unresolved)
+{
+	if ((((uintptr_t) d_summary) & 15u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_summary must be 16-byte aligned", what);
+	if ((((uintptr_t) d_unresolved) & 7u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_unresolved must be 8-byte aligned", what);
+	if (use_gradient && !d_gradient)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: the summary holds no on-the-fly gradient (use_gradient needs d_gradient)", what);
+	if (!cells_launch_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: map too large for one launch", what);
+	return VKV_OK;
+}
+
+int vkv_occupancy_map_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_volume, const uint8_t *d_gradient, const uint8_t *d_tf,
+                                   const VkvTransferFunctionUniform *tf, VkvExtent3D extent, uint8_t *d_map, VkvExtent3D map_extent, uint64_t *d_unresolved,
+                                   void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_summary || !d_volume || !d_tf || !tf || !d_map || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "occupancy_map_from_summary: null pointer or bad extent");
+	int rc = check_from_summary(ctx, "occupancy_map_from_summary", d_summary, d_gradient, tf->use_gradient, extent, map_extent, d_unresolved);
+	if (rc != VKV_OK)
+		return rc;
+	const hipStream_t s       = (hipStream_t) stream;
+	uint8_t *         scratch = stream_scratch(ctx, s);
+	if (!scratch)
+		return VKV_E_UNSUPPORTED;
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
+	if ((rc = launch_tf_bits(ctx, d_tf, d_bits, s)) != VKV_OK)
+		return rc;
+	return launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf->use_gradient != 0, d_bits, extent, d_map, map_extent, d_unresolved, s);
+}
+
+// vkv_update_transfer_function with the occupancy map from the summary and the count from the histogram: every argument is checked first
+int vkv_update_transfer_function_from_summary(vkv_ctx *ctx, const VkvVolumeOptions *options, const uint8_t *d_volume, const uint8_t *d_gradient,
+                                              VkvExtent3D extent, uint8_t *d_tf, uint32_t *d_tables, uint8_t *const d_maps[8], uint8_t *d_swap,
+                                              VkvExtent3D map_extent, int32_t skipping_type, uint64_t *d_occupied_count, const void *d_summary,
+                                              const uint64_t *d_histogram, uint64_t *d_unresolved, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!options || !d_volume || !d_tf || !d_tables || !d_maps || !d_summary || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: null pointer or bad extent");
+	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: bad skipping_type %d", (int) skipping_type);
+	if (((uintptr_t) d_tf & 3u) != 0 || ((uintptr_t) d_tables & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_transfer_function and d_tables must be 4-byte aligned");
+	if (d_occupied_count && !d_histogram)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_occupied_count needs d_histogram");
+	if ((((uintptr_t) d_occupied_count) | ((uintptr_t) d_histogram)) & 7u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_occupied_count and d_histogram must be 8-byte aligned");
+	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
+	const int  n     = aniso ? 8 : 1;
+	for (int i = 0; i < n; ++i)
+		if (!d_maps[i])
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: map %d is null", i);
+	if (aniso || skipping_type == VKV_SKIP_DISTANCE)
+	{
+		if (!d_swap)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: null swap buffer");
+		for (int i = 0; i < n; ++i)
+			if (d_maps[i] == d_swap)
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: map %d aliases the swap buffer", i);
+	}
+	VkvTransferFunctionUniform tf;
+	vkv_transfer_function_uniform(options, &tf);
+	int rc = check_from_summary(ctx, "update_transfer_function_from_summary", d_summary, d_gradient, tf.use_gradient, extent, map_extent, d_unresolved);
+	if (rc != VKV_OK)
+		return rc;
+	const hipStream_t s       = (hipStream_t) stream;
+	uint8_t *         scratch = stream_scratch(ctx, s);
+	if (!scratch)
+		return VKV_E_UNSUPPORTED;
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
+	if (d_occupied_count && (rc = launch_histogram_occupied_count(ctx, d_histogram, &tf, d_occupied_count, s)) != VKV_OK)
+		return rc;
+	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, d_bits, s)) != VKV_OK)
+		return rc;
+	if ((rc = launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf.use_gradient != 0, d_bits, extent, d_maps[n - 1], map_extent,
+	                                        d_unresolved, s)) != VKV_OK)
+		return rc;
+	if (aniso)
+		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, s);
+	if (skipping_type == VKV_SKIP_DISTANCE)
+		return launch_distance_map(ctx, d_maps[0], d_swap, map_extent, s);
+	return VKV_OK;        // None / Block use the raw 0/255 occupancy map
 }
 
 // argument checks shared by vkv_render and vkv_render_batch

@@ -2084,6 +2084,13 @@ __global__ void __launch_bounds__(256) k_tf_build(uint32_t *__restrict__ tex, ui
 		bits[2048u + (i >> 5)] = (uint32_t) c, bits[2048u + (i >> 5) + 1u] = (uint32_t) (c >> 32);
 }
 
+// the occupancy bit table of an RGBA8 texture (k_tf_bits alone: vkv_occupancy_map_from_summary has no use for the column mask)
+int launch_tf_bits(vkv_ctx *ctx, const uint8_t *d_tf, uint32_t *d_bits, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
+	return check_launch(ctx, "transfer_function_bits");
+}
+
 int launch_tf_build(vkv_ctx *ctx, const VkvTransferFunctionUniform *tf, uint8_t *d_tf, uint32_t *d_tables, uint32_t *d_bits, hipStream_t s)
 {
 	hipLaunchKernelGGL(k_tf_build, dim3(256), dim3(256), 0, s, reinterpret_cast<uint32_t *>(d_tf), d_tables, d_bits, tf->intensity_min,

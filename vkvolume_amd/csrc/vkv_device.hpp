@@ -291,11 +291,15 @@ constexpr size_t   kCaptureSlotBytes = 96 * 1024;  // >= the pull heads + VKV_MA
 constexpr uint32_t kMaxDynamicLds  = 64 * 1024 - 1024;        // what a lean kernel may ask for as dynamic LDS (its tables; no hipFuncSetAttribute is called)
 constexpr size_t kTfBitsOffset     = 0;           // 256*256 bits = 8 KiB: TF bit table of the map update / the voxel count (+ 8 words behind it: its column mask)
 constexpr size_t kQueueHeadsOffset = 8192 + 64;       // 8 x u32 tile-queue heads of the persistent ray-march scheduler
+constexpr size_t kTfRangesOffset   = 16 * 1024;       // 64 KiB: row-range ORs / ANDs of the bit table (cells.hip, k_tf_ranges), written and read
+                                                      // within one occupancy-from-summary launch pair; shares bytes with the batch argument
+                                                      // blocks below, which only a later launch on the same stream writes (stream order)
 constexpr size_t kPullHeadsBytes   = 2048;        // 8 ticket counters of k_raymarch_lean_pull, 256 bytes apart (one memory channel each), directly in
                                                   // front of the argument blocks: one upload zeroes the counters and brings the arguments
 constexpr uint32_t kPullHeadStride = 64;         // in uint32 words
 constexpr size_t kBatchArgsOffset  = 32 * 1024 + kPullHeadsBytes;        // vkv_render_batch: kMaxBatch argument blocks
 constexpr uint32_t kMaxBatch       = VKV_MAX_BATCH;
+static_assert(kTfRangesOffset >= kQueueHeadsOffset + 32 && kTfRangesOffset + 4 * 2048 * 8 <= kScratchBytes, "the range table must fit the scratch block");
 
 // Every device entry point runs on the context's device whatever the calling thread's current device is, and leaves the
 // caller's current device as it found it.

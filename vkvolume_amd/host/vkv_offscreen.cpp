@@ -13,10 +13,12 @@
 //                 [--virtual-ranks=N --dump-assembled=file]   the multi-GPU decomposition on one GPU: rank r of N renders
 //                                  VolumeRenderSubpass::rank_schedule(r, N) - its share of the tiles of the frame's screen rectangle - into a compact
 //                                  buffer, vkv_scatter_tiles assembles the N buffers (what the frame's owner does behind ncclGather)
-//                 [--tf-drag=N --tf-path=host|device]   N transfer-function slider moves after the first frame: each shifts intensity_min by
+//                 [--tf-drag=N --tf-path=host|device|summary]   N transfer-function slider moves after the first frame: each shifts intensity_min by
 //                                  a small step, updates the texture and the maps and renders one frame; prints ms per move from device events
 //                                  (two warm-up moves untimed).  host = the blocking update (CPU texture, upload, wait, tables, occupancy +
-//                                  transform); device = Volume::update_transfer_function, one enqueue with no host wait
+//                                  transform); device = Volume::update_transfer_function, one enqueue with no host wait; summary =
+//                                  Volume::update_transfer_function_from_summary (the cell summary built once before the moves), and the line
+//                                  "tf-drag summary: unresolved cells X% (last move)"
 //                 [--stream-slabs=N]   progressive loading: the volume starts all zero (its maps built as for any volume), then arrives in N
 //                                  z-slabs - read from the raw file, or cut from the synthetic volume generated into a staging buffer - each
 //                                  written with Volume::update_region and followed by one frame; --dump-rgba8 writes the last frame
@@ -64,7 +66,7 @@ struct Args
 	int         virtual_ranks    = 0;         // --virtual-ranks=N: this GPU plays N ranks in turn, --dump-assembled gets their assembled frame
 	std::string dump_assembled;
 	int         tf_drag = 0;              // --tf-drag=N: slider moves
-	std::string tf_path = "device";        // --tf-path=host|device
+	std::string tf_path = "device";        // --tf-path=host|device|summary
 	uint32_t    stream_slabs = 0;          // --stream-slabs=N: z-slabs of a progressive load
 	std::string histogram;                 // --histogram=file: the volume's joint histogram
 };
@@ -125,8 +127,8 @@ Args parse(int argc, char **argv)
 		else if (flag(s, "--tf-drag", v)) a.tf_drag = std::max(0, std::stoi(v));
 		else if (flag(s, "--tf-path", v))
 		{
-			if (v != "host" && v != "device")
-				throw std::runtime_error("--tf-path=host|device");
+			if (v != "host" && v != "device" && v != "summary")
+				throw std::runtime_error("--tf-path=host|device|summary");
 			a.tf_path = v;
 		}
 		else if (flag(s, "--stream-slabs", v)) a.stream_slabs = (uint32_t) std::stoul(v);
@@ -426,7 +428,13 @@ int main(int argc, char **argv)
 		}
 		if (args.tf_drag > 0)
 		{        // slider moves (src/volume_render.cpp:392-445 per move), each followed by one frame into the same target
-			const bool  device_path = args.tf_path == "device";
+			const bool  device_path = args.tf_path == "device", summary_path = args.tf_path == "summary";
+			uint64_t *  d_unresolved = nullptr;
+			if (summary_path)
+			{
+				d_unresolved = device_alloc<uint64_t>(1);
+				volume.cell_summary(dc);
+			}
 			const int   warmup      = 2;
 			const float step        = 0.005f;
 			hipEvent_t  ev0 = nullptr, ev1 = nullptr;
@@ -444,6 +452,8 @@ int main(int argc, char **argv)
 				volume.options.intensity_min = args.imin + step * (float) k;
 				if (device_path)
 					volume.update_transfer_function(dc, static_cast<int32_t>(render_options.skipping_type));
+				else if (summary_path)
+					volume.update_transfer_function_from_summary(dc, static_cast<int32_t>(render_options.skipping_type), nullptr, nullptr, d_unresolved);
 				else
 				{
 					volume.update_transfer_function_texture(dc);
@@ -460,6 +470,16 @@ int main(int argc, char **argv)
 			            ms / args.tf_drag, wall / args.tf_drag);
 			(void) hipEventDestroy(ev0);
 			(void) hipEventDestroy(ev1);
+			if (summary_path)
+			{
+				uint64_t   unresolved = 0;
+				const bool ok = hipMemcpy(&unresolved, d_unresolved, sizeof(unresolved), hipMemcpyDeviceToHost) == hipSuccess;
+				(void) hipFree(d_unresolved);
+				if (!ok)
+					throw std::runtime_error("unresolved-cell count download failed");
+				const auto &me = volume.get_distance_map_swap().extent;
+				std::printf("tf-drag summary: unresolved cells %g%% (last move)\n", 100.0 * (double) unresolved / ((double) me.width * me.height * me.depth));
+			}
 		}
 		{
 			// Benchmark frames go round-robin over a few HIP streams, each with its own colour target - what the reference gets from

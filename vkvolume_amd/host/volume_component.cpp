@@ -1,6 +1,8 @@
 // volume_component.cpp — see volume_component.h.
 #include "volume_component.h"
 
+#include <algorithm>
+
 #include <hip/hip_runtime_api.h>
 
 #include <stdexcept>
@@ -49,6 +51,9 @@ void Volume::release()
 		(void) hipFree(transfer_function_bits);
 	if (region_staging)
 		(void) hipFree(region_staging);
+	if (cell_summary_buf)
+		(void) hipFree(cell_summary_buf);
+	cell_summary_buf     = nullptr;
 	region_staging       = nullptr;
 	region_staging_bytes = 0;
 	packed                 = nullptr;
@@ -208,6 +213,49 @@ void Volume::update_region(DeviceContext &dc, VkvBox box, const void *host_raw, 
 	                                   options.use_precomputed_gradient ? gradient.data : nullptr, packed, volume.extent, transfer_function.data, &tf,
 	                                   have ? maps : nullptr, distance_map_swap.data, distance_map_swap.extent, skipping_type, dc.stream),
 	          "volume region update");
+	if (cell_summary_buf)
+	{        // the summary of every cell the grown box meets: the gradient changes one voxel around the box
+		const VkvExtent3D &e  = volume.extent;
+		const uint32_t     x0 = box.x0 ? box.x0 - 1 : 0, y0 = box.y0 ? box.y0 - 1 : 0, z0 = box.z0 ? box.z0 - 1 : 0;
+		const uint32_t     x1 = std::min(box.x0 + box.width + 1, e.width), y1 = std::min(box.y0 + box.height + 1, e.height),
+		               z1 = std::min(box.z0 + box.depth + 1, e.depth);
+		const VkvBox grown{x0, y0, z0, x1 - x0, y1 - y0, z1 - z0};
+		cell_summary(dc, &grown);
+	}
+}
+
+void Volume::cell_summary(DeviceContext &dc, const VkvBox *box)
+{
+	const VkvExtent3D &me = distance_map_swap.extent;
+	if (!cell_summary_buf)
+	{
+		if (box)
+			throw std::runtime_error("cell summary: build the whole summary first");
+		cell_summary_buf = device_alloc((size_t) me.width * me.height * me.depth * VKV_CELL_SUMMARY_BYTES);
+	}
+	vkv_check(dc,
+	          vkv_cell_summary(dc.ctx, volume.data, options.use_precomputed_gradient ? gradient.data : nullptr, volume.extent, me, box, cell_summary_buf,
+	                           dc.stream),
+	          "cell summary");
+}
+
+void Volume::update_transfer_function_from_summary(DeviceContext &dc, int32_t skipping_type, uint64_t *d_occupied_count, const uint64_t *d_histogram,
+                                                   uint64_t *d_unresolved)
+{
+	if (!cell_summary_buf)
+		throw std::runtime_error("TF update from summary: no cell summary (call cell_summary first)");
+	const VkvVolumeOptions o{options.sampling_factor, options.voxel_alpha_factor, options.use_precomputed_gradient ? 1u : 0u,
+	                         options.intensity_min,   options.intensity_max,      options.gradient_min, options.gradient_max};
+	set_number_of_distance_maps(dc, skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 8 : 1);
+	uint8_t *maps[8] = {nullptr};
+	for (size_t i = 0; i < distance_maps.size() && i < 8; ++i)
+		maps[i] = distance_maps[i].data;
+	vkv_check(dc,
+	          vkv_update_transfer_function_from_summary(dc.ctx, &o, volume.data, options.use_precomputed_gradient ? gradient.data : nullptr,
+	                                                    volume.extent, transfer_function.data, transfer_function_bits, maps, distance_map_swap.data,
+	                                                    distance_map_swap.extent, skipping_type, d_occupied_count, cell_summary_buf, d_histogram,
+	                                                    d_unresolved, dc.stream),
+	          "TF update from summary");
 }
 
 void Volume::histogram(DeviceContext &dc, uint64_t *d_histogram, const VkvBox *box, int32_t mode)

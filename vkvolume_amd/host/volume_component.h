@@ -82,6 +82,16 @@ class Volume
 	// d_histogram, set / added / subtracted as `mode` (a VkvHistogramMode) says (vkv_volume_histogram), on dc.stream; the gradient map is used
 	// when options.use_precomputed_gradient is set, else every voxel counts in gradient row 0
 	void histogram(DeviceContext &dc, uint64_t *d_histogram, const VkvBox *box = nullptr, int32_t mode = VKV_HISTOGRAM_SET);
+	// Per-cell summaries of the occupancy map (vkv_cell_summary) of every cell (box == nullptr) or of the cells that meet `box`, into a device
+	// buffer the volume allocates at the first call (build the whole summary first); built from the gradient map when
+	// options.use_precomputed_gradient is set.  update_region keeps a built summary current (it rebuilds the update's box grown by one voxel).
+	void cell_summary(DeviceContext &dc, const VkvBox *box = nullptr);
+	const void *get_cell_summary() const { return cell_summary_buf; }
+	// update_transfer_function with the occupancy map decided from the summary (vkv_update_transfer_function_from_summary; call cell_summary
+	// first): same texture, tables and maps.  d_occupied_count needs d_histogram (a histogram() of the volume); d_unresolved receives the
+	// number of cells evaluated from their voxels
+	void update_transfer_function_from_summary(DeviceContext &dc, int32_t skipping_type, uint64_t *d_occupied_count = nullptr,
+	                                           const uint64_t *d_histogram = nullptr, uint64_t *d_unresolved = nullptr);
 
 	// vkb::sg::Node stand-in: the node's world matrix (benchmark mode rescales it, src/volume_render.cpp:224-238)
 	vkv::mat4 node_transform;
@@ -104,5 +114,6 @@ class Volume
 	uint32_t *         transfer_function_bits = nullptr;
 	void *             region_staging         = nullptr;        // update_region's device copy of the raw box
 	size_t             region_staging_bytes   = 0;
+	void *             cell_summary_buf       = nullptr;        // cell_summary's VKV_CELL_SUMMARY_BYTES per occupancy cell
 	vkv::mat4          image_transform;
 };

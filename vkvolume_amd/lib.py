@@ -22,6 +22,7 @@ EXPORTS = [
     "vkv_release_stream", "vkv_trim", "vkv_release_captured", "vkv_screen_tile_rect",
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
+    "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -97,6 +98,10 @@ def load():
                                            P(abi.TransferFunctionUniform), P(vp), vp, abi.Extent3D, i32, vp]
     L.vkv_volume_histogram.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), i32, vp, vp]
     L.vkv_histogram_occupied_count.argtypes = [vp, vp, P(abi.TransferFunctionUniform), vp, vp]
+    L.vkv_cell_summary.argtypes = [vp, vp, vp, abi.Extent3D, abi.Extent3D, P(abi.Box), vp, vp]
+    L.vkv_occupancy_map_from_summary.argtypes = [vp, vp, vp, vp, vp, P(abi.TransferFunctionUniform), abi.Extent3D, vp, abi.Extent3D, vp, vp]
+    L.vkv_update_transfer_function_from_summary.argtypes = [vp, P(abi.VolumeOptions), vp, vp, abi.Extent3D, vp, vp, P(vp), vp, abi.Extent3D, i32, vp,
+                                                            vp, vp, vp, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -290,6 +295,39 @@ class Context:
 
     def histogram_occupied_count_rc(self, d_histogram, tf, d_count, stream=0):
         return self._lib.vkv_histogram_occupied_count(self.handle, d_histogram, None if tf is None else C.byref(tf), d_count, stream)
+
+    def cell_summary(self, d_volume, d_gradient, extent, map_extent, box, d_summary, stream=0):
+        """vkv_cell_summary: the 16-byte summaries of every occupancy cell (box None), or of the cells that meet `box`, into d_summary;
+        d_gradient None records gradient byte 255 for every voxel"""
+        self.check(self.cell_summary_rc(d_volume, d_gradient, extent, map_extent, box, d_summary, stream))
+
+    def cell_summary_rc(self, d_volume, d_gradient, extent, map_extent, box, d_summary, stream=0):
+        """Like cell_summary() but returns the status code (error-path tests)."""
+        return self._lib.vkv_cell_summary(self.handle, d_volume, d_gradient, extent, map_extent, None if box is None else C.byref(box), d_summary, stream)
+
+    def occupancy_map_from_summary(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
+        """vkv_occupancy_map_from_summary: vkv_occupancy_map's map, decided from the cell summaries where they are certain; d_unresolved
+        receives the number of cells evaluated from their voxels"""
+        self.check(self.occupancy_map_from_summary_rc(d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved, stream))
+
+    def occupancy_map_from_summary_rc(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
+        return self._lib.vkv_occupancy_map_from_summary(self.handle, d_summary, d_volume, d_gradient, d_tf, None if tf is None else C.byref(tf), extent,
+                                                        d_map, map_extent, d_unresolved, stream)
+
+    def update_transfer_function_from_summary(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
+                                              d_count, d_summary, d_histogram, d_unresolved=None, stream=0):
+        """vkv_update_transfer_function_from_summary: update_transfer_function() with the occupancy from the cell summaries and the count
+        (d_count not None) from the histogram"""
+        self.check(self.update_transfer_function_from_summary_rc(options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent,
+                                                                 skipping_type, d_count, d_summary, d_histogram, d_unresolved, stream))
+
+    def update_transfer_function_from_summary_rc(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
+                                                 d_count, d_summary, d_histogram, d_unresolved=None, stream=0):
+        """Like update_transfer_function_from_summary() but returns the status code; d_maps None passes a NULL array."""
+        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
+        return self._lib.vkv_update_transfer_function_from_summary(self.handle, None if options is None else C.byref(options), d_volume, d_gradient,
+                                                                   extent, d_tf, d_tables, arr, d_swap, map_extent, skipping_type, d_count, d_summary,
+                                                                   d_histogram, d_unresolved, stream)
 
     def debug_tf_scratch(self, d_out, stream=0):
         """vkv_debug_tf_scratch: the bit table + column mask (2056 words) in `stream`'s scratch block, copied to d_out"""

@@ -42,6 +42,7 @@ class Volume:
         self.distance_maps = []
         self.distance_map_swap = None
         self.extent = self.map_extent = None
+        self.cell_summary = None  # vkv_cell_summary of the current volume (build_cell_summary), kept current by update_region
 
     # -- load_from_file's device half (src/volume_component.cpp:55-153): take voxels, allocate images --
     def load_from_array(self, voxels_dhw, distance_map_block_size=4, image_transform=None):
@@ -65,7 +66,7 @@ class Volume:
         self.gradient_valid = False  # set by ComputeGradientMap.compute; the packed image must not be built from an empty map
         self.transfer_function = torch.zeros((256, 256, 4), dtype=torch.uint8, device=self.device)
         self.transfer_function_bits = torch.zeros(abi.TF_BITS_WORDS, dtype=torch.int32, device=self.device)
-        self.packed = None
+        self.packed = self.cell_summary = None
         self.distance_map_swap = torch.empty((self.map_extent.depth, self.map_extent.height, self.map_extent.width),
                                              dtype=torch.uint8, device=self.device)
         self.distance_maps = []
@@ -107,6 +108,41 @@ class Volume:
                                           _ptr(self.transfer_function_bits), [_ptr(m) for m in self.distance_maps], _ptr(self.distance_map_swap),
                                           self.map_extent, skipping_type, _ptr(d_count), _stream())
 
+    def _gradient_or_none(self):
+        return self.gradient if self.options.use_precomputed_gradient else None
+
+    def build_cell_summary(self, box=None):
+        """The per-cell summaries of the occupancy map (vkv_cell_summary) on the current stream: of every cell (box None), or of the cells
+        that meet ``box`` (an abi.Box or ((x0, y0, z0), (width, height, depth))).  The (cells, 16) uint8 buffer is allocated at the first
+        call and kept in ``cell_summary``; it is built from the gradient map when use_precomputed_gradient is set.  update_region() keeps
+        it current by rebuilding it over the update's box grown by one voxel per side."""
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if self.cell_summary is None:
+            if box is not None:
+                raise ValueError("Volume.build_cell_summary: build the whole summary (box=None) first")
+            me = self.map_extent
+            self.cell_summary = torch.empty((me.width * me.height * me.depth, abi.CELL_SUMMARY_BYTES), dtype=torch.uint8, device=self.device)
+        self.ctx.cell_summary(_ptr(self.volume), _ptr(self._gradient_or_none()), self.extent, self.map_extent, box, _ptr(self.cell_summary), _stream())
+        return self.cell_summary
+
+    def update_transfer_function_from_summary(self, skipping_type, d_count=None, histogram=None, d_unresolved=None):
+        """update_transfer_function() with the occupancy map decided from the cell summaries (vkv_update_transfer_function_from_summary):
+        same texture, tables and maps.  ``d_count`` (an int64 device tensor) receives the occupied-voxel count read off ``histogram``
+        (a histogram() result built with the same gradient setting), which it then requires; ``d_unresolved`` (an int64 device tensor)
+        receives the number of cells evaluated from their voxels.  Call build_cell_summary() first."""
+        if self.cell_summary is None:
+            raise RuntimeError("Volume.update_transfer_function_from_summary: no cell summary (call build_cell_summary first)")
+        if d_count is not None and histogram is None:
+            raise ValueError("Volume.update_transfer_function_from_summary: d_count needs the histogram")
+        self.set_number_of_distance_maps(8 if skipping_type == abi.SKIP_ANISOTROPIC_DISTANCE else 1)
+        self.ctx.update_transfer_function_from_summary(self.options, _ptr(self.volume), _ptr(self._gradient_or_none()), self.extent,
+                                                       _ptr(self.transfer_function), _ptr(self.transfer_function_bits),
+                                                       [_ptr(m) for m in self.distance_maps], _ptr(self.distance_map_swap), self.map_extent,
+                                                       skipping_type, _ptr(d_count), _ptr(self.cell_summary), _ptr(histogram), _ptr(d_unresolved),
+                                                       _stream())
+
     _DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1, np.dtype(np.uint16): 2, np.dtype(np.int16): 3}  # VkvVoxelType
     _TORCH_DTYPES = {torch.uint8: 0, torch.int8: 1, torch.int16: 3}
 
@@ -117,7 +153,8 @@ class Volume:
         (staged through pinned memory) or CUDA tensor of raw elements of ``voxel_type`` (default: from the dtype; a uint16 file's raw bytes
         come as int16 / uint16 with voxel_type = VKV_VOXEL_UINT16), converted like the loader converts a file: byte order, then
         ``normalisation_range`` (default (0, 255): uint8 voxels are stored as they are).  Precondition: the derived buffers are up to date
-        (ComputeGradientMap / pack / ComputeDistanceMap with the current options and transfer function texture)."""
+        (ComputeGradientMap / pack / ComputeDistanceMap with the current options and transfer function texture).  A cell summary built with
+        build_cell_summary() is rebuilt over the box grown by one voxel per side, clamped to the volume (vkv_cell_summary's maintenance rule)."""
         if torch.is_tensor(voxels_dhw):
             src = voxels_dhw.to(self.device).contiguous()
             vt = self._TORCH_DTYPES.get(src.dtype) if voxel_type is None else voxel_type
@@ -143,6 +180,11 @@ class Volume:
                                       _ptr(self.packed), self.extent, _ptr(self.transfer_function), self.get_transfer_function_uniform(), maps,
                                       _ptr(self.distance_map_swap), self.map_extent, skipping_type, _stream())
         src.record_stream(torch.cuda.current_stream())  # the source stays allocated until the update has read it
+        if self.cell_summary is not None:  # the summary of every cell the grown box meets (the gradient changes one voxel around the box)
+            e = self.extent
+            x0, y0, z0 = max(x - 1, 0), max(y - 1, 0), max(z - 1, 0)
+            x1, y1, z1 = min(x + w + 1, e.width), min(y + h + 1, e.height), min(z + d + 1, e.depth)
+            self.build_cell_summary(abi.Box(x0, y0, z0, x1 - x0, y1 - y0, z1 - z0))
 
     _HISTOGRAM_MODES = (abi.HISTOGRAM_SET, abi.HISTOGRAM_ADD, abi.HISTOGRAM_SUBTRACT)
 
