@@ -25,6 +25,17 @@
  *     address arithmetic in registers: the same bits, a few per cent slower) until vkv_trim
  *     empties it; the scratch blocks of streams have a region of their own (16 streams) and
  *     are never starved by tables;
+ *   - THREADS: any number of host threads may call the device functions of one context at
+ *     the same time, on their own streams or on a shared one (the null stream included).
+ *     Per-stream device scratch has a lock that an entry point holds from its first write
+ *     into the block to its last enqueue, so calls from several threads on ONE stream run
+ *     in some order, each one whole.  hipStreamPerThread is a different stream in every
+ *     thread: the context keeps its scratch block and captured-launch slots per (handle,
+ *     calling thread), and vkv_release_stream / vkv_release_captured with that handle
+ *     release the calling thread's.  vkv_last_error is ONE buffer per context: with
+ *     several threads, rely on the return codes (the text may be another thread's).
+ *     vkv_trim, vkv_forget_target and vkv_destroy must not run concurrently with launches
+ *     (see there);
  *   - pointers named `d_*` are device pointers owned by the caller; POD structs are
  *     passed by const pointer and copied at call time;
  *   - volumes are dense uint8, x fastest: index = (z*height + y)*width + x
@@ -514,7 +525,8 @@ int vkv_forget_target(vkv_ctx *ctx, const void *d_target);
 int vkv_trim(vkv_ctx *ctx);
 
 /* Gives the 128 KiB scratch block vkv_render_batch / vkv_compute_distance_map / ... keep per HIP stream back to the context's pool.
- * Call it before destroying a stream that was handed to this context, when all work enqueued on it has completed (it does not wait). */
+ * Call it before destroying a stream that was handed to this context, when all work enqueued on it has completed (it does not wait).
+ * For hipStreamPerThread it gives back the calling thread's block: call it from each thread that used the handle, before the thread ends. */
 int vkv_release_stream(vkv_ctx *ctx, void *stream);
 
 /* VolumeRenderSubpass::draw, src/volume_render_subpass.cpp:159-294 (shaders/volume_render.frag). */

@@ -23,7 +23,7 @@ namespace vkv
 {
 int launch_gradient_map(vkv_ctx *, const uint8_t *, uint8_t *, VkvExtent3D, const VkvTransferFunctionUniform *, hipStream_t);
 int launch_occupancy_map(vkv_ctx *, const uint8_t *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint8_t *,
-                         VkvExtent3D, hipStream_t, bool bits_ready = false);
+                         VkvExtent3D, hipStream_t, uint32_t *d_bits, bool bits_ready = false);
 int launch_distance_map(vkv_ctx *, uint8_t *, uint8_t *, VkvExtent3D, hipStream_t);
 int launch_distance_map_anisotropic(vkv_ctx *, uint8_t *const[8], uint8_t *, VkvExtent3D, hipStream_t);
 int launch_synth_volume(vkv_ctx *, uint8_t *, VkvExtent3D, uint32_t, uint32_t, hipStream_t);
@@ -39,7 +39,7 @@ int launch_check_numerics(vkv_ctx *, int, uint32_t, uint64_t, unsigned long long
 int launch_tf_tables(vkv_ctx *, const uint8_t *, const VkvTransferFunctionUniform *, uint32_t *, hipStream_t);
 int launch_tf_build(vkv_ctx *, const VkvTransferFunctionUniform *, uint8_t *, uint32_t *, uint32_t *, hipStream_t);
 int launch_convert_volume(vkv_ctx *, const void *, int, bool, float, float, uint64_t, uint8_t *, hipStream_t);
-int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t);
+int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t, uint32_t *);
 int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float, const VkvBox &, uint8_t *, uint8_t *, void *, VkvExtent3D, const uint8_t *,
                                 const VkvTransferFunctionUniform *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
 int launch_volume_histogram(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, const VkvBox &, int, uint64_t *, hipStream_t);
@@ -47,7 +47,7 @@ int launch_histogram_occupied_count(vkv_ctx *, const uint64_t *, const VkvTransf
 int launch_tf_bits(vkv_ctx *, const uint8_t *, uint32_t *, hipStream_t);
 bool cells_launch_ok(VkvExtent3D, VkvExtent3D);
 int launch_cell_summary(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, VkvExtent3D, const VkvBox *, void *, hipStream_t);
-int launch_occupancy_from_summary(vkv_ctx *, const void *, const uint8_t *, const uint8_t *, bool, const uint32_t *, VkvExtent3D, uint8_t *, VkvExtent3D,
+int launch_occupancy_from_summary(vkv_ctx *, const void *, const uint8_t *, const uint8_t *, bool, uint8_t *, VkvExtent3D, uint8_t *, VkvExtent3D,
                                   uint64_t *, hipStream_t);
 
 int set_error(vkv_ctx *ctx, int code, const char *fmt, ...)
@@ -93,40 +93,68 @@ static void *arena_take_table(vkv_ctx *ctx, size_t bytes, bool setup, bool *from
 	return p;
 }
 
-uint8_t *stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup)
+VkvStreamKey stream_key(hipStream_t stream)
 {
-	std::lock_guard<std::mutex> lock(ctx->mutex);
-	auto                        it = ctx->scratch.find(stream);
-	if (it != ctx->scratch.end())
-		return it->second;
-	uint8_t *p = nullptr;
-	if (!ctx->free_scratch.empty())
-	{
-		p = ctx->free_scratch.back();
-		ctx->free_scratch.pop_back();
-	}
-	else if (ctx->arena && ctx->scratch_used + kScratchBytes <= ctx->table_base)
-	{
-		p = ctx->arena + ctx->scratch_used;
-		ctx->scratch_used += kScratchBytes;
-	}
-	else if (setup)
-	{        // more streams than the arena reserves blocks for: a set-up call may allocate (freed by vkv_destroy)
-		void *q = nullptr;
-		if (hipMalloc(&q, kScratchBytes) == hipSuccess)
+	VkvStreamKey k;
+	k.stream = stream;
+	if (stream == hipStreamPerThread)
+		k.thread = std::this_thread::get_id();
+	return k;
+}
+
+StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup)
+{
+	vkv_ctx::ScratchBlock *b = nullptr;
+	{        // the block under ctx->mutex, its lock after: the lock order is "block, then ctx->mutex"
+		std::lock_guard<std::mutex> lock(ctx->mutex);
+		const VkvStreamKey          key = stream_key(stream);
+		auto                        it  = ctx->scratch.find(key);
+		if (it != ctx->scratch.end())
+			b = it->second;
+		else
 		{
-			ctx->overflow_scratch.push_back(q);
-			p = static_cast<uint8_t *>(q);
+			uint8_t *p = nullptr;
+			if (!ctx->free_scratch.empty())
+			{
+				b = ctx->free_scratch.back();
+				ctx->free_scratch.pop_back();
+			}
+			else if (ctx->arena && ctx->scratch_used + kScratchBytes <= ctx->table_base)
+			{
+				p = ctx->arena + ctx->scratch_used;
+				ctx->scratch_used += kScratchBytes;
+			}
+			else if (setup)
+			{        // more streams than the arena reserves blocks for: a set-up call may allocate (freed by vkv_destroy)
+				void *q = nullptr;
+				if (hipMalloc(&q, kScratchBytes) == hipSuccess)
+				{
+					ctx->overflow_scratch.push_back(q);
+					p = static_cast<uint8_t *>(q);
+				}
+			}
+			if (p)
+			{
+				b = new (std::nothrow) vkv_ctx::ScratchBlock;        // (out of host memory: the bytes stay unused until vkv_destroy)
+				if (b)
+				{
+					b->p = p;
+					ctx->scratch_blocks.emplace_back(b);
+				}
+			}
+			if (!b)
+			{
+				set_error(ctx, VKV_E_UNSUPPORTED, "no scratch block left for a new stream: the arena reserves %zu (call vkv_prepare_render for the stream at set-up "
+				                                  "time, give finished streams back with vkv_release_stream, or raise VKV_ARENA_BYTES)", ctx->table_base / kScratchBytes);
+				return StreamScratch{};
+			}
+			ctx->scratch.emplace(key, b);
 		}
 	}
-	if (!p)
-	{
-		set_error(ctx, VKV_E_UNSUPPORTED, "no scratch block left for a new stream: the arena reserves %zu (call vkv_prepare_render for the stream at set-up "
-		                                  "time, give finished streams back with vkv_release_stream, or raise VKV_ARENA_BYTES)", ctx->table_base / kScratchBytes);
-		return nullptr;
-	}
-	ctx->scratch.emplace(stream, p);
-	return p;
+	StreamScratch r;
+	r.lock = std::unique_lock<std::mutex>(b->lock);
+	r.p    = b->p;
+	return r;
 }
 
 // Device copy of a new table: memory out of the arena, asynchronous upload from the entry's own host copy on the launch's stream, an
@@ -179,7 +207,8 @@ static const uint32_t *table_on_stream(vkv_ctx::Table &t, hipStream_t s, bool se
 		t.ready = true;
 		return t.d;
 	}
-	if (s != t.upload_stream && hipStreamWaitEvent(s, t.uploaded, 0) != hipSuccess)
+	// (hipStreamPerThread is another stream in every thread: a launch on it waits for the upload even when the upload went through that handle)
+	if ((s != t.upload_stream || s == hipStreamPerThread) && hipStreamWaitEvent(s, t.uploaded, 0) != hipSuccess)
 		return nullptr;
 	return t.d;
 }
@@ -425,7 +454,7 @@ static void drop_capture_blocks(vkv_ctx *ctx)
 	{
 		if (c.pooled)
 		{
-			c.in_use = false, c.owner = nullptr;
+			c.in_use = false, c.owner = VkvStreamKey{};
 			kept.push_back(c);
 		}
 		else
@@ -442,9 +471,10 @@ int vkv_release_captured(vkv_ctx *ctx, void *stream)
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	std::lock_guard<std::mutex> lock(ctx->mutex);
+	const VkvStreamKey          key = stream_key((hipStream_t) stream);
 	for (auto &c : ctx->capture_slots)
-		if (c.in_use && c.owner == (hipStream_t) stream)
-			c.in_use = false, c.owner = nullptr;
+		if (c.in_use && c.owner == key)
+			c.in_use = false, c.owner = VkvStreamKey{};
 	return VKV_OK;
 }
 
@@ -577,7 +607,7 @@ int vkv_release_stream(vkv_ctx *ctx, void *stream)
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	std::lock_guard<std::mutex> lock(ctx->mutex);
-	auto                        it = ctx->scratch.find((hipStream_t) stream);
+	auto                        it = ctx->scratch.find(stream_key((hipStream_t) stream));        // hipStreamPerThread: the calling thread's block
 	if (it != ctx->scratch.end())
 	{
 		ctx->free_scratch.push_back(it->second);
@@ -687,10 +717,10 @@ int vkv_debug_tf_scratch(vkv_ctx *ctx, uint32_t *d_out, void *stream)
 	DeviceGuard guard(ctx->device);
 	if (!d_out)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "debug_tf_scratch: null pointer");
-	uint8_t *scratch = stream_scratch(ctx, (hipStream_t) stream);
-	if (!scratch)
+	const StreamScratch scratch = stream_scratch(ctx, (hipStream_t) stream);
+	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
-	const hipError_t e = hipMemcpyAsync(d_out, scratch + kTfBitsOffset, (2048 + 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t) stream);
+	const hipError_t e = hipMemcpyAsync(d_out, scratch.p + kTfBitsOffset, (2048 + 8) * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t) stream);
 	return e == hipSuccess ? VKV_OK : set_error(ctx, (int) e, "debug_tf_scratch: %s", hipGetErrorString(e));
 }
 
@@ -837,7 +867,11 @@ int vkv_occupancy_map(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gr
 	DeviceGuard guard(ctx->device);
 	if (!d_volume || !d_tf || !tf || !d_map || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "occupancy_map: null pointer or bad extent");
-	return launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, (hipStream_t) stream);
+	const StreamScratch scratch = stream_scratch(ctx, (hipStream_t) stream);        // the bit table, written and read by the launches below
+	if (!scratch.p)
+		return VKV_E_UNSUPPORTED;
+	return launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, (hipStream_t) stream,
+	                            reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset));
 }
 
 int vkv_distance_map(vkv_ctx *ctx, uint8_t *d_map, uint8_t *d_swap, VkvExtent3D map_extent, void *stream)
@@ -892,7 +926,10 @@ int vkv_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_
 	DeviceGuard guard(ctx->device);
 	if (!d_volume || !tf || !d_count || !extent_ok(extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "occupied_voxel_count: null pointer or zero extent");
-	return launch_occupied_voxel_count(ctx, d_volume, d_gradient, tf, extent, d_count, (hipStream_t) stream);
+	const StreamScratch scratch = stream_scratch(ctx, (hipStream_t) stream);
+	if (!scratch.p)
+		return VKV_E_UNSUPPORTED;
+	return launch_occupied_voxel_count(ctx, d_volume, d_gradient, tf, extent, d_count, (hipStream_t) stream, reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset));
 }
 
 // ---- loader (host side; the C++ class throws, the C ABI returns codes) ------------------------------------------
@@ -1035,19 +1072,20 @@ int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, 
 			if (d_maps[i] == d_swap)
 				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: map %d aliases the swap buffer", i);
 	}
-	const hipStream_t s       = (hipStream_t) stream;
-	uint8_t *         scratch = stream_scratch(ctx, s);
-	if (!scratch)
+	const hipStream_t   s       = (hipStream_t) stream;
+	const StreamScratch scratch = stream_scratch(ctx, s);        // held until the occupancy pass is enqueued
+	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset);
 	VkvTransferFunctionUniform tf;
 	vkv_transfer_function_uniform(options, &tf);
 	int rc = VKV_OK;
 	// the count first: it stages its own (analytic) bit table in the same scratch words that k_tf_build fills for the occupancy pass
-	if (d_occupied_count && (rc = launch_occupied_voxel_count(ctx, d_volume, d_gradient, &tf, extent, d_occupied_count, s)) != VKV_OK)
+	if (d_occupied_count && (rc = launch_occupied_voxel_count(ctx, d_volume, d_gradient, &tf, extent, d_occupied_count, s, d_bits)) != VKV_OK)
 		return rc;
-	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset), s)) != VKV_OK)
+	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, d_bits, s)) != VKV_OK)
 		return rc;
-	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, &tf, extent, d_maps[n - 1], map_extent, s, true)) != VKV_OK)
+	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, &tf, extent, d_maps[n - 1], map_extent, s, d_bits, true)) != VKV_OK)
 		return rc;
 	if (aniso)
 		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, s);
@@ -1189,14 +1227,13 @@ int vkv_occupancy_map_from_summary(vkv_ctx *ctx, const void *d_summary, const ui
 	int rc = check_from_summary(ctx, "occupancy_map_from_summary", d_summary, d_gradient, tf->use_gradient, extent, map_extent, d_unresolved);
 	if (rc != VKV_OK)
 		return rc;
-	const hipStream_t s       = (hipStream_t) stream;
-	uint8_t *         scratch = stream_scratch(ctx, s);
-	if (!scratch)
+	const hipStream_t   s       = (hipStream_t) stream;
+	const StreamScratch scratch = stream_scratch(ctx, s);
+	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
-	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
-	if ((rc = launch_tf_bits(ctx, d_tf, d_bits, s)) != VKV_OK)
+	if ((rc = launch_tf_bits(ctx, d_tf, reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset), s)) != VKV_OK)
 		return rc;
-	return launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf->use_gradient != 0, d_bits, extent, d_map, map_extent, d_unresolved, s);
+	return launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf->use_gradient != 0, scratch.p, extent, d_map, map_extent, d_unresolved, s);
 }
 
 // vkv_update_transfer_function with the occupancy map from the summary and the count from the histogram: every argument is checked first
@@ -1236,16 +1273,16 @@ int vkv_update_transfer_function_from_summary(vkv_ctx *ctx, const VkvVolumeOptio
 	int rc = check_from_summary(ctx, "update_transfer_function_from_summary", d_summary, d_gradient, tf.use_gradient, extent, map_extent, d_unresolved);
 	if (rc != VKV_OK)
 		return rc;
-	const hipStream_t s       = (hipStream_t) stream;
-	uint8_t *         scratch = stream_scratch(ctx, s);
-	if (!scratch)
+	const hipStream_t   s       = (hipStream_t) stream;
+	const StreamScratch scratch = stream_scratch(ctx, s);        // held until the classification is enqueued
+	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
-	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset);
 	if (d_occupied_count && (rc = launch_histogram_occupied_count(ctx, d_histogram, &tf, d_occupied_count, s)) != VKV_OK)
 		return rc;
 	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, d_bits, s)) != VKV_OK)
 		return rc;
-	if ((rc = launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf.use_gradient != 0, d_bits, extent, d_maps[n - 1], map_extent,
+	if ((rc = launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf.use_gradient != 0, scratch.p, extent, d_maps[n - 1], map_extent,
 	                                        d_unresolved, s)) != VKV_OK)
 		return rc;
 	if (aniso)

@@ -332,15 +332,13 @@ int launch_cell_summary(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gra
 	return check_launch(ctx, "cell_summary");
 }
 
-// the occupancy map from the summary, with the bit table already in the stream's scratch block (d_bits): the range table behind it, then the
-// classification.  use_gradient: tf->use_gradient (d_grad is then non-null: the entry points refuse the on-the-fly gradient)
-int launch_occupancy_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_vol, const uint8_t *d_grad, bool use_gradient, const uint32_t *d_bits,
+// the occupancy map from the summary, with the bit table already in the stream's scratch block (the caller holds its lock): the range table
+// behind it, then the classification.  use_gradient: tf->use_gradient (d_grad is then non-null: the entry points refuse the on-the-fly gradient)
+int launch_occupancy_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_vol, const uint8_t *d_grad, bool use_gradient, uint8_t *scratch,
                                   VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, uint64_t *d_unresolved, hipStream_t s)
 {
-	uint8_t *scratch = stream_scratch(ctx, s);
-	if (!scratch)
-		return VKV_E_UNSUPPORTED;
-	uint2 *        d_ranges   = reinterpret_cast<uint2 *>(scratch + kTfRangesOffset);
+	const uint32_t *d_bits     = reinterpret_cast<const uint32_t *>(scratch + kTfBitsOffset);
+	uint2 *         d_ranges   = reinterpret_cast<uint2 *>(scratch + kTfRangesOffset);
 	auto *         unresolved = reinterpret_cast<unsigned long long *>(d_unresolved);
 	hipLaunchKernelGGL(k_tf_ranges, dim3(kRangeLevels * 2048 / 256), dim3(256), 0, s, d_bits, d_ranges, unresolved);
 	ClassifyArgs a;

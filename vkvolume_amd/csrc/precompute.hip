@@ -1558,15 +1558,12 @@ static int fill_empty(vkv_ctx *ctx, uint8_t *d_map, size_t n, hipStream_t s, boo
 	return em == hipSuccess ? VKV_OK : set_error(ctx, (int) em, "occupancy_map: fill: %s", hipGetErrorString(em));
 }
 
-// bits_ready: k_tf_build has already left the bit table and its column mask in the stream's scratch block (vkv_update_transfer_function);
-// d_tf is then not read, and the map is filled by a kernel (k_fill_empty)
+// d_bits: the bit table in the stream's scratch block (per stream: map updates on different streams do not share it; the caller holds the
+// block's lock).  bits_ready: k_tf_build has already left the bit table and its column mask there (vkv_update_transfer_function); d_tf is
+// then not read, and the map is filled by a kernel (k_fill_empty)
 int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
-                         VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s, bool bits_ready)
+                         VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s, uint32_t *d_bits, bool bits_ready)
 {
-	uint8_t *scratch = stream_scratch(ctx, s);        // per stream: map updates on different streams do not share the bit table
-	if (!scratch)
-		return VKV_E_UNSUPPORTED;
-	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
 	if (!bits_ready)
 	{
 		hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
@@ -1681,13 +1678,10 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 	return check_launch(ctx, "occupancy_map");
 }
 
+// d_bits: the bit table in the stream's scratch block (the caller holds its lock)
 int launch_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const VkvTransferFunctionUniform *tf, VkvExtent3D e,
-                                uint64_t *d_count, hipStream_t s)
+                                uint64_t *d_count, hipStream_t s, uint32_t *d_bits)
 {
-	uint8_t *scratch = stream_scratch(ctx, s);
-	if (!scratch)
-		return VKV_E_UNSUPPORTED;
-	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
 	hipLaunchKernelGGL(k_tf_bits_analytic, dim3(8), dim3(256), 0, s, d_bits, tf->intensity_min, tf->intensity_range_inv, tf->gradient_min,
 	                   tf->gradient_range_inv);
 	const hipError_t me = hipMemsetAsync(d_count, 0, sizeof(uint64_t), s);
@@ -2227,7 +2221,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE, transform = aniso || skipping_type == VKV_SKIP_DISTANCE;
 	int        blk[3] = {1, 1, 1};
 	uint32_t   c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
-	uint8_t *  scratch = nullptr;
+	StreamScratch scratch;        // held from the bit table to the last map pass
 	if (d_maps)
 	{
 		if (transform && me.width > 2048)
@@ -2238,7 +2232,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 		const int cpb = 256 / blk[0] > 0 ? 256 / blk[0] : 1;
 		if ((uint64_t) ((me.width + cpb - 1) / cpb) * me.height > 0xffffffull || me.depth > 65535u)
 			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map too large for one launch");
-		if (!(scratch = stream_scratch(ctx, s)))
+		if (!(scratch = stream_scratch(ctx, s)).p)
 			return VKV_E_UNSUPPORTED;
 	}
 	// ---- 1. convert the source box into the volume
@@ -2279,7 +2273,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 	if (!d_maps)
 		return VKV_OK;
 	// ---- 4. occupancy of the cells that meet the grown box, from the bit table of the texture (staged in the stream's scratch block)
-	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch + kTfBitsOffset);
+	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset);
 	hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
 	hipLaunchKernelGGL(k_tf_columns, dim3(1), dim3(256), 0, s, d_bits);
 	if ((rc = check_launch(ctx, "update_volume_region: bit table")) != VKV_OK)
@@ -2287,7 +2281,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 	uint8_t *occ = d_maps[aniso ? 7 : 0];
 	if (c0[0] == 0 && c0[1] == 0 && c0[2] == 0 && c1[0] == me.width && c1[1] == me.height && c1[2] == me.depth)
 	{        // every cell: the whole-map pass writes them all (its EMPTY fill is a kernel here)
-		if ((rc = launch_occupancy_map(ctx, d_vol, d_grad, d_tf, tf, e, occ, me, s, true)) != VKV_OK)
+		if ((rc = launch_occupancy_map(ctx, d_vol, d_grad, d_tf, tf, e, occ, me, s, d_bits, true)) != VKV_OK)
 			return rc;
 	}
 	else

@@ -556,7 +556,7 @@ int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream
 		load_render_code(P[i].options.skipping_type, P[i].options.early_ray_termination != 0);
 	}
 	load_feedback_code();
-	if (!stream_scratch(ctx, s, true))
+	if (!stream_scratch(ctx, s, true).p)
 		return VKV_E_UNSUPPORTED;
 	return VKV_OK;
 }
@@ -565,7 +565,8 @@ int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream
 int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, const float *alpha_luts, hipStream_t s)
 {
 	// the argument blocks go through this stream's scratch buffer: an earlier batch on the same stream has finished with it by the
-	// time the copy (same stream) runs
+	// time the copy (same stream) runs, and the block's lock keeps other threads' writes into it (same stream) out from the copy to the
+	// launch
 	static_assert(kMaxBatch * sizeof(RayMarchArgs) <= kScratchBytes - kBatchArgsOffset, "batch argument blocks must fit the stream scratch");
 	static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kCaptureSlotBytes, "a captured launch's upload must fit its pinned slot");
 	const VkvTuning           T = tuning_of(ctx);
@@ -601,11 +602,11 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 	bool any_sort = false;
 	for (uint32_t i = 0; i < n && P[0].options.early_ray_termination != 0; ++i)
 		any_sort = apply_feedback(ctx, host[i], s) || any_sort;
-	uint8_t *scratch = stream_scratch(ctx, s);
-	if (!scratch)
+	const StreamScratch scratch = stream_scratch(ctx, s);
+	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
-	RayMarchArgs *   d_frames = reinterpret_cast<RayMarchArgs *>(scratch + kBatchArgsOffset);
-	uint32_t *       d_heads  = reinterpret_cast<uint32_t *>(scratch + kBatchArgsOffset - kPullHeadsBytes);
+	RayMarchArgs *   d_frames = reinterpret_cast<RayMarchArgs *>(scratch.p + kBatchArgsOffset);
+	uint32_t *       d_heads  = reinterpret_cast<uint32_t *>(scratch.p + kBatchArgsOffset - kPullHeadsBytes);
 	// one upload: the (zeroed) ticket counters of the pull kernel, then the argument blocks
 	std::vector<uint8_t> upload(kPullHeadsBytes + n * sizeof(RayMarchArgs), 0);
 	std::memcpy(upload.data() + kPullHeadsBytes, host.data(), n * sizeof(RayMarchArgs));
@@ -622,7 +623,7 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 				return;
 			std::lock_guard<std::mutex> lock(ctx->mutex);
 			if (index < ctx->capture_slots.size())
-				ctx->capture_slots[index].in_use = false, ctx->capture_slots[index].owner = nullptr;
+				ctx->capture_slots[index].in_use = false, ctx->capture_slots[index].owner = VkvStreamKey{};
 		}
 	} slot_guard{ctx, 0, false};
 	{        // A stream that is being captured into a hipGraph records the copy's SOURCE POINTER and reads it at every replay: the block then has to
@@ -662,7 +663,7 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 				ctx->capture_slots.push_back(c);
 				slot = &ctx->capture_slots.back();
 			}
-			slot->in_use = true, slot->owner = s;
+			slot->in_use = true, slot->owner = stream_key(s);
 			slot_guard.index = (size_t) (slot - ctx->capture_slots.data()), slot_guard.armed = true;
 			std::memcpy(slot->pinned, upload.data(), upload.size());
 			upload_src = slot->pinned;

@@ -66,11 +66,12 @@ static int launch_one(vkv_ctx *ctx, int sched, const VkvTuning &T, RayMarchArgs 
 		    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_raymarch_persistent<SKIP, ERT, GRAD, PACKED>, 256, 0) != hipSuccess || per_cu < 1)
 			return set_error(ctx, VKV_E_NO_DEVICE, "render: occupancy query failed");
 		const uint32_t resident = (uint32_t) per_cu * (uint32_t) prop.multiProcessorCount;
-		// the tile-queue heads live in this stream's scratch: launches on other streams have their own
-		uint8_t *scratch = stream_scratch(ctx, s);
-		if (!scratch)
+		// the tile-queue heads live in this stream's scratch: launches on other streams have their own; its lock is held until the kernel
+		// that reads them is enqueued
+		const StreamScratch scratch = stream_scratch(ctx, s);
+		if (!scratch.p)
 			return VKV_E_UNSUPPORTED;
-		a.queue_heads      = reinterpret_cast<uint32_t *>(scratch + kQueueHeadsOffset);
+		a.queue_heads      = reinterpret_cast<uint32_t *>(scratch.p + kQueueHeadsOffset);
 		const hipError_t e = hipMemsetAsync(a.queue_heads, 0, 8 * sizeof(uint32_t), s);
 		if (e != hipSuccess)
 			return set_error(ctx, (int) e, "render: queue reset: %s", hipGetErrorString(e));

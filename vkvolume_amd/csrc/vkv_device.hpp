@@ -9,7 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <memory>
 #include <mutex>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -177,8 +180,12 @@ __host__ __device__ __forceinline__ size_t packed_brick_offset(int bx, int by, i
 }        // namespace vkv
 
 // Host-side context (capi.hip owns it).
-// Device scratch is handed out PER STREAM (stream_scratch): calls on one stream are ordered, so they may share a buffer; calls on
-// different streams never touch the same bytes, which makes every entry point re-entrant across streams of one context.
+// Device scratch is handed out PER STREAM (stream_scratch): calls on different streams never touch the same bytes.  Calls on one stream are
+// ordered on the device, but an entry point enqueues several operations that pass data through the block (a bit table, argument blocks,
+// queue heads), and two host threads enqueueing on the same stream could interleave them: each block has a lock, held by the entry point
+// from its first write into the block to its last enqueue (stream_scratch returns the block locked).  hipStreamPerThread is one handle for
+// a different stream in every thread: per-stream state is keyed by (handle, calling thread) for it (stream_key).  Lock order: a block's
+// lock, then ctx->mutex briefly; ctx->mutex is never held while a block's lock is being taken.
 //
 // Device memory policy (include/vkvolume_amd.h, "Conventions"): vkv_create allocates one ARENA with two regions - the scratch blocks of
 // up to kScratchReserve streams, and the small immutable tables a launch needs (tile start orders, address tables) - plus a pinned host
@@ -187,6 +194,15 @@ __host__ __device__ __forceinline__ size_t packed_brick_offset(int bx, int by, i
 // re-used while a launch could read it: tables stay until vkv_trim (a set-up call that waits for the device, then empties the region) or
 // vkv_destroy; when the region is full a launch runs without the table.  Only set-up calls (vkv_prepare_render, vkv_register_target) fall
 // back to hipMalloc when a region is full.
+// the key of a stream's state in the context: the handle, and for hipStreamPerThread also the calling thread
+struct VkvStreamKey
+{
+	hipStream_t     stream = nullptr;
+	std::thread::id thread;
+	bool operator<(const VkvStreamKey &o) const { return stream != o.stream ? stream < o.stream : thread < o.thread; }
+	bool operator==(const VkvStreamKey &o) const { return stream == o.stream && thread == o.thread; }
+};
+
 struct vkv_ctx
 {
 	int   device;
@@ -213,13 +229,20 @@ struct vkv_ctx
 	struct CaptureSlot
 	{
 		uint8_t *   pinned = nullptr, *device = nullptr;
-		hipStream_t owner = nullptr;
-		bool        in_use = false, pooled = false;
+		VkvStreamKey owner;
+		bool         in_use = false, pooled = false;
 	};
 	uint8_t *                capture_pool = nullptr, *capture_pool_device = nullptr;
 	std::vector<CaptureSlot> capture_slots;
-	std::unordered_map<hipStream_t, uint8_t *> scratch;        // stream -> kScratchBytes of device memory
-	std::vector<uint8_t *>                     free_scratch;   // blocks given back by vkv_release_stream
+	// a stream's scratch block: kScratchBytes of device memory and the lock of the entry point that is passing data through it
+	struct ScratchBlock
+	{
+		uint8_t *  p = nullptr;
+		std::mutex lock;
+	};
+	std::vector<std::unique_ptr<ScratchBlock>> scratch_blocks;        // every block the context has handed out (stable addresses)
+	std::map<VkvStreamKey, ScratchBlock *>     scratch;               // stream -> its block
+	std::vector<ScratchBlock *>                free_scratch;          // blocks given back by vkv_release_stream
 	// an immutable device table with its host copy (the source of the asynchronous upload: it must outlive the call)
 	struct Table
 	{
@@ -269,9 +292,15 @@ namespace vkv
 {
 int  set_error(vkv_ctx *ctx, int code, const char *fmt, ...);
 int  check_launch(vkv_ctx *ctx, const char *what);
-// this stream's scratch block (out of the arena on first use, kept until vkv_release_stream / vkv_destroy); nullptr + error set when
-// there is no room
-uint8_t *stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = false);
+VkvStreamKey stream_key(hipStream_t stream);
+// this stream's scratch block (out of the arena on first use, kept until vkv_release_stream / vkv_destroy), LOCKED until the object goes:
+// an entry point keeps it from its first write into the block to its last enqueue.  p == nullptr + error set when there is no room.
+struct StreamScratch
+{
+	uint8_t *                    p = nullptr;
+	std::unique_lock<std::mutex> lock;
+};
+StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = false);
 // start order of a tile schedule: entry indices sorted by the distance of the tile's centre from the image centre (device array of
 // `count` uint32, cached per schedule shape); nullptr when the table cannot be allocated (the kernel then takes the tiles in order)
 // Per-axis byte offsets of the packed sampling image: the offset of the footprint whose padded base texel is (bx, by, bz) is
