@@ -599,6 +599,45 @@ int vkv_assemble_frames(vkv_ctx *ctx, const void *d_tiles, void *d_gathered, voi
                         uint32_t image_height, uint32_t tile_width, uint32_t tile_height, const VkvTileRect *rects, uint32_t n_ranks, uint32_t rank,
                         uint32_t bytes_per_pixel, int32_t root, const int32_t *roots, void *nccl_comm, void *stream);
 
+/* ---- maximum-intensity projection ------------------------------------------------------------------------------
+ * The per-cell max map: one byte per cell of map_extent (block = ceil(extent / map_extent) per axis, as for the occupancy map), in map order
+ * (x fastest).  Each byte is the largest voxel of the cell's voxel box grown by ONE voxel on every side, clipped to the volume: every voxel that
+ * a trilinear sample within half a voxel of the cell can read.  Cells past the volume hold 0.  box == NULL rebuilds every cell; a box rebuilds
+ * every cell whose grown box meets it, so after vkv_update_volume_region(box) a vkv_max_map(box) on the same stream leaves the map byte-equal to
+ * a full rebuild.  Every argument is checked before anything is enqueued: a rejected call writes nothing.  Kernels only: no memset, no
+ * allocation, no host wait, so after one direct call on `stream` it can be captured into a hipGraph.  Voxel rows are read at any width and
+ * alignment, never past the last row. */
+int vkv_max_map(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box, uint8_t *d_max_map,
+                void *stream);
+
+typedef struct VkvMipOptions
+{
+	float          threshold;       /* a sample counts if its filtered intensity is > threshold (finite; 1.0 or more: nothing counts)      */
+	float          window_max;      /* grey level g = clamp((m - threshold) / (window_max - threshold), 0, 1); window_max <= threshold: g = 1 */
+	const uint8_t *d_max_map;       /* vkv_max_map of d_volume with params->map_extent, or NULL (dense: every sample is filtered)          */
+	float *        d_out_intensity; /* m per pixel (0 without a counted sample), indexed like the other outputs; or NULL                   */
+	uint32_t       flags;           /* must be 0 */
+} VkvMipOptions;
+
+/* Maximum-intensity projection of one volume.  The rays and samples are vkv_render's with VKV_SKIP_NONE (ray generator, box, clipping plane,
+ * options.depth_attachment with d_in_depth, transfer_function.sampling_factor, sample i at fma(i, step, entry)); a sample's value v_i is the
+ * integrator's filtered intensity (linear buffer or d_packed_volume: the same bits).  v_i counts if v_i > threshold; m = the largest counted
+ * v_i, k = the first index where v_i == m.  A pixel with a fragment and a counted sample gets d_out_intensity = m, RGBA32F (g, g, g, 1), RGBA8
+ * its round-to-nearest, d_out_depth the reverse-Z depth of sample k (the integrator's first-hit formula).  Every other pixel gets what the
+ * integrator gives a pixel without colour: clear colour, intensity 0, depth 0 (the scene depth under depth_attachment).  d_out_counts (3 x u32
+ * per pixel): samples filtered, max-map bytes read, samples skipped; [0] + [2] is the ray's sample count on every path.
+ * With d_max_map a ray jumps over the samples of a cell whose byte cannot beat max(threshold, its best so far), and stops once its best is
+ * 255 / 255: the results equal the dense path's bit for bit (the argument is in DESIGN.md §5.9).
+ * Read: camera, ray_cast, ray_gen, options.clip_distance (through the uniforms), options.depth_attachment / d_in_depth, sampling_factor,
+ * volume_extent, map_extent (with a max map), d_volume, d_packed_volume, the outputs and `tiles` (whole image, rect, compact, strided: a
+ * compact per-rank share assembles through vkv_scatter_tiles / vkv_assemble_frame as a render share does).  Ignored: skipping_type, distance
+ * maps, transfer-function texture and tables, gradient, early_ray_termination.  VKV_E_UNSUPPORTED: blend_over_target, tiles.fill_outside,
+ * options.test != VKV_TEST_NONE.  VKV_E_INVALID_ARGUMENT: a non-finite threshold or NaN window_max, a max map without a valid map_extent,
+ * flags != 0, and what vkv_render rejects of the fields read.  Every argument is checked before anything is enqueued: a rejected call writes
+ * nothing.  The call enqueues one kernel and nothing else (no scratch block, no table, no allocation, no host wait; the kernels use no
+ * scratch memory), so after one direct call on `stream` it can be captured into a hipGraph; it replays with the parameters it was captured with. */
+int vkv_render_mip(vkv_ctx *ctx, const VkvRenderParams *params, const VkvMipOptions *mip, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

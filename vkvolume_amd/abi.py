@@ -126,6 +126,12 @@ class RenderParams(C.Structure):
                 ("blend_over_target", C.c_uint32)]
 
 
+
+class MipOptions(C.Structure):
+    """VkvMipOptions (vkv_render_mip): threshold, grey window, optional max map (vkv_max_map), optional intensity output, flags (0)"""
+    _fields_ = [("threshold", C.c_float), ("window_max", C.c_float), ("d_max_map", C.c_void_p), ("d_out_intensity", C.c_void_p),
+                ("flags", C.c_uint32)]
+
 class Tuning(C.Structure):
     """VkvTuning"""
     _fields_ = [("struct_size", C.c_uint32), ("scheduler", C.c_int32), ("batch_mode", C.c_int32), ("batch_sequential", C.c_int32),

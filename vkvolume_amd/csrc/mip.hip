@@ -1,0 +1,470 @@
+// mip.hip — maximum-intensity projection: the per-cell max map (vkv_max_map) and the MIP render (vkv_render_mip).  DESIGN.md §5.9 pins the
+// definition and says why skipping over the max map gives the dense path's bits.
+//
+// Max map: one byte per occupancy-map cell, the largest voxel of the cell's voxel box grown by one voxel per side (clipped to the volume): every
+// voxel a trilinear sample whose voxel coordinate lies within half a voxel of the cell can read.  One lane per cell, voxel rows read a dword at
+// a time at any alignment (load4_clipped: nothing past a row's last byte).
+//
+// Render: the integrator's rays (ray_setup<VKV_SKIP_NONE>, unchanged), one lane per ray, a workgroup = 16x16 pixels dealt to the XCDs and
+// started as the integrator's are, a wave = the 64-pixel patch shape the integrator picks for the view (4x16, 8x8 or 16x4).
+// A sample is the integrator's filtered intensity (sample_linear, or sample_packed<false>: four footprint dwords).  The skipping variant reads
+// the max-map byte of the cell a ray enters and jumps over the samples of that cell when the byte cannot beat max(threshold, best so far).
+#include <algorithm>
+#include <cmath>
+
+#include "raymarch_core.hpp"
+
+namespace
+{
+
+// voxels x .. x + 3 of a row of W voxels (x < W) as one dword; the bytes of x + i >= W are zero
+__device__ __forceinline__ uint32_t load4_clipped(const uint8_t *row, int x, int W)
+{
+	if (x + 4 <= W)
+		return load_u32_any(row + x);
+	if (W >= 4)
+		return load_u32_any(row + (W - 4)) >> (8 * (x + 4 - W));
+	uint32_t r = 0;
+	for (int i = 0; x + i < W; ++i)
+		r |= (uint32_t) row[x + i] << (8 * i);
+	return r;
+}
+
+__device__ __forceinline__ uint32_t max_byte(uint32_t d) { return max(max(d & 255u, (d >> 8) & 255u), max((d >> 16) & 255u, d >> 24)); }
+
+struct MaxMapArgs
+{
+	const uint8_t *vol;
+	uint8_t *      map;
+	int            W, H, D, mw, mh, bx, by, bz;
+	int            cx0, cy0, cz0, ncx, ncy, ncz;        // the launch's cells
+};
+
+__global__ void __launch_bounds__(256) k_max_map(const MaxMapArgs a)
+{
+	const uint64_t t = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+	if (t >= (uint64_t) a.ncx * (uint64_t) a.ncy * (uint64_t) a.ncz)
+		return;
+	const int      cx = a.cx0 + (int) (t % (uint64_t) a.ncx);
+	const uint64_t r  = t / (uint64_t) a.ncx;
+	const int      cy = a.cy0 + (int) (r % (uint64_t) a.ncy), cz = a.cz0 + (int) (r / (uint64_t) a.ncy);
+	uint32_t       m  = 0u;
+	if (cx * a.bx < a.W && cy * a.by < a.H && cz * a.bz < a.D)        // (cells past the volume hold 0)
+	{
+		const int x0 = max(cx * a.bx - 1, 0), x1 = min(cx * a.bx + a.bx, a.W - 1);        // inclusive
+		const int y0 = max(cy * a.by - 1, 0), y1 = min(cy * a.by + a.by, a.H - 1);
+		const int z0 = max(cz * a.bz - 1, 0), z1 = min(cz * a.bz + a.bz, a.D - 1);
+		for (int z = z0; z <= z1; ++z)
+			for (int y = y0; y <= y1; ++y)
+			{
+				const uint8_t *row = a.vol + ((size_t) z * (size_t) a.H + (size_t) y) * (size_t) a.W;
+				for (int x = x0; x <= x1; x += 4)
+				{
+					const int      nv = min(4, x1 + 1 - x);
+					const uint32_t d  = load4_clipped(row, x, a.W) & (nv == 4 ? ~0u : ((1u << (8 * nv)) - 1u));
+					m                 = max(m, max_byte(d));
+				}
+			}
+	}
+	a.map[((size_t) cz * (size_t) a.mh + (size_t) cy) * (size_t) a.mw + (size_t) cx] = (uint8_t) m;
+}
+
+struct MipArgs
+{
+	RayMarchArgs   A;               // the fields ray_setup, start_entry and the samplers read (fill_mip_args)
+	float          threshold, window_max;
+	const uint8_t *max_map;         // skipping variant only
+	float *        out_intensity;   // or null
+	int            bx, by, bz;      // voxels per map cell per axis
+	int            lcx, lcy, lcz;   // last map cell per axis that holds a voxel: (extent - 1) / block
+	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
+};
+
+// the largest value a sample can take (a footprint of 255s)
+constexpr float kMaxSample = 255.0f * kInv255;
+
+template <bool PACKED>
+__device__ __forceinline__ float mip_sample(const RayMarchArgs &A, float posx, float posy, float posz)
+{
+	if (PACKED)
+	{
+		float v, unused;
+		sample_packed<false>(A.packed, A.W, A.H, A.D, A.pmx, A.pmy, posx, posy, posz, v, unused);
+		return v;
+	}
+	return sample_linear(A.vol, A.W, A.H, A.D, posx, posy, posz);
+}
+
+// samples i .. i + G - 1 of a ray: every load first, then the filters (the same bits as mip_sample one by one)
+constexpr int kDenseGroup = 4;
+template <bool PACKED, int G>
+__device__ __forceinline__ void mip_samples(const RayMarchArgs &A, const Ray &R, int i, float *v)
+{
+	if (PACKED)
+	{
+		uint32_t q[G][4];
+		float    w[G][3];
+#pragma unroll
+		for (int j = 0; j < G; ++j)
+		{
+			const float    fi = (float) (i + j);
+			const uint8_t *b  = packed_footprint(A.packed, A.W, A.H, A.D, A.pmx, A.pmy, __builtin_fmaf(fi, R.sx, R.ex), __builtin_fmaf(fi, R.sy, R.ey),
+			                                     __builtin_fmaf(fi, R.sz, R.ez), w[j][0], w[j][1], w[j][2]);
+			q[j][0] = *reinterpret_cast<const u32_align2 *>(b);
+			q[j][1] = *reinterpret_cast<const u32_align2 *>(b + 10);
+			q[j][2] = *reinterpret_cast<const u32_align2 *>(b + 50);
+			q[j][3] = *reinterpret_cast<const u32_align2 *>(b + 60);
+		}
+#pragma unroll
+		for (int j = 0; j < G; ++j)
+		{
+			float unused;
+			packed_filter<false>(q[j][0], q[j][1], q[j][2], q[j][3], w[j][0], w[j][1], w[j][2], v[j], unused);
+		}
+	}
+	else
+	{
+#pragma unroll
+		for (int j = 0; j < G; ++j)
+		{
+			const float fi = (float) (i + j);
+			v[j] = sample_linear(A.vol, A.W, A.H, A.D, __builtin_fmaf(fi, R.sx, R.ex), __builtin_fmaf(fi, R.sy, R.ey), __builtin_fmaf(fi, R.sz, R.ez));
+		}
+	}
+}
+
+// c = the sampler's voxel coordinate of a sample on one axis; true when it lies in [lo - 1, lo + b): the sample then reads only voxels of the
+// cell [lo, lo + b) grown by one voxel
+__device__ __forceinline__ bool in_grown(float c, int lo, int b) { return c >= (float) (lo - 1) && c < (float) (lo + b); }
+
+template <bool PACKED, bool SKIP>
+__global__ void __launch_bounds__(256) k_mip(const MipArgs M)
+{
+	const RayMarchArgs &A = M.A;
+	// the integrator's deal of workgroups (lean_block): XCD x = id & 7 takes the schedule's tiles x, x + 8, ..., whose blocks are neighbouring
+	// ids on that XCD (L2 locality); a schedule that holds every tile of its rectangle starts them ring by ring from the middle (start_entry),
+	// so the long rays through the volume start first
+	const uint32_t x = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
+	if (rank >= A.tile_count)
+		return;
+	const uint32_t k_tile = A.order_h ? start_entry(A, rank) : rank;
+	if (k_tile >= A.tile_count)
+		return;
+	// the wave's 64 pixels: a (1 << wave_pw_log2)-wide patch of the 16x16 block, the shape the integrator picks for the view (fill_render_args)
+	const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u, pw = A.wave_pw_log2;
+	const uint32_t bx = (w & ((16u >> pw) - 1u)) << pw, by = (w >> (4u - pw)) * (64u >> pw);
+	const uint32_t t  = A.tile_first + k_tile * A.tile_stride;
+	const uint32_t lx = (sb % A.blocks_per_tile_x) * 16u + bx + (lane & ((1u << pw) - 1u)), ly = (sb / A.blocks_per_tile_x) * 16u + by + (lane >> pw);
+	const uint32_t px = A.org_x + (t % A.tiles_x) * A.tile_w + lx, py = A.org_y + (t / A.tiles_x) * A.tile_h + ly;
+	const uint32_t o  = A.compact ? (k_tile * A.tile_h + ly) * A.tile_w + lx : py * A.img_w + px;
+	if (px >= A.img_w || py >= A.img_h)
+		return;
+	Ray R;
+	R.o                = o;
+	const bool marched = ray_setup<VKV_SKIP_NONE>(A, px, py, R);
+	float      best    = M.threshold;        // max(threshold, largest counted sample)
+	int        k       = -1;                 // first index of the largest counted sample
+	uint32_t   n_filt = 0, n_probe = 0, n_skip = 0;
+	if (!SKIP && marched)
+	{
+		// dense: kDenseGroup samples per round, their footprint loads all issued before the first filter (memory-level parallelism: a lane has
+		// nothing else to hide the gather latency behind); the groups are taken in order, so `k` stays the first index of the maximum
+		const int n = R.n_steps;
+		int       i = 0;
+		for (; i + kDenseGroup <= n; i += kDenseGroup)
+		{
+			float v[kDenseGroup];
+			mip_samples<PACKED, kDenseGroup>(A, R, i, v);
+#pragma unroll
+			for (int j = 0; j < kDenseGroup; ++j)
+				if (v[j] > best)
+					best = v[j], k = i + j;
+		}
+		for (; i < n; ++i)
+		{
+			const float fi = (float) i;
+			const float v  = mip_sample<PACKED>(A, __builtin_fmaf(fi, R.sx, R.ex), __builtin_fmaf(fi, R.sy, R.ey), __builtin_fmaf(fi, R.sz, R.ez));
+			if (v > best)
+				best = v, k = i;
+		}
+		n_filt = (uint32_t) n;
+	}
+	if (SKIP && marched)
+	{
+		const int   n  = R.n_steps;
+		const float fW = (float) A.W, fH = (float) A.H, fD = (float) A.D;
+		uint32_t    last_cell = ~0u;
+		int         i         = 0;
+		while (i < n)
+		{
+			const float fi   = (float) i;
+			const float posx = __builtin_fmaf(fi, R.sx, R.ex), posy = __builtin_fmaf(fi, R.sy, R.ey), posz = __builtin_fmaf(fi, R.sz, R.ez);
+			if (SKIP)
+			{
+				// the sampler's own voxel coordinates of this sample (sample_linear / packed_footprint)
+				const float cx = __builtin_fmaf(posx, fW, -0.5f), cy = __builtin_fmaf(posy, fH, -0.5f), cz = __builtin_fmaf(posz, fD, -0.5f);
+				const int   mx = i_clamp((int) __builtin_floorf((cx + 0.5f) * M.rbx), 0, M.lcx);
+				const int   my = i_clamp((int) __builtin_floorf((cy + 0.5f) * M.rby), 0, M.lcy);
+				const int   mz = i_clamp((int) __builtin_floorf((cz + 0.5f) * M.rbz), 0, M.lcz);
+				const uint32_t cell = ((uint32_t) mz * (uint32_t) A.mh + (uint32_t) my) * (uint32_t) A.mw + (uint32_t) mx;
+				if (cell != last_cell)
+				{
+					++n_probe;
+					last_cell = cell;
+					const int lx = mx * M.bx, ly = my * M.by, lz = mz * M.bz;
+					if ((float) M.max_map[cell] * kInv255 <= best && in_grown(cx, lx, M.bx) && in_grown(cy, ly, M.by) && in_grown(cz, lz, M.bz))
+					{
+						// samples i .. i + kk: the estimate aims a quarter voxel past the cell's edge (inside the half-voxel margin); the last one is
+						// checked exactly below, and the sampler's coordinates are monotone in the sample index, so every sample between lies in the
+						// grown cell too
+						const float sx = R.sx * fW, sy = R.sy * fH, sz = R.sz * fD;
+						const float tx = sx > 0.0f ? ((float) (lx + M.bx) - 0.25f - cx) / sx : (sx < 0.0f ? ((float) lx - 0.75f - cx) / sx : INFINITY);
+						const float ty = sy > 0.0f ? ((float) (ly + M.by) - 0.25f - cy) / sy : (sy < 0.0f ? ((float) ly - 0.75f - cy) / sy : INFINITY);
+						const float tz = sz > 0.0f ? ((float) (lz + M.bz) - 0.25f - cz) / sz : (sz < 0.0f ? ((float) lz - 0.75f - cz) / sz : INFINITY);
+						const float tm = g_min(g_min(tx, ty), g_min(tz, (float) (n - 1 - i)));
+						int         kk = tm > 0.0f ? (int) tm : 0;
+						if (kk > 0)
+						{
+							const float fl = (float) (i + kk);
+							const float qx = __builtin_fmaf(__builtin_fmaf(fl, R.sx, R.ex), fW, -0.5f);
+							const float qy = __builtin_fmaf(__builtin_fmaf(fl, R.sy, R.ey), fH, -0.5f);
+							const float qz = __builtin_fmaf(__builtin_fmaf(fl, R.sz, R.ez), fD, -0.5f);
+							if (!(in_grown(qx, lx, M.bx) && in_grown(qy, ly, M.by) && in_grown(qz, lz, M.bz)))
+								kk = 0;
+						}
+						i += kk + 1;
+						n_skip += (uint32_t) (kk + 1);
+						last_cell = ~0u;
+						continue;
+					}
+				}
+			}
+			const float v = mip_sample<PACKED>(A, posx, posy, posz);
+			++n_filt;
+			if (v > best)
+				best = v, k = i;
+			++i;
+			if (SKIP && best >= kMaxSample)
+			{        // nothing can beat it
+				n_skip += (uint32_t) (n - i);
+				break;
+			}
+		}
+	}
+	const size_t po = o;
+	float        g = 0.0f, a = 0.0f, intensity = 0.0f;
+	float        depth = A.depth_attachment ? A.in_depth[po] : 0.0f;        // what the integrator gives a pixel without colour
+	if (k >= 0)
+	{
+		intensity = best;
+		g         = M.window_max <= M.threshold ? 1.0f : g_clamp((best - M.threshold) / (M.window_max - M.threshold), 0.0f, 1.0f);
+		a         = 1.0f;
+		if (A.out_depth)
+		{        // the integrator's first_hit depth (ray_finish), at sample k
+			const float fk   = (float) k;
+			const float p[4] = {__builtin_fmaf(fk, R.sx, R.ex) - 0.5f, __builtin_fmaf(fk, R.sy, R.ey) - 0.5f, __builtin_fmaf(fk, R.sz, R.ez) - 0.5f, 1.0f};
+			float       a4[4], b4[4], c4[4];
+			mat4_mul_vec4(A.model, p, a4);
+			mat4_mul_vec4(A.view, a4, b4);
+			mat4_mul_vec4(A.proj, b4, c4);
+			depth = c4[2] / c4[3];
+		}
+	}
+	if (A.out_color)
+		store_float4_nt(A.out_color, po, g, g, g, a);
+	if (A.out_rgba8)
+	{
+		const uint32_t q = (uint32_t) quantise_rgba8(g);
+		__builtin_nontemporal_store(q | (q << 8) | (q << 16) | ((uint32_t) quantise_rgba8(a) << 24), reinterpret_cast<uint32_t *>(A.out_rgba8) + po);
+	}
+	if (M.out_intensity)
+		__builtin_nontemporal_store(intensity, M.out_intensity + po);
+	if (A.out_counts)
+		A.out_counts[po * 3 + 0] = n_filt, A.out_counts[po * 3 + 1] = n_probe, A.out_counts[po * 3 + 2] = n_skip;
+	if (A.out_depth)
+		__builtin_nontemporal_store(depth, A.out_depth + po);
+}
+
+bool extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
+bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
+uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
+
+// the checks of vkv_render_mip; VKV_OK or the code (nothing is enqueued before they pass)
+int check_mip(vkv_ctx *ctx, const VkvRenderParams *P, const VkvMipOptions *M)
+{
+	if (!P || !M)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: null params or options");
+	if (M->flags != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: flags must be 0");
+	if (!std::isfinite(M->threshold) || std::isnan(M->window_max))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: threshold must be finite and window_max not NaN");
+	if (P->blend_over_target)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "render_mip: blend_over_target is not supported");
+	if (P->tiles.fill_outside)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "render_mip: tiles.fill_outside is not supported");
+	if (P->options.test != VKV_TEST_NONE)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "render_mip: test modes are not supported");
+	if (P->options.depth_attachment && !P->d_in_depth)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: options.depth_attachment needs d_in_depth");
+	if (!extent_ok(P->volume_extent) || P->image_width == 0 || P->image_height == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: zero extent");
+	if (!P->d_volume)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: null volume");
+	if (!(P->transfer_function.sampling_factor > 0.0f))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: sampling_factor must be positive");
+	if (M->d_max_map)
+	{
+		if (!map_extent_ok(P->volume_extent, P->map_extent))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: the max map needs a valid map_extent");
+		if ((uint64_t) P->map_extent.width * P->map_extent.height * P->map_extent.depth > 0xffffffffull)
+			return set_error(ctx, VKV_E_UNSUPPORTED, "render_mip: max maps with more than 2^32 cells are not supported");
+	}
+	const VkvTileSchedule &t = P->tiles;
+	if (t.tile_width == 0 || t.tile_height == 0 || (t.tile_width % 16) || (t.tile_height % 16) || t.tile_stride == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: tile size must be a positive multiple of 16 and tile_stride > 0");
+	const uint64_t tiles_x = (P->image_width + t.tile_width - 1) / t.tile_width, tiles_y = (P->image_height + t.tile_height - 1) / t.tile_height;
+	const bool     whole   = t.rect.w == 0 || t.rect.h == 0;
+	if (!whole && ((uint64_t) t.rect.x0 + t.rect.w > tiles_x || (uint64_t) t.rect.y0 + t.rect.h > tiles_y))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: the schedule's tile rectangle runs past the image");
+	const uint64_t scheduled = whole ? tiles_x * tiles_y : (uint64_t) t.rect.w * t.rect.h;
+	if (t.tile_count && (uint64_t) t.tile_first + (uint64_t) (t.tile_count - 1) * t.tile_stride >= scheduled)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: tile schedule runs past the %s", whole ? "image" : "tile rectangle");
+	if (P->d_packed_volume && ((uintptr_t) P->d_packed_volume & 255u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: d_packed_volume must be 256-byte aligned");
+	if (!P->d_out_color && !P->d_out_rgba8 && !P->d_out_counts && !P->d_out_depth && !M->d_out_intensity)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: no output buffer");
+	const uint64_t nb = (uint64_t) (t.tile_width / 16) * (t.tile_height / 16) * t.tile_count;
+	if (nb > 0x3fffffffull || (uint64_t) P->image_width * P->image_height > 0xffffffffull / 4 || nb * 256 > 0xffffffffull / 4)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "render_mip: frame too large for one launch");
+	return VKV_OK;
+}
+
+// VkvRenderParams -> the fields of RayMarchArgs the MIP kernel reads (the rest stays zero)
+void fill_mip_args(const VkvRenderParams *P, RayMarchArgs &a)
+{
+	a = RayMarchArgs{};
+	for (int i = 0; i < 3; ++i)
+		a.dir00[i] = P->ray_gen.dir00[i], a.ddx[i] = P->ray_gen.ddx[i], a.ddy[i] = P->ray_gen.ddy[i], a.cam[i] = P->ray_cast.camera_pos_tex[i];
+	for (int i = 0; i < 4; ++i)
+		a.plane_tex[i] = P->ray_cast.plane_tex[i];
+	for (int i = 0; i < 16; ++i)
+		a.model[i] = P->camera.model[i], a.view[i] = P->camera.camera_view[i], a.proj[i] = P->camera.camera_proj[i],
+		a.view_proj_inv[i] = P->camera.camera_view_proj_inv[i], a.model_inv[i] = P->camera.model_inv[i];
+	a.sampling_factor = P->transfer_function.sampling_factor;
+	a.W = (int) P->volume_extent.width, a.H = (int) P->volume_extent.height, a.D = (int) P->volume_extent.depth;
+	a.mw = (int) P->map_extent.width, a.mh = (int) P->map_extent.height, a.md = (int) P->map_extent.depth;
+	a.vol    = P->d_volume;
+	a.packed = static_cast<const uint8_t *>(P->d_packed_volume);
+	{
+		const PackedDims pd = packed_dims(a.W, a.H, a.D);
+		a.pmx = pd.mx, a.pmy = pd.my;
+	}
+	a.out_color = P->d_out_color, a.out_rgba8 = P->d_out_rgba8, a.out_counts = P->d_out_counts, a.out_depth = P->d_out_depth;
+	a.in_depth         = P->options.depth_attachment ? P->d_in_depth : nullptr;
+	a.depth_attachment = P->options.depth_attachment != 0;
+	a.img_w = P->image_width, a.img_h = P->image_height;
+	a.tile_w = P->tiles.tile_width, a.tile_h = P->tiles.tile_height;
+	a.tile_first = P->tiles.tile_first, a.tile_stride = P->tiles.tile_stride, a.tile_count = P->tiles.tile_count, a.compact = P->tiles.compact;
+	const VkvTileRect &r     = P->tiles.rect;
+	const bool         whole = r.w == 0 || r.h == 0;
+	a.tiles_x                = whole ? (a.img_w + a.tile_w - 1) / a.tile_w : r.w;
+	a.org_x = whole ? 0u : r.x0 * a.tile_w, a.org_y = whole ? 0u : r.y0 * a.tile_h;
+	a.blocks_per_tile_x = a.tile_w / 16;
+	a.blocks_per_tile   = a.blocks_per_tile_x * (a.tile_h / 16);
+	a.nblocks           = a.blocks_per_tile * a.tile_count;
+	a.test              = VKV_TEST_NONE;
+	{        // shape of a wave's pixel patch, as the integrator picks it: voxels per pixel step in x against y
+		double vx = 0.0, vy = 0.0;
+		const double dim[3] = {(double) a.W, (double) a.H, (double) a.D};
+		for (int k = 0; k < 3; ++k)
+			vx += (double) a.ddx[k] * dim[k] * (double) a.ddx[k] * dim[k], vy += (double) a.ddy[k] * dim[k] * (double) a.ddy[k] * dim[k];
+		const double q = (vx > 0.0 && vy > 0.0) ? std::sqrt(vx / vy) : 1.0;
+		a.wave_pw_log2 = q >= 1.6 ? 2u : (q <= 1.0 / 1.6 ? 4u : 3u);        // 4x16, 16x4 or 8x8 pixels
+	}
+	// a schedule over every tile of its rectangle (the whole image or VkvTileSchedule.rect) starts in the integrator's ring order
+	const uint32_t rows = whole ? (a.img_h + a.tile_h - 1) / a.tile_h : r.h;
+	a.order_h           = (a.tile_first == 0 && a.tile_stride == 1 && (uint64_t) a.tile_count == (uint64_t) a.tiles_x * rows) ? rows : 0u;
+}
+
+}        // namespace
+
+extern "C" {
+
+int vkv_max_map(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box, uint8_t *d_max_map, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	if (!d_volume || !d_max_map || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: null pointer or bad extent");
+	MaxMapArgs a;
+	a.vol = d_volume, a.map = d_max_map;
+	a.W = (int) extent.width, a.H = (int) extent.height, a.D = (int) extent.depth, a.mw = (int) map_extent.width, a.mh = (int) map_extent.height;
+	a.bx = (int) block_of(extent.width, map_extent.width), a.by = (int) block_of(extent.height, map_extent.height), a.bz = (int) block_of(extent.depth, map_extent.depth);
+	if (box)
+	{
+		const VkvBox b = *box;
+		if (b.width == 0 || b.height == 0 || b.depth == 0)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: empty box");
+		if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width, b.height,
+			                 b.depth);
+		// the cells whose grown voxel box [c b - 1, c b + b] meets [x0, x0 + width - 1]: ceil(x0 / b) - 1 <= c <= (x0 + width) / b, clamped to the map
+		const uint32_t lo[3] = {b.x0, b.y0, b.z0}, n[3] = {b.width, b.height, b.depth}, bs[3] = {(uint32_t) a.bx, (uint32_t) a.by, (uint32_t) a.bz};
+		const uint32_t me[3] = {map_extent.width, map_extent.height, map_extent.depth};
+		int            c0[3], nc[3];
+		for (int k = 0; k < 3; ++k)
+		{
+			const uint32_t up = (uint32_t) (((uint64_t) lo[k] + bs[k] - 1) / bs[k]);        // ceil(x0 / b)
+			const uint32_t first = up > 0 ? up - 1 : 0u, last = std::min((uint32_t) (((uint64_t) lo[k] + n[k]) / bs[k]), me[k] - 1);
+			c0[k] = (int) first, nc[k] = (int) (last - first + 1);
+		}
+		a.cx0 = c0[0], a.cy0 = c0[1], a.cz0 = c0[2], a.ncx = nc[0], a.ncy = nc[1], a.ncz = nc[2];
+	}
+	else
+		a.cx0 = a.cy0 = a.cz0 = 0, a.ncx = (int) map_extent.width, a.ncy = (int) map_extent.height, a.ncz = (int) map_extent.depth;
+	const uint64_t cells  = (uint64_t) a.ncx * a.ncy * a.ncz;
+	const uint64_t groups = (cells + 255) / 256;
+	if (groups > 0x7fffffffull)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "max_map: map too large for one launch");
+	hipLaunchKernelGGL(k_max_map, dim3((uint32_t) groups), dim3(256), 0, (hipStream_t) stream, a);
+	return check_launch(ctx, "max_map");
+}
+
+int vkv_render_mip(vkv_ctx *ctx, const VkvRenderParams *P, const VkvMipOptions *M, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	DeviceGuard guard(ctx->device);
+	const int rc = check_mip(ctx, P, M);
+	if (rc != VKV_OK)
+		return rc;
+	MipArgs m;
+	fill_mip_args(P, m.A);
+	if (m.A.nblocks == 0)
+		return VKV_OK;
+	m.threshold = M->threshold, m.window_max = M->window_max, m.max_map = M->d_max_map, m.out_intensity = M->d_out_intensity;
+	m.bx = m.by = m.bz = 1, m.lcx = m.lcy = m.lcz = 0, m.rbx = m.rby = m.rbz = 1.0f;
+	if (M->d_max_map)
+	{
+		const VkvExtent3D e = P->volume_extent, me = P->map_extent;
+		m.bx = (int) block_of(e.width, me.width), m.by = (int) block_of(e.height, me.height), m.bz = (int) block_of(e.depth, me.depth);
+		m.lcx = (int) (e.width - 1) / m.bx, m.lcy = (int) (e.height - 1) / m.by, m.lcz = (int) (e.depth - 1) / m.bz;
+		m.rbx = 1.0f / (float) m.bx, m.rby = 1.0f / (float) m.by, m.rbz = 1.0f / (float) m.bz;
+	}
+	const hipStream_t s      = (hipStream_t) stream;
+	const dim3        grid((m.A.tile_count + 7u) / 8u * 8u * m.A.blocks_per_tile), block(256);
+	const bool        packed = m.A.packed != nullptr;
+	if (M->d_max_map && packed)
+		hipLaunchKernelGGL((k_mip<true, true>), grid, block, 0, s, m);
+	else if (M->d_max_map)
+		hipLaunchKernelGGL((k_mip<false, true>), grid, block, 0, s, m);
+	else if (packed)
+		hipLaunchKernelGGL((k_mip<true, false>), grid, block, 0, s, m);
+	else
+		hipLaunchKernelGGL((k_mip<false, false>), grid, block, 0, s, m);
+	return check_launch(ctx, "render_mip");
+}
+
+}        // extern "C"

@@ -25,6 +25,9 @@
 //                 [--histogram=file]   after the gradient map: the joint (gradient byte, intensity byte) histogram of the volume (Volume::histogram),
 //                                  written as 65536 little-endian uint64 bins (bin g * 256 + i), and the line "Occupied voxels (histogram): X%"
 //                                  (vkv_histogram_occupied_count of the options' transfer function; in benchmark mode next to "Occupied voxels")
+//                 [--mip=THRESHOLD[,WINDOW_MAX]] [--mip-dense]   maximum-intensity projection instead of the integrator (VolumeRenderSubpass::draw_mip,
+//                                  window_max 1 by default): the frame the dumps read, and with --benchmark=N N frames on one stream, "mip: N frames,
+//                                  X ms per frame (device events)".  Skips over the volume's max map unless --mip-dense
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -69,6 +72,8 @@ struct Args
 	std::string tf_path = "device";        // --tf-path=host|device|summary
 	uint32_t    stream_slabs = 0;          // --stream-slabs=N: z-slabs of a progressive load
 	std::string histogram;                 // --histogram=file: the volume's joint histogram
+	bool        mip = false, mip_dense = false;        // --mip=THRESHOLD[,WINDOW_MAX], --mip-dense
+	float       mip_threshold = 0.0f, mip_window_max = 1.0f;
 };
 
 bool flag(const char *arg, const char *name, std::string &value)
@@ -133,6 +138,13 @@ Args parse(int argc, char **argv)
 		}
 		else if (flag(s, "--stream-slabs", v)) a.stream_slabs = (uint32_t) std::stoul(v);
 		else if (flag(s, "--histogram", v)) a.histogram = v;
+		else if (flag(s, "--mip-dense", v)) a.mip_dense = true;
+		else if (flag(s, "--mip", v))
+		{
+			if (std::sscanf(v.c_str(), "%f,%f", &a.mip_threshold, &a.mip_window_max) < 1)
+				throw std::runtime_error("--mip=THRESHOLD[,WINDOW_MAX]");
+			a.mip = true;
+		}
 		else if (s[0] != '-') a.dataset = s;
 		else throw std::runtime_error(std::string("unknown flag ") + s);
 	}
@@ -481,6 +493,35 @@ int main(int argc, char **argv)
 				std::printf("tf-drag summary: unresolved cells %g%% (last move)\n", 100.0 * (double) unresolved / ((double) me.width * me.height * me.depth));
 			}
 		}
+		if (args.mip)
+		{        // maximum-intensity projection: the frame the dumps read, then (benchmark) `frames` frames on one stream
+			if (!args.mip_dense)
+				volume.build_max_map(dc);
+			subpass.draw_mip(target, args.mip_threshold, args.mip_window_max, nullptr, !args.mip_dense);
+			(void) hipStreamSynchronize(stream);
+			if (benchmark)
+			{
+				RenderTarget frame = target;
+				frame.counts       = nullptr;
+				hipEvent_t ev0 = nullptr, ev1 = nullptr;
+				if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)
+					throw std::runtime_error("hipEventCreate failed");
+				(void) hipEventRecord(ev0, stream);
+				for (int f = 0; f < frames; ++f)
+					subpass.draw_mip(frame, args.mip_threshold, args.mip_window_max, nullptr, !args.mip_dense);
+				(void) hipEventRecord(ev1, stream);
+				(void) hipEventSynchronize(ev1);
+				float ms = 0.0f;
+				(void) hipEventElapsedTime(&ms, ev0, ev1);
+				std::printf("mip: %d frames, %g ms per frame (device events)\n", frames, ms / frames);
+				std::printf("ran %d frames, averaged %g fps\n", frames, 1000.0 * frames / ms);
+				(void) hipEventDestroy(ev0);
+				(void) hipEventDestroy(ev1);
+				subpass.draw_mip(target, args.mip_threshold, args.mip_window_max, nullptr, !args.mip_dense);        // the frame the dumps read
+				(void) hipStreamSynchronize(stream);
+			}
+		}
+		else
 		{
 			// Benchmark frames go round-robin over a few HIP streams, each with its own colour target - what the reference gets from
 			// its per-swap-chain-image command buffers: the long tail of one frame overlaps the start of the next.

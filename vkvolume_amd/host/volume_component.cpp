@@ -53,7 +53,10 @@ void Volume::release()
 		(void) hipFree(region_staging);
 	if (cell_summary_buf)
 		(void) hipFree(cell_summary_buf);
+	if (max_map_buf)
+		(void) hipFree(max_map_buf);
 	cell_summary_buf     = nullptr;
+	max_map_buf          = nullptr;
 	region_staging       = nullptr;
 	region_staging_bytes = 0;
 	packed                 = nullptr;
@@ -222,6 +225,20 @@ void Volume::update_region(DeviceContext &dc, VkvBox box, const void *host_raw, 
 		const VkvBox grown{x0, y0, z0, x1 - x0, y1 - y0, z1 - z0};
 		cell_summary(dc, &grown);
 	}
+	if (max_map_buf)        // vkv_max_map rebuilds every cell whose grown box meets the update's box
+		build_max_map(dc, &box);
+}
+
+void Volume::build_max_map(DeviceContext &dc, const VkvBox *box)
+{
+	const VkvExtent3D &me = distance_map_swap.extent;
+	if (!max_map_buf)
+	{
+		if (box)
+			throw std::runtime_error("max map: build the whole map first");
+		max_map_buf = static_cast<uint8_t *>(device_alloc((size_t) me.width * me.height * me.depth));
+	}
+	vkv_check(dc, vkv_max_map(dc.ctx, volume.data, volume.extent, me, box, max_map_buf, dc.stream), "max map");
 }
 
 void Volume::cell_summary(DeviceContext &dc, const VkvBox *box)

@@ -87,6 +87,11 @@ class Volume
 	// options.use_precomputed_gradient is set.  update_region keeps a built summary current (it rebuilds the update's box grown by one voxel).
 	void cell_summary(DeviceContext &dc, const VkvBox *box = nullptr);
 	const void *get_cell_summary() const { return cell_summary_buf; }
+	// The max map (vkv_max_map: per occupancy cell the largest voxel of the cell grown by one voxel per side) of every cell (box == nullptr) or of
+	// the cells whose grown box meets `box`, into a device buffer the volume allocates at the first call (build the whole map first).
+	// update_region keeps a built map current.  VolumeRenderSubpass::draw_mip skips over it.
+	void build_max_map(DeviceContext &dc, const VkvBox *box = nullptr);
+	const uint8_t *get_max_map() const { return max_map_buf; }
 	// update_transfer_function with the occupancy map decided from the summary (vkv_update_transfer_function_from_summary; call cell_summary
 	// first): same texture, tables and maps.  d_occupied_count needs d_histogram (a histogram() of the volume); d_unresolved receives the
 	// number of cells evaluated from their voxels
@@ -115,5 +120,6 @@ class Volume
 	void *             region_staging         = nullptr;        // update_region's device copy of the raw box
 	size_t             region_staging_bytes   = 0;
 	void *             cell_summary_buf       = nullptr;        // cell_summary's VKV_CELL_SUMMARY_BYTES per occupancy cell
+	uint8_t *          max_map_buf            = nullptr;        // build_max_map's byte per occupancy cell
 	vkv::mat4          image_transform;
 };

@@ -79,6 +79,12 @@ class VolumeRenderSubpass
 	// tiles == nullptr: every frame through frame_schedule() - the tiles of its screen rectangle, the rest of the frame filled by the same launch.
 	void draw_batch(const std::vector<RenderTarget> &targets, const VkvTileSchedule *tiles = nullptr);
 
+	// Maximum-intensity projection of the first volume into `target` (vkv_render_mip): samples > threshold count, grey level
+	// (m - threshold) / (window_max - threshold) clamped to [0, 1] into color / rgba8, m into `intensity` (may be null), the depth of the brightest
+	// sample into depth.  skip: jump over the cells of the volume's max map (Volume::build_max_map first; the same bits as the dense path).
+	void draw_mip(const RenderTarget &target, float threshold, float window_max, float *intensity = nullptr, bool skip = true,
+	              const VkvTileSchedule *tiles = nullptr);
+
 	// The schedule of a whole frame on one GPU (round 6): the 16x16 tiles of the rectangle the clipped box projects into (vkv_screen_tile_rect: the
 	// rasteriser of the reference only shades the box's faces, :262-293) with VkvTileSchedule.fill_outside - the launch's workgroups write the
 	// no-fragment result everywhere else, so the frame is complete without a workgroup per empty tile (C3: half of the frame's tiles, 2.7 % of its time).

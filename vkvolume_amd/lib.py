@@ -23,6 +23,7 @@ EXPORTS = [
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
+    "vkv_max_map", "vkv_render_mip",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -102,6 +103,8 @@ def load():
     L.vkv_occupancy_map_from_summary.argtypes = [vp, vp, vp, vp, vp, P(abi.TransferFunctionUniform), abi.Extent3D, vp, abi.Extent3D, vp, vp]
     L.vkv_update_transfer_function_from_summary.argtypes = [vp, P(abi.VolumeOptions), vp, vp, abi.Extent3D, vp, vp, P(vp), vp, abi.Extent3D, i32, vp,
                                                             vp, vp, vp, vp]
+    L.vkv_max_map.argtypes = [vp, vp, abi.Extent3D, abi.Extent3D, P(abi.Box), vp, vp]
+    L.vkv_render_mip.argtypes = [vp, P(abi.RenderParams), P(abi.MipOptions), vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -304,6 +307,21 @@ class Context:
     def cell_summary_rc(self, d_volume, d_gradient, extent, map_extent, box, d_summary, stream=0):
         """Like cell_summary() but returns the status code (error-path tests)."""
         return self._lib.vkv_cell_summary(self.handle, d_volume, d_gradient, extent, map_extent, None if box is None else C.byref(box), d_summary, stream)
+
+    def max_map(self, d_volume, extent, map_extent, box, d_max_map, stream=0):
+        """vkv_max_map: per cell of map_extent the largest voxel of the cell grown by one voxel per side (box None: every cell; else the
+        cells whose grown box meets `box`)"""
+        self.check(self.max_map_rc(d_volume, extent, map_extent, box, d_max_map, stream))
+
+    def max_map_rc(self, d_volume, extent, map_extent, box, d_max_map, stream=0):
+        return self._lib.vkv_max_map(self.handle, d_volume, extent, map_extent, None if box is None else C.byref(box), d_max_map, stream)
+
+    def render_mip(self, params, mip, stream=0):
+        """vkv_render_mip: maximum-intensity projection of params' volume with the abi.MipOptions `mip`"""
+        self.check(self.render_mip_rc(params, mip, stream))
+
+    def render_mip_rc(self, params, mip, stream=0):
+        return self._lib.vkv_render_mip(self.handle, None if params is None else C.byref(params), None if mip is None else C.byref(mip), stream)
 
     def occupancy_map_from_summary(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
         """vkv_occupancy_map_from_summary: vkv_occupancy_map's map, decided from the cell summaries where they are certain; d_unresolved

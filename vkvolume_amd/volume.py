@@ -43,6 +43,7 @@ class Volume:
         self.distance_map_swap = None
         self.extent = self.map_extent = None
         self.cell_summary = None  # vkv_cell_summary of the current volume (build_cell_summary), kept current by update_region
+        self.max_map = None  # vkv_max_map of the current volume (build_max_map), kept current by update_region
 
     # -- load_from_file's device half (src/volume_component.cpp:55-153): take voxels, allocate images --
     def load_from_array(self, voxels_dhw, distance_map_block_size=4, image_transform=None):
@@ -66,7 +67,7 @@ class Volume:
         self.gradient_valid = False  # set by ComputeGradientMap.compute; the packed image must not be built from an empty map
         self.transfer_function = torch.zeros((256, 256, 4), dtype=torch.uint8, device=self.device)
         self.transfer_function_bits = torch.zeros(abi.TF_BITS_WORDS, dtype=torch.int32, device=self.device)
-        self.packed = self.cell_summary = None
+        self.packed = self.cell_summary = self.max_map = None
         self.distance_map_swap = torch.empty((self.map_extent.depth, self.map_extent.height, self.map_extent.width),
                                              dtype=torch.uint8, device=self.device)
         self.distance_maps = []
@@ -127,6 +128,22 @@ class Volume:
         self.ctx.cell_summary(_ptr(self.volume), _ptr(self._gradient_or_none()), self.extent, self.map_extent, box, _ptr(self.cell_summary), _stream())
         return self.cell_summary
 
+    def build_max_map(self, box=None):
+        """The max map of the volume (vkv_max_map) on the current stream: per occupancy cell the largest voxel of the cell grown by one voxel
+        per side, for every cell (box None) or the cells whose grown box meets ``box`` (an abi.Box or ((x0, y0, z0), (width, height, depth))).
+        The (map depth, height, width) uint8 buffer is allocated at the first call and kept in ``max_map``; update_region() keeps it current.
+        VolumeRenderSubpass.draw_mip(skip=True) skips over it."""
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if self.max_map is None:
+            if box is not None:
+                raise ValueError("Volume.build_max_map: build the whole map (box=None) first")
+            me = self.map_extent
+            self.max_map = torch.empty((me.depth, me.height, me.width), dtype=torch.uint8, device=self.device)
+        self.ctx.max_map(_ptr(self.volume), self.extent, self.map_extent, box, _ptr(self.max_map), _stream())
+        return self.max_map
+
     def update_transfer_function_from_summary(self, skipping_type, d_count=None, histogram=None, d_unresolved=None):
         """update_transfer_function() with the occupancy map decided from the cell summaries (vkv_update_transfer_function_from_summary):
         same texture, tables and maps.  ``d_count`` (an int64 device tensor) receives the occupied-voxel count read off ``histogram``
@@ -154,7 +171,8 @@ class Volume:
         come as int16 / uint16 with voxel_type = VKV_VOXEL_UINT16), converted like the loader converts a file: byte order, then
         ``normalisation_range`` (default (0, 255): uint8 voxels are stored as they are).  Precondition: the derived buffers are up to date
         (ComputeGradientMap / pack / ComputeDistanceMap with the current options and transfer function texture).  A cell summary built with
-        build_cell_summary() is rebuilt over the box grown by one voxel per side, clamped to the volume (vkv_cell_summary's maintenance rule)."""
+        build_cell_summary() is rebuilt over the box grown by one voxel per side, clamped to the volume (vkv_cell_summary's maintenance rule); a max
+        map built with build_max_map() is rebuilt over the box."""
         if torch.is_tensor(voxels_dhw):
             src = voxels_dhw.to(self.device).contiguous()
             vt = self._TORCH_DTYPES.get(src.dtype) if voxel_type is None else voxel_type
@@ -185,6 +203,8 @@ class Volume:
             x0, y0, z0 = max(x - 1, 0), max(y - 1, 0), max(z - 1, 0)
             x1, y1, z1 = min(x + w + 1, e.width), min(y + h + 1, e.height), min(z + d + 1, e.depth)
             self.build_cell_summary(abi.Box(x0, y0, z0, x1 - x0, y1 - y0, z1 - z0))
+        if self.max_map is not None:  # vkv_max_map rebuilds every cell whose grown box meets the update's box
+            self.build_max_map(abi.Box(x, y, z, w, h, d))
 
     _HISTOGRAM_MODES = (abi.HISTOGRAM_SET, abi.HISTOGRAM_ADD, abi.HISTOGRAM_SUBTRACT)
 
@@ -308,6 +328,23 @@ class VolumeRenderSubpass:
         params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
         params.d_in_depth, params.blend_over_target = _ptr(in_depth), 1 if blend else 0
         self.ctx.render(params, _stream())
+
+    def draw_mip(self, params, threshold, window_max, color=None, rgba8=None, intensity=None, depth=None, counts=None, skip=True, in_depth=None):
+        """Maximum-intensity projection (vkv_render_mip) of ``params``' rays into the given buffers: samples > ``threshold`` count, the grey
+        level is (m - threshold) / (window_max - threshold) clamped to [0, 1].  ``skip``: jump over the cells of the volume's max map
+        (build_max_map() first; the same bits as the dense path); False: filter every sample.  ``in_depth``: scene depth for
+        options.depth_attachment."""
+        max_map = None
+        if skip:
+            if self.volume.max_map is None:
+                raise RuntimeError("VolumeRenderSubpass.draw_mip: skip=True needs the volume's max map (call Volume.build_max_map first)")
+            max_map = self.volume.max_map
+        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
+        params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
+        params.d_in_depth, params.blend_over_target = _ptr(in_depth), 0
+        mip = abi.MipOptions(threshold=float(threshold), window_max=float(window_max), d_max_map=_ptr(max_map), d_out_intensity=_ptr(intensity),
+                             flags=0)
+        self.ctx.render_mip(params, mip, _stream())
 
 
 def default_scene(volume, voxel_size=(1.0, 1.0, 1.0), axis_angle=(1.0, 0.0, 0.0, 0.0)):
