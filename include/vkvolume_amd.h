@@ -294,7 +294,8 @@ int vkv_distance_map_anisotropic(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t
                                  VkvExtent3D map_extent, void *stream);
 
 /* ComputeDistanceMap::compute, src/compute_distance_map.cpp:65-101: occupancy into
- * d_maps[n-1] (n = 8 for anisotropic, else 1), then the transform selected by skipping_type. */
+ * d_maps[n-1] (n = 8 for anisotropic, else 1), then the transform selected by skipping_type.
+ * Every argument is checked before anything is enqueued: a rejected call writes nothing. */
 int vkv_compute_distance_map(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient,
                              const uint8_t *d_transfer_function, const VkvTransferFunctionUniform *tf,
                              VkvExtent3D extent, uint8_t *const d_maps[8], uint8_t *d_swap,

@@ -364,8 +364,23 @@ def test_argument_errors_write_nothing(ctx):
     for a in bad:
         assert ctx.update_transfer_function_from_summary_rc(**a) == inv, a
     assert ctx.update_transfer_function_from_summary_rc(**args(d_gradient=None)) == uns
+    # map rows too long for the distance transform: refused before the count, the texture or the classification is enqueued
+    e2 = ext(2049, 1, 1)
+    vol2 = torch.zeros((1, 1, 2049), dtype=torch.uint8, device="cuda")
+    summ2 = torch.zeros((2049, SB), dtype=torch.uint8, device="cuda")
+    tex2 = torch.full((256, 256, 4), 7, dtype=torch.uint8, device="cuda")
+    tables2 = torch.full((abi.TF_BITS_WORDS,), 7, dtype=torch.int32, device="cuda")
+    cnt2 = torch.full((2,), 7, dtype=torch.int64, device="cuda")
+    map2, swap2 = (torch.full((2049,), 7, dtype=torch.uint8, device="cuda") for _ in range(2))
+    rc = ctx.update_transfer_function_from_summary_rc(**args(d_volume=ptr(vol2), d_gradient=ptr(vol2), extent=e2, d_tf=ptr(tex2), d_tables=ptr(tables2),
+                                                            d_maps=[ptr(map2)], d_swap=ptr(swap2), map_extent=e2, skipping_type=abi.SKIP_DISTANCE,
+                                                            d_count=ptr(cnt2), d_summary=ptr(summ2), d_histogram=ptr(hist)))
+    assert rc == uns, rc
+    err = ctx.last_error()
     torch.cuda.synchronize()
     assert (summ == 0xA5).all() and (mp == 0x5A).all() and (tables == 0).all() and (swap == 0).all()
+    assert all((t == 7).all() for t in (tex2, tables2, cnt2, map2, swap2))
+    assert err.startswith("update_transfer_function_from_summary:"), err
 
 
 # ---- 7. the C++ driver -----------------------------------------------------------------------------------------------------------------

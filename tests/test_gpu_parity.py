@@ -564,6 +564,19 @@ def test_render_error_paths(ctx, shell_scene):
         ctx.distance_map(out.data_ptr(), out.data_ptr(), abi.Extent3D(4, 4, 4))  # aliased buffers
     with pytest.raises(lib.VkvError):
         ctx.distance_map(out.data_ptr(), out.data_ptr() + 64, abi.Extent3D(4096, 4, 4))  # axis > 2048
+    # vkv_compute_distance_map checks every argument before its occupancy pass: a rejected call leaves the map as it was
+    e = abi.Extent3D(2049, 1, 1)
+    vol = torch.zeros((1, 1, 2049), dtype=torch.uint8, device="cuda")
+    occ, swap = (torch.full((1, 1, 2049), 7, dtype=torch.uint8, device="cuda") for _ in range(2))
+    errors = []
+    for d_swap, code in ((swap.data_ptr(), abi.VKV_E_UNSUPPORTED), (None, abi.VKV_E_INVALID_ARGUMENT)):
+        with pytest.raises(lib.VkvError) as err:
+            ctx.compute_distance_map(vol.data_ptr(), None, v.transfer_function.data_ptr(), tf, e, [occ.data_ptr()], d_swap, e, abi.SKIP_DISTANCE)
+        assert err.value.code == code, str(err.value)
+        errors.append(ctx.last_error())
+    torch.cuda.synchronize()
+    assert (occ == 7).all() and (swap == 7).all()
+    assert all(m.startswith("compute_distance_map:") for m in errors), errors
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -350,8 +350,21 @@ def test_argument_errors_enqueue_nothing(ctx):
     assert ctx._lib.vkv_transfer_function_texture_device(ctx.handle, None, tex.data_ptr(), tab.data_ptr(), st()) == E
     assert ctx._lib.vkv_transfer_function_texture_device(ctx.handle, C.byref(opt), None, tab.data_ptr(), st()) == E
     assert ctx._lib.vkv_transfer_function_texture_device(ctx.handle, C.byref(opt), tex.data_ptr(), tab.data_ptr() + 2, st()) == E
+    # launch limits are checked up front as well: map rows too long for the distance transform, too many map layers for the occupancy pass
+    limited, errors = [], []
+    for shape, skip in (((2049, 1, 1), abi.SKIP_DISTANCE), ((2049, 1, 1), abi.SKIP_ANISOTROPIC_DISTANCE), ((1, 1, 65536), abi.SKIP_NONE)):
+        e = abi.Extent3D(*shape)
+        vol = torch.zeros(shape[::-1], dtype=torch.uint8, device="cuda")
+        bufs = [torch.full(shape[::-1], 7, dtype=torch.uint8, device="cuda") for _ in range(9)]  # 8 maps + swap
+        limited += bufs
+        rc = ctx.update_transfer_function_rc(**dict(ok, d_volume=vol.data_ptr(), extent=e, d_maps=[b.data_ptr() for b in bufs[:8]],
+                                                    d_swap=bufs[8].data_ptr(), map_extent=e, skipping_type=skip))
+        assert rc == abi.VKV_E_UNSUPPORTED, (shape, skip, rc)
+        errors.append(ctx.last_error())
     torch.cuda.synchronize()
     assert (tex == 7).all() and (tab == 7).all() and (swap == 7).all() and (cnt == 7).all() and all((m == 7).all() for m in maps)
+    assert all((b == 7).all() for b in limited)
+    assert all(m.startswith("update_transfer_function:") for m in errors), errors
     # the same arguments without the fault go through
     ctx.update_transfer_function(**ok)
     torch.cuda.synchronize()

@@ -375,9 +375,17 @@ def test_argument_errors_write_nothing(ctx):
             a[i] = val
         rc = ctx.update_volume_region_rc(*a, stream=st())
         assert rc == E, "%s: rc %d" % (label, rc)
+    # map rows too long for the distance transform (VKV_E_UNSUPPORTED), refused before anything is enqueued
+    e = abi.Extent3D(2049, 1, 1)
+    wide = [torch.full((1, 1, 2049), 7, dtype=torch.uint8, device="cuda") for _ in range(4)]  # volume, gradient, map, swap
+    src8 = torch.full((1,), 200, dtype=torch.uint8, device="cuda")
+    rc = ctx.update_volume_region_rc(ptr(src8), U8, False, 0.0, 255.0, abi.Box(0, 0, 0, 1, 1, 1), ptr(wide[0]), ptr(wide[1]), None, e,
+                                     good[10], good[11], [ptr(wide[2])], ptr(wide[3]), e, abi.SKIP_DISTANCE, stream=st())
+    assert rc == abi.VKV_E_UNSUPPORTED and ctx.last_error().startswith("update_volume_region:"), rc
     torch.cuda.synchronize()
     for (name, b), (_, a) in zip(before, s.snapshot()):
         assert b is None or torch.equal(a, b), "%s changed by a rejected call" % name
+    assert all((t == 7).all() for t in wide)
     assert ctx.update_volume_region_rc(*good, stream=st()) == abi.VKV_OK  # the unchanged arguments are accepted
     torch.cuda.synchronize()
 

@@ -45,7 +45,11 @@ int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float
 int launch_volume_histogram(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, const VkvBox &, int, uint64_t *, hipStream_t);
 int launch_histogram_occupied_count(vkv_ctx *, const uint64_t *, const VkvTransferFunctionUniform *, uint64_t *, hipStream_t);
 int launch_tf_bits(vkv_ctx *, const uint8_t *, uint32_t *, hipStream_t);
+bool occupancy_launch_ok(VkvExtent3D, VkvExtent3D);
+bool distance_launch_ok(VkvExtent3D);
+bool count_launch_ok(VkvExtent3D);
 bool cells_launch_ok(VkvExtent3D, VkvExtent3D);
+int launch_map_transform(vkv_ctx *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
 int launch_cell_summary(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, VkvExtent3D, const VkvBox *, void *, hipStream_t);
 int launch_occupancy_from_summary(vkv_ctx *, const void *, const uint8_t *, const uint8_t *, bool, uint8_t *, VkvExtent3D, uint8_t *, VkvExtent3D,
                                   uint64_t *, hipStream_t);
@@ -332,6 +336,50 @@ static bool extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.d
 
 // ceil(volume / map) must reproduce a valid block size (src/compute_distance_map.cpp:110-113)
 static bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
+
+int check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box)
+{
+	if (!box)
+		return VKV_OK;
+	const VkvBox b = *box;
+	if (b.width == 0 || b.height == 0 || b.depth == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: empty box", what);
+	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: box (%u, %u, %u) + (%u, %u, %u) outside the volume", what, b.x0, b.y0, b.z0, b.width, b.height,
+		                 b.depth);
+	return VKV_OK;
+}
+
+// skipping_type's maps: 8 for ANISOTROPIC_DISTANCE, else 1, and for the distance transforms a swap buffer that is none of them
+static int check_map_buffers(vkv_ctx *ctx, const char *what, uint8_t *const d_maps[8], const uint8_t *d_swap, int32_t skipping_type)
+{
+	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: bad skipping_type %d", what, (int) skipping_type);
+	if (!d_maps)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null maps", what);
+	const bool transform = skipping_type == VKV_SKIP_DISTANCE || skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
+	const int  n         = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 8 : 1;
+	if (transform && !d_swap)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null swap buffer", what);
+	for (int i = 0; i < n; ++i)
+		if (!d_maps[i] || (transform && d_maps[i] == d_swap))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: map %d %s", what, i, d_maps[i] ? "aliases the swap buffer" : "is null");
+	return VKV_OK;
+}
+
+// the maps' buffers (VKV_E_INVALID_ARGUMENT), then the limits of the occupancy pass (from_summary: the classify launch) and of the transform
+// (VKV_E_UNSUPPORTED): what an entry point that builds the maps checks before it enqueues anything (extent and map_extent are valid)
+static int check_maps(vkv_ctx *ctx, const char *what, uint8_t *const d_maps[8], const uint8_t *d_swap, VkvExtent3D extent, VkvExtent3D map_extent,
+                      int32_t skipping_type, bool from_summary = false)
+{
+	if (const int rc = check_map_buffers(ctx, what, d_maps, d_swap, skipping_type))
+		return rc;
+	if (!(from_summary ? cells_launch_ok(extent, map_extent) : occupancy_launch_ok(extent, map_extent)))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: map too large for one launch", what);
+	if ((skipping_type == VKV_SKIP_DISTANCE || skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE) && !distance_launch_ok(map_extent))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: map rows too long for the distance transform", what);
+	return VKV_OK;
+}
 
 }        // namespace vkv
 
@@ -879,9 +927,8 @@ int vkv_distance_map(vkv_ctx *ctx, uint8_t *d_map, uint8_t *d_swap, VkvExtent3D 
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	DeviceGuard guard(ctx->device);
-	if (!d_map || !d_swap || d_map == d_swap)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_map: null or aliased buffers");
-	return launch_distance_map(ctx, d_map, d_swap, map_extent, (hipStream_t) stream);
+	const int rc = check_map_buffers(ctx, "distance_map", &d_map, d_swap, VKV_SKIP_DISTANCE);
+	return rc != VKV_OK ? rc : launch_distance_map(ctx, d_map, d_swap, map_extent, (hipStream_t) stream);
 }
 
 int vkv_distance_map_anisotropic(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent, void *stream)
@@ -889,33 +936,30 @@ int vkv_distance_map_anisotropic(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	DeviceGuard guard(ctx->device);
-	if (!d_maps || !d_swap)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_map_anisotropic: null pointer");
-	for (int i = 0; i < 8; ++i)
-		if (!d_maps[i] || d_maps[i] == d_swap)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_map_anisotropic: map %d null or aliasing swap", i);
-	return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, (hipStream_t) stream);
+	const int rc = check_map_buffers(ctx, "distance_map_anisotropic", d_maps, d_swap, VKV_SKIP_ANISOTROPIC_DISTANCE);
+	return rc != VKV_OK ? rc : launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, (hipStream_t) stream);
 }
 
-// src/compute_distance_map.cpp:65-101
+// src/compute_distance_map.cpp:65-101: every argument is checked before the first launch
 int vkv_compute_distance_map(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
                              VkvExtent3D extent, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type, void *stream)
 {
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	DeviceGuard guard(ctx->device);
-	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE || !d_maps)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "compute_distance_map: bad skipping_type or null maps");
-	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
-	const int  n     = aniso ? 8 : 1;
-	int        rc    = vkv_occupancy_map(ctx, d_volume, d_gradient, d_tf, tf, extent, d_maps[n - 1], map_extent, stream);
-	if (rc)
+	if (!d_volume || !d_tf || !tf || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "compute_distance_map: null pointer or bad extent");
+	int rc = check_maps(ctx, "compute_distance_map", d_maps, d_swap, extent, map_extent, skipping_type);
+	if (rc != VKV_OK)
 		return rc;
-	if (aniso)
-		return vkv_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, stream);
-	if (skipping_type == VKV_SKIP_DISTANCE)
-		return vkv_distance_map(ctx, d_maps[0], d_swap, map_extent, stream);
-	return VKV_OK;        // None / Block use the raw 0/255 occupancy map (:96-99)
+	const hipStream_t   s       = (hipStream_t) stream;
+	const StreamScratch scratch = stream_scratch(ctx, s);        // the bit table, written and read by the occupancy pass
+	if (!scratch.p)
+		return VKV_E_UNSUPPORTED;
+	uint8_t *occ = d_maps[skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 7 : 0];
+	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, tf, extent, occ, map_extent, s, reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset))) != VKV_OK)
+		return rc;
+	return launch_map_transform(ctx, d_maps, d_swap, map_extent, skipping_type, s);
 }
 
 int vkv_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, const VkvTransferFunctionUniform *tf, VkvExtent3D extent,
@@ -1053,25 +1097,15 @@ int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, 
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
 	DeviceGuard guard(ctx->device);
-	if (!options || !d_volume || !d_tf || !d_tables || !d_maps || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
+	if (!options || !d_volume || !d_tf || !d_tables || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: null pointer or bad extent");
-	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: bad skipping_type %d", (int) skipping_type);
 	if (((uintptr_t) d_tf & 3u) != 0 || ((uintptr_t) d_tables & 3u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: d_transfer_function and d_tables must be 4-byte aligned");
-	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
-	const int  n     = aniso ? 8 : 1;
-	for (int i = 0; i < n; ++i)
-		if (!d_maps[i])
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: map %d is null", i);
-	if (aniso || skipping_type == VKV_SKIP_DISTANCE)
-	{
-		if (!d_swap)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: null swap buffer");
-		for (int i = 0; i < n; ++i)
-			if (d_maps[i] == d_swap)
-				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function: map %d aliases the swap buffer", i);
-	}
+	int rc = check_maps(ctx, "update_transfer_function", d_maps, d_swap, extent, map_extent, skipping_type);
+	if (rc != VKV_OK)
+		return rc;
+	if (d_occupied_count && !count_launch_ok(extent))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "update_transfer_function: volume too large for the voxel count");
 	const hipStream_t   s       = (hipStream_t) stream;
 	const StreamScratch scratch = stream_scratch(ctx, s);        // held until the occupancy pass is enqueued
 	if (!scratch.p)
@@ -1079,22 +1113,18 @@ int vkv_update_transfer_function(vkv_ctx *ctx, const VkvVolumeOptions *options, 
 	uint32_t *d_bits = reinterpret_cast<uint32_t *>(scratch.p + kTfBitsOffset);
 	VkvTransferFunctionUniform tf;
 	vkv_transfer_function_uniform(options, &tf);
-	int rc = VKV_OK;
 	// the count first: it stages its own (analytic) bit table in the same scratch words that k_tf_build fills for the occupancy pass
 	if (d_occupied_count && (rc = launch_occupied_voxel_count(ctx, d_volume, d_gradient, &tf, extent, d_occupied_count, s, d_bits)) != VKV_OK)
 		return rc;
 	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, d_bits, s)) != VKV_OK)
 		return rc;
-	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, &tf, extent, d_maps[n - 1], map_extent, s, d_bits, true)) != VKV_OK)
+	uint8_t *occ = d_maps[skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 7 : 0];
+	if ((rc = launch_occupancy_map(ctx, d_volume, d_gradient, d_tf, &tf, extent, occ, map_extent, s, d_bits, true)) != VKV_OK)
 		return rc;
-	if (aniso)
-		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, s);
-	if (skipping_type == VKV_SKIP_DISTANCE)
-		return launch_distance_map(ctx, d_maps[0], d_swap, map_extent, s);
-	return VKV_OK;        // None / Block use the raw 0/255 occupancy map
+	return launch_map_transform(ctx, d_maps, d_swap, map_extent, skipping_type, s);
 }
 
-// every argument is checked before the first launch (launch_update_volume_region checks the launches' size limits the same way)
+// every argument is checked before the first launch (the volume's size limits by launch_update_volume_region)
 int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int32_t big_endian, float range_min, float range_max, const VkvBox *box,
                              uint8_t *d_volume, uint8_t *d_gradient, void *d_packed, VkvExtent3D extent, const uint8_t *d_tf,
                              const VkvTransferFunctionUniform *tf, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type,
@@ -1105,12 +1135,9 @@ int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int3
 	DeviceGuard guard(ctx->device);
 	if (!d_src || !box || !d_volume || !tf || !extent_ok(extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null pointer or zero extent");
-	const VkvBox b = *box;
-	if (b.width == 0 || b.height == 0 || b.depth == 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: empty box");
-	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
-		                 b.height, b.depth);
+	int rc = check_box(ctx, "update_volume_region", extent, box);
+	if (rc != VKV_OK)
+		return rc;
 	if (type < VKV_VOXEL_UINT8 || type > VKV_VOXEL_INT16)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: unsupported image data type %d", (int) type);
 	if ((type == VKV_VOXEL_UINT16 || type == VKV_VOXEL_INT16) && (((uintptr_t) d_src) & 1u))
@@ -1121,23 +1148,10 @@ int vkv_update_volume_region(vkv_ctx *ctx, const void *d_src, int32_t type, int3
 	{
 		if (!d_tf || !map_extent_ok(extent, map_extent))
 			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null transfer function or bad map extent");
-		if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: bad skipping_type %d", (int) skipping_type);
-		const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
-		const int  n     = aniso ? 8 : 1;
-		for (int i = 0; i < n; ++i)
-			if (!d_maps[i])
-				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: map %d is null", i);
-		if (aniso || skipping_type == VKV_SKIP_DISTANCE)
-		{
-			if (!d_swap)
-				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: null swap buffer");
-			for (int i = 0; i < n; ++i)
-				if (d_maps[i] == d_swap)
-					return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_volume_region: map %d aliases the swap buffer", i);
-		}
+		if ((rc = check_maps(ctx, "update_volume_region", d_maps, d_swap, extent, map_extent, skipping_type)) != VKV_OK)
+			return rc;
 	}
-	return launch_update_volume_region(ctx, d_src, type, big_endian != 0, range_min, range_max, b, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
+	return launch_update_volume_region(ctx, d_src, type, big_endian != 0, range_min, range_max, *box, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
 	                                   d_swap, map_extent, skipping_type, (hipStream_t) stream);
 }
 
@@ -1150,16 +1164,13 @@ int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d
 	DeviceGuard guard(ctx->device);
 	if (!d_volume || !d_histogram || !extent_ok(extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: null pointer or zero extent");
-	const VkvBox b = box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth};
-	if (b.width == 0 || b.height == 0 || b.depth == 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: empty box");
-	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
-		                 b.height, b.depth);
+	if (const int rc = check_box(ctx, "volume_histogram", extent, box))
+		return rc;
 	if (mode < VKV_HISTOGRAM_SET || mode > VKV_HISTOGRAM_SUBTRACT)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: bad mode %d", (int) mode);
 	if (((uintptr_t) d_histogram & 7u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: d_histogram must be 8-byte aligned");
+	const VkvBox b = box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth};
 	return launch_volume_histogram(ctx, d_volume, d_gradient, extent, b, mode, d_histogram, (hipStream_t) stream);
 }
 
@@ -1186,32 +1197,25 @@ int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gra
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: null pointer or bad extent");
 	if (((uintptr_t) d_summary & 15u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: d_summary must be 16-byte aligned");
-	if (box)
-	{
-		const VkvBox b = *box;
-		if (b.width == 0 || b.height == 0 || b.depth == 0)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: empty box");
-		if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "cell_summary: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width,
-			                 b.height, b.depth);
-	}
+	if (const int rc = check_box(ctx, "cell_summary", extent, box))
+		return rc;
 	if (!cells_launch_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "cell_summary: map too large for one launch");
 	return launch_cell_summary(ctx, d_volume, d_gradient, extent, map_extent, box, d_summary, (hipStream_t) stream);
 }
 
-// the checks the two summary-based map calls share (after their own null checks)
+// the checks the two summary-based map calls share (after their own null checks): check_maps with the classify launch's limits
 static int check_from_summary(vkv_ctx *ctx, const char *what, const void *d_summary, const uint8_t *d_gradient, int32_t use_gradient, VkvExtent3D extent,
-                              VkvExtent3D map_extent, const uint64_t *d_unresolved)
+                              uint8_t *const d_maps[8], const uint8_t *d_swap, VkvExtent3D map_extent, int32_t skipping_type, const uint64_t *d_unresolved)
 {
 	if ((((uintptr_t) d_summary) & 15u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_summary must be 16-byte aligned", what);
 	if ((((uintptr_t) d_unresolved) & 7u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_unresolved must be 8-byte aligned", what);
+	if (const int rc = check_maps(ctx, what, d_maps, d_swap, extent, map_extent, skipping_type, true))
+		return rc;
 	if (use_gradient && !d_gradient)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: the summary holds no on-the-fly gradient (use_gradient needs d_gradient)", what);
-	if (!cells_launch_ok(extent, map_extent))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: map too large for one launch", what);
 	return VKV_OK;
 }
 
@@ -1224,7 +1228,8 @@ int vkv_occupancy_map_from_summary(vkv_ctx *ctx, const void *d_summary, const ui
 	DeviceGuard guard(ctx->device);
 	if (!d_summary || !d_volume || !d_tf || !tf || !d_map || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "occupancy_map_from_summary: null pointer or bad extent");
-	int rc = check_from_summary(ctx, "occupancy_map_from_summary", d_summary, d_gradient, tf->use_gradient, extent, map_extent, d_unresolved);
+	int rc = check_from_summary(ctx, "occupancy_map_from_summary", d_summary, d_gradient, tf->use_gradient, extent, &d_map, nullptr, map_extent,
+	                            VKV_SKIP_NONE, d_unresolved);
 	if (rc != VKV_OK)
 		return rc;
 	const hipStream_t   s       = (hipStream_t) stream;
@@ -1247,30 +1252,16 @@ int vkv_update_transfer_function_from_summary(vkv_ctx *ctx, const VkvVolumeOptio
 	DeviceGuard guard(ctx->device);
 	if (!options || !d_volume || !d_tf || !d_tables || !d_maps || !d_summary || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: null pointer or bad extent");
-	if (skipping_type < VKV_SKIP_NONE || skipping_type > VKV_SKIP_ANISOTROPIC_DISTANCE)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: bad skipping_type %d", (int) skipping_type);
 	if (((uintptr_t) d_tf & 3u) != 0 || ((uintptr_t) d_tables & 3u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_transfer_function and d_tables must be 4-byte aligned");
 	if (d_occupied_count && !d_histogram)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_occupied_count needs d_histogram");
 	if ((((uintptr_t) d_occupied_count) | ((uintptr_t) d_histogram)) & 7u)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: d_occupied_count and d_histogram must be 8-byte aligned");
-	const bool aniso = skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE;
-	const int  n     = aniso ? 8 : 1;
-	for (int i = 0; i < n; ++i)
-		if (!d_maps[i])
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: map %d is null", i);
-	if (aniso || skipping_type == VKV_SKIP_DISTANCE)
-	{
-		if (!d_swap)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: null swap buffer");
-		for (int i = 0; i < n; ++i)
-			if (d_maps[i] == d_swap)
-				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "update_transfer_function_from_summary: map %d aliases the swap buffer", i);
-	}
 	VkvTransferFunctionUniform tf;
 	vkv_transfer_function_uniform(options, &tf);
-	int rc = check_from_summary(ctx, "update_transfer_function_from_summary", d_summary, d_gradient, tf.use_gradient, extent, map_extent, d_unresolved);
+	int rc = check_from_summary(ctx, "update_transfer_function_from_summary", d_summary, d_gradient, tf.use_gradient, extent, d_maps, d_swap, map_extent,
+	                            skipping_type, d_unresolved);
 	if (rc != VKV_OK)
 		return rc;
 	const hipStream_t   s       = (hipStream_t) stream;
@@ -1282,14 +1273,11 @@ int vkv_update_transfer_function_from_summary(vkv_ctx *ctx, const VkvVolumeOptio
 		return rc;
 	if ((rc = launch_tf_build(ctx, &tf, d_tf, d_tables, d_bits, s)) != VKV_OK)
 		return rc;
-	if ((rc = launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf.use_gradient != 0, scratch.p, extent, d_maps[n - 1], map_extent,
-	                                        d_unresolved, s)) != VKV_OK)
+	uint8_t *occ = d_maps[skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE ? 7 : 0];
+	if ((rc = launch_occupancy_from_summary(ctx, d_summary, d_volume, d_gradient, tf.use_gradient != 0, scratch.p, extent, occ, map_extent, d_unresolved,
+	                                        s)) != VKV_OK)
 		return rc;
-	if (aniso)
-		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, map_extent, s);
-	if (skipping_type == VKV_SKIP_DISTANCE)
-		return launch_distance_map(ctx, d_maps[0], d_swap, map_extent, s);
-	return VKV_OK;        // None / Block use the raw 0/255 occupancy map
+	return launch_map_transform(ctx, d_maps, d_swap, map_extent, skipping_type, s);
 }
 
 // argument checks shared by vkv_render and vkv_render_batch

@@ -398,6 +398,8 @@ int vkv_max_map(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, VkvEx
 	DeviceGuard guard(ctx->device);
 	if (!d_volume || !d_max_map || !extent_ok(extent) || !map_extent_ok(extent, map_extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: null pointer or bad extent");
+	if (const int rc = check_box(ctx, "max_map", extent, box))
+		return rc;
 	MaxMapArgs a;
 	a.vol = d_volume, a.map = d_max_map;
 	a.W = (int) extent.width, a.H = (int) extent.height, a.D = (int) extent.depth, a.mw = (int) map_extent.width, a.mh = (int) map_extent.height;
@@ -405,11 +407,6 @@ int vkv_max_map(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, VkvEx
 	if (box)
 	{
 		const VkvBox b = *box;
-		if (b.width == 0 || b.height == 0 || b.depth == 0)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: empty box");
-		if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "max_map: box (%u, %u, %u) + (%u, %u, %u) outside the volume", b.x0, b.y0, b.z0, b.width, b.height,
-			                 b.depth);
 		// the cells whose grown voxel box [c b - 1, c b + b] meets [x0, x0 + width - 1]: ceil(x0 / b) - 1 <= c <= (x0 + width) / b, clamped to the map
 		const uint32_t lo[3] = {b.x0, b.y0, b.z0}, n[3] = {b.width, b.height, b.depth}, bs[3] = {(uint32_t) a.bx, (uint32_t) a.by, (uint32_t) a.bz};
 		const uint32_t me[3] = {map_extent.width, map_extent.height, map_extent.depth};

@@ -1558,12 +1558,21 @@ static int fill_empty(vkv_ctx *ctx, uint8_t *d_map, size_t n, hipStream_t s, boo
 	return em == hipSuccess ? VKV_OK : set_error(ctx, (int) em, "occupancy_map: fill: %s", hipGetErrorString(em));
 }
 
+// what the occupancy pass (whole map or a region update's) can take in one launch: the grid of k_occupancy_map
+bool occupancy_launch_ok(VkvExtent3D e, VkvExtent3D me)
+{
+	const int bx = (int) ((e.width + me.width - 1) / me.width), cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
+	return (uint64_t) ((me.width + cells_per_block - 1) / cells_per_block) * me.height <= 0xffffffull && me.depth <= 65535u;
+}
+
 // d_bits: the bit table in the stream's scratch block (per stream: map updates on different streams do not share it; the caller holds the
 // block's lock).  bits_ready: k_tf_build has already left the bit table and its column mask there (vkv_update_transfer_function); d_tf is
 // then not read, and the map is filled by a kernel (k_fill_empty)
 int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
                          VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s, uint32_t *d_bits, bool bits_ready)
 {
+	if (!occupancy_launch_ok(e, me))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "occupancy_map: map too large for one launch");
 	if (!bits_ready)
 	{
 		hipLaunchKernelGGL(k_tf_bits, dim3(8), dim3(256), 0, s, d_tf, d_bits);
@@ -1574,8 +1583,6 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 	          bz = (int) ((e.depth + me.depth - 1) / me.depth);
 	const int      cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
 	const uint32_t blocks_x        = (me.width + cells_per_block - 1) / cells_per_block;
-	if ((uint64_t) blocks_x * me.height > 0xffffffull || me.depth > 65535u)
-		return set_error(ctx, VKV_E_UNSUPPORTED, "occupancy_map: map too large for one launch");
 	const dim3 grid(blocks_x * me.height, me.depth);
 	const int W = (int) e.width, H = (int) e.height, D = (int) e.depth, mw = (int) me.width, mh = (int) me.height, md = (int) me.depth;
 	const bool precomputed = tf->use_gradient && d_grad;
@@ -1678,10 +1685,15 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 	return check_launch(ctx, "occupancy_map");
 }
 
+// what the voxel count can take: its groups of four rows are counted in 32 bits
+bool count_launch_ok(VkvExtent3D e) { return ((uint64_t) e.height * e.depth + 3) / 4 <= 0xffffffffull; }
+
 // d_bits: the bit table in the stream's scratch block (the caller holds its lock)
 int launch_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const VkvTransferFunctionUniform *tf, VkvExtent3D e,
                                 uint64_t *d_count, hipStream_t s, uint32_t *d_bits)
 {
+	if (!count_launch_ok(e))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "occupied_voxel_count: volume too large");
 	hipLaunchKernelGGL(k_tf_bits_analytic, dim3(8), dim3(256), 0, s, d_bits, tf->intensity_min, tf->intensity_range_inv, tf->gradient_min,
 	                   tf->gradient_range_inv);
 	const hipError_t me = hipMemsetAsync(d_count, 0, sizeof(uint64_t), s);
@@ -1691,10 +1703,7 @@ int launch_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_
 	const bool     dwords       = e.width >= 4 && (!tf->use_gradient || d_grad);
 	const bool     aligned      = (e.width & 3u) == 0 && ((((uintptr_t) d_vol) | ((uintptr_t) d_grad)) & 3u) == 0;
 	const uint32_t blocks_x     = dwords ? ((e.width + 3) / 4 + 63) / 64 : (e.width + 63) / 64;
-	const uint64_t rows         = (uint64_t) e.height * e.depth;
-	const uint64_t n_row_groups = (rows + 3) / 4;
-	if (n_row_groups > 0xffffffffull)
-		return set_error(ctx, VKV_E_UNSUPPORTED, "occupied_voxel_count: volume too large");
+	const uint64_t n_row_groups = ((uint64_t) e.height * e.depth + 3) / 4;
 	// ~8 workgroups per CU, grid-stride over the row groups: one atomic per workgroup, few thousand in total
 	const uint32_t groups = (uint32_t) (n_row_groups < 2048 / blocks_x + 1 ? n_row_groups : 2048 / blocks_x + 1);
 	const dim3     grid(blocks_x * groups);
@@ -1731,10 +1740,13 @@ template <int MODE>
 static int launch_dm_rmq_passes(vkv_ctx *ctx, int axis, const DmPasses &passes, uint32_t n_passes, VkvExtent3D me, hipStream_t s);
 static bool dm_whole_lines(int axis, VkvExtent3D me) { return (axis == 1 ? me.height : me.depth) <= 512u; }        // a workgroup stages the whole line: in place is safe
 
+// what the distance transforms can take in one launch: map rows of at most 2048 cells (the x pass)
+bool distance_launch_ok(VkvExtent3D me) { return me.width <= 2048; }
+
 template <int MODE>
 static int launch_dm_x(vkv_ctx *ctx, const uint8_t *src, uint8_t *dst, VkvExtent3D me, hipStream_t s)
 {
-	if (me.width <= 2048)        // round 6: also rows of 1025 .. 2048 cells in registers (32 cells per lane; the serial scan below was 14 x slower per cell)
+	if (distance_launch_ok(me))        // round 6: also rows of 1025 .. 2048 cells in registers (32 cells per lane; the serial scan below was 14 x slower per cell)
 		return launch_dm_rmq<MODE>(ctx, 0, src, dst, nullptr, me, s);
 	// longer rows: serial row scan out of LDS (in place, like the table kernel for short rows)
 	const uint32_t n_rows = me.height * me.depth;
@@ -1773,7 +1785,7 @@ static int launch_dm_rmq(vkv_ctx *ctx, int axis, const uint8_t *src, uint8_t *ds
 		else if (len <= 1024)
 			VKV_DM_XW(16);
 		else
-			VKV_DM_XW(32);        // up to 2048 cells (the widest map dm_check_extent lets through)
+			VKV_DM_XW(32);        // up to 2048 cells (the widest map distance_launch_ok lets through)
 #undef VKV_DM_XW
 		return check_launch(ctx, "distance_map x pass");
 	}
@@ -1835,7 +1847,7 @@ static int dm_check_extent(vkv_ctx *ctx, VkvExtent3D me)
 {
 	if (me.width == 0 || me.height == 0 || me.depth == 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_map: zero map extent");
-	if (me.width > 2048)
+	if (!distance_launch_ok(me))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_map: map rows longer than 2048 cells (LDS strip limit of the x pass)");
 	return VKV_OK;
 }
@@ -1902,6 +1914,14 @@ int launch_distance_map_anisotropic(vkv_ctx *ctx, uint8_t *const m[8], uint8_t *
 	if ((rc = launch_dm_axis<-1>(ctx, 1, m[7], swap, me, s))) return rc;          // stage2(7, -1)
 	if ((rc = launch_dm_axis<1>(ctx, 2, swap, m[6], me, s))) return rc;           // stage3(6, +1)
 	return launch_dm_axis<-1>(ctx, 2, swap, m[7], me, s);                         // stage3(7, -1)
+}
+
+// skipping_type's transform of the occupancy map (NONE and BLOCK use the raw 0/255 map: src/compute_distance_map.cpp:96-99)
+int launch_map_transform(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D me, int skipping_type, hipStream_t s)
+{
+	if (skipping_type == VKV_SKIP_ANISOTROPIC_DISTANCE)
+		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, me, s);
+	return skipping_type == VKV_SKIP_DISTANCE ? launch_distance_map(ctx, d_maps[0], d_swap, me, s) : VKV_OK;
 }
 
 int launch_check_numerics(vkv_ctx *ctx, int what, uint32_t first_bits, uint64_t count, unsigned long long *d_mismatches, hipStream_t s)
@@ -2224,14 +2244,11 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 	StreamScratch scratch;        // held from the bit table to the last map pass
 	if (d_maps)
 	{
-		if (transform && me.width > 2048)
-			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map rows longer than 2048 cells (LDS strip limit of the x pass)");
+		if (!occupancy_launch_ok(e, me) || (transform && !distance_launch_ok(me)))
+			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map too large for one launch");
 		const uint32_t mext[3] = {me.width, me.height, me.depth};
 		for (int a = 0; a < 3; ++a)        // src/compute_distance_map.cpp:110-113; the cells that meet the grown box
 			blk[a] = (int) ((ext[a] + mext[a] - 1) / mext[a]), c0[a] = g0[a] / (uint32_t) blk[a], c1[a] = (g1[a] - 1) / (uint32_t) blk[a] + 1;
-		const int cpb = 256 / blk[0] > 0 ? 256 / blk[0] : 1;
-		if ((uint64_t) ((me.width + cpb - 1) / cpb) * me.height > 0xffffffull || me.depth > 65535u)
-			return set_error(ctx, VKV_E_UNSUPPORTED, "update_volume_region: map too large for one launch");
 		if (!(scratch = stream_scratch(ctx, s)).p)
 			return VKV_E_UNSUPPORTED;
 	}
@@ -2311,11 +2328,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 			return rc;
 	}
 	// ---- 5. the whole-map transform
-	if (aniso)
-		return launch_distance_map_anisotropic(ctx, d_maps, d_swap, me, s);
-	if (skipping_type == VKV_SKIP_DISTANCE)
-		return launch_distance_map(ctx, d_maps[0], d_swap, me, s);
-	return VKV_OK;
+	return launch_map_transform(ctx, d_maps, d_swap, me, skipping_type, s);
 }
 
 }        // namespace vkv

@@ -292,6 +292,7 @@ namespace vkv
 {
 int  set_error(vkv_ctx *ctx, int code, const char *fmt, ...);
 int  check_launch(vkv_ctx *ctx, const char *what);
+int  check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box);        // VKV_OK for null (the whole volume) or a box inside extent
 VkvStreamKey stream_key(hipStream_t stream);
 // this stream's scratch block (out of the arena on first use, kept until vkv_release_stream / vkv_destroy), LOCKED until the object goes:
 // an entry point keeps it from its first write into the block to its last enqueue.  p == nullptr + error set when there is no room.

@@ -38,6 +38,11 @@ class VkvError(RuntimeError):
 _LIB = None
 
 
+def _maps_array(d_maps):
+    """the d_maps[8] argument of the C ABI: the given map pointers padded with NULL; None passes a NULL array"""
+    return None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
+
+
 def load():
     """Load the HIP library (once).  Raises VkvError if it has not been built — there is no CPU path."""
     global _LIB
@@ -154,12 +159,10 @@ class Context:
         self.check(self._lib.vkv_distance_map(self.handle, d_map, d_swap, map_extent, stream))
 
     def distance_map_anisotropic(self, d_maps, d_swap, map_extent, stream=0):
-        arr = (C.c_void_p * 8)(*d_maps)
-        self.check(self._lib.vkv_distance_map_anisotropic(self.handle, arr, d_swap, map_extent, stream))
+        self.check(self._lib.vkv_distance_map_anisotropic(self.handle, _maps_array(d_maps), d_swap, map_extent, stream))
 
     def compute_distance_map(self, d_volume, d_gradient, d_tf, tf, extent, d_maps, d_swap, map_extent, skipping_type, stream=0):
-        arr = (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
-        self.check(self._lib.vkv_compute_distance_map(self.handle, d_volume, d_gradient, d_tf, C.byref(tf), extent, arr,
+        self.check(self._lib.vkv_compute_distance_map(self.handle, d_volume, d_gradient, d_tf, C.byref(tf), extent, _maps_array(d_maps),
                                                       d_swap, map_extent, skipping_type, stream))
 
     def render(self, params, stream=0):
@@ -263,9 +266,8 @@ class Context:
     def update_transfer_function_rc(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
                                     d_count=None, stream=0):
         """Like update_transfer_function() but returns the status code (error-path tests); d_maps None passes a NULL array."""
-        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
         return self._lib.vkv_update_transfer_function(self.handle, None if options is None else C.byref(options), d_volume, d_gradient, extent, d_tf,
-                                                      d_tables, arr, d_swap, map_extent, skipping_type, d_count, stream)
+                                                      d_tables, _maps_array(d_maps), d_swap, map_extent, skipping_type, d_count, stream)
 
     def update_volume_region(self, d_src, voxel_type, big_endian, range_min, range_max, box, d_volume, d_gradient, d_packed, extent, d_tf, tf, d_maps,
                              d_swap, map_extent, skipping_type, stream=0):
@@ -277,10 +279,9 @@ class Context:
     def update_volume_region_rc(self, d_src, voxel_type, big_endian, range_min, range_max, box, d_volume, d_gradient, d_packed, extent, d_tf, tf,
                                 d_maps, d_swap, map_extent, skipping_type, stream=0):
         """Like update_volume_region() but returns the status code (error-path tests); box / tf / d_maps None pass NULL."""
-        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
         return self._lib.vkv_update_volume_region(self.handle, d_src, int(voxel_type), 1 if big_endian else 0, range_min, range_max,
                                                   None if box is None else C.byref(box), d_volume, d_gradient, d_packed, extent, d_tf,
-                                                  None if tf is None else C.byref(tf), arr, d_swap, map_extent, skipping_type, stream)
+                                                  None if tf is None else C.byref(tf), _maps_array(d_maps), d_swap, map_extent, skipping_type, stream)
 
     def volume_histogram(self, d_volume, d_gradient, extent, box, mode, d_histogram, stream=0):
         """vkv_volume_histogram: the (gradient byte, intensity byte) histogram of `box` (None: the whole volume) into the 65536 uint64 bins
@@ -342,10 +343,9 @@ class Context:
     def update_transfer_function_from_summary_rc(self, options, d_volume, d_gradient, extent, d_tf, d_tables, d_maps, d_swap, map_extent, skipping_type,
                                                  d_count, d_summary, d_histogram, d_unresolved=None, stream=0):
         """Like update_transfer_function_from_summary() but returns the status code; d_maps None passes a NULL array."""
-        arr = None if d_maps is None else (C.c_void_p * 8)(*(list(d_maps) + [None] * (8 - len(d_maps))))
         return self._lib.vkv_update_transfer_function_from_summary(self.handle, None if options is None else C.byref(options), d_volume, d_gradient,
-                                                                   extent, d_tf, d_tables, arr, d_swap, map_extent, skipping_type, d_count, d_summary,
-                                                                   d_histogram, d_unresolved, stream)
+                                                                   extent, d_tf, d_tables, _maps_array(d_maps), d_swap, map_extent, skipping_type, d_count,
+                                                                   d_summary, d_histogram, d_unresolved, stream)
 
     def debug_tf_scratch(self, d_out, stream=0):
         """vkv_debug_tf_scratch: the bit table + column mask (2056 words) in `stream`'s scratch block, copied to d_out"""
