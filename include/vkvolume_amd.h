@@ -639,6 +639,40 @@ typedef struct VkvMipOptions
  * scratch memory), so after one direct call on `stream` it can be captured into a hipGraph; it replays with the parameters it was captured with. */
 int vkv_render_mip(vkv_ctx *ctx, const VkvRenderParams *params, const VkvMipOptions *mip, void *stream);
 
+/* ---- isosurface ------------------------------------------------------------------------------------------------- */
+typedef struct VkvIsoOptions
+{
+	float          iso;             /* a sample hits if its filtered intensity v >= iso (finite; > 1: nothing hits; <= 0: the first sample hits) */
+	uint32_t       refine_steps;    /* 0 .. 16 bisection steps between samples k - 1 and k                                                        */
+	float          base_color[3];   /* surface colour, each finite and >= 0                                                                       */
+	float          ambient, diffuse, specular; /* finite, >= 0                                                                                    */
+	uint32_t       shininess;       /* 1 .. 1024, integer exponent of the specular term                                                           */
+	const uint8_t *d_max_map;       /* vkv_max_map of d_volume with params->map_extent, or NULL (dense: every sample up to the hit is filtered)     */
+	float *        d_out_normal;    /* 4 floats per pixel, indexed like the other outputs: world-space unit normal facing the camera, w = 1;      */
+	                                /* zeros without a hit; or NULL                                                                                */
+	uint32_t       flags;           /* must be 0 */
+} VkvIsoOptions;
+
+/* Shaded isosurface of one volume.  Rays, samples, clipping plane, options.depth_attachment with d_in_depth, sampling_factor and the filter
+ * (linear buffer or d_packed_volume: the same bits) are vkv_render_mip's; e = the ray's entry, s = its step (texture space).  k = the first
+ * sample index with v_k >= iso.  The hit parameter t is 0 for k == 0, else refine_steps bisection steps from lo = k - 1, hi = k (mid =
+ * (lo + hi) * 0.5, filtered at fma(mid, s, e): hi = mid if v >= iso, else lo = mid; t = hi), the hit point p = fma(t, s, e).  A pixel with a hit
+ * gets: d_out_depth the reverse-Z depth of p (the integrator's first-hit formula); the normal n from the integrator's tetrahedron gradient at p
+ * (g_tex = (gx W, gy H, gz D), n = transpose(model_inv[3x3]) g_tex normalised, turned to face the view vector v = -(model[3x3] s) normalised;
+ * v itself where that has no length); a headlight: d = clamp(n . v, 0, 1), L = (ambient + diffuse d) + specular d^shininess, RGBA32F
+ * (clamp(base_color L, 0, 1), 1) and its RGBA8 round-to-nearest; d_out_normal (n, 1).  Every other pixel gets what the integrator gives a pixel
+ * without colour: clear colour, depth 0 (the scene depth under depth_attachment), normal zeros.  Every step is IEEE arithmetic in an order
+ * DESIGN.md §5.10 fixes, so every output is specified to the bit.  d_out_counts (3 x u32 per pixel): samples filtered, max-map bytes read,
+ * samples skipped; [0] + [2] is k + 1 on a hit and the ray's sample count without one (refinement and gradient taps are not counted).
+ * With d_max_map a ray jumps over the samples of a cell whose byte B gives B * kInv255 < iso and stops at its first hit: the results equal
+ * the dense path's bit for bit.  VKV_E_UNSUPPORTED: blend_over_target, tiles.fill_outside, options.test != VKV_TEST_NONE.
+ * VKV_E_INVALID_ARGUMENT: a non-finite iso, refine_steps > 16, a negative or non-finite colour or coefficient, shininess outside 1 .. 1024,
+ * flags != 0, a max map without a valid map_extent, and what vkv_render_mip rejects of the fields read.  Every argument is checked before
+ * anything is enqueued: a rejected call writes nothing.  One kernel launch and nothing else (no scratch, no table, no allocation, no host
+ * wait), so after one direct call on `stream` it can be captured into a hipGraph.  Schedules as vkv_render_mip: whole image, rect, compact
+ * strided shares that assemble through vkv_scatter_tiles. */
+int vkv_render_isosurface(vkv_ctx *ctx, const VkvRenderParams *params, const VkvIsoOptions *iso, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

@@ -132,6 +132,14 @@ class MipOptions(C.Structure):
     _fields_ = [("threshold", C.c_float), ("window_max", C.c_float), ("d_max_map", C.c_void_p), ("d_out_intensity", C.c_void_p),
                 ("flags", C.c_uint32)]
 
+
+class IsoOptions(C.Structure):
+    """VkvIsoOptions (vkv_render_isosurface): iso value, bisection steps, headlight shading (base colour, ambient, diffuse, specular,
+    shininess), optional max map (vkv_max_map), optional normal output, flags (0)"""
+    _fields_ = [("iso", C.c_float), ("refine_steps", C.c_uint32), ("base_color", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float),
+                ("specular", C.c_float), ("shininess", C.c_uint32), ("d_max_map", C.c_void_p), ("d_out_normal", C.c_void_p), ("flags", C.c_uint32)]
+
+
 class Tuning(C.Structure):
     """VkvTuning"""
     _fields_ = [("struct_size", C.c_uint32), ("scheduler", C.c_int32), ("batch_mode", C.c_int32), ("batch_sequential", C.c_int32),

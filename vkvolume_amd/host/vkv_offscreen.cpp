@@ -28,6 +28,10 @@
 //                 [--mip=THRESHOLD[,WINDOW_MAX]] [--mip-dense]   maximum-intensity projection instead of the integrator (VolumeRenderSubpass::draw_mip,
 //                                  window_max 1 by default): the frame the dumps read, and with --benchmark=N N frames on one stream, "mip: N frames,
 //                                  X ms per frame (device events)".  Skips over the volume's max map unless --mip-dense
+//                 [--iso=VALUE[,REFINE]] [--iso-dense]   shaded isosurface instead of the integrator (VolumeRenderSubpass::draw_iso, REFINE
+//                                  bisection steps, 4 by default; white, ambient 0.1, diffuse 0.8, specular 0.3, shininess 32): the frame the dumps
+//                                  read, and with --benchmark=N N frames on one stream, "iso: N frames, X ms per frame (device events)".  Skips
+//                                  over the volume's max map unless --iso-dense
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -74,6 +78,9 @@ struct Args
 	std::string histogram;                 // --histogram=file: the volume's joint histogram
 	bool        mip = false, mip_dense = false;        // --mip=THRESHOLD[,WINDOW_MAX], --mip-dense
 	float       mip_threshold = 0.0f, mip_window_max = 1.0f;
+	bool        iso = false, iso_dense = false;        // --iso=VALUE[,REFINE], --iso-dense
+	float       iso_value = 0.5f;
+	uint32_t    iso_refine = 4;
 };
 
 bool flag(const char *arg, const char *name, std::string &value)
@@ -144,6 +151,15 @@ Args parse(int argc, char **argv)
 			if (std::sscanf(v.c_str(), "%f,%f", &a.mip_threshold, &a.mip_window_max) < 1)
 				throw std::runtime_error("--mip=THRESHOLD[,WINDOW_MAX]");
 			a.mip = true;
+		}
+		else if (flag(s, "--iso-dense", v)) a.iso_dense = true;
+		else if (flag(s, "--iso", v))
+		{
+			unsigned refine = a.iso_refine;
+			if (std::sscanf(v.c_str(), "%f,%u", &a.iso_value, &refine) < 1)
+				throw std::runtime_error("--iso=VALUE[,REFINE]");
+			a.iso_refine = refine;
+			a.iso        = true;
 		}
 		else if (s[0] != '-') a.dataset = s;
 		else throw std::runtime_error(std::string("unknown flag ") + s);
@@ -518,6 +534,38 @@ int main(int argc, char **argv)
 				(void) hipEventDestroy(ev0);
 				(void) hipEventDestroy(ev1);
 				subpass.draw_mip(target, args.mip_threshold, args.mip_window_max, nullptr, !args.mip_dense);        // the frame the dumps read
+				(void) hipStreamSynchronize(stream);
+			}
+		}
+		else if (args.iso)
+		{        // shaded isosurface: the frame the dumps read, then (benchmark) `frames` frames on one stream
+			VkvIsoOptions iso{};
+			iso.iso = args.iso_value, iso.refine_steps = args.iso_refine;
+			iso.base_color[0] = iso.base_color[1] = iso.base_color[2] = 1.0f;
+			iso.ambient = 0.1f, iso.diffuse = 0.8f, iso.specular = 0.3f, iso.shininess = 32;
+			if (!args.iso_dense)
+				volume.build_max_map(dc);
+			subpass.draw_iso(target, iso, !args.iso_dense);
+			(void) hipStreamSynchronize(stream);
+			if (benchmark)
+			{
+				RenderTarget frame = target;
+				frame.counts       = nullptr;
+				hipEvent_t ev0 = nullptr, ev1 = nullptr;
+				if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)
+					throw std::runtime_error("hipEventCreate failed");
+				(void) hipEventRecord(ev0, stream);
+				for (int f = 0; f < frames; ++f)
+					subpass.draw_iso(frame, iso, !args.iso_dense);
+				(void) hipEventRecord(ev1, stream);
+				(void) hipEventSynchronize(ev1);
+				float ms = 0.0f;
+				(void) hipEventElapsedTime(&ms, ev0, ev1);
+				std::printf("iso: %d frames, %g ms per frame (device events)\n", frames, ms / frames);
+				std::printf("ran %d frames, averaged %g fps\n", frames, 1000.0 * frames / ms);
+				(void) hipEventDestroy(ev0);
+				(void) hipEventDestroy(ev1);
+				subpass.draw_iso(target, iso, !args.iso_dense);        // the frame the dumps read
 				(void) hipStreamSynchronize(stream);
 			}
 		}

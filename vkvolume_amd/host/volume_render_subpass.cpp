@@ -121,6 +121,21 @@ void VolumeRenderSubpass::draw_mip(const RenderTarget &target, float threshold, 
 		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_mip: ") + vkv_last_error(dc.ctx));
 }
 
+void VolumeRenderSubpass::draw_iso(const RenderTarget &target, const VkvIsoOptions &iso, bool skip, const VkvTileSchedule *tiles)
+{
+	Volume *volume = volumes.front();
+	if (!volume->get_packed_volume())
+		volume->pack(dc);
+	if (skip && !volume->get_max_map())
+		throw std::runtime_error("VolumeRenderSubpass::draw_iso: skip needs the volume's max map (Volume::build_max_map)");
+	VkvRenderParams p = make_params(*volume, target, tiles, false);
+	p.options.test    = VKV_TEST_NONE;        // the test modes are the integrator's outputs (benchmark mode sets one)
+	VkvIsoOptions o   = iso;
+	o.d_max_map       = skip ? volume->get_max_map() : nullptr;
+	if (vkv_render_isosurface(dc.ctx, &p, &o, dc.stream) != VKV_OK)
+		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_iso: ") + vkv_last_error(dc.ctx));
+}
+
 void VolumeRenderSubpass::draw_batch(const std::vector<RenderTarget> &targets, const VkvTileSchedule *tiles)
 {
 	if (volumes.size() != 1 || targets.empty() || targets.size() > VKV_MAX_BATCH)

@@ -85,6 +85,11 @@ class VolumeRenderSubpass
 	void draw_mip(const RenderTarget &target, float threshold, float window_max, float *intensity = nullptr, bool skip = true,
 	              const VkvTileSchedule *tiles = nullptr);
 
+	// Shaded isosurface of the first volume into `target` (vkv_render_isosurface): the first sample >= iso, refined by
+	// `refine_steps` bisection steps, lit by a headlight (iso->base_color etc.; `iso` fills every field of VkvIsoOptions but d_max_map, which
+	// comes from the volume when skip is set: Volume::build_max_map first; the same bits as the dense path).
+	void draw_iso(const RenderTarget &target, const VkvIsoOptions &iso, bool skip = true, const VkvTileSchedule *tiles = nullptr);
+
 	// The schedule of a whole frame on one GPU (round 6): the 16x16 tiles of the rectangle the clipped box projects into (vkv_screen_tile_rect: the
 	// rasteriser of the reference only shades the box's faces, :262-293) with VkvTileSchedule.fill_outside - the launch's workgroups write the
 	// no-fragment result everywhere else, so the frame is complete without a workgroup per empty tile (C3: half of the frame's tiles, 2.7 % of its time).

@@ -23,7 +23,7 @@ EXPORTS = [
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
-    "vkv_max_map", "vkv_render_mip",
+    "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -110,6 +110,7 @@ def load():
                                                             vp, vp, vp, vp]
     L.vkv_max_map.argtypes = [vp, vp, abi.Extent3D, abi.Extent3D, P(abi.Box), vp, vp]
     L.vkv_render_mip.argtypes = [vp, P(abi.RenderParams), P(abi.MipOptions), vp]
+    L.vkv_render_isosurface.argtypes = [vp, P(abi.RenderParams), P(abi.IsoOptions), vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -323,6 +324,13 @@ class Context:
 
     def render_mip_rc(self, params, mip, stream=0):
         return self._lib.vkv_render_mip(self.handle, None if params is None else C.byref(params), None if mip is None else C.byref(mip), stream)
+
+    def render_isosurface(self, params, iso, stream=0):
+        """vkv_render_isosurface: shaded isosurface of params' volume with the abi.IsoOptions `iso`"""
+        self.check(self.render_isosurface_rc(params, iso, stream))
+
+    def render_isosurface_rc(self, params, iso, stream=0):
+        return self._lib.vkv_render_isosurface(self.handle, None if params is None else C.byref(params), None if iso is None else C.byref(iso), stream)
 
     def occupancy_map_from_summary(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
         """vkv_occupancy_map_from_summary: vkv_occupancy_map's map, decided from the cell summaries where they are certain; d_unresolved

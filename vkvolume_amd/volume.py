@@ -346,6 +346,26 @@ class VolumeRenderSubpass:
                              flags=0)
         self.ctx.render_mip(params, mip, _stream())
 
+    def draw_iso(self, params, iso, refine_steps=4, base_color=(1.0, 1.0, 1.0), ambient=0.1, diffuse=0.8, specular=0.3, shininess=32, color=None,
+                 rgba8=None, depth=None, normal=None, counts=None, skip=True, in_depth=None):
+        """Shaded isosurface (vkv_render_isosurface) of ``params``' rays into the given buffers: the first sample whose filtered intensity is
+        >= ``iso``, refined by ``refine_steps`` bisection steps, lit by a headlight (``base_color`` times ambient + diffuse + specular with the
+        integer exponent ``shininess``); ``normal``: 4 floats per pixel, the world-space unit normal facing the camera.  ``skip``: jump over the
+        cells of the volume's max map (build_max_map() first; the same bits as the dense path); False: filter every sample up to the hit.
+        ``in_depth``: scene depth for options.depth_attachment."""
+        max_map = None
+        if skip:
+            if self.volume.max_map is None:
+                raise RuntimeError("VolumeRenderSubpass.draw_iso: skip=True needs the volume's max map (call Volume.build_max_map first)")
+            max_map = self.volume.max_map
+        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
+        params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
+        params.d_in_depth, params.blend_over_target = _ptr(in_depth), 0
+        opts = abi.IsoOptions(iso=float(iso), refine_steps=int(refine_steps), base_color=(C.c_float * 3)(*[float(c) for c in base_color]),
+                              ambient=float(ambient), diffuse=float(diffuse), specular=float(specular), shininess=int(shininess),
+                              d_max_map=_ptr(max_map), d_out_normal=_ptr(normal), flags=0)
+        self.ctx.render_isosurface(params, opts, _stream())
+
 
 def default_scene(volume, voxel_size=(1.0, 1.0, 1.0), axis_angle=(1.0, 0.0, 0.0, 0.0)):
     """image transform from the header fields + benchmark-mode node scale (src/load_volume.cpp:82-83,
