@@ -88,6 +88,16 @@ def assert_same_bits(a, b, what=""):
     assert np.all(cb[:, 1] == 0) and np.all(cb[:, 2] == 0), (what, "dense counts")
 
 
+def assert_matches_numpy(got, ref, what=""):
+    """the dense isosurface against iso_np, bit for bit on every pixel: colour, RGBA8, depth, normal and the sample count"""
+    n = got["counts"].shape[0]
+    for key in KEYS:
+        assert np.array_equal(bits(got[key].reshape(n, -1)), bits(np.ascontiguousarray(ref[key]).reshape(n, -1))), (what, key)
+    k = ref["k"].reshape(-1)
+    assert np.array_equal(got["counts"][:, 0].astype(np.int64), np.where(k >= 0, k + 1, ref["n_steps"].reshape(-1))), (what, "counts")
+    assert np.all(got["counts"][:, 1:] == 0), (what, "counts")
+
+
 def scene_volume(shape=(37, 29, 23), seed=5):
     return O.synth_volume(shape, 1, seed)
 
@@ -113,16 +123,8 @@ def test_dense_iso_matches_numpy_bit_for_bit(ctx, packed, cam):
             ref = iso_np(p, vol, opts)
             found = ref["found"].reshape(-1)
             assert found.sum() > 50, (cam, shape, sf)
-            k, n = ref["k"].reshape(-1), ref["n_steps"].reshape(-1)
-            want_counts = np.where(found, k + 1, n)
-            # (the restatement's fma goes through float64: a ray whose sample count it rounds differently is left out, at most two)
-            same = got["counts"][:, 0] == want_counts.astype(np.int32)
-            assert (~same).sum() <= 2, (cam, shape, sf)
-            assert np.all(got["counts"][:, 1:] == 0)
-            for key in KEYS:
-                g, r = got[key].reshape(len(same), -1), ref[key].reshape(len(same), -1)
-                assert np.array_equal(bits(g)[same], bits(np.ascontiguousarray(r))[same]), (cam, shape, sf, key)
-            assert np.all(got["normal"][~found & same] == 0)
+            assert_matches_numpy(got, ref, (cam, shape, sf))
+            assert np.all(got["normal"][~found] == 0)
 
 
 # ---- skipping against dense --------------------------------------------------------------------------------------------------------------
@@ -245,10 +247,7 @@ def test_depth_attachment(ctx):
         assert_same_bits(fast, dense, ("depth attachment", packed))
         opts = iso_options(0.3)
         ref = iso_np(p, vol, opts, in_depth=scene)
-        same = dense["counts"][:, 0] == np.where(ref["found"].reshape(-1), ref["k"].reshape(-1) + 1, ref["n_steps"].reshape(-1)).astype(np.int32)
-        assert (~same).sum() <= 2
-        for key in KEYS:
-            assert np.array_equal(bits(dense[key].reshape(len(same), -1))[same], bits(np.ascontiguousarray(ref[key].reshape(len(same), -1)))[same]), key
+        assert_matches_numpy(dense, ref, ("depth attachment", packed))
         hit = dense["rgba8"][:, 3] == 255
         none = ~hit
         assert np.array_equal(dense["depth"][none].view(np.uint32), scene[none].view(np.uint32))  # the scene depth where nothing hits
@@ -273,9 +272,7 @@ def test_max_map_kept_current_across_volume_region_updates(ctx):
             fast = draw(sp, p, iso, skip=True)
             assert_same_bits(fast, dense, (origin, iso))
             ref = iso_np(p, vol, iso_options(iso))
-            same = dense["counts"][:, 0] == np.where(ref["found"].reshape(-1), ref["k"].reshape(-1) + 1, ref["n_steps"].reshape(-1)).astype(np.int32)
-            assert (~same).sum() <= 2
-            assert np.array_equal(bits(dense["rgba8"])[same], ref["rgba8"].reshape(-1, 4)[same]), (origin, iso)
+            assert_matches_numpy(dense, ref, (origin, iso))
 
 
 def test_schedules_rect_and_compact_strided(ctx):

@@ -1,0 +1,111 @@
+"""GPU: a seeded sweep of max-map skipping in both renderers (VKV_TEST_FUZZ_SEEDS=n draws per family).  Each draw takes a volume shape (axes
+1 and 2 voxels thick, (1, 1, 1), odd widths), a map extent per axis (block 1, blocks 2-9, one cell, cells past the volume), one of six
+kinds of content, an anisotropic / rotated voxel grid, a camera outside, inside behind the clipping plane or exactly axis-parallel on an
+odd image, a sampling factor, bounds on and beside the map's bytes, packed or linear sampling and, on some draws, a depth attachment
+(tests/test_max_map_skip_cpu.py: draw_geometry).  For every draw: vkv_max_map equals max_map_np; the skipping MIP / isosurface equal the
+dense ones bit for bit on every output; the dense ones equal mip_np / iso_np bit for bit; the skipping path's three counters equal the
+restated walk's (max_map_skip_np) pixel by pixel; and the draw skipped samples."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import helpers as T
+from tests.test_gpu_iso import assert_matches_numpy as assert_iso_matches_numpy
+from tests.test_gpu_iso import assert_same_bits as assert_iso_same_bits
+from tests.test_gpu_iso import draw as draw_iso
+from tests.test_gpu_mip import assert_matches_numpy as assert_mip_matches_numpy
+from tests.test_gpu_mip import assert_same_bits as assert_mip_same_bits
+from tests.test_gpu_mip import draw as draw_mip
+from tests.test_iso_cpu import iso_np, iso_options
+from tests.test_max_map_skip_cpu import FAMILIES, draw_bounds, draw_geometry
+from tests.test_mip_cpu import max_map_np, max_map_skip_np, mip_np, rays_np, samples_np
+from vkvolume_amd import abi, lib, volume as V
+
+pytestmark = pytest.mark.gpu
+SEEDS = int(os.environ.get("VKV_TEST_FUZZ_SEEDS", "6"))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    torch.cuda.set_device(0)
+    c = lib.Context(0)
+    yield c
+    c.close()
+
+
+def assert_counts_equal_walk(got, walk, what):
+    c = got["counts"].astype(np.int64)
+    for j, key in enumerate(("n_filt", "n_probe", "n_skip")):
+        assert np.array_equal(c[:, j], walk[key]), (what, key, int(np.sum(c[:, j] != walk[key])))
+
+
+@pytest.mark.parametrize("seed", range(SEEDS))
+@pytest.mark.parametrize("family", FAMILIES)
+def test_max_map_skipping_sweep(ctx, family, seed):
+    rng = np.random.default_rng(31000 + 100 * seed + FAMILIES.index(family))
+    g = draw_geometry(rng, family)
+    vol = g["vol"]
+    me = g["map_extent"]
+    packed, depth_attachment = bool(rng.integers(0, 2)), rng.random() < 0.3
+    what = dict(family=family, seed=seed, shape=g["shape"], map_extent=me, voxel=g["voxel_size"], axis_angle=g["axis_angle"], camera=g["camera"],
+                sf=g["sampling_factor"], packed=packed, depth=depth_attachment)
+    # the volume, and its max map for this map extent (checked against the restatement first)
+    v = V.Volume(ctx)
+    v.options = abi.VolumeOptions(use_precomputed_gradient=0, intensity_min=0.1, intensity_max=1.0, gradient_min=0.0, gradient_max=0.2,
+                                  sampling_factor=1.0, voxel_alpha_factor=1.0)
+    v.load_from_array(vol)
+    V.default_scene(v, voxel_size=g["voxel_size"], axis_angle=g["axis_angle"])
+    v.use_packed = packed
+    mm = torch.full((me[2], me[1], me[0]), 0xAB, dtype=torch.uint8, device="cuda")
+    ctx.max_map(v.volume.data_ptr(), v.extent, abi.Extent3D(*me), None, mm.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    mm_np = max_map_np(vol, me)
+    assert np.array_equal(mm.cpu().numpy(), mm_np), what
+    v.max_map = mm
+    # the frame
+    size = (47, 33) if g["axis_parallel"] else (48, 40)
+    az, el, radius, clip = g["camera"]
+    sp = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=abi.SKIP_NONE, clip_distance=clip, early_ray_termination=0,
+                                                         depth_attachment=1 if depth_attachment else 0), size)
+    view, proj = T.orbit(az, el, radius, image_size=size)
+    p = sp.make_params(view, proj)
+    p.transfer_function.sampling_factor = g["sampling_factor"]
+    p.map_extent = abi.Extent3D(*me)
+    scene, d_scene = None, None
+    if depth_attachment:
+        # a scene depth inside the volume's depth range for half the pixels, far (0) elsewhere
+        sp0 = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=abi.SKIP_NONE, clip_distance=clip, early_ray_termination=0), size)
+        p0 = sp0.make_params(view, proj)
+        p0.transfer_function.sampling_factor = g["sampling_factor"]
+        probe = draw_mip(sp0, p0, -1.0, 1.0, skip=False, size=size)
+        zs = probe["depth"][probe["rgba8"][:, 3] == 255]
+        lo, hi = (float(zs.min()), float(zs.max())) if zs.size else (0.0, 1.0)
+        scene = np.where(rng.random(size[0] * size[1]) < 0.5, rng.uniform(lo, hi, size[0] * size[1]), 0.0).astype(np.float32)
+        d_scene = torch.from_numpy(scene).cuda()
+    R = rays_np(p, scene)
+    assert R["marched"].sum() > 0, what
+    S = samples_np(vol, R)
+    skipped = 0
+    for thr in draw_bounds(rng, g, mm_np):
+        wmax = float(rng.choice([0.0, 0.5, 1.0]))
+        dense = draw_mip(sp, p, thr, wmax, skip=False, size=size, in_depth=d_scene)
+        fast = draw_mip(sp, p, thr, wmax, skip=True, size=size, in_depth=d_scene)
+        at = dict(what, renderer="mip", threshold=float(thr))
+        assert_mip_same_bits(fast, dense, at)
+        assert_mip_matches_numpy(dense, mip_np(p, vol, abi.MipOptions(threshold=float(thr), window_max=wmax), in_depth=scene, S=S), at)
+        assert_counts_equal_walk(fast, max_map_skip_np(p, vol, mm_np, thr, False, R, S), at)
+        skipped += int(fast["counts"][:, 2].sum())
+    for iso in draw_bounds(rng, g, mm_np):
+        opts = iso_options(float(iso), refine_steps=int(rng.integers(0, 17)), shininess=int(rng.integers(1, 65)))
+        kw = dict(refine_steps=opts.refine_steps, base_color=tuple(opts.base_color), ambient=opts.ambient, diffuse=opts.diffuse,
+                  specular=opts.specular, shininess=opts.shininess)
+        dense = draw_iso(sp, p, opts.iso, skip=False, size=size, in_depth=d_scene, **kw)
+        fast = draw_iso(sp, p, opts.iso, skip=True, size=size, in_depth=d_scene, **kw)
+        at = dict(what, renderer="iso", iso=float(iso))
+        assert_iso_same_bits(fast, dense, at)
+        assert_iso_matches_numpy(dense, iso_np(p, vol, opts, in_depth=scene, S=S), at)
+        assert_counts_equal_walk(fast, max_map_skip_np(p, vol, mm_np, opts.iso, True, R, S), at)
+        skipped += int(fast["counts"][:, 2].sum())
+    assert skipped > 0, what

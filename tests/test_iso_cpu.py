@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.test_mip_cpu import _fma, _gmax, _gmin, _mat4_mul, params_np, rays_np, sample_linear_np
+from tests.test_mip_cpu import _fma, _gmax, _gmin, _mat4_mul, params_np, rays_np, sample_linear_np, samples_np
 from vkvolume_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,10 +47,18 @@ def power_bits(d, shininess):
     return r
 
 
-def iso_np(p, vol, o, in_depth=None):
+def iso_walk_dense(v, n, iso):
+    """the dense isosurface's hit over a samples_np matrix: the first index of a sample >= iso (-1: none)"""
+    if v.shape[1] == 0:
+        return np.full(n.size, -1, np.int64)
+    hit = (np.arange(v.shape[1])[None, :] < n[:, None]) & (v >= F(iso))
+    return np.where(hit.any(axis=1), hit.argmax(axis=1), -1).astype(np.int64)
+
+
+def iso_np(p, vol, o, in_depth=None, S=None):
     """The isosurface of DESIGN.md §5.10 for the whole image of RenderParams p and IsoOptions o over the (D, H, W) uint8 volume: dict of
     (h, w)-shaped arrays color (h, w, 4), rgba8 (h, w, 4), depth, normal (h, w, 4), k (-1: no hit), t, n_steps, and the flat per-pixel
-    hit point / refined value (for the self-checks)."""
+    hit point / refined value (for the self-checks).  S: samples_np of the same rays, if already at hand."""
     assert isinstance(o, abi.IsoOptions) and o.flags == 0
     R = rays_np(p, in_depth)
     w, h = p.image_width, p.image_height
@@ -59,15 +67,8 @@ def iso_np(p, vol, o, in_depth=None):
     N = n.size
     iso = F(o.iso)
     D, H, W = vol.shape
-    k = np.full(N, -1, np.int64)
+    k = iso_walk_dense((samples_np(vol, R) if S is None else S)["v"], n, iso)
     with np.errstate(all="ignore"):
-        for i in range(int(n.max()) if N else 0):
-            live = (i < n) & (k < 0)
-            if not live.any():
-                break
-            fi = F(i)
-            v = sample_linear_np(vol, _fma(fi, s[0], e[0]), _fma(fi, s[1], e[1]), _fma(fi, s[2], e[2]))
-            k = np.where(live & (v >= iso), i, k)
         found = k >= 0
         # refinement
         lo, hi = (k - 1).astype(F), k.astype(F)

@@ -1,8 +1,10 @@
 """Maximum-intensity projection without a GPU: the ctypes mirror of VkvMipOptions against the C header, the two facts the skipping path's
 exactness rests on (every lerp of the filter lies between its endpoints; x * kInv255 is monotone), the numpy restatements of
-vkv_max_map (max_map_np) and of the dense MIP (mip_np) on analytic volumes, and the compiled MIP kernels' listing (no scratch).
+vkv_max_map (max_map_np) and of the dense MIP (mip_np) on analytic volumes, the correctly rounded fp32 fma of the restatements (_fma)
+against an exact one, and the compiled MIP kernels' listing (no scratch).
 
-max_map_np and mip_np are the references tests/test_gpu_mip.py compares the device against."""
+max_map_np and mip_np are the references tests/test_gpu_mip.py compares the device against; max_map_skip_np restates the skip walk of both
+renderers (tests/test_max_map_skip_cpu.py, tests/test_gpu_max_map_sweep.py)."""
 import ctypes as C
 import os
 import re
@@ -41,8 +43,19 @@ def max_map_np(vol, map_extent):
 
 
 def _fma(a, b, c):
-    """fp32 fma through float64 (the product of two floats is exact in float64)"""
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F)
+    """fp32 fma, correctly rounded: the product of two floats is exact in float64 (24 + 24 bits), TwoSum gives the rounding error of the
+    float64 sum exactly, and the sum rounded to odd (53 >= 2 * 24 + 2 bits) then rounds to the float32 nearest the exact value.  (A plain
+    float64 sum rounded twice can land on a float32 tie the exact value is not on.)  Non-finite operands give float64's inf / NaN."""
+    a, b, c = (np.asarray(x, F).astype(np.float64) for x in (a, b, c))
+    with np.errstate(all="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        even = (np.asarray(s).view(np.uint64) & np.uint64(1)) == 0
+        fix = np.isfinite(err) & (err != 0) & even
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return np.asarray(s).astype(F)
 
 
 def _gmin(x, y):
@@ -148,31 +161,45 @@ def rays_np(p, in_depth=None):
     return dict(fragment=frag, marched=ok, e=e, s=s, n_steps=n_steps, no_colour_depth=no_colour_depth)
 
 
-def mip_np(p, vol, mip, in_depth=None):
+def samples_np(vol, R):
+    """every sample of every ray of rays_np's R: (rays, max n_steps) arrays v (the filtered intensity, 0 past a ray's n_steps) and cx, cy,
+    cz (the sampler's voxel coordinates fma(pos, extent, -0.5) of each sample)"""
+    D, H, W = vol.shape
+    n, e, s = R["n_steps"], R["e"], R["s"]
+    m = int(n.max()) if n.size else 0
+    live = np.arange(m)[None, :] < n[:, None]
+    fi = np.arange(m, dtype=F)[None, :]
+    with np.errstate(all="ignore"):
+        pos = [np.where(live, _fma(fi, s[a][:, None], e[a][:, None]), F(0.5)) for a in range(3)]  # (the dead samples read the centre)
+        v = np.where(live, sample_linear_np(vol, *pos), F(0))
+        cx, cy, cz = _fma(pos[0], F(W), F(-0.5)), _fma(pos[1], F(H), F(-0.5)), _fma(pos[2], F(D), F(-0.5))
+    return dict(v=v, cx=cx, cy=cy, cz=cz, live=live)
+
+
+def mip_walk_dense(v, n, threshold):
+    """the dense MIP over a samples_np matrix: best (threshold if nothing counts) and k (the first index of the largest sample > threshold,
+    -1 if none)"""
+    best = np.full(n.size, F(threshold), F)
+    k = np.full(n.size, -1, np.int64)
+    for i in range(v.shape[1]):
+        up = (i < n) & (v[:, i] > best)
+        best = np.where(up, v[:, i], best)
+        k = np.where(up, i, k)
+    return best, k
+
+
+def mip_np(p, vol, mip, in_depth=None, S=None):
     """The dense MIP of DESIGN.md §5.9 for the whole image of RenderParams p and MipOptions mip (threshold, window_max) over the (D, H, W)
-    uint8 volume: dict of (h, w) arrays intensity, color (h, w, 4), rgba8 (h, w, 4), depth, n_steps, and second (the largest counted sample
-    other than at index k, -inf if none: depth is only well defined where the top two differ)."""
+    uint8 volume: dict of (h, w) arrays intensity, color (h, w, 4), rgba8 (h, w, 4), depth, n_steps, k (the first index of the largest
+    counted sample, -1: none) and found.  S: samples_np of the same rays, if already at hand."""
     assert isinstance(mip, MipOptions) and mip.flags == 0
     threshold, window_max = F(mip.threshold), F(mip.window_max)
     R = rays_np(p, in_depth)
     w, h = p.image_width, p.image_height
     n = R["n_steps"]
     thr = F(threshold)
-    best = np.full(n.size, thr, F)
-    k = np.full(n.size, -1, np.int64)
-    second = np.full(n.size, -np.inf, F)
     e, s = R["e"], R["s"]
-    for i in range(int(n.max()) if n.size else 0):
-        live = i < n
-        fi = F(i)
-        with np.errstate(all="ignore"):
-            v = sample_linear_np(vol, _fma(fi, s[0], e[0]), _fma(fi, s[1], e[1]), _fma(fi, s[2], e[2]))
-        v = np.where(live, v, F(0))
-        up = live & (v > best)
-        counted = live & (v > thr)
-        second = np.where(up, np.where(k >= 0, best, second), np.where(counted, _gmax(second, v), second))
-        best = np.where(up, v, best)
-        k = np.where(up, i, k)
+    best, k = mip_walk_dense((samples_np(vol, R) if S is None else S)["v"], n, thr)
     found = k >= 0
     intensity = np.where(found, best, F(0))
     if window_max <= threshold:
@@ -193,21 +220,140 @@ def mip_np(p, vol, mip, in_depth=None):
             depth = np.where(found, c4[2] / c4[3], depth)
     shp = (h, w)
     return dict(intensity=intensity.reshape(shp), color=color.reshape(h, w, 4), rgba8=rgba8.reshape(h, w, 4), depth=depth.reshape(shp).astype(F),
-                n_steps=n.reshape(shp), second=second.reshape(shp), found=found.reshape(shp))
+                n_steps=n.reshape(shp), k=k.reshape(shp), found=found.reshape(shp))
+
+
+KMAX_SAMPLE = F(255) * INV255  # kMaxSample of mip.hip: the largest value a sample can take
+
+
+def max_map_geometry_np(extent_whd, map_extent_whd):
+    """fill_max_map_geometry: per axis the block ceil(extent / map extent), the last cell that holds a voxel (extent - 1) / block, and
+    1 / block as a float"""
+    b = [-(-e // m) for e, m in zip(extent_whd, map_extent_whd)]
+    return b, [(e - 1) // bb for e, bb in zip(extent_whd, b)], [F(1) / F(bb) for bb in b]
+
+
+def _in_grown(c, lo, b):
+    """in_grown of max_map_skip.hpp: c in [lo - 1, lo + b)"""
+    return (c >= (lo - 1).astype(F)) & (c < (lo + b).astype(F))
+
+
+def max_map_skip_np(p, vol, max_map, bound, strict, R=None, S=None):
+    """The skip walk of the max-map MIP (strict=False: mip.hip's inline step, bound = the threshold) or of the max-map isosurface (strict=True:
+    max_map_skip<true>, bound = iso) over the (md, mh, mw) max map and p.map_extent, with the device's float32 operations in order,
+    vectorised over the rays of the whole image.  Per sample i of a ray: the cell of its voxel coordinates (clamped to the last cell that
+    holds a voxel); on entering a cell other than the last probed one, a probe; when the byte cannot reach the bound (MIP: B * kInv255 <=
+    max(threshold, best so far); iso: B * kInv255 < iso) and the sample lies in the grown cell, samples i .. i + kk are skipped (kk from the
+    per-axis IEEE estimate, 0 unless sample i + kk lies in the grown cell too) and the next sample probes again.  Otherwise the sample is
+    filtered; the MIP stops at kMaxSample (the rest counts as skipped), the isosurface at its hit.
+
+    Returns a dict of flat per-ray arrays: best (MIP: max(threshold, largest sample)), k (MIP: first index of the largest sample > threshold;
+    iso: first index of a sample >= iso; -1: none), n_filt, n_probe, n_skip (the kernel's counters), and skipped (rays, max n_steps) bool /
+    skip_top (the byte value B * kInv255 of the cell each skipped sample was skipped by)."""
+    if R is None:
+        R = rays_np(p)
+    if S is None:
+        S = samples_np(vol, R)
+    D, H, W = vol.shape
+    me = (p.map_extent.width, p.map_extent.height, p.map_extent.depth)
+    (bx, by, bz), (lcx, lcy, lcz), (rbx, rby, rbz) = max_map_geometry_np((W, H, D), me)
+    mw, mh = me[0], me[1]
+    n = R["n_steps"]
+    N, M = S["v"].shape
+    cx, cy, cz = S["cx"], S["cy"], S["cz"]
+    # per sample, as the probe at that sample computes it: the cell, its byte, the grown-cell test, and the last index the skip would reach
+    with np.errstate(all="ignore"):
+        cell_of = lambda c, rb, lc: np.clip(np.floor((c + F(0.5)) * rb).clip(-2 ** 30, 2 ** 30).astype(np.int64), 0, lc)  # noqa: E731
+        mx, my, mz = cell_of(cx, rbx, lcx), cell_of(cy, rby, lcy), cell_of(cz, rbz, lcz)
+        cell = (mz * mh + my) * mw + mx
+        top = max_map.reshape(-1)[cell].astype(F) * INV255
+        lx, ly, lz = mx * bx, my * by, mz * bz
+        grown = _in_grown(cx, lx, bx) & _in_grown(cy, ly, by) & _in_grown(cz, lz, bz)
+        fW, fH, fD = F(W), F(H), F(D)
+
+        def t_axis(step, scale, c, lo, b):
+            sv = (step * scale)[:, None]
+            up = ((lo + b).astype(F) - F(0.25) - c) / sv
+            dn = (lo.astype(F) - F(0.75) - c) / sv
+            return np.where(sv > 0, up, np.where(sv < 0, dn, F(np.inf))).astype(F)
+        s = R["s"]
+        tx, ty, tz = t_axis(s[0], fW, cx, lx, bx), t_axis(s[1], fH, cy, ly, by), t_axis(s[2], fD, cz, lz, bz)
+        idx = np.arange(M)[None, :]
+        rest = (n[:, None] - 1 - idx).astype(F)
+        tm = _gmin(_gmin(tx, ty), _gmin(tz, rest))
+        kk = np.where(tm > 0, np.floor(np.where(tm > 0, tm, F(0))).astype(np.int64), 0)
+        j = np.clip(idx + kk, 0, max(M - 1, 0))
+        rows = np.arange(N)[:, None]
+        q_ok = _in_grown(cx[rows, j], lx, bx) & _in_grown(cy[rows, j], ly, by) & _in_grown(cz[rows, j], lz, bz)
+        last = idx + np.where((kk > 0) & ~q_ok, 0, kk)
+    # the walk: one event per active ray and round (a skip, or one filtered sample)
+    v = S["v"]
+    best = np.full(N, F(bound), F)
+    k = np.full(N, -1, np.int64)
+    i = np.zeros(N, np.int64)
+    last_cell = np.full(N, -1, np.int64)
+    n_filt, n_probe, n_skip = (np.zeros(N, np.int64) for _ in range(3))
+    skip_start = np.zeros((N, M + 1), np.int64)
+    skip_top = np.full((N, M), np.nan, F)
+    done = i >= n
+    while True:
+        r = np.nonzero(~done)[0]
+        if r.size == 0:
+            break
+        ii = i[r]
+        c = cell[r, ii]
+        probe = c != last_cell[r]
+        n_probe[r] += probe
+        last_cell[r] = np.where(probe, c, last_cell[r])
+        t = top[r, ii]
+        low = t < best[r] if strict else t <= best[r]
+        sk = probe & low & grown[r, ii]
+        # skips
+        rs, i0, i1 = r[sk], ii[sk], last[r[sk], ii[sk]]
+        n_skip[rs] += i1 + 1 - i0
+        np.add.at(skip_start, (rs, i0), 1)
+        np.add.at(skip_start, (rs, i1 + 1), -1)
+        skip_top[rs, i0] = t[sk]
+        i[rs] = i1 + 1
+        last_cell[rs] = -1
+        # filtered samples
+        rf, fi = r[~sk], ii[~sk]
+        n_filt[rf] += 1
+        x = v[rf, fi]
+        if strict:
+            hit = x >= best[rf]
+            k[rf[hit]] = fi[hit]
+            done[rf[hit]] = True
+        else:
+            up = x > best[rf]
+            best[rf] = np.where(up, x, best[rf])
+            k[rf] = np.where(up, fi, k[rf])
+            stop = best[rf] >= KMAX_SAMPLE
+            n_skip[rf[stop]] += n[rf[stop]] - (fi[stop] + 1)
+            done[rf[stop]] = True
+        i[rf] = fi + 1
+        done |= i >= n
+    skipped = np.cumsum(skip_start, axis=1)[:, :M] > 0
+    # the byte each skipped sample was skipped by: the one recorded at the start of its run
+    start = np.where(~np.isnan(skip_top), np.arange(M)[None, :], -1)
+    run = np.maximum.accumulate(start, axis=1)
+    skip_top = np.where(skipped, skip_top[np.arange(N)[:, None], np.maximum(run, 0)], np.nan)
+    return dict(best=best, k=k, n_filt=n_filt, n_probe=n_probe, n_skip=n_skip, skipped=skipped, skip_top=skip_top)
 
 
 # ---- a scene without the device: uniforms from the C helper -----------------------------------------------------------------------------
 
-def params_np(extent_whd, image_size=(48, 40), azimuth=30.0, elevation=20.0, radius=150.0, sampling_factor=1.0, block=4):
-    """RenderParams of an orbit camera through lib.build_uniforms (pure CPU)"""
+def params_np(extent_whd, image_size=(48, 40), azimuth=30.0, elevation=20.0, radius=150.0, sampling_factor=1.0, block=4, map_extent=None,
+              voxel_size=(1.0, 1.0, 1.0), axis_angle=(1.0, 0.0, 0.0, 0.0), clip=50.0):
+    """RenderParams of an orbit camera through lib.build_uniforms (pure CPU); map_extent (w, h, d) overrides the one of `block`"""
     from vkvolume_amd import camera
     w, h, d = extent_whd
     ext = abi.Extent3D(w, h, d)
-    mext = abi.Extent3D(-(-w // block), -(-h // block), -(-d // block))
-    image_t = camera.image_transform((1.0, 1.0, 1.0), (w, h, d), (1.0, 0.0, 0.0, 0.0))
+    mext = abi.Extent3D(*map_extent) if map_extent is not None else abi.Extent3D(-(-w // block), -(-h // block), -(-d // block))
+    image_t = camera.image_transform(voxel_size, (w, h, d), axis_angle)
     node_t = camera.benchmark_node_transform(image_t)
     view, proj = camera.orbit_camera(azimuth, elevation, radius), camera.perspective_vulkan(60.0, image_size[0] / image_size[1])
-    cam, rc, rg = lib.build_uniforms(view, proj, node_t, image_t, 50.0, image_size, ext, mext)
+    cam, rc, rg = lib.build_uniforms(view, proj, node_t, image_t, clip, image_size, ext, mext)
     p = abi.RenderParams()
     p.camera, p.ray_cast, p.ray_gen = cam, rc, rg
     p.transfer_function.sampling_factor = sampling_factor
@@ -344,3 +490,46 @@ def test_mip_kernels_use_no_scratch(tmp_path):
     assert len(mip) == 4, kernels
     assert any("k_max_map" in k for k in kernels), kernels
     assert all(v == 0 for v in kernels.values()), kernels
+
+
+def test_fma_is_correctly_rounded():
+    from tests.golden.frag_literal import _fma as fma_exact
+    u = 2.0 ** -23
+    cases = []
+    for e1 in (-20, -3, 0, 1, 7, 30):
+        for e2 in (-40, -5, 0, 2, 11):
+            a, b, c = (1 + u) * 2.0 ** e1, 2.0 ** -24 * (1 - u) * 2.0 ** e2, (1 + u) * 2.0 ** (e1 + e2)
+            # a * b + c lies just below a float32 tie, on which the float64 sum lands: rounding twice gives the even neighbour above
+            cases += [(a, b, c), (-a, b, -c), (a, -b, -c), (b, a, c)]
+    a, b, c = (np.array(x, F) for x in zip(*cases))
+    got = _fma(a, b, c)
+    want = np.array([fma_exact(x, y, z) for x, y, z in zip(a, b, c)], F)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    twice = (a.astype(np.float64) * b + c).astype(F)
+    assert np.all(twice != want), "the constructed triples no longer show double rounding"
+    assert _fma(F(1 + u), F(2.0 ** -24 * (1 - u)), F(1 + u)) == F(1 + u)
+    # random operands over a wide range of exponents (normal float32 results), with sums that cancel
+    rng = np.random.default_rng(17)
+    m = 20000
+    a = (rng.standard_normal(m) * 2.0 ** rng.integers(-30, 30, m)).astype(F)
+    b = (rng.standard_normal(m) * 2.0 ** rng.integers(-30, 30, m)).astype(F)
+    c = np.where(rng.random(m) < 0.3, -(a.astype(np.float64) * b), rng.standard_normal(m) * 2.0 ** rng.integers(-60, 60, m)).astype(F)
+    c[:200] = 1.0
+    b[:200] = (rng.integers(1, 1 << 24, 200) * 2.0 ** -48).astype(F)  # products near half an ulp of c
+    got = _fma(a, b, c)
+    want = np.array([fma_exact(x, y, z) for x, y, z in zip(a, b, c)], F)
+    ok = np.isfinite(want) & ((want == 0) | (np.abs(want) >= np.finfo(F).tiny))
+    assert ok.sum() > 0.95 * m
+    assert np.array_equal(got[ok].view(np.uint32), want[ok].view(np.uint32))
+    # zeros (their signs as IEEE fma gives them) and the non-finite cases rays_np feeds it
+    for x, y, z, r in ((0.0, 5.0, 0.0, 0.0), (-0.0, 5.0, 0.0, 0.0), (-0.0, 5.0, -0.0, -0.0), (0.0, -5.0, -0.0, -0.0), (2.0, 3.0, -6.0, 0.0),
+                       (np.inf, 2.0, 1.0, np.inf), (np.inf, -2.0, 1.0, -np.inf), (1.0, 2.0, -np.inf, -np.inf), (np.inf, 0.0, 1.0, np.nan),
+                       (np.inf, 1.0, -np.inf, np.nan), (np.nan, 1.0, 1.0, np.nan), (1.0, 1.0, np.nan, np.nan), (3e38, 3e38, 0.0, np.inf)):
+        g = _fma(F(x), F(y), F(z))
+        assert g.dtype == F
+        if np.isnan(r):
+            assert np.isnan(g), (x, y, z)
+        else:
+            assert g == r and np.signbit(g) == np.signbit(r), (x, y, z, g)
+    # arrays of every shape broadcast as before
+    assert _fma(np.ones((3, 1), F), np.ones(4, F), F(1)).shape == (3, 4)
