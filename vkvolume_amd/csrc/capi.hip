@@ -16,6 +16,7 @@
 
 #include "../host/load_volume.h"
 #include "../host/vkv_math.hpp"
+#include "addr_tables.hpp"
 #include "vkv_device.hpp"
 #include "../../include/vkvolume_amd_debug.h"
 
@@ -144,6 +145,16 @@ StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup)
 				{
 					b->p = p;
 					ctx->scratch_blocks.emplace_back(b);
+					const size_t index = (size_t) (p - ctx->arena) / kScratchBytes;        // (a block outside the arena: a huge index, no ring)
+					if (ctx->upload_pool && p >= ctx->arena && index < kScratchReserve)
+						for (uint32_t k = 0; k < vkv_ctx::kUploadRing; ++k)
+						{        // the block's share of the pinned pool; a slot whose event cannot be created stays unused
+							vkv_ctx::UploadSlot &u = b->upload[k];
+							if (hipEventCreateWithFlags(&u.done, hipEventDisableTiming) == hipSuccess)
+								u.pinned = ctx->upload_pool + (index * vkv_ctx::kUploadRing + k) * kUploadSlotBytes;
+							else
+								u.done = nullptr;
+						}
 				}
 			}
 			if (!b)
@@ -156,8 +167,9 @@ StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup)
 		}
 	}
 	StreamScratch r;
-	r.lock = std::unique_lock<std::mutex>(b->lock);
-	r.p    = b->p;
+	r.lock  = std::unique_lock<std::mutex>(b->lock);
+	r.p     = b->p;
+	r.block = b;
 	return r;
 }
 
@@ -219,48 +231,34 @@ static const uint32_t *table_on_stream(vkv_ctx::Table &t, hipStream_t s, bool se
 
 constexpr size_t kMaxCachedTables = 1024;        // per kind; beyond that a launch runs without (never evicts: a launch may still read any of them)
 
-const uint32_t *packed_addr_lut(vkv_ctx *ctx, int W, int H, int D, uint32_t *lut_y, uint32_t *lut_z, uint32_t *words, hipStream_t stream, bool setup)
+const uint32_t *packed_addr_lut(vkv_ctx *ctx, int W, int H, int D, uint32_t *lut_y, uint32_t *lut_z, uint32_t *words, uint32_t *full, hipStream_t stream, bool setup)
 {
 	std::lock_guard<std::mutex> lock(ctx->mutex);
 	for (auto *t : ctx->addr_luts)
 		if (t->W == W && t->H == H && t->D == D)
 		{
-			*lut_y = t->lut_y, *lut_z = t->lut_z, *words = t->words;
+			*lut_y = t->lut_y, *lut_z = t->lut_z, *words = t->words, *full = t->full;
 			return table_on_stream(t->table, stream, setup);
 		}
 	if (ctx->addr_luts.size() >= kMaxCachedTables)
 		return nullptr;
-	// two levels per axis: position inside a macro-brick (32 entries: padded index b & 31) and the macro-brick term (b >> 5)
-	const PackedDims pd  = packed_dims(W, H, D);
-	const uint32_t   nmx = (uint32_t) (W + 1) / 32 + 1, nmy = (uint32_t) (H + 1) / 32 + 1, nmz = (uint32_t) (D + 1) / 32 + 1;
-	const uint32_t   ny = 96 + nmx, nz = (ny + nmy + 1) & ~1u, total = nz + 2 * nmz;
-	auto *           e  = new (std::nothrow) vkv_ctx::AddrLut{W, H, D, ny, nz, total, {}};
+	// two levels per axis: position inside a macro-brick (32 entries: padded index b & 31) and the macro-brick term (b >> 5); behind them the
+	// per-voxel-index tables as a workgroup's LDS holds them (addr_tables.hpp), where a kernel can use them: offsets in units of two bytes
+	// in 32 bits (a packed image of up to 8 GiB) and tables that fit the dynamic LDS a lean kernel may ask for
+	const PackedDims pd = packed_dims(W, H, D);
+	const bool       with_full = packed_bytes(pd) <= (1ull << 33) && ((size_t) W + 2 + (size_t) H + 2 + (size_t) D + 2) * 4 <= kMaxDynamicLds;
+	auto *           e = new (std::nothrow) vkv_ctx::AddrLut{W, H, D, 0, 0, 0, 0, {}};
 	if (!e)
 		return nullptr;
-	std::vector<uint32_t> &h = e->table.host;
-	h.assign(total, 0u);
-	for (uint32_t j = 0; j < 32; ++j)
-	{
-		h[j]      = (((j >> 2) & 7u) << 8) + (j & 3u) * 2u;
-		h[32 + j] = (((j >> 2) & 7u) << 11) + (j & 3u) * 10u;
-		h[64 + j] = (((j >> 2) & 7u) << 14) + (j & 3u) * 50u;
-	}
-	for (uint32_t m = 0; m < nmx; ++m)
-		h[96 + m] = m << 17;
-	for (uint32_t m = 0; m < nmy; ++m)
-		h[ny + m] = (m * (uint32_t) pd.mx) << 17;
-	for (uint32_t m = 0; m < nmz; ++m)
-	{
-		const uint64_t z = ((uint64_t) m * (uint64_t) pd.my * (uint64_t) pd.mx) << 17;
-		h[nz + 2 * m] = (uint32_t) z, h[nz + 2 * m + 1] = (uint32_t) (z >> 32);
-	}
+	const AddrTables t = build_addr_tables(W, H, D, pd.mx, pd.my, with_full, e->table.host);
+	e->lut_y = t.lut_y, e->lut_z = t.lut_z, e->words = t.words, e->full = t.full;
 	if (!table_upload(ctx, e->table, stream, setup))
 	{
 		delete e;
 		return nullptr;
 	}
 	ctx->addr_luts.push_back(e);
-	*lut_y = ny, *lut_z = nz, *words = total;
+	*lut_y = e->lut_y, *lut_z = e->lut_z, *words = e->words, *full = e->full;
 	return e->table.d;
 }
 
@@ -592,6 +590,9 @@ int vkv_create(int device_ordinal, vkv_ctx **out_ctx)
 		}
 		else if (cp)
 			(void) hipHostFree(cp);
+		void *up = nullptr;        // (without it vkv_render_batch uploads from pageable memory)
+		if (hipHostMalloc(&up, kScratchReserve * vkv_ctx::kUploadRing * kUploadSlotBytes, hipHostMallocDefault) == hipSuccess)
+			ctx->upload_pool = static_cast<uint8_t *>(up);
 	}
 	*out_ctx      = ctx;        // the caller's current device is left as it is: every entry point switches to ctx->device itself
 	return VKV_OK;
@@ -614,6 +615,12 @@ void vkv_destroy(vkv_ctx *ctx)
 		for (void *p : ctx->overflow_scratch)
 			(void) hipFree(p);
 		drop_capture_blocks(ctx);
+		for (auto &b : ctx->scratch_blocks)
+			for (auto &u : b->upload)
+				if (u.done)
+					(void) hipEventDestroy(u.done);
+		if (ctx->upload_pool)
+			(void) hipHostFree(ctx->upload_pool);
 		if (ctx->capture_pool)
 			(void) hipHostFree(ctx->capture_pool);
 		if (ctx->capture_pool_device)
@@ -1346,6 +1353,31 @@ static void build_alpha_lut(const VkvTransferFunctionUniform &tf, float *lut)
 	}
 }
 
+// the same table out of the context's cache: it depends on two floats that change when a slider moves, not when the camera does
+static void cached_alpha_lut(vkv_ctx *ctx, const VkvTransferFunctionUniform &tf, float *lut)
+{
+	uint32_t factor_bits, sampling_bits;
+	std::memcpy(&factor_bits, &tf.voxel_alpha_factor, 4), std::memcpy(&sampling_bits, &tf.sampling_factor, 4);
+	{
+		std::lock_guard<std::mutex> lock(ctx->mutex);
+		for (const auto &e : ctx->alpha_luts)
+			if (e.factor_bits == factor_bits && e.sampling_bits == sampling_bits)
+			{
+				std::memcpy(lut, e.lut, sizeof(e.lut));
+				return;
+			}
+	}
+	build_alpha_lut(tf, lut);        // (outside the lock; two threads that miss on the same key store the same bits)
+	vkv_ctx::AlphaLut e;
+	e.factor_bits = factor_bits, e.sampling_bits = sampling_bits;
+	std::memcpy(e.lut, lut, sizeof(e.lut));
+	std::lock_guard<std::mutex> lock(ctx->mutex);
+	if (ctx->alpha_luts.size() < kAlphaLuts)
+		ctx->alpha_luts.push_back(e);
+	else
+		ctx->alpha_luts[ctx->alpha_next++ % kAlphaLuts] = e;
+}
+
 int vkv_render(vkv_ctx *ctx, const VkvRenderParams *P, void *stream)
 {
 	if (!ctx)
@@ -1355,7 +1387,7 @@ int vkv_render(vkv_ctx *ctx, const VkvRenderParams *P, void *stream)
 	if (rc != VKV_OK)
 		return rc;
 	float lut[256];
-	build_alpha_lut(P->transfer_function, lut);
+	cached_alpha_lut(ctx, P->transfer_function, lut);
 	return launch_render(ctx, P, lut, (hipStream_t) stream);
 }
 
@@ -1377,7 +1409,16 @@ int vkv_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t count, voi
 		    (a.transfer_function.use_gradient != 0) != (b.transfer_function.use_gradient != 0) ||
 		    (a.use_precomputed_gradient != 0) != (b.use_precomputed_gradient != 0))
 			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: frame %u needs a different kernel variant than frame 0", i);
-		build_alpha_lut(a.transfer_function, luts.data() + (size_t) i * 256);
+		// frames of the batch with the same two floats share one table (and one look at the cache)
+		uint32_t same = i;
+		for (uint32_t j = 0; j < i && same == i; ++j)
+			if (std::memcmp(&P[j].transfer_function.voxel_alpha_factor, &a.transfer_function.voxel_alpha_factor, 4) == 0 &&
+			    std::memcmp(&P[j].transfer_function.sampling_factor, &a.transfer_function.sampling_factor, 4) == 0)
+				same = j;
+		if (same != i)
+			std::memcpy(luts.data() + (size_t) i * 256, luts.data() + (size_t) same * 256, 256 * sizeof(float));
+		else
+			cached_alpha_lut(ctx, a.transfer_function, luts.data() + (size_t) i * 256);
 	}
 	return launch_render_batch(ctx, P, count, luts.data(), (hipStream_t) stream);
 }

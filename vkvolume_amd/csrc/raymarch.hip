@@ -136,7 +136,7 @@ LeanChoice choose_lean(const RayMarchArgs &a, const VkvTuning &T)
 	const size_t      full_end = kFullLutWord * 4 + full_lut_bytes(a.W, a.H, a.D);        // from the start of RmLds
 	// the full tables hold offsets in units of two bytes in 32 bits: a packed image of up to 8 GiB
 	const bool        fits_u32 = packed_bytes(packed_dims(a.W, a.H, a.D)) <= (1ull << 33);
-	if (!no_full && fits_u32 && full_end <= (size_t) T.full_table_lds_limit)
+	if (!no_full && fits_u32 && a.lut_full != 0 && full_end <= (size_t) T.full_table_lds_limit)        // (lut_full: the prebuilt tables exist)
 		return {2, lean_lds_bytes(2, a.lut_words, a.W, a.H, a.D)};
 	return {1, lean_lds_bytes(1, a.lut_words, a.W, a.H, a.D)};
 }
@@ -407,9 +407,9 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 		for (int k = 0; k < 3; ++k)
 			a.mapf[k] = m[k], a.mapb[k] = std::nextafterf(m[k], 0.0f);
 	}
-	a.addr_lut = nullptr, a.lut_y = a.lut_z = a.lut_words = 0;
+	a.addr_lut = nullptr, a.lut_y = a.lut_z = a.lut_words = a.lut_full = 0;
 	if (a.packed && T.address_tables != 0)
-		a.addr_lut = packed_addr_lut(ctx, a.W, a.H, a.D, &a.lut_y, &a.lut_z, &a.lut_words, s, setup);
+		a.addr_lut = packed_addr_lut(ctx, a.W, a.H, a.D, &a.lut_y, &a.lut_z, &a.lut_words, &a.lut_full, s, setup);
 	screen_bound_of_box(a, T);
 	// Start order.  Whole-image schedules: centre of the image first (a cached table per schedule shape).  A schedule that holds every tile of a
 	// tile rectangle computes the same kind of order in the kernel (start_entry: the rectangle's rings from the innermost outwards) - a table per
@@ -569,8 +569,39 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 	// launch
 	static_assert(kMaxBatch * sizeof(RayMarchArgs) <= kScratchBytes - kBatchArgsOffset, "batch argument blocks must fit the stream scratch");
 	static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kCaptureSlotBytes, "a captured launch's upload must fit its pinned slot");
-	const VkvTuning           T = tuning_of(ctx);
-	std::vector<RayMarchArgs> host(n);
+	static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kUploadSlotBytes, "a launch's upload must fit a slot of the block's pinned ring");
+	const VkvTuning     T = tuning_of(ctx);
+	const StreamScratch scratch = stream_scratch(ctx, s);
+	if (!scratch.p)
+		return VKV_E_UNSUPPORTED;
+	hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+	const bool             capturing = hipStreamIsCapturing(s, &capture) == hipSuccess && capture == hipStreamCaptureStatusActive;
+	// The upload - the (zeroed) ticket counters of the pull kernel, then the argument blocks - is assembled once, in place, in a pinned slot of
+	// the block's ring: no pageable source that the runtime has to stage, nothing allocated.  A slot is free once the event behind the copy
+	// that read it has completed; with every slot still in flight (or none: a block beyond the reserve, a captured launch, which has a slot
+	// of its own below) the upload comes from pageable memory as before - never a wait.
+	const size_t          upload_bytes = kPullHeadsBytes + n * sizeof(RayMarchArgs);
+	vkv_ctx::UploadSlot * ring_slot = nullptr;
+	for (uint32_t k = 0; k < vkv_ctx::kUploadRing && !capturing && !ring_slot; ++k)
+	{
+		vkv_ctx::UploadSlot &u = scratch.block->upload[(scratch.block->upload_next + k) % vkv_ctx::kUploadRing];
+		if (!u.pinned)
+			continue;
+		if (u.pending && hipEventQuery(u.done) == hipSuccess)
+			u.pending = false;
+		if (!u.pending)
+		{
+			ring_slot                  = &u;
+			scratch.block->upload_next = (scratch.block->upload_next + k + 1) % vkv_ctx::kUploadRing;
+		}
+	}
+	(void) hipGetLastError();        // (a slot that is still being read answers hipErrorNotReady: not this launch's error)
+	std::vector<uint8_t> pageable;
+	if (!ring_slot)
+		pageable.resize(upload_bytes);
+	uint8_t *const upload = ring_slot ? ring_slot->pinned : pageable.data();
+	std::memset(upload, 0, upload_bytes);        // the counters, and every field fill_render_args leaves alone (an empty frame's block)
+	RayMarchArgs *const host = reinterpret_cast<RayMarchArgs *>(upload + kPullHeadsBytes);
 	for (uint32_t i = 0; i < n; ++i)
 	{
 		const int rc = fill_render_args(ctx, &P[i], alpha_luts + (size_t) i * 256, host[i], s, T, false, true);
@@ -602,15 +633,9 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 	bool any_sort = false;
 	for (uint32_t i = 0; i < n && P[0].options.early_ray_termination != 0; ++i)
 		any_sort = apply_feedback(ctx, host[i], s) || any_sort;
-	const StreamScratch scratch = stream_scratch(ctx, s);
-	if (!scratch.p)
-		return VKV_E_UNSUPPORTED;
 	RayMarchArgs *   d_frames = reinterpret_cast<RayMarchArgs *>(scratch.p + kBatchArgsOffset);
 	uint32_t *       d_heads  = reinterpret_cast<uint32_t *>(scratch.p + kBatchArgsOffset - kPullHeadsBytes);
-	// one upload: the (zeroed) ticket counters of the pull kernel, then the argument blocks
-	std::vector<uint8_t> upload(kPullHeadsBytes + n * sizeof(RayMarchArgs), 0);
-	std::memcpy(upload.data() + kPullHeadsBytes, host.data(), n * sizeof(RayMarchArgs));
-	const void *upload_src = upload.data();
+	const void *upload_src = upload;
 	// a capture slot taken below returns to the context on every error path: only a launch that was recorded keeps it
 	struct SlotGuard
 	{
@@ -628,8 +653,7 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 	} slot_guard{ctx, 0, false};
 	{        // A stream that is being captured into a hipGraph records the copy's SOURCE POINTER and reads it at every replay: the block then has to
 		 // outlive the call - a pinned slot the context keeps until vkv_trim / vkv_destroy
-		hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-		if (hipStreamIsCapturing(s, &capture) == hipSuccess && capture == hipStreamCaptureStatusActive)
+		if (capturing)
 		{
 			// A captured launch gets a slot of its own - pinned source AND device target of the upload: the graph can be replayed on any stream,
 			// concurrently with other graphs and with live launches on the capture stream, so it must not go through that stream's scratch block
@@ -665,15 +689,22 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 			}
 			slot->in_use = true, slot->owner = stream_key(s);
 			slot_guard.index = (size_t) (slot - ctx->capture_slots.data()), slot_guard.armed = true;
-			std::memcpy(slot->pinned, upload.data(), upload.size());
+			std::memcpy(slot->pinned, upload, upload_bytes);
 			upload_src = slot->pinned;
 			d_heads    = reinterpret_cast<uint32_t *>(slot->device);
 			d_frames   = reinterpret_cast<RayMarchArgs *>(slot->device + kPullHeadsBytes);
 		}
 	}
-	const hipError_t e = hipMemcpyAsync(d_heads, upload_src, upload.size(), hipMemcpyHostToDevice, s);
+	const hipError_t e = hipMemcpyAsync(d_heads, upload_src, upload_bytes, hipMemcpyHostToDevice, s);
 	if (e != hipSuccess)
 		return set_error(ctx, (int) e, "render_batch: argument upload: %s", hipGetErrorString(e));
+	if (ring_slot)
+	{        // the slot is the copy's source until this event has completed; if it cannot be recorded, wait for the copy here
+		if (hipEventRecord(ring_slot->done, s) == hipSuccess)
+			ring_slot->pending = true;
+		else
+			(void) hipStreamSynchronize(s);
+	}
 	const uint64_t grid = (uint64_t) ((max_tiles + 7u) / 8u) * 8u * host[0].blocks_per_tile * n;
 	if (grid > 0x7fffffffull)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "render_batch: too many workgroups for one launch");

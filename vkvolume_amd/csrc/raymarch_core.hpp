@@ -66,7 +66,8 @@ struct RayMarchArgs
 	float           mapf[3], mapb[3];        // k_raymarch_lean, clamp-free loop: the map extent as floats, and the largest floats below them
 	uint32_t        wave_pw_log2;            // k_raymarch_lean: log2 of the width in pixels of a wave's 64-pixel patch (2, 3, 4: 4x16, 8x8, 16x4)
 	const uint32_t *addr_lut;       // k_raymarch_lean: per-axis byte offsets of the packed image (packed_addr_lut, vkv_device.hpp), or null
-	uint32_t        lut_y, lut_z, lut_words;        // word offsets of the y and z tables inside addr_lut and its total length
+	uint32_t        lut_y, lut_z, lut_words;        // word offsets of the y and z tables inside addr_lut and the length of the two-level tables
+	uint32_t        lut_full;       // word offset inside addr_lut of the prebuilt per-voxel-index tables (16-byte aligned, zero-padded to 16 bytes), 0 = none
 	uint32_t        cull_x0, cull_x1, cull_y0, cull_y1;        // k_raymarch_lean: pixels outside [x0, x1] x [y0, y1] cannot see the volume's box
 	                                                           // (conservative screen bound from the launcher); 0, ~0, 0, ~0 = no bound
 	const uint32_t *tile_order;     // k_raymarch_lean: the r-th tile to be started is schedule entry tile_order[r] (centre of the image first), or null
@@ -877,9 +878,14 @@ __device__ __forceinline__ bool tf_is_separable(const RayMarchArgs &A)
 	return A.tf_bits != nullptr && (A.tf_bits[kTfFlagWord] & kTfFlagSeparable) != 0u;        // wave-uniform (scalar load)
 }
 
-__device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L)
+// sync = false: the caller has more to write into the LDS and ends with the barrier itself (the copy of the address tables: full_lut_commit)
+__device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L, bool sync = true)
 {
 	const bool sep = tf_is_separable(A);
+	// the table pointer comes out of the argument block, which hides its address space: as a flat pointer its loads could alias the LDS writes
+	// and each would wait for the write in front of it (three round trips in a row).  All loads first, then the writes.
+	typedef const __attribute__((address_space(1))) uint32_t *global_u32_ptr;
+	const global_u32_ptr tf_words = (global_u32_ptr) (uintptr_t) A.tf_bits;
 	for (int i = threadIdx.x; i < 256; i += blockDim.x)
 	{
 		const float a = A.alpha_lut[i];
@@ -887,10 +893,10 @@ __device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L)
 			L.g.alpha[i] = a;
 		if (sep)
 		{
-			L.s.ai[i]   = __uint_as_float(A.tf_bits[kTfAiWord + i]);
-			L.s.ag[i]   = __uint_as_float(A.tf_bits[kTfAgWord + i]);
+			const float ai = __uint_as_float(tf_words[kTfAiWord + i]), ag = __uint_as_float(tf_words[kTfAgWord + i]);
+			L.s.ai[i] = ai, L.s.ag[i] = ag;
 			if (i == 255)
-				L.s.ai[256] = L.s.ai[255], L.s.ag[256] = L.s.ag[255];
+				L.s.ai[256] = ai, L.s.ag[256] = ag;
 			L.s.pair[i] = i == 0 ? make_float2(0.0f, 0.0f) : make_float2(a, unorm8(i) * a);        // (alpha byte 0 blends nothing: lean_march relies on it)
 		}
 		else
@@ -899,7 +905,8 @@ __device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L)
 	if (!sep && A.tf_bits)
 		for (int i = threadIdx.x; i < 2048; i += blockDim.x)
 			L.g.bits[i] = A.tf_bits[i];
-	__syncthreads();
+	if (sync)
+		__syncthreads();
 	return sep;
 }
 // ray `rb` (0..255) of 16x16 block `b` of the tile schedule -> pixel and output index.  A wave's 64/W rays form a compact patch.
@@ -1139,8 +1146,8 @@ __device__ __forceinline__ const uint8_t *packed_footprint_lut(const RayMarchArg
 }
 
 // kLeanFull — one table entry per padded voxel index and axis, so an axis costs one LDS read and no shift / mask / add: X[W + 2],
-// Y[H + 2], Z[D + 2], 32-bit offsets in units of TWO bytes (every term is even; a packed image of up to 8 GiB).  Built by the workgroup
-// from the two-level tables (each entry = in-macro term + macro term).  11.4 KB at 1024 x 1024 x 795: too much on top of the general
+// Y[H + 2], Z[D + 2], 32-bit offsets in units of TWO bytes (every term is even; a packed image of up to 8 GiB).  Each entry = in-macro term +
+// macro term of the two-level tables, summed once on the host (addr_tables.hpp) and copied by the workgroup.  11.4 KB at 1024 x 1024 x 795: too much on top of the general
 // transfer-function tables, so they are only used with the separable transfer function, whose tables end 4 112 bytes into RmLds: the
 // full tables start there and run on past the end of RmLds (the launcher sizes the segment: lean_lds_bytes).  Small on purpose: a workgroup
 // keeps its LDS until its longest wave is done, so the LDS per workgroup decides how many waves a CU holds on average.
@@ -1160,24 +1167,58 @@ __host__ __forceinline__ size_t lean_lds_bytes(int kind, uint32_t lut_words, int
 		return kLdsBase + sizeof(RmLds);
 	if (kind == 1)
 		return two_level;
-	const size_t full_end = kLdsBase + (size_t) kFullLutWord * 4 + full_lut_bytes(W, H, D);
+	const size_t full_end = kLdsBase + (size_t) kFullLutWord * 4 + ((full_lut_bytes(W, H, D) + 15u) & ~(size_t) 15u);        // copied in 16-byte pieces
 	return two_level > full_end ? two_level : full_end;
 }
 
 __device__ __forceinline__ uint32_t *full_lut_base(const RmLds &L) { return const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(&L)) + kFullLutWord; }
 
-__device__ __forceinline__ void stage_full_lut(const RayMarchArgs &A, RmLds &L)
+// The tables are a function of the extents alone: packed_addr_lut builds them once per volume (addr_tables.hpp) and a workgroup copies
+// them, 16 bytes per thread and round.  Up to kFullLdsLimit they are at most kFullCopyRounds rounds of a 256-thread workgroup, all loaded
+// ahead of one wait (the index of a thread past the end is clamped: its load is harmless and its store left out); beyond that
+// (VkvTuning.full_table_lds_limit raised, the lab's smaller workgroups) a plain loop copies the rest.  Split in two so that the caller can
+// issue its other loads (stage_tables_er) between the loads and the LDS writes: one round trip for all of them.
+typedef uint32_t lut_v4u __attribute__((ext_vector_type(4)));
+constexpr uint32_t kFullCopyRounds = 4;
+static_assert((kLdsBase + kFullLutWord * 4) % 16 == 0, "the full tables are written with 16-byte LDS stores");
+static_assert(kFullLdsLimit - kFullLutWord * 4 <= kFullCopyRounds * 256 * 16, "the unrolled rounds cover the tables of the default LDS limit");
+
+struct FullLutCopy
+{
+	lut_v4u  r[kFullCopyRounds];
+	uint32_t nvec;        // 16-byte pieces of the padded tables
+};
+
+__device__ __forceinline__ FullLutCopy full_lut_issue(const RayMarchArgs &A)
+{
+	typedef const __attribute__((address_space(1))) lut_v4u *global_v4u_ptr;
+	FullLutCopy          c;
+	const global_v4u_ptr g = (global_v4u_ptr) (uintptr_t) (A.addr_lut + A.lut_full);
+	c.nvec                 = ((uint32_t) (A.W + 2 + A.H + 2 + A.D + 2) + 3u) >> 2;
+#pragma unroll
+	for (uint32_t k = 0; k < kFullCopyRounds; ++k)
+		c.r[k] = g[min(threadIdx.x + k * blockDim.x, c.nvec - 1u)];
+	return c;
+}
+
+__device__ __forceinline__ void full_lut_commit(const RayMarchArgs &A, const FullLutCopy &c, RmLds &L)
 {
 	static_assert(sizeof(((RmLds *) nullptr)->s) == kFullLutWord * 4, "full tables start behind the separable TF tables");
-	const uint32_t  nx = (uint32_t) A.W + 2u, ny = (uint32_t) A.H + 2u, nz = (uint32_t) A.D + 2u;
-	uint32_t *      fx = full_lut_base(L), *fy = fx + nx, *fz = fy + ny;
-	const uint32_t *g  = A.addr_lut;
-	for (uint32_t b = threadIdx.x; b < nx; b += blockDim.x)
-		fx[b] = (g[b & 31u] + g[kLutXm + (b >> 5)]) >> 1;
-	for (uint32_t b = threadIdx.x; b < ny; b += blockDim.x)
-		fy[b] = (g[32u + (b & 31u)] + g[A.lut_y + (b >> 5)]) >> 1;
-	for (uint32_t b = threadIdx.x; b < nz; b += blockDim.x)
-		fz[b] = (uint32_t) ((((((uint64_t) g[A.lut_z + 2u * (b >> 5) + 1u]) << 32) | g[A.lut_z + 2u * (b >> 5)]) + g[64u + (b & 31u)]) >> 1);
+	typedef const __attribute__((address_space(1))) lut_v4u *global_v4u_ptr;
+	lut_v4u *dst = reinterpret_cast<lut_v4u *>(full_lut_base(L));
+#pragma unroll
+	for (uint32_t k = 0; k < kFullCopyRounds; ++k)
+		if (threadIdx.x + k * blockDim.x < c.nvec)
+			dst[threadIdx.x + k * blockDim.x] = c.r[k];
+	const global_v4u_ptr g = (global_v4u_ptr) (uintptr_t) (A.addr_lut + A.lut_full);
+	for (uint32_t i = threadIdx.x + kFullCopyRounds * blockDim.x; i < c.nvec; i += blockDim.x)
+		dst[i] = g[i];
+}
+
+__device__ __forceinline__ void stage_full_lut(const RayMarchArgs &A, RmLds &L)
+{
+	const FullLutCopy c = full_lut_issue(A);
+	full_lut_commit(A, c, L);
 }
 
 // Loop-invariant operands of packed_footprint_full, worked out once per ray.  They pass through an empty asm so that the compiler keeps
@@ -1799,14 +1840,20 @@ __device__ __forceinline__ void lean_block(const RayMarchArgs &A, uint32_t bid, 
 	// 60 % of the workgroups of a frame hold no ray that enters the volume: they skip the LDS tables (and their barrier) altogether
 	if (wg_any(marched))
 	{
-		if ((LF & kLeanLut) != 0 && PACKED && GRAD != 2)
-		{        // before the barrier of stage_tables_er
-			if ((LF & kLeanFull) != 0 && tf_is_separable(A))
-				stage_full_lut(A, L);
-			else
-				stage_addr_lut(A);
+		bool sep;
+		if ((LF & kLeanLut) != 0 && (LF & kLeanFull) != 0 && PACKED && GRAD != 2 && tf_is_separable(A))
+		{        // the table copy's loads, the loads of stage_tables_er, then the LDS writes of both behind one wait, and the barrier
+			const FullLutCopy c = full_lut_issue(A);
+			sep                 = stage_tables_er(A, L, false);
+			full_lut_commit(A, c, L);
+			__syncthreads();
 		}
-		const bool sep = stage_tables_er(A, L);
+		else
+		{
+			if ((LF & kLeanLut) != 0 && PACKED && GRAD != 2)
+				stage_addr_lut(A);        // before the barrier of stage_tables_er
+			sep = stage_tables_er(A, L);
+		}
 		if (marched)
 		{
 			if (sep)
@@ -2012,14 +2059,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 	lean_lds_check();
 	RmLds &             L  = lean_lds();
 	const RayMarchArgs &A0 = frames[0];
-	if ((LF & kLeanLut) != 0 && GRAD != 2)
-	{        // before the barrier of stage_tables_er
-		if ((LF & kLeanFull) != 0 && tf_is_separable(A0))
-			stage_full_lut(A0, L);
-		else
-			stage_addr_lut(A0);
+	bool sep;
+	if ((LF & kLeanLut) != 0 && (LF & kLeanFull) != 0 && GRAD != 2 && tf_is_separable(A0))
+	{        // as in lean_block: every load ahead of one wait
+		const FullLutCopy c = full_lut_issue(A0);
+		sep                 = stage_tables_er(A0, L, false);
+		full_lut_commit(A0, c, L);
+		__syncthreads();
 	}
-	if (stage_tables_er(A0, L))
+	else
+	{
+		if ((LF & kLeanLut) != 0 && GRAD != 2)
+			stage_addr_lut(A0);        // before the barrier of stage_tables_er
+		sep = stage_tables_er(A0, L);
+	}
+	if (sep)
 		pull_units<SKIP, ERT, GRAD, LF, true>(frames, n, heads, L);
 	else
 		pull_units<SKIP, ERT, GRAD, LF, false>(frames, n, heads, L);

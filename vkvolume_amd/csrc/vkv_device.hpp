@@ -235,11 +235,33 @@ struct vkv_ctx
 	uint8_t *                capture_pool = nullptr, *capture_pool_device = nullptr;
 	std::vector<CaptureSlot> capture_slots;
 	// a stream's scratch block: kScratchBytes of device memory and the lock of the entry point that is passing data through it
+	// upload: a small ring of pinned host slots (carved out of upload_pool by vkv_create, for the arena's blocks) in which vkv_render_batch
+	// assembles the argument blocks it uploads into the block; a slot is taken again only after the event recorded behind the copy that read
+	// it has completed (claimed under the block's lock).  A block without slots (beyond the reserve), or with every slot still being read,
+	// uploads from pageable memory.
+	struct UploadSlot
+	{
+		uint8_t *  pinned = nullptr;
+		hipEvent_t done = nullptr;
+		bool       pending = false;        // `done` has been recorded and not yet seen complete
+	};
+	static constexpr uint32_t kUploadRing = 4;
 	struct ScratchBlock
 	{
 		uint8_t *  p = nullptr;
 		std::mutex lock;
+		UploadSlot upload[kUploadRing];
+		uint32_t   upload_next = 0;
 	};
+	uint8_t *upload_pool = nullptr;        // pinned, kScratchReserve x kUploadRing x kUploadSlotBytes; freed by vkv_destroy
+	// opacity-correction tables by the two floats they depend on (bit compare): a camera move re-uses them, a slider move adds one
+	struct AlphaLut
+	{
+		uint32_t factor_bits, sampling_bits;
+		float    lut[256];
+	};
+	std::vector<AlphaLut> alpha_luts;        // at most kAlphaLuts, replaced round robin
+	uint32_t              alpha_next = 0;
 	std::vector<std::unique_ptr<ScratchBlock>> scratch_blocks;        // every block the context has handed out (stable addresses)
 	std::map<VkvStreamKey, ScratchBlock *>     scratch;               // stream -> its block
 	std::vector<ScratchBlock *>                free_scratch;          // blocks given back by vkv_release_stream
@@ -265,6 +287,7 @@ struct vkv_ctx
 	{
 		int      W, H, D;
 		uint32_t lut_y, lut_z, words;
+		uint32_t full;        // word offset of the per-voxel-index tables behind the two-level ones (addr_tables.hpp), 0 = none
 		Table    table;
 	};
 	std::vector<AddrLut *> addr_luts;
@@ -300,6 +323,7 @@ struct StreamScratch
 {
 	uint8_t *                    p = nullptr;
 	std::unique_lock<std::mutex> lock;
+	vkv_ctx::ScratchBlock *      block = nullptr;        // its pinned upload ring (used under `lock`)
 };
 StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = false);
 // start order of a tile schedule: entry indices sorted by the distance of the tile's centre from the image centre (device array of
@@ -307,16 +331,20 @@ StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = fals
 // Per-axis byte offsets of the packed sampling image: the offset of the footprint whose padded base texel is (bx, by, bz) is
 // X(bx) + Y(by) + Z(bz) (the brick index and the position inside the brick are sums of per-axis terms), each in two levels:
 // in-macro-brick term of b & 31 + macro-brick term of b >> 5.  Layout of the device array (uint32 words): in-macro tables of x, y, z
-// at 0, 32, 64; macro terms of x at 96, of y at *lut_y, of z as 64-bit values at *lut_z (even); nullptr if it cannot be allocated.
+// at 0, 32, 64; macro terms of x at 96, of y at *lut_y, of z as 64-bit values at *lut_z (even), *words in all; behind them, at word *full
+// (16-byte aligned; 0 = not built), the sums X[W + 2], Y[H + 2], Z[D + 2] per padded voxel index in units of two bytes, zero-padded to a multiple
+// of 16 bytes: what a workgroup's LDS holds (stage_full_lut), built once per extent.  nullptr if it cannot be allocated.
 // Both tables come out of the context's arena and are uploaded on `stream` when new (see vkv_ctx); `setup` = called from a set-up entry
 // point: may fall back to hipMalloc when the arena is full.  nullptr when there is no room: the launch then runs without the table.
-const uint32_t *packed_addr_lut(vkv_ctx *ctx, int W, int H, int D, uint32_t *lut_y, uint32_t *lut_z, uint32_t *words, hipStream_t stream, bool setup = false);
+const uint32_t *packed_addr_lut(vkv_ctx *ctx, int W, int H, int D, uint32_t *lut_y, uint32_t *lut_z, uint32_t *words, uint32_t *full, hipStream_t stream, bool setup = false);
 const uint32_t *tile_start_order(vkv_ctx *ctx, uint32_t img_w, uint32_t img_h, uint32_t tile_w, uint32_t tile_h, uint32_t first, uint32_t stride, uint32_t count,
                                  hipStream_t stream, bool setup = false);
 VkvTuning tuning_of(vkv_ctx *ctx);        // a copy of the context's tuning block (taken under its mutex)
 constexpr size_t kScratchBytes     = 128 * 1024;
 constexpr size_t kScratchReserve   = 16;          // scratch blocks the arena keeps for streams (2 MiB of the default 8 MiB)
 constexpr uint32_t kCaptureSlots   = 32;          // vkv_render_batch launches one context may have captured into hipGraphs
+constexpr size_t   kUploadSlotBytes = 64 * 1024;   // pinned slot of a scratch block's upload ring: the pull heads + VKV_MAX_BATCH argument blocks
+constexpr size_t   kAlphaLuts = 8;
 constexpr size_t   kCaptureSlotBytes = 96 * 1024;  // >= the pull heads + VKV_MAX_BATCH argument blocks (= the scratch block's argument area)
 constexpr uint32_t kMaxDynamicLds  = 64 * 1024 - 1024;        // what a lean kernel may ask for as dynamic LDS (its tables; no hipFuncSetAttribute is called)
 constexpr size_t kTfBitsOffset     = 0;           // 256*256 bits = 8 KiB: TF bit table of the map update / the voxel count (+ 8 words behind it: its column mask)
