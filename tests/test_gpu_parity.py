@@ -130,7 +130,7 @@ def test_gradient_map_smooth_volume(ctx):
 @pytest.mark.parametrize("shape,block", [((64, 64, 64), 4), ((61, 45, 30), 4), ((50, 33, 21), 3), ((40, 40, 40), 2),
                                          ((67, 31, 18), 5), ((48, 48, 48), 6), ((20, 9, 7), 1), ((68, 30, 21), 4), ((132, 17, 9), 2), ((12, 5, 3), 1),
                                          ((1028, 9, 6), 4),
-                                         # dword-aligned rows with block widths that are not 1, 2 or 4 (k_occupancy_map_dword_any), several workgroups per row
+                                         # dword-aligned rows with block widths that are not 1, 2 or 4, several spans of 64 dwords per row
                                          ((52, 33, 21), 3), ((2052, 7, 5), 3), ((1300, 6, 7), 5), ((1040, 5, 4), 7), ((2048, 1, 1), 100), ((2056, 1, 1), 130)])
 @pytest.mark.parametrize("variant", ["precomputed", "on_the_fly", "no_gradient"])
 def test_occupancy_map_parity(ctx, shape, block, variant):
@@ -192,8 +192,10 @@ def test_gradient_and_occupancy_fuzz(ctx, seed):
 def test_occupancy_map_extents_beyond_the_volume(ctx, seed):
     """the ABI accepts any map extent <= the volume's; block = ceil(extent / map extent) can then leave whole cell rows / slices
     outside the volume (16^3 voxels under a 7^3 map: block 3, cells 6 of y and z hold no voxel).  Such cells stay EMPTY (the reference's loop
-    over a cell's voxels is clipped at the volume edge, occupancy_map.comp:52-53) - in the wave kernel, the workgroup-per-cell-row kernels
-    (VkvTuning.occupancy_kernel = 1) and the oracle alike, and nothing is read past the volume."""
+    over a cell's voxels is clipped at the volume edge, occupancy_map.comp:52-53) - in the wave kernel, the workgroup-per-cell-row kernel
+    and the oracle alike, and nothing is read past the volume.  Per seed: the wave kernel (precomputed gradient or none), then the
+    workgroup-per-cell-row kernel twice - with the on-the-fly gradient on the same volume and map extent (k_occupancy_map<2>), and with the
+    seed's gradient variant on a volume of width 1 .. 3 (k_occupancy_map<1> / <0>: the wave kernel needs four voxels per row)."""
     rng = np.random.default_rng(4200 + seed)
     if seed == 0:
         shape, me = (16, 16, 16), abi.Extent3D(7, 7, 7)
@@ -202,27 +204,24 @@ def test_occupancy_map_extents_beyond_the_volume(ctx, seed):
     else:
         shape = (int(rng.choice([16, 64, 68, 132, 256, 260])), int(rng.integers(5, 70)), int(rng.integers(5, 50)))
         me = abi.Extent3D(*(int(rng.integers(max(1, -(-n // int(rng.integers(2, 7)))), n + 1)) for n in shape))
-    vol = T.random_volume(shape, seed=seed, sparsity=0.9)
+    narrow = (1 + seed % 3, int(rng.integers(5, 70)), int(rng.integers(5, 50)))
+    narrow_me = abi.Extent3D(*(int(rng.integers(max(1, -(-n // int(rng.integers(2, 7)))), n + 1)) for n in narrow))
     variant = ("precomputed", "no_gradient")[seed % 2]
     opt = abi.VolumeOptions(intensity_min=0.1, gradient_min=0.0, gradient_max=0.0) if variant == "no_gradient" else abi.VolumeOptions(**T.APP_TF)
-    scene = T.OracleScene(vol, opt, 4)
-    expect = O.occupancy_map(scene.vol, scene.grad, scene.tex, scene.tf, 0, map_extent_override=me)
-    v, tf = make_gpu_volume(ctx, scene)
     st = torch.cuda.current_stream().cuda_stream
-    t0 = ctx.get_tuning()
-    got = {}
-    try:
-        for kernel in (0, 1):
-            ctx.set_tuning(occupancy_kernel=kernel)
-            d_map = torch.full(expect.shape, 77, dtype=torch.uint8, device="cuda")
-            ctx.occupancy_map(v.volume.data_ptr(), v.gradient.data_ptr() if variant == "precomputed" else None, v.transfer_function.data_ptr(), tf,
-                              v.extent, d_map.data_ptr(), me, st)
-            got[kernel] = d_map.cpu().numpy()
-    finally:
-        ctx.set_tuning(occupancy_kernel=t0.occupancy_kernel)
-    what = "shape %s map %s %s" % (shape, me.as_tuple(), variant)
-    assert np.array_equal(got[0], expect), "wave kernel, " + what
-    assert np.array_equal(got[1], expect), "row kernels, " + what
+
+    def check(kernel, shape, me, variant, opt):
+        scene = T.OracleScene(T.random_volume(shape, seed=seed, sparsity=0.9), opt, 4)
+        expect = O.occupancy_map(scene.vol, scene.grad, scene.tex, scene.tf, 0, map_extent_override=me)  # scene.grad None: the on-the-fly gradient
+        v, tf = make_gpu_volume(ctx, scene)
+        d_map = torch.full(expect.shape, 77, dtype=torch.uint8, device="cuda")
+        ctx.occupancy_map(v.volume.data_ptr(), v.gradient.data_ptr() if variant == "precomputed" else None, v.transfer_function.data_ptr(), tf,
+                          v.extent, d_map.data_ptr(), me, st)
+        assert np.array_equal(d_map.cpu().numpy(), expect), "%s, shape %s map %s %s" % (kernel, shape, me.as_tuple(), variant)
+
+    check("wave kernel", shape, me, variant, opt)
+    check("row kernel", shape, me, "on_the_fly", abi.VolumeOptions(use_precomputed_gradient=False, **T.APP_TF))
+    check("row kernel", narrow, narrow_me, variant, opt)
 
 
 def sparse_occupancy(shape_dhw, seed, p):

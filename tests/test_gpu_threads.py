@@ -268,8 +268,7 @@ def test_one_context_per_thread(ctx, n_threads):
 # b. / e. one context shared by 4 threads, a stream each; the first use of a frame size and a volume extent, vkv_prepare_render and
 # vkv_register_target race the other threads' launches; (e) a fifth thread switches the tuning block all the while
 # ---------------------------------------------------------------------------------------------------------------------------------
-TUNING_SWITCHES = dict(address_tables=(0, 1, 2), wave_shape=(0, 4, 8, 16), clamp_always=(0, 1), scheduler=(0, 1), batch_mode=(0, 1), feedback=(0, 1),
-                       occupancy_kernel=(0, 1))
+TUNING_SWITCHES = dict(address_tables=(0, 1, 2), wave_shape=(0, 4, 8, 16), clamp_always=(0, 1), scheduler=(0, 1), batch_mode=(0, 1), feedback=(0, 1))
 
 
 @pytest.mark.parametrize("tuning_thread", [False, True], ids=["streams", "streams_and_tuning"])

@@ -29,7 +29,7 @@ def timeit(fn, n=10):
     return s.elapsed_time(e) / n
 
 
-print("# %s %dx%dx%d, library %s, VKV_OCCUPANCY_KERNEL=%s" % (name, *extent, os.environ.get("VKV_LIB_PATH", "(this tree)"), os.environ.get("VKV_OCCUPANCY_KERNEL", "(default)")))
+print("# %s %dx%dx%d, library %s" % (name, *extent, os.environ.get("VKV_LIB_PATH", "(this tree)")))
 print("%5s %14s %10s %12s %12s %12s" % ("block", "map", "occ ms", "occ GB/s", "update iso", "update aniso"))
 for b in (2, 3, 4, 5, 6):
     v = V.Volume(ctx)

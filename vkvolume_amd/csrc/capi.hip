@@ -17,44 +17,11 @@
 #include "../host/load_volume.h"
 #include "../host/vkv_math.hpp"
 #include "addr_tables.hpp"
-#include "vkv_device.hpp"
+#include "launchers.hpp"
 #include "../../include/vkvolume_amd_debug.h"
 
 namespace vkv
 {
-int launch_gradient_map(vkv_ctx *, const uint8_t *, uint8_t *, VkvExtent3D, const VkvTransferFunctionUniform *, hipStream_t);
-int launch_occupancy_map(vkv_ctx *, const uint8_t *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint8_t *,
-                         VkvExtent3D, hipStream_t, uint32_t *d_bits, bool bits_ready = false);
-int launch_distance_map(vkv_ctx *, uint8_t *, uint8_t *, VkvExtent3D, hipStream_t);
-int launch_distance_map_anisotropic(vkv_ctx *, uint8_t *const[8], uint8_t *, VkvExtent3D, hipStream_t);
-int launch_synth_volume(vkv_ctx *, uint8_t *, VkvExtent3D, uint32_t, uint32_t, hipStream_t);
-int launch_scatter_tiles_frames(vkv_ctx *, uint32_t, void *const *, const void *const *, const VkvTileRect *, const uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
-                                uint32_t, hipStream_t);
-void screen_tile_rect(const VkvRayCastUniform *, const VkvRayGen *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, VkvTileRect *);
-int prepare_render(vkv_ctx *, const VkvRenderParams *, uint32_t, hipStream_t);
-void load_feedback_code();
-int launch_render(vkv_ctx *, const VkvRenderParams *, const float *, hipStream_t);
-int launch_render_batch(vkv_ctx *, const VkvRenderParams *, uint32_t, const float *, hipStream_t);
-int launch_pack_volume(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, void *, hipStream_t);
-int launch_check_numerics(vkv_ctx *, int, uint32_t, uint64_t, unsigned long long *, hipStream_t);
-int launch_tf_tables(vkv_ctx *, const uint8_t *, const VkvTransferFunctionUniform *, uint32_t *, hipStream_t);
-int launch_tf_build(vkv_ctx *, const VkvTransferFunctionUniform *, uint8_t *, uint32_t *, uint32_t *, hipStream_t);
-int launch_convert_volume(vkv_ctx *, const void *, int, bool, float, float, uint64_t, uint8_t *, hipStream_t);
-int launch_occupied_voxel_count(vkv_ctx *, const uint8_t *, const uint8_t *, const VkvTransferFunctionUniform *, VkvExtent3D, uint64_t *, hipStream_t, uint32_t *);
-int launch_update_volume_region(vkv_ctx *, const void *, int, bool, float, float, const VkvBox &, uint8_t *, uint8_t *, void *, VkvExtent3D, const uint8_t *,
-                                const VkvTransferFunctionUniform *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
-int launch_volume_histogram(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, const VkvBox &, int, uint64_t *, hipStream_t);
-int launch_histogram_occupied_count(vkv_ctx *, const uint64_t *, const VkvTransferFunctionUniform *, uint64_t *, hipStream_t);
-int launch_tf_bits(vkv_ctx *, const uint8_t *, uint32_t *, hipStream_t);
-bool occupancy_launch_ok(VkvExtent3D, VkvExtent3D);
-bool distance_launch_ok(VkvExtent3D);
-bool count_launch_ok(VkvExtent3D);
-bool cells_launch_ok(VkvExtent3D, VkvExtent3D);
-int launch_map_transform(vkv_ctx *, uint8_t *const[8], uint8_t *, VkvExtent3D, int, hipStream_t);
-int launch_cell_summary(vkv_ctx *, const uint8_t *, const uint8_t *, VkvExtent3D, VkvExtent3D, const VkvBox *, void *, hipStream_t);
-int launch_occupancy_from_summary(vkv_ctx *, const void *, const uint8_t *, const uint8_t *, bool, uint8_t *, VkvExtent3D, uint8_t *, VkvExtent3D,
-                                  uint64_t *, hipStream_t);
-
 int set_error(vkv_ctx *ctx, int code, const char *fmt, ...)
 {
 	if (ctx)
@@ -392,8 +359,8 @@ const char *vkv_version(void) { return "vkvolume_amd 0.1.0 (gfx950)"; }
 static const char *tuning_problem(const VkvTuning &t)
 {
 	if (t.scheduler < 0 || t.scheduler > 1 || t.batch_mode < 0 || t.batch_mode > 1 || t.address_tables < 0 || t.address_tables > 2 || t.feedback_period == 0 ||
-	    t.gradient_segment > 255u || (t.pack_tile != 0 && t.pack_tile != 2 && t.pack_tile != 4) || t.clamp_always < 0 || t.clamp_always > 1 ||
-	    t.occupancy_kernel < 0 || t.occupancy_kernel > 1 || (t.wave_shape != 0 && t.wave_shape != 4 && t.wave_shape != 8 && t.wave_shape != 16))
+	    t.gradient_segment > 255u || t.clamp_always < 0 || t.clamp_always > 1 ||
+	    (t.wave_shape != 0 && t.wave_shape != 4 && t.wave_shape != 8 && t.wave_shape != 16))
 		return "field out of range";
 	// a tile mix that is not a number never compares equal to a cached schedule's: every launch would build a new table
 	if (!std::isfinite(t.tile_mix_heavy) || !std::isfinite(t.tile_mix_spread) || t.tile_mix_heavy < 0.0f || t.tile_mix_heavy > 1.0f || t.tile_mix_spread < 0.0f ||
@@ -444,8 +411,6 @@ static void default_tuning(VkvTuning &t)
 	}
 	if (const char *e = env("VKV_GRADIENT_SEGMENT"))
 		t.gradient_segment = (uint32_t) std::min(std::max(std::atol(e), 0l), 255l);
-	if (const char *e = env("VKV_PACK_TILE"))
-		t.pack_tile = std::atoi(e);
 	if (const char *e = env("VKV_ARENA_BYTES"))
 		t.arena_bytes = (uint32_t) std::min(std::max(std::atol(e), 1l << 20), 1l << 30);
 	if (const char *e = env("VKV_RAYMARCH_CLAMP"))
@@ -455,8 +420,6 @@ static void default_tuning(VkvTuning &t)
 		const int v = std::atoi(e);
 		t.wave_shape = (v == 4 || v == 8 || v == 16) ? v : 0;
 	}
-	if (const char *e = env("VKV_OCCUPANCY_KERNEL"))
-		t.occupancy_kernel = e[0] == 'r';
 	// the environment gets the checks vkv_set_tuning applies: an out-of-range value falls back to the built-in default of its group
 	clamp_tuning(t);
 	if (tuning_problem(t))
@@ -464,8 +427,6 @@ static void default_tuning(VkvTuning &t)
 		if (!std::isfinite(t.tile_mix_heavy) || !std::isfinite(t.tile_mix_spread) || t.tile_mix_heavy < 0.0f || t.tile_mix_heavy > 1.0f || t.tile_mix_spread < 0.0f ||
 		    t.tile_mix_spread > 1.0f)
 			t.tile_mix_heavy = t.tile_mix_spread = 0.0f;
-		if (t.pack_tile != 0 && t.pack_tile != 2 && t.pack_tile != 4)
-			t.pack_tile = 0;
 	}
 }
 

@@ -14,7 +14,8 @@
 // workgroup then evaluates the listed cells' voxels, one lane per (cell, voxel row, dword) - no lane waits on another lane's cell.
 #include <algorithm>
 
-#include "vkv_device.hpp"
+#include "launchers.hpp"
+#include "row_loads.hpp"
 
 using namespace vkv;
 
@@ -22,19 +23,6 @@ namespace
 {
 constexpr int      kClassifyLanes = 256, kCellsPerLane = 4, kCellsPerGroup = kClassifyLanes * kCellsPerLane;
 constexpr uint32_t kRangeLevels = 4;        // row ranges of 2, 4, 8 and 16 rows; a query covers up to 32 rows with two lookups
-
-// voxels x .. x + 3 of a row of W voxels (x < W) as one dword; the bytes of x + i >= W are zero (the caller masks them anyway)
-__device__ __forceinline__ uint32_t load4_clipped(const uint8_t *row, int x, int W)
-{
-	if (x + 4 <= W)
-		return load_u32_any(row + x);
-	if (W >= 4)
-		return load_u32_any(row + (W - 4)) >> (8 * (x + 4 - W));
-	uint32_t r = 0;
-	for (int i = 0; x + i < W; ++i)
-		r |= (uint32_t) row[x + i] << (8 * i);
-	return r;
-}
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)

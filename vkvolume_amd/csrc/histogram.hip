@@ -11,7 +11,7 @@
 // region update's few thousand voxels do not pay for clearing and scanning 128 KiB of LDS per workgroup.
 #include <algorithm>
 
-#include "vkv_device.hpp"
+#include "launchers.hpp"
 
 using namespace vkv;
 

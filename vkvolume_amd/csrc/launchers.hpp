@@ -1,0 +1,105 @@
+// launchers.hpp — every function of the library that crosses a translation unit on the host side: the kernel launchers, the limits the
+// entry points check before they enqueue anything, and the few helpers of raymarch.hip that capi.hip calls.  capi.hip and every file that
+// defines one of them include it, so a changed signature is a compile error, not a link error.  All of them return VKV_OK or an error code
+// with the context's error text set; `s` is the stream the work is enqueued on; device pointers are named d_*.
+#pragma once
+
+#include "vkv_device.hpp"
+
+namespace vkv
+{
+// ---- gradient.hip
+// vkv_gradient_map: the gradient of every voxel of e; _box: of the voxels of b (inside e)
+int launch_gradient_map(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, VkvExtent3D e, const VkvTransferFunctionUniform *tf, hipStream_t s);
+int launch_gradient_map_box(vkv_ctx *ctx, const uint8_t *d_vol, uint8_t *d_grad, VkvExtent3D e, const VkvBox &b, const VkvTransferFunctionUniform *tf,
+                            hipStream_t s);
+// vkv_debug_check: device arithmetic `what` (0 .. 4) against its IEEE definition for `count` floats from bit pattern first_bits
+int launch_check_numerics(vkv_ctx *ctx, int what, uint32_t first_bits, uint64_t count, unsigned long long *d_mismatches, hipStream_t s);
+
+// ---- occupancy.hip
+// what the occupancy pass (whole map or a region update's cells) can take in one launch
+bool occupancy_launch_ok(VkvExtent3D e, VkvExtent3D me);
+// what the voxel count can take
+bool count_launch_ok(VkvExtent3D e);
+// the occupancy bit table of an RGBA8 texture in d_bits (the stream's scratch block; the caller holds its lock); _columns: and the column
+// mask behind it, i.e. what launch_occupancy_map takes as bits_ready
+int launch_tf_bits(vkv_ctx *ctx, const uint8_t *d_tf, uint32_t *d_bits, hipStream_t s);
+int launch_tf_bits_columns(vkv_ctx *ctx, const uint8_t *d_tf, uint32_t *d_bits, hipStream_t s);
+// vkv_occupancy_map: every cell of the map.  bits_ready: d_bits already holds the bit table and its column mask; d_tf is then not read, and
+// the map is filled by a kernel, not a memset
+int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
+                         VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, hipStream_t s, uint32_t *d_bits, bool bits_ready = false);
+// the cells [c0, c1) per axis of the map from the bit table in d_bits (ready); from_distance: d_map holds a distance transform of the
+// occupancy and is first turned back into it
+int launch_occupancy_map_cells(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const VkvTransferFunctionUniform *tf, VkvExtent3D e,
+                               uint8_t *d_map, VkvExtent3D me, const uint32_t c0[3], const uint32_t c1[3], bool from_distance, hipStream_t s,
+                               uint32_t *d_bits);
+// vkv_occupied_voxel_count: the analytic transfer function's occupied voxels into *d_count (d_bits as above)
+int launch_occupied_voxel_count(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, const VkvTransferFunctionUniform *tf, VkvExtent3D e,
+                                uint64_t *d_count, hipStream_t s, uint32_t *d_bits);
+
+// ---- distance.hip
+// what the distance transforms can take in one launch
+bool distance_launch_ok(VkvExtent3D me);
+// vkv_distance_map: d_map in place (d_swap: a buffer of the map's size); _anisotropic: the eight octant maps from the occupancy in d_maps[7]
+int launch_distance_map(vkv_ctx *ctx, uint8_t *d_map, uint8_t *d_swap, VkvExtent3D me, hipStream_t s);
+int launch_distance_map_anisotropic(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D me, hipStream_t s);
+// skipping_type's transform of the occupancy map in d_maps[0] (anisotropic: d_maps[7]); nothing for NONE and BLOCK
+int launch_map_transform(vkv_ctx *ctx, uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D me, int skipping_type, hipStream_t s);
+
+// ---- pack.hip
+// vkv_pack_volume: every brick of the packed sampling image; _bricks: the bricks [b0, b1) per axis
+int launch_pack_volume(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, void *d_packed, hipStream_t s);
+int launch_pack_volume_bricks(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, const int b0[3], const int b1[3], void *d_packed,
+                              hipStream_t s);
+
+// ---- tf_tables.hip
+// the integrator's tables of an RGBA8 texture (bit table, separable alpha tables, flag word); tf null: no separable claim
+int launch_tf_tables(vkv_ctx *ctx, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf, uint32_t *d_tables, hipStream_t s);
+// the texture, its tables and (d_bits non-null) the occupancy bit table + column mask from the uniform's fields alone
+int launch_tf_build(vkv_ctx *ctx, const VkvTransferFunctionUniform *tf, uint8_t *d_tf, uint32_t *d_tables, uint32_t *d_bits, hipStream_t s);
+
+// ---- volume_io.hip
+// vkv_synth_volume: kind 0 = sphere, 1 (+ modifiers in the upper bits) = shells of `seed`
+int launch_synth_volume(vkv_ctx *ctx, uint8_t *d_vol, VkvExtent3D e, uint32_t kind, uint32_t seed, hipStream_t s);
+// the loader's conversion of n raw elements (VKV_VOXEL_* type, [lo, hi] -> [0, 255]); _box: of a box's elements into its voxels of the volume e
+int launch_convert_volume(vkv_ctx *ctx, const void *d_raw, int type, bool big_endian, float lo, float hi, uint64_t n, uint8_t *d_out, hipStream_t s);
+int launch_convert_box(vkv_ctx *ctx, const void *d_raw, int type, bool big_endian, float lo, float hi, const VkvBox &box, uint8_t *d_vol, VkvExtent3D e,
+                       hipStream_t s);
+// vkv_scatter_tiles: n frames (1 .. VKV_MAX_BATCH) of gathered per-rank tile buffers into their images
+int launch_scatter_tiles_frames(vkv_ctx *ctx, uint32_t n, void *const *images, const void *const *srcs, const VkvTileRect *rects, const uint32_t *strides,
+                                uint32_t iw, uint32_t ih, uint32_t tw, uint32_t th, uint32_t n_ranks, uint32_t bpp, hipStream_t s);
+
+// ---- region.hip
+// vkv_update_volume_region after the entry point's argument checks: convert the box, then its gradient, bricks, occupancy cells and the transform
+int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool big_endian, float lo, float hi, const VkvBox &box, uint8_t *d_vol,
+                                uint8_t *d_grad, void *d_packed, VkvExtent3D e, const uint8_t *d_tf, const VkvTransferFunctionUniform *tf,
+                                uint8_t *const d_maps[8], uint8_t *d_swap, VkvExtent3D me, int skipping_type, hipStream_t s);
+
+// ---- histogram.hip
+// vkv_volume_histogram after the entry point's argument checks; the occupied-voxel count of the analytic transfer function from a histogram
+int launch_volume_histogram(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, const VkvBox &b, int mode, uint64_t *d_hist,
+                            hipStream_t s);
+int launch_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_hist, const VkvTransferFunctionUniform *tf, uint64_t *d_count, hipStream_t s);
+
+// ---- cells.hip
+// what the summary and classify launches can take
+bool cells_launch_ok(VkvExtent3D e, VkvExtent3D me);
+// vkv_cell_summary: the cells that meet b (the whole map when b is null)
+int launch_cell_summary(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_grad, VkvExtent3D e, VkvExtent3D me, const VkvBox *b, void *d_summary,
+                        hipStream_t s);
+// the occupancy map from the summary, with the bit table already in the stream's scratch block `scratch` (the caller holds its lock)
+int launch_occupancy_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_vol, const uint8_t *d_grad, bool use_gradient, uint8_t *scratch,
+                                  VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, uint64_t *d_unresolved, hipStream_t s);
+
+// ---- raymarch.hip
+// vkv_render / vkv_render_batch (n frames in one launch) after the entry point's argument checks
+int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);
+int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, const float *alpha_luts, hipStream_t s);
+// vkv_prepare_render: everything a later launch of these n parameter blocks on s takes from the context, created now
+int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream_t s);
+// vkv_screen_tile_rect: the screen bound of the volume's box in whole tiles
+void screen_tile_rect(const VkvRayCastUniform *rc, const VkvRayGen *rg, uint32_t iw, uint32_t ih, uint32_t tw, uint32_t th, uint32_t align, VkvTileRect *out);
+// loads the start-order kernels' code object on the current device (vkv_register_target)
+void load_feedback_code();
+}        // namespace vkv

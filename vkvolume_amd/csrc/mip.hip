@@ -14,22 +14,10 @@
 
 #include "raymarch_core.hpp"
 #include "max_map_skip.hpp"
+#include "row_loads.hpp"
 
 namespace
 {
-
-// voxels x .. x + 3 of a row of W voxels (x < W) as one dword; the bytes of x + i >= W are zero
-__device__ __forceinline__ uint32_t load4_clipped(const uint8_t *row, int x, int W)
-{
-	if (x + 4 <= W)
-		return load_u32_any(row + x);
-	if (W >= 4)
-		return load_u32_any(row + (W - 4)) >> (8 * (x + 4 - W));
-	uint32_t r = 0;
-	for (int i = 0; x + i < W; ++i)
-		r |= (uint32_t) row[x + i] << (8 * i);
-	return r;
-}
 
 __device__ __forceinline__ uint32_t max_byte(uint32_t d) { return max(max(d & 255u, (d >> 8) & 255u), max((d >> 16) & 255u, d >> 24)); }
 

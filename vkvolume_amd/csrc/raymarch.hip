@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "raymarch_inst.hpp"
+#include "launchers.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
 // Start order from measured costs: one workgroup per frame sorts the schedule entries 0 .. count - 1 by the cost the previous frame
