@@ -670,6 +670,45 @@ typedef struct VkvIsoOptions
  * strided shares that assemble through vkv_scatter_tiles. */
 int vkv_render_isosurface(vkv_ctx *ctx, const VkvRenderParams *params, const VkvIsoOptions *iso, void *stream);
 
+/* ---- oblique slices and thick slabs: multi-planar reformatting ------------------------------------------------------- */
+enum VkvSlabMode { VKV_SLAB_MAX = 0, VKV_SLAB_MIN = 1, VKV_SLAB_MEAN = 2 };
+
+typedef struct VkvSlabOptions
+{
+	float          origin[3];   /* texture coordinates ([0,1]^3 = the volume) of pixel (0, 0), sample 0 */
+	float          du[3];       /* texture-space step per pixel column */
+	float          dv[3];       /* texture-space step per pixel row    */
+	float          dn[3];       /* texture-space step per slab sample  */
+	uint32_t       samples;     /* 1 .. 4096 samples per pixel; 1 = a plain slice */
+	int32_t        mode;        /* VkvSlabMode */
+	float          window_min, window_max; /* grey g = clamp((value - window_min) / (window_max - window_min), 0, 1); window_max <= window_min: g = 1 */
+	const uint8_t *d_max_map;   /* vkv_max_map of d_volume with params->map_extent, or NULL (dense); VKV_SLAB_MAX only */
+	float *        d_out_value; /* the slab's value per pixel (0 without a counted sample), indexed like the other outputs; or NULL */
+	uint32_t       flags;       /* must be 0 */
+} VkvSlabOptions;
+
+/* A plane through one volume, or a slab of finite thickness about it, without a camera.  Every step is fp32 IEEE arithmetic in this order:
+ * pixel (x, y) has the base point p_c = fma((float) y, dv_c, fma((float) x, du_c, origin_c)) per component c, its samples lie at
+ * q_c = fma((float) j, dn_c, p_c), j = 0 .. samples - 1, and sample j counts if 0 <= q_c <= 1 on all three axes (fma is monotone in j: the
+ * counted indices are one contiguous range).  A sample's value v_j is the integrator's filtered intensity at q (linear buffer or
+ * d_packed_volume: the same bits).  VKV_SLAB_MAX: the largest counted v_j; VKV_SLAB_MIN: the smallest; VKV_SLAB_MEAN: acc = 0, acc = acc + v_j
+ * over the counted j in rising order, acc / (float) count.  A pixel with a counted sample gets d_out_value = that value, RGBA32F (g, g, g, 1)
+ * and RGBA8 its round-to-nearest; every other pixel gets value 0 and colour zeros.  d_out_counts (3 x u32 per pixel): samples filtered,
+ * max-map bytes read, samples skipped; [0] + [2] is the number of counted samples on every path, and [1] = [2] = 0 without a max map.
+ * With d_max_map (VKV_SLAB_MAX only) a pixel's column walks like a MIP ray with entry p and step dn over the counted range: the samples of a
+ * cell whose byte B gives B * kInv255 <= the best so far are jumped over (there is no best before the first filtered sample, so the first
+ * counted sample is always filtered), and the walk stops once the best is 255 / 255: the results equal the dense path's bit for bit.
+ * Read: image_width, image_height, `tiles` (whole image, rect, compact, strided: a compact per-rank share assembles through
+ * vkv_scatter_tiles / vkv_assemble_frame as a MIP share does), volume_extent, map_extent (with a max map), d_volume, d_packed_volume,
+ * d_out_color, d_out_rgba8, d_out_counts.  Ignored: camera, ray_cast, ray_gen, transfer function, gradient, distance maps, skipping_type (a
+ * zero-filled camera is fine).  VKV_E_UNSUPPORTED: blend_over_target, tiles.fill_outside, options.test != VKV_TEST_NONE,
+ * options.depth_attachment, a non-NULL d_out_depth.  VKV_E_INVALID_ARGUMENT: null params or slab, flags != 0, samples outside 1 .. 4096, an
+ * unknown mode, a non-finite component of origin, du, dv or dn, a NaN window_min or window_max, d_max_map with a mode other than VKV_SLAB_MAX
+ * or without a valid map_extent, no output at all, a null d_volume, a zero extent, and what vkv_render_mip rejects of `tiles`.  Every argument
+ * is checked before anything is enqueued: a rejected call writes nothing.  One kernel launch and nothing else (no memset, no table, no
+ * allocation, no host wait; the kernels use no scratch memory), so after one direct call on `stream` it can be captured into a hipGraph. */
+int vkv_render_slab(vkv_ctx *ctx, const VkvRenderParams *params, const VkvSlabOptions *slab, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

@@ -140,6 +140,17 @@ class IsoOptions(C.Structure):
                 ("specular", C.c_float), ("shininess", C.c_uint32), ("d_max_map", C.c_void_p), ("d_out_normal", C.c_void_p), ("flags", C.c_uint32)]
 
 
+SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2  # VkvSlabMode
+
+
+class SlabOptions(C.Structure):
+    """VkvSlabOptions (vkv_render_slab): the plane (origin, du, dv) and the slab's sample step dn in texture space, samples per pixel, mode
+    (SLAB_MAX / SLAB_MIN / SLAB_MEAN), grey window, optional max map (SLAB_MAX only), optional value output, flags (0)"""
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dn", C.c_float * 3), ("samples", C.c_uint32),
+                ("mode", C.c_int32), ("window_min", C.c_float), ("window_max", C.c_float), ("d_max_map", C.c_void_p), ("d_out_value", C.c_void_p),
+                ("flags", C.c_uint32)]
+
+
 class Tuning(C.Structure):
     """VkvTuning"""
     _fields_ = [("struct_size", C.c_uint32), ("scheduler", C.c_int32), ("batch_mode", C.c_int32), ("batch_sequential", C.c_int32),

@@ -84,3 +84,48 @@ def orbit_camera(azimuth_deg, elevation_deg, radius, centre=(0.0, 0.0, 0.0)):
     eye = np.asarray(centre, np.float64) + radius * np.array([math.cos(el) * math.sin(az), math.sin(el),
                                                               math.cos(el) * math.cos(az)])
     return look_at(eye, centre)
+
+
+def slab_plane(extent_whd, centre_voxel=None, normal=None, up=None, image_size=None, pixel_voxels=1.0, thickness_voxels=0.0, sample_voxels=1.0,
+               axis=None, index=None):
+    """The plane of a slice or slab for vkv_render_slab (VolumeRenderSubpass.draw_slab), pure numpy: a dict with ``origin``, ``du``, ``dv``,
+    ``dn`` (float32, texture coordinates), ``samples`` = max(1, round(thickness_voxels / sample_voxels) + 1) and ``image_size``.
+
+    Voxel space: voxel i of an axis has its centre at coordinate i (the sampler's voxel coordinate), so the texture coordinate of voxel
+    coordinate c is (c + 0.5) / extent.  The frame is orthonormal in voxel space: n = ``normal`` normalised, v = ``up`` made orthogonal to n
+    and normalised (image rows advance along v), u = v x n (image columns advance along u).  A pixel step is ``pixel_voxels`` long, a sample
+    step ``sample_voxels`` along n; the image is centred on ``centre_voxel`` (default: the volume's centre) and the slab on the plane.
+
+    ``axis`` = "x" | "y" | "z" with ``index`` = k: slice k of that axis, one pixel per voxel, columns and rows along the remaining axes in
+    x, y, z order (axis z: du = (1/W, 0, 0), dv = (0, 1/H, 0), origin_z = (k + 0.5) / D; image (W, H) unless ``image_size`` is given), dn
+    along the axis."""
+    ext = np.asarray(extent_whd, np.float64)
+    if axis is not None:
+        a = "xyz".index(axis)
+        cu, cv = [c for c in range(3) if c != a]
+        n, u, v = np.zeros(3), np.zeros(3), np.zeros(3)
+        n[a], u[cu], v[cv] = 1.0, 1.0, 1.0
+        if image_size is None:
+            image_size = (int(ext[cu]), int(ext[cv]))
+        if centre_voxel is None:
+            centre_voxel = (ext - 1.0) * 0.5
+        centre = np.asarray(centre_voxel, np.float64).copy()
+        if index is not None:
+            centre[a] = float(index)
+    else:
+        n = np.asarray(normal, np.float64)
+        n = n / np.linalg.norm(n)
+        v = np.asarray(up, np.float64)
+        v = v - np.dot(v, n) * n
+        if not np.linalg.norm(v) > 0.0:
+            raise ValueError("slab_plane: up is parallel to normal")
+        v = v / np.linalg.norm(v)
+        u = np.cross(v, n)
+        centre = (ext - 1.0) * 0.5 if centre_voxel is None else np.asarray(centre_voxel, np.float64)
+    w, h = image_size
+    samples = max(1, int(round(thickness_voxels / sample_voxels)) + 1)
+    du_v, dv_v, dn_v = u * pixel_voxels, v * pixel_voxels, n * sample_voxels
+    origin_v = centre - 0.5 * (w - 1) * du_v - 0.5 * (h - 1) * dv_v - 0.5 * (samples - 1) * dn_v
+    f32 = lambda x: np.ascontiguousarray(x, np.float32)  # noqa: E731
+    return dict(origin=f32((origin_v + 0.5) / ext), du=f32(du_v / ext), dv=f32(dv_v / ext), dn=f32(dn_v / ext), samples=samples,
+                image_size=(int(w), int(h)))

@@ -1,4 +1,4 @@
-// max_map_skip.hpp — the sample path of the maximum-intensity projection (k_mip) that the isosurface (k_iso, §5.10) shares:
+// max_map_skip.hpp — the sample path of the maximum-intensity projection (k_mip) that the isosurface (k_iso, §5.10) and the slab (k_slab, §5.11) share:
 // the filtered intensity of one sample or of a group of samples, the grown-cell test, the exact skip step over the per-cell max map
 // (vkv_max_map) as a helper, and the host-side checks and arguments of both entry points.  k_mip keeps its own inline copy of the skip step:
 // calling max_map_skip cost its skipping variant 1-2 % (§5.10).  Included after raymarch_core.hpp.
@@ -60,6 +60,9 @@ __device__ __forceinline__ void mip_samples(const RayMarchArgs &A, const Ray &R,
 	}
 }
 
+// the largest value a sample can take (a footprint of 255s)
+constexpr float kMaxSample = 255.0f * kInv255;
+
 // c = the sampler's voxel coordinate of a sample on one axis; true when it lies in [lo - 1, lo + b): the sample then reads only voxels of the
 // cell [lo, lo + b) grown by one voxel
 __device__ __forceinline__ bool in_grown(float c, int lo, int b) { return c >= (float) (lo - 1) && c < (float) (lo + b); }
@@ -109,15 +112,17 @@ __device__ __forceinline__ int max_map_skip(const RayMarchArgs &A, const MM &M, 
 	return i + kk;
 }
 
-// ---- host side: the checks and arguments vkv_render_mip and vkv_render_isosurface share --------------------------------------------------
+// ---- host side: the checks and arguments vkv_render_mip, vkv_render_isosurface and vkv_render_slab share --------------------------------------------------
 
 bool     extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
 bool     map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
 uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
 
 // the checks of the fields of P a MIP / isosurface call reads (`what`: the entry point's name in the messages), with the max map d_max_map
-// (or null) and `has_output`: an output of the call's own options is set; VKV_OK or the code (nothing is enqueued before they pass)
-int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, const uint8_t *d_max_map, bool has_output)
+// (or null) and `has_output`: an output of the call's own options is set; VKV_OK or the code (nothing is enqueued before they pass).
+// rays = false (vkv_render_slab): the call casts no rays, so it has no depth (options.depth_attachment and d_out_depth are unsupported) and
+// reads no sampling_factor
+int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, const uint8_t *d_max_map, bool has_output, bool rays = true)
 {
 	if (P->blend_over_target)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: blend_over_target is not supported", what);
@@ -125,13 +130,15 @@ int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: tiles.fill_outside is not supported", what);
 	if (P->options.test != VKV_TEST_NONE)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: test modes are not supported", what);
+	if (!rays && (P->options.depth_attachment || P->d_out_depth))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: options.depth_attachment and d_out_depth are not supported", what);
 	if (P->options.depth_attachment && !P->d_in_depth)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: options.depth_attachment needs d_in_depth", what);
 	if (!extent_ok(P->volume_extent) || P->image_width == 0 || P->image_height == 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: zero extent", what);
 	if (!P->d_volume)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null volume", what);
-	if (!(P->transfer_function.sampling_factor > 0.0f))
+	if (rays && !(P->transfer_function.sampling_factor > 0.0f))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: sampling_factor must be positive", what);
 	if (d_max_map)
 	{

@@ -69,10 +69,7 @@ struct MipArgs
 	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
 };
 
-// the largest value a sample can take (a footprint of 255s)
-constexpr float kMaxSample = 255.0f * kInv255;
-
-// (mip_sample, mip_samples and in_grown are in max_map_skip.hpp, shared with k_iso.  The skip step below is written out here rather than
+// (kMaxSample, mip_sample, mip_samples and in_grown are in max_map_skip.hpp, shared with k_iso.  The skip step below is written out here rather than
 // calling max_map_skip: the shared helper's control flow cost the skipping variant 1-2 %)
 
 template <bool PACKED, bool SKIP>

@@ -136,6 +136,23 @@ void VolumeRenderSubpass::draw_iso(const RenderTarget &target, const VkvIsoOptio
 		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_iso: ") + vkv_last_error(dc.ctx));
 }
 
+void VolumeRenderSubpass::draw_slab(const RenderTarget &target, const VkvSlabOptions &slab, bool skip, const VkvTileSchedule *tiles)
+{
+	Volume *volume = volumes.front();
+	if (!volume->get_packed_volume())
+		volume->pack(dc);
+	const bool use_map = skip && slab.mode == VKV_SLAB_MAX;        // the max map bounds a maximum only
+	if (use_map && !volume->get_max_map())
+		throw std::runtime_error("VolumeRenderSubpass::draw_slab: skip needs the volume's max map (Volume::build_max_map)");
+	VkvRenderParams p = make_params(*volume, target, tiles, false);
+	p.options.test    = VKV_TEST_NONE;        // the test modes are the integrator's outputs (benchmark mode sets one)
+	p.options.depth_attachment = 0, p.d_out_depth = nullptr, p.d_in_depth = nullptr;        // a slab has no depth
+	VkvSlabOptions o  = slab;
+	o.d_max_map       = use_map ? volume->get_max_map() : nullptr;
+	if (vkv_render_slab(dc.ctx, &p, &o, dc.stream) != VKV_OK)
+		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_slab: ") + vkv_last_error(dc.ctx));
+}
+
 void VolumeRenderSubpass::draw_batch(const std::vector<RenderTarget> &targets, const VkvTileSchedule *tiles)
 {
 	if (volumes.size() != 1 || targets.empty() || targets.size() > VKV_MAX_BATCH)

@@ -90,6 +90,11 @@ class VolumeRenderSubpass
 	// comes from the volume when skip is set: Volume::build_max_map first; the same bits as the dense path).
 	void draw_iso(const RenderTarget &target, const VkvIsoOptions &iso, bool skip = true, const VkvTileSchedule *tiles = nullptr);
 
+	// Oblique slice or thick slab of the first volume into `target` (vkv_render_slab): no camera, `slab` gives the plane, the
+	// sample step, the mode and the grey window (every field of VkvSlabOptions but d_max_map, which comes from the volume when skip is set
+	// and the mode is VKV_SLAB_MAX: Volume::build_max_map first; the same bits as the dense path).  target.depth is not written.
+	void draw_slab(const RenderTarget &target, const VkvSlabOptions &slab, bool skip = true, const VkvTileSchedule *tiles = nullptr);
+
 	// The schedule of a whole frame on one GPU (round 6): the 16x16 tiles of the rectangle the clipped box projects into (vkv_screen_tile_rect: the
 	// rasteriser of the reference only shades the box's faces, :262-293) with VkvTileSchedule.fill_outside - the launch's workgroups write the
 	// no-fragment result everywhere else, so the frame is complete without a workgroup per empty tile (C3: half of the frame's tiles, 2.7 % of its time).

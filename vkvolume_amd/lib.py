@@ -23,7 +23,7 @@ EXPORTS = [
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
-    "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface",
+    "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -111,6 +111,7 @@ def load():
     L.vkv_max_map.argtypes = [vp, vp, abi.Extent3D, abi.Extent3D, P(abi.Box), vp, vp]
     L.vkv_render_mip.argtypes = [vp, P(abi.RenderParams), P(abi.MipOptions), vp]
     L.vkv_render_isosurface.argtypes = [vp, P(abi.RenderParams), P(abi.IsoOptions), vp]
+    L.vkv_render_slab.argtypes = [vp, P(abi.RenderParams), P(abi.SlabOptions), vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -331,6 +332,13 @@ class Context:
 
     def render_isosurface_rc(self, params, iso, stream=0):
         return self._lib.vkv_render_isosurface(self.handle, None if params is None else C.byref(params), None if iso is None else C.byref(iso), stream)
+
+    def render_slab(self, params, slab, stream=0):
+        """vkv_render_slab: an oblique slice or thick slab (max / min / mean) of params' volume with the abi.SlabOptions `slab`"""
+        self.check(self.render_slab_rc(params, slab, stream))
+
+    def render_slab_rc(self, params, slab, stream=0):
+        return self._lib.vkv_render_slab(self.handle, None if params is None else C.byref(params), None if slab is None else C.byref(slab), stream)
 
     def occupancy_map_from_summary(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
         """vkv_occupancy_map_from_summary: vkv_occupancy_map's map, decided from the cell summaries where they are certain; d_unresolved

@@ -366,6 +366,28 @@ class VolumeRenderSubpass:
                               d_max_map=_ptr(max_map), d_out_normal=_ptr(normal), flags=0)
         self.ctx.render_isosurface(params, opts, _stream())
 
+    def draw_slab(self, params, plane, samples=1, mode=abi.SLAB_MAX, window=(0.0, 1.0), skip=True, color=None, rgba8=None, value=None, counts=None):
+        """Oblique slice or thick slab (vkv_render_slab) into the given buffers.  ``plane``: (origin, du, dv, dn) in texture coordinates, or
+        the dict camera.slab_plane returns (pass its ``samples`` as ``samples``); pixel (x, y), sample j lies at origin + x du + y dv + j dn.  ``mode``: abi.SLAB_MAX / SLAB_MIN / SLAB_MEAN over the samples inside the volume; ``window``:
+        (window_min, window_max) of the grey level; ``value``: one float per pixel, the slab's value.  ``skip`` (SLAB_MAX only; ignored by
+        the other modes): jump over the cells of the volume's max map (build_max_map() first; the same bits as the dense path).  Only the
+        image size, schedule and extents of ``params`` are read: no camera is needed."""
+        if isinstance(plane, dict):
+            plane = (plane["origin"], plane["du"], plane["dv"], plane["dn"])
+        max_map = None
+        if skip and mode == abi.SLAB_MAX:
+            if self.volume.max_map is None:
+                raise RuntimeError("VolumeRenderSubpass.draw_slab: skip=True needs the volume's max map (call Volume.build_max_map first)")
+            max_map = self.volume.max_map
+        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
+        params.d_out_counts, params.d_out_depth = _ptr(counts), None
+        params.d_in_depth, params.blend_over_target = None, 0
+        vec = lambda a: (C.c_float * 3)(*[float(x) for x in a])  # noqa: E731
+        origin, du, dv, dn = plane
+        opts = abi.SlabOptions(origin=vec(origin), du=vec(du), dv=vec(dv), dn=vec(dn), samples=int(samples), mode=int(mode),
+                               window_min=float(window[0]), window_max=float(window[1]), d_max_map=_ptr(max_map), d_out_value=_ptr(value), flags=0)
+        self.ctx.render_slab(params, opts, _stream())
+
 
 def default_scene(volume, voxel_size=(1.0, 1.0, 1.0), axis_angle=(1.0, 0.0, 0.0, 0.0)):
     """image transform from the header fields + benchmark-mode node scale (src/load_volume.cpp:82-83,
