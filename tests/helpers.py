@@ -1,6 +1,12 @@
 """Shared scene construction for the parity tests: the same call order as the reference's
 VolumeRender::prepare (src/volume_render.cpp:186-238): load -> gradient -> TF texture -> occupancy/distance -> render."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
+import pytest
 
 from oracle import vkv_oracle as O
 from vkvolume_amd import abi, camera, lib
@@ -98,3 +104,57 @@ def brute_force_chebyshev_octant(occ, k):
         d = np.maximum(np.maximum(dz, dy), dx)
         out = np.where(ok, np.minimum(out, d), out)
     return np.minimum(out, 255).astype(np.uint8)
+
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vkvolume_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def kernel_listing(source, out):
+    """Compiles vkvolume_amd/csrc/<source> (a file of the Makefile's SRCS) for gfx950 with the Makefile's FLAGS into the listing `out`
+    (hipcc cross-compiles without a GPU; skips the test without hipcc); {kernel: {"NumVgprs": n, "ScratchSize": n}}."""
+    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
+    assert re.search(r"^(SRCS|RMINST)\s*:=.*\b%s\b" % re.escape(source), text, flags=re.M), source
+    flags = [f.replace("$(ARCH)", "gfx950") for f in re.search(r"^FLAGS\s*:=\s*(.*)$", text, flags=re.M).group(1).split() if not f.startswith("$(")]
+    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc"] + flags + ["--offload-arch=gfx950", "-S", "--cuda-device-only", os.path.join(CSRC, source), "-o", str(out)]
+    subprocess.run(cmd, check=True, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+    kernels, name = {}, None
+    for line in open(out):
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1)
+        m = re.match(r";\s*(NumVgprs|ScratchSize):\s*(\d+)", line)
+        if m and name:
+            kernels.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return kernels
+
+
+def compact_pixels(size, tiles):
+    """(index into the launch's compact tile buffers, index into the image) of every pixel of the image that the schedule `tiles` (an
+    abi.TileSchedule with compact = 1) renders: entry k is tile tile_first + k * tile_stride of the rectangle (row-major; all zero: the whole
+    image), whose pixel (lx, ly) lies at (k * tile_height + ly) * tile_width + lx"""
+    w, h = size
+    tw, th, r = tiles.tile_width, tiles.tile_height, tiles.rect
+    x0, y0, cols = (r.x0, r.y0, r.w) if r.w and r.h else (0, 0, (w + tw - 1) // tw)
+    k, ly, lx = np.meshgrid(np.arange(tiles.tile_count), np.arange(th), np.arange(tw), indexing="ij")
+    t = tiles.tile_first + k * tiles.tile_stride
+    px, py = (x0 + t % cols) * tw + lx, (y0 + t // cols) * th + ly
+    ok = (px < w) & (py < h)
+    return ((k * th + ly) * tw + lx)[ok], (py * w + px)[ok]
+
+
+def stretched_orbit(azimuth, elevation, radius, image_size, stretch, fov=60.0):
+    """orbit() with a projection whose aspect is `stretch` times the image's: a pixel step in x covers `stretch` times the angle of one in y"""
+    return camera.orbit_camera(azimuth, elevation, radius), camera.perspective_vulkan(fov, stretch * image_size[0] / image_size[1])
+
+
+def wave_patch_log2(p):
+    """log2 of the width of a wave's 64-pixel patch for the view of RenderParams p (2, 3, 4: 4x16, 8x8, 16x4 pixels): the voxels a pixel step
+    in x covers against one in y, in double precision, with the thresholds 1.6 and 1 / 1.6.  A test that asserts it checks its own premise
+    (the view asks for that shape), not the kernel: every patch shape gives the same frame."""
+    dim = np.array([p.volume_extent.width, p.volume_extent.height, p.volume_extent.depth], np.float64)
+    vx, vy = (float(np.sum((np.array(list(d)[:3], np.float64) * dim) ** 2)) for d in (p.ray_gen.ddx, p.ray_gen.ddy))
+    q = np.sqrt(vx / vy) if vx > 0.0 and vy > 0.0 else 1.0
+    return 2 if q >= 1.6 else (4 if q <= 1.0 / 1.6 else 3)

@@ -14,6 +14,7 @@ import torch
 from oracle import vkv_oracle as O
 from tests import helpers as T
 from tests.test_iso_cpu import iso_np, iso_options
+from tests.test_mip_cpu import max_map_np, max_map_skip_np, rays_np, samples_np
 from vkvolume_amd import abi, lib, volume as V
 
 pytestmark = pytest.mark.gpu
@@ -312,6 +313,50 @@ def test_schedules_rect_and_compact_strided(ctx):
     assert_same_bits(whole[True], whole[False], "whole")
 
 
+@pytest.mark.parametrize("tile,rect", [((16, 16), (2, 1, 3, 3)), ((32, 16), (0, 1, 3, 3))])
+@pytest.mark.parametrize("stretch,patch", [(4.0, 2), (0.25, 4)])
+def test_compact_strided_share_of_an_inner_rectangle_matches_numpy(ctx, tile, rect, stretch, patch):
+    """the deal of workgroups and lanes to pixels: every second tile, from the second, of a tile rectangle off the origin that reaches the
+    image's partial last column and row, into compact buffers; views whose waves take 4x16 and 16x4 pixel patches"""
+    shape, size = (24, 20, 16), (72, 56)
+    w, h = size
+    vol = scene_volume(shape, 7)
+    v = make_volume(ctx, vol)
+    sp = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=abi.SKIP_NONE, clip_distance=50.0, early_ray_termination=0), size)
+    p = sp.make_params(*T.stretched_orbit(30.0, 20.0, 40.0, size, stretch))
+    assert T.wave_patch_log2(p) == patch
+    p.tiles = abi.full_frame_tiles(w, h, tile[0], tile[1], rank=1, world=2, compact=True, rect=abi.TileRect(*rect))
+    assert (p.tiles.tile_first, p.tiles.tile_stride, p.tiles.compact, p.tiles.tile_count) == (1, 2, 1, 4)
+    ci, ii = T.compact_pixels(size, p.tiles)
+    assert np.any(ii % w >= w - w % tile[0]) and np.any(ii // w >= h - h % tile[1]) and ci.size < 4 * tile[0] * tile[1]
+    R = rays_np(p)
+    S = samples_np(vol, R)
+    opts = iso_options(0.7, 5)
+    ref = iso_np(p, vol, opts, S=S)
+    assert R["marched"][ii].sum() > 100 and (ref["k"].reshape(-1)[ii] >= 0).sum() > 100
+    n = 4 * tile[0] * tile[1]
+    frames = {}
+    for skip in (False, True):
+        o = outputs(n)
+        sp.draw_iso(abi.RenderParams.from_buffer_copy(p), opts.iso, color=o["color"], rgba8=o["rgba8"], depth=o["depth"], normal=o["normal"],
+                    counts=o["counts"], skip=skip, **kw_of(opts))
+        torch.cuda.synchronize()
+        frames[skip] = {k: t.cpu().numpy() for k, t in o.items()}
+    dense, fast = frames[False], frames[True]
+    at = (tile, rect, stretch)
+    ref_at = {k: np.ascontiguousarray(ref[k]).reshape(w * h, -1)[ii] for k in KEYS + ("k", "n_steps")}
+    assert_matches_numpy({k: a[ci] for k, a in dense.items()}, ref_at, at)
+    assert_same_bits({k: a[ci] for k, a in fast.items()}, {k: a[ci] for k, a in dense.items()}, at)
+    me = v.map_extent
+    walk = max_map_skip_np(p, vol, max_map_np(vol, (me.width, me.height, me.depth)), opts.iso, True, R, S)
+    for j, key in enumerate(("n_filt", "n_probe", "n_skip")):
+        assert np.array_equal(fast["counts"][ci, j].astype(np.int64), walk[key][ii]), (at, key)
+    rest = np.ones(n, bool)
+    rest[ci] = False        # the tiles' pixels past the image
+    for k in dense:
+        assert np.all(dense[k][rest] == 7) and np.all(fast[k][rest] == 7), (at, k)
+
+
 # ---- the call's guarantees ---------------------------------------------------------------------------------------------------------------
 
 def test_rejected_calls_write_nothing(ctx):
@@ -329,24 +374,27 @@ def test_rejected_calls_write_nothing(ctx):
         g.d_max_map = ptr(v.max_map)
         return g
 
+    U, I = abi.VKV_E_UNSUPPORTED, abi.VKV_E_INVALID_ARGUMENT
     cases = []
     P = lambda: abi.RenderParams.from_buffer_copy(p)  # noqa: E731
-    q = P(); q.blend_over_target = 1; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    q = P(); q.tiles.fill_outside = 1; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    q = P(); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    for field, value in (("iso", float("nan")), ("iso", float("inf")), ("refine_steps", 17), ("ambient", -0.1), ("diffuse", float("nan")),
-                         ("specular", float("inf")), ("shininess", 0), ("shininess", 1025), ("flags", 1)):
-        m = good(); setattr(m, field, value); cases.append((P(), m, abi.VKV_E_INVALID_ARGUMENT))
+    q = P(); q.blend_over_target = 1; cases.append((q, good(), U, "blend_over_target"))
+    q = P(); q.tiles.fill_outside = 1; cases.append((q, good(), U, "tiles.fill_outside"))
+    q = P(); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), U, "test modes"))
+    for field, value, message in (("iso", float("nan"), "iso must be finite"), ("iso", float("inf"), "iso must be finite"),
+                                  ("refine_steps", 17, "refine_steps must be"), ("ambient", -0.1, "base_color, ambient"),
+                                  ("diffuse", float("nan"), "base_color, ambient"), ("specular", float("inf"), "base_color, ambient"),
+                                  ("shininess", 0, "shininess must be"), ("shininess", 1025, "shininess must be"), ("flags", 1, "flags must be 0")):
+        m = good(); setattr(m, field, value); cases.append((P(), m, I, message))
     for c in (0, 1, 2):
         for value in (-1.0, float("nan")):
-            m = good(); m.base_color[c] = value; cases.append((P(), m, abi.VKV_E_INVALID_ARGUMENT))
-    q = P(); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), abi.VKV_E_INVALID_ARGUMENT))
-    q = P(); q.options.depth_attachment = 1; q.d_in_depth = None; cases.append((q, good(), abi.VKV_E_INVALID_ARGUMENT))
-    q = P(); q.transfer_function.sampling_factor = 0.0; cases.append((q, good(), abi.VKV_E_INVALID_ARGUMENT))
-    for q, m, code in cases:
-        assert call(q, m) == code
-    assert ctx.render_isosurface_rc(None, good(), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.render_isosurface_rc(p, None, st()) == abi.VKV_E_INVALID_ARGUMENT
+            m = good(); m.base_color[c] = value; cases.append((P(), m, I, "base_color, ambient"))
+    q = P(); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), I, "the max map needs a valid map_extent"))
+    q = P(); q.options.depth_attachment = 1; q.d_in_depth = None; cases.append((q, good(), I, "options.depth_attachment needs d_in_depth"))
+    q = P(); q.transfer_function.sampling_factor = 0.0; cases.append((q, good(), I, "sampling_factor must be positive"))
+    for q, m, code, message in cases:
+        assert call(q, m) == code and ctx.last_error().startswith("render_isosurface: " + message), (message, ctx.last_error())
+    assert ctx.render_isosurface_rc(None, good(), st()) == I and ctx.last_error().startswith("render_isosurface: null params or options")
+    assert ctx.render_isosurface_rc(p, None, st()) == I and ctx.last_error().startswith("render_isosurface: null params or options")
     torch.cuda.synchronize()
     for k, t in o.items():
         assert np.all(t.cpu().numpy() == 0x5A), k

@@ -13,7 +13,7 @@ import torch
 
 from oracle import vkv_oracle as O
 from tests import helpers as T
-from tests.test_mip_cpu import max_map_np, mip_np
+from tests.test_mip_cpu import max_map_np, max_map_skip_np, mip_np, rays_np, samples_np
 from vkvolume_amd import abi, lib, volume as V
 
 pytestmark = pytest.mark.gpu
@@ -249,6 +249,45 @@ def test_schedules_rect_and_compact_strided(ctx):
     assert_same_bits(whole[True], whole[False], "whole")
 
 
+@pytest.mark.parametrize("tile,rect", [((16, 16), (2, 1, 3, 3)), ((32, 16), (0, 1, 3, 3))])
+@pytest.mark.parametrize("stretch,patch", [(4.0, 2), (0.25, 4)])
+def test_compact_strided_share_of_an_inner_rectangle_matches_numpy(ctx, tile, rect, stretch, patch):
+    """the deal of workgroups and lanes to pixels: every second tile, from the second, of a tile rectangle off the origin that reaches the
+    image's partial last column and row, into compact buffers; views whose waves take 4x16 and 16x4 pixel patches"""
+    shape, size = (24, 20, 16), (72, 56)
+    w, h = size
+    vol = scene_volume(shape, 7)
+    v = make_volume(ctx, vol)
+    sp = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=abi.SKIP_NONE, clip_distance=50.0, early_ray_termination=0), size)
+    p = sp.make_params(*T.stretched_orbit(30.0, 20.0, 40.0, size, stretch))
+    assert T.wave_patch_log2(p) == patch
+    p.tiles = abi.full_frame_tiles(w, h, tile[0], tile[1], rank=1, world=2, compact=True, rect=abi.TileRect(*rect))
+    assert (p.tiles.tile_first, p.tiles.tile_stride, p.tiles.compact, p.tiles.tile_count) == (1, 2, 1, 4)
+    ci, ii = T.compact_pixels(size, p.tiles)
+    assert np.any(ii % w >= w - w % tile[0]) and np.any(ii // w >= h - h % tile[1]) and ci.size < 4 * tile[0] * tile[1]
+    R = rays_np(p)
+    S = samples_np(vol, R)
+    thr, wmax = 0.2, 0.8
+    ref = mip_np(p, vol, abi.MipOptions(threshold=thr, window_max=wmax), S=S)
+    assert R["marched"][ii].sum() > 100 and ref["found"].reshape(-1)[ii].sum() > 100
+    n = 4 * tile[0] * tile[1]
+    dense = draw(sp, p, thr, wmax, skip=False, size=size, n_pixels=n)
+    fast = draw(sp, p, thr, wmax, skip=True, size=size, n_pixels=n)
+    at = (tile, rect, stretch)
+    ref_at = {k: np.ascontiguousarray(a).reshape(w * h, -1)[ii] for k, a in ref.items() if k in ("intensity", "color", "depth", "rgba8", "n_steps")}
+    assert_matches_numpy({k: a[ci] for k, a in dense.items()}, ref_at, at)
+    assert_same_bits({k: a[ci] for k, a in fast.items()}, {k: a[ci] for k, a in dense.items()}, at)
+    me = v.map_extent
+    walk = max_map_skip_np(p, vol, max_map_np(vol, (me.width, me.height, me.depth)), thr, False, R, S)
+    for j, key in enumerate(("n_filt", "n_probe", "n_skip")):
+        assert np.array_equal(fast["counts"][ci, j].astype(np.int64), walk[key][ii]), (at, key)
+    assert walk["n_skip"][ii].sum() > 0
+    rest = np.ones(n, bool)
+    rest[ci] = False        # the tiles' pixels past the image
+    for k in dense:
+        assert np.all(dense[k][rest] == 7) and np.all(fast[k][rest] == 7), (at, k)
+
+
 def test_bright_object_in_front_filters_fewer_samples(ctx):
     D = H = W = 48
     vol = np.zeros((D, H, W), np.uint8)
@@ -279,27 +318,30 @@ def test_rejected_calls_write_nothing(ctx):
     def good():
         return abi.MipOptions(threshold=0.2, window_max=0.8, d_max_map=ptr(v.max_map), flags=0)
 
+    U, I = abi.VKV_E_UNSUPPORTED, abi.VKV_E_INVALID_ARGUMENT
     cases = []
-    q = abi.RenderParams.from_buffer_copy(p); q.blend_over_target = 1; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    q = abi.RenderParams.from_buffer_copy(p); q.tiles.fill_outside = 1; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    q = abi.RenderParams.from_buffer_copy(p); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), abi.VKV_E_UNSUPPORTED))
-    m = good(); m.threshold = float("nan"); cases.append((abi.RenderParams.from_buffer_copy(p), m, abi.VKV_E_INVALID_ARGUMENT))
-    m = good(); m.window_max = float("nan"); cases.append((abi.RenderParams.from_buffer_copy(p), m, abi.VKV_E_INVALID_ARGUMENT))
-    m = good(); m.flags = 1; cases.append((abi.RenderParams.from_buffer_copy(p), m, abi.VKV_E_INVALID_ARGUMENT))
-    q = abi.RenderParams.from_buffer_copy(p); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), abi.VKV_E_INVALID_ARGUMENT))
-    q = abi.RenderParams.from_buffer_copy(p); q.options.depth_attachment = 1; q.d_in_depth = None; cases.append((q, good(), abi.VKV_E_INVALID_ARGUMENT))
-    for q, m, code in cases:
-        assert call(q, m) == code
-    assert ctx.render_mip_rc(None, good(), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.render_mip_rc(p, None, st()) == abi.VKV_E_INVALID_ARGUMENT
+    q = abi.RenderParams.from_buffer_copy(p); q.blend_over_target = 1; cases.append((q, good(), U, "render_mip: blend_over_target"))
+    q = abi.RenderParams.from_buffer_copy(p); q.tiles.fill_outside = 1; cases.append((q, good(), U, "render_mip: tiles.fill_outside"))
+    q = abi.RenderParams.from_buffer_copy(p); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), U, "render_mip: test modes"))
+    m = good(); m.threshold = float("nan"); cases.append((abi.RenderParams.from_buffer_copy(p), m, I, "render_mip: threshold must be finite"))
+    m = good(); m.window_max = float("nan"); cases.append((abi.RenderParams.from_buffer_copy(p), m, I, "render_mip: threshold must be finite"))
+    m = good(); m.flags = 1; cases.append((abi.RenderParams.from_buffer_copy(p), m, I, "render_mip: flags must be 0"))
+    q = abi.RenderParams.from_buffer_copy(p); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), I, "render_mip: the max map needs a valid map_extent"))
+    q = abi.RenderParams.from_buffer_copy(p); q.options.depth_attachment = 1; q.d_in_depth = None
+    cases.append((q, good(), I, "render_mip: options.depth_attachment needs d_in_depth"))
+    for q, m, code, message in cases:
+        assert call(q, m) == code and ctx.last_error().startswith(message), (message, ctx.last_error())
+    assert ctx.render_mip_rc(None, good(), st()) == I and ctx.last_error().startswith("render_mip: null params or options")
+    assert ctx.render_mip_rc(p, None, st()) == I and ctx.last_error().startswith("render_mip: null params or options")
     # max map: bad extents, empty box, box outside
     mm = torch.full((4,), 0x5A, dtype=torch.uint8, device="cuda")
     e = v.extent
-    assert ctx.max_map_rc(ptr(v.volume), e, abi.Extent3D(0, 1, 1), None, ptr(mm), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.max_map_rc(ptr(v.volume), e, abi.Extent3D(e.width + 1, 1, 1), None, ptr(mm), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.max_map_rc(ptr(v.volume), e, abi.Extent3D(2, 2, 1), abi.Box(0, 0, 0, 0, 1, 1), ptr(mm), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.max_map_rc(ptr(v.volume), e, abi.Extent3D(2, 2, 1), abi.Box(e.width - 1, 0, 0, 2, 1, 1), ptr(mm), st()) == abi.VKV_E_INVALID_ARGUMENT
-    assert ctx.max_map_rc(None, e, abi.Extent3D(2, 2, 1), None, ptr(mm), st()) == abi.VKV_E_INVALID_ARGUMENT
+    for args, message in (((ptr(v.volume), e, abi.Extent3D(0, 1, 1), None), "max_map: null pointer or bad extent"),
+                          ((ptr(v.volume), e, abi.Extent3D(e.width + 1, 1, 1), None), "max_map: null pointer or bad extent"),
+                          ((ptr(v.volume), e, abi.Extent3D(2, 2, 1), abi.Box(0, 0, 0, 0, 1, 1)), "max_map: empty box"),
+                          ((ptr(v.volume), e, abi.Extent3D(2, 2, 1), abi.Box(e.width - 1, 0, 0, 2, 1, 1)), "max_map: box ("),
+                          ((None, e, abi.Extent3D(2, 2, 1), None), "max_map: null pointer or bad extent")):
+        assert ctx.max_map_rc(*args, ptr(mm), st()) == I and ctx.last_error().startswith(message), (message, ctx.last_error())
     torch.cuda.synchronize()
     for k, t in o.items():
         assert np.all(t.cpu().numpy() == 0x5A), k

@@ -546,19 +546,19 @@ def test_render_error_paths(ctx, shell_scene):
     assert ctx.render_rc(p) == 0
     bad = abi.RenderParams.from_buffer_copy(p)
     bad.options.depth_attachment = 1
-    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and "depth_attachment" in ctx.last_error()  # needs d_in_depth
+    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and ctx.last_error().startswith("render: options.depth_attachment needs d_in_depth")
     bad = abi.RenderParams.from_buffer_copy(p)
     bad.d_volume = None
-    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT
+    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and ctx.last_error().startswith("render: null volume or transfer function")
     bad = abi.RenderParams.from_buffer_copy(p)
     bad.tiles.tile_width = 12
-    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT
+    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and ctx.last_error().startswith("render: tile size must be")
     bad = abi.RenderParams.from_buffer_copy(p)
     bad.options.skipping_type = 9
-    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT
+    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and ctx.last_error().startswith("render: bad skipping_type 9")
     bad = abi.RenderParams.from_buffer_copy(p)
     bad.d_out_color = None
-    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT
+    assert ctx.render_rc(bad) == abi.VKV_E_INVALID_ARGUMENT and ctx.last_error().startswith("render: no output buffer")
     with pytest.raises(lib.VkvError):
         ctx.distance_map(out.data_ptr(), out.data_ptr(), abi.Extent3D(4, 4, 4))  # aliased buffers
     with pytest.raises(lib.VkvError):

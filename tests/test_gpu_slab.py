@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import vkv_oracle as O
+from tests import helpers as T
 from tests.test_mip_cpu import max_map_np
 from tests.test_slab_cpu import random_plane, slab_np, slab_options, slab_params, slab_samples_np, slab_skip_np, sparse_scene
 from vkvolume_amd import abi, camera, lib, volume as V
@@ -212,6 +213,42 @@ def test_schedules_rect_and_compact_strided(ctx):
             assert np.array_equal(imgv.cpu().numpy().reshape(-1).view(np.uint32), whole["value"].view(np.uint32)), ("compact", n_ranks, mode, skip)
 
 
+@pytest.mark.parametrize("tile,rect", [((16, 16), (2, 1, 3, 3)), ((32, 16), (0, 1, 3, 3))])
+def test_compact_strided_share_of_an_inner_rectangle_matches_numpy(ctx, tile, rect):
+    """the deal of workgroups and lanes to pixels (8x8 patches): every second tile, from the second, of a tile rectangle off the origin that
+    reaches the image's partial last column and row, into compact buffers"""
+    shape, size = (24, 20, 16), (72, 56)
+    w, h = size
+    vol = scene_volume(shape, 7)
+    v = make_volume(ctx, vol)
+    tiles = abi.full_frame_tiles(w, h, tile[0], tile[1], rank=1, world=2, compact=True, rect=abi.TileRect(*rect))
+    assert (tiles.tile_first, tiles.tile_stride, tiles.compact, tiles.tile_count) == (1, 2, 1, 4)
+    sp, p = bound(v, size, tiles)
+    ci, ii = T.compact_pixels(size, tiles)
+    assert np.any(ii % w >= w - w % tile[0]) and np.any(ii // w >= h - h % tile[1]) and ci.size < 4 * tile[0] * tile[1]
+    rng = np.random.default_rng(33)
+    plane = camera.slab_plane(shape, (12.0, 10.0, 8.0), rng.standard_normal(3), rng.standard_normal(3), size, pixel_voxels=0.4, thickness_voxels=9.0,
+                              sample_voxels=0.75)
+    n = 4 * tile[0] * tile[1]
+    rest = np.ones(n, bool)
+    rest[ci] = False        # the tiles' pixels past the image
+    me = v.map_extent
+    mm = max_map_np(vol, (me.width, me.height, me.depth))
+    for mode, skip in ((abi.SLAB_MEAN, False), (abi.SLAB_MAX, False), (abi.SLAB_MAX, True)):
+        o = slab_options(plane, mode=mode, window=(0.1, 0.8))
+        S = slab_samples_np(p, vol, o)
+        ref = slab_skip_np(p, vol, mm, o, S) if skip else slab_np(p, vol, o, S)
+        assert (ref["count"][ii] > 0).sum() > 100
+        got = draw(sp, p, o, skip=skip, n=n)
+        ref_at = {k: np.ascontiguousarray(ref[k]).reshape(w * h, -1)[ii] for k in KEYS}
+        ref_at["count"] = ref["count"][ii]
+        assert_matches({k: a[ci] for k, a in got.items()}, ref_at, (tile, rect, mode, skip), counts=ref["counts"][ii] if skip else None)
+        if skip:
+            assert ref["counts"][ii, 2].sum() > 0
+        for k in got:
+            assert np.all(got[k][rest] == 7), (tile, rect, mode, skip, k)
+
+
 def test_max_map_kept_current_across_volume_region_updates(ctx):
     rng = np.random.default_rng(11)
     vol = scene_volume((45, 33, 27), 9)
@@ -262,37 +299,38 @@ def test_rejected_calls_write_nothing(ctx):
 
     U, I = abi.VKV_E_UNSUPPORTED, abi.VKV_E_INVALID_ARGUMENT
     cases = []
-    q = P(); q.blend_over_target = 1; cases.append((q, good(), U))
-    q = P(); q.tiles.fill_outside = 1; cases.append((q, good(), U))
-    q = P(); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), U))
-    q = P(); q.options.depth_attachment = 1; q.d_in_depth = ptr(depth); cases.append((q, good(), U))
-    q = P(); q.d_out_depth = ptr(depth); cases.append((q, good(), U))
-    for field, value in (("flags", 1), ("samples", 0), ("samples", 4097), ("mode", 3), ("mode", -1), ("window_min", float("nan")),
-                         ("window_max", float("nan"))):
-        m = good(); setattr(m, field, value); cases.append((P(), m, I))
+    q = P(); q.blend_over_target = 1; cases.append((q, good(), U, "blend_over_target"))
+    q = P(); q.tiles.fill_outside = 1; cases.append((q, good(), U, "tiles.fill_outside"))
+    q = P(); q.options.test = abi.TEST_RAY_ENTRY; cases.append((q, good(), U, "test modes"))
+    q = P(); q.options.depth_attachment = 1; q.d_in_depth = ptr(depth); cases.append((q, good(), U, "options.depth_attachment and d_out_depth"))
+    q = P(); q.d_out_depth = ptr(depth); cases.append((q, good(), U, "options.depth_attachment and d_out_depth"))
+    for field, value, message in (("flags", 1, "flags must be 0"), ("samples", 0, "samples must be"), ("samples", 4097, "samples must be"),
+                                  ("mode", 3, "unknown mode"), ("mode", -1, "unknown mode"), ("window_min", float("nan"), "window_min and window_max"),
+                                  ("window_max", float("nan"), "window_min and window_max")):
+        m = good(); setattr(m, field, value); cases.append((P(), m, I, message))
     for field in ("origin", "du", "dv", "dn"):
         for c in (0, 1, 2):
             for value in (float("nan"), float("inf"), -float("inf")):
-                m = good(); getattr(m, field)[c] = value; cases.append((P(), m, I))
-    cases.append((P(), good(abi.SLAB_MIN), I))   # a max map with a mode other than MAX
-    cases.append((P(), good(abi.SLAB_MEAN), I))
-    q = P(); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), I))
-    q = P(); q.map_extent = abi.Extent3D(34, 5, 5); cases.append((q, good(), I))
-    q = P(); q.d_out_color = q.d_out_rgba8 = q.d_out_counts = None; m = good(); m.d_out_value = None; cases.append((q, m, I))
-    q = P(); q.d_volume = None; cases.append((q, good(), I))
-    q = P(); q.volume_extent = abi.Extent3D(33, 0, 17); cases.append((q, good(), I))
-    q = P(); q.image_width = 0; cases.append((q, good(), I))
+                m = good(); getattr(m, field)[c] = value; cases.append((P(), m, I, "origin, du, dv and dn must be finite"))
+    cases.append((P(), good(abi.SLAB_MIN), I, "a max map bounds VKV_SLAB_MAX only"))   # a max map with a mode other than MAX
+    cases.append((P(), good(abi.SLAB_MEAN), I, "a max map bounds VKV_SLAB_MAX only"))
+    q = P(); q.map_extent = abi.Extent3D(0, 0, 0); cases.append((q, good(), I, "the max map needs a valid map_extent"))
+    q = P(); q.map_extent = abi.Extent3D(34, 5, 5); cases.append((q, good(), I, "the max map needs a valid map_extent"))
+    q = P(); q.d_out_color = q.d_out_rgba8 = q.d_out_counts = None; m = good(); m.d_out_value = None; cases.append((q, m, I, "no output buffer"))
+    q = P(); q.d_volume = None; cases.append((q, good(), I, "null volume"))
+    q = P(); q.volume_extent = abi.Extent3D(33, 0, 17); cases.append((q, good(), I, "zero extent"))
+    q = P(); q.image_width = 0; cases.append((q, good(), I, "zero extent"))
     # what vkv_render_mip rejects of `tiles`
-    q = P(); q.tiles.tile_width = 24; cases.append((q, good(), I))
-    q = P(); q.tiles.tile_height = 0; cases.append((q, good(), I))
-    q = P(); q.tiles.tile_stride = 0; cases.append((q, good(), I))
-    q = P(); q.tiles.tile_count = q.tiles.tile_count + 1; cases.append((q, good(), I))
-    q = P(); q.tiles.rect = abi.TileRect(1, 1, 3, 2); cases.append((q, good(), I))  # (the rectangle runs past the image)
-    q = P(); q.tiles = abi.full_frame_tiles(*size, rect=abi.TileRect(2, 1, 2, 2)); cases.append((q, good(), I))  # the rectangle runs past the image
-    for i, (q, m, code) in enumerate(cases):
-        assert ctx.render_slab_rc(q, m, st()) == code, i
-    assert ctx.render_slab_rc(None, good(), st()) == I
-    assert ctx.render_slab_rc(P(), None, st()) == I
+    q = P(); q.tiles.tile_width = 24; cases.append((q, good(), I, "tile size must be"))
+    q = P(); q.tiles.tile_height = 0; cases.append((q, good(), I, "tile size must be"))
+    q = P(); q.tiles.tile_stride = 0; cases.append((q, good(), I, "tile size must be"))
+    q = P(); q.tiles.tile_count = q.tiles.tile_count + 1; cases.append((q, good(), I, "tile schedule runs past the image"))
+    q = P(); q.tiles.rect = abi.TileRect(1, 1, 3, 2); cases.append((q, good(), I, "the schedule's tile rectangle runs past the image"))
+    q = P(); q.tiles = abi.full_frame_tiles(*size, rect=abi.TileRect(2, 1, 2, 2)); cases.append((q, good(), I, "the schedule's tile rectangle runs past the image"))
+    for i, (q, m, code, message) in enumerate(cases):
+        assert ctx.render_slab_rc(q, m, st()) == code and ctx.last_error().startswith("render_slab: " + message), (i, message, ctx.last_error())
+    assert ctx.render_slab_rc(None, good(), st()) == I and ctx.last_error().startswith("render_slab: null params or options")
+    assert ctx.render_slab_rc(P(), None, st()) == I and ctx.last_error().startswith("render_slab: null params or options")
     torch.cuda.synchronize()
     for k, t in o.items():
         assert np.all(t.cpu().numpy() == 0x5A), k

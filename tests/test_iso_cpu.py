@@ -5,18 +5,16 @@ iso_np is the reference tests/test_gpu_iso.py compares the device against."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import helpers as T
 from tests.test_mip_cpu import _fma, _gmax, _gmin, _mat4_mul, params_np, rays_np, sample_linear_np, samples_np
 from vkvolume_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vkvolume_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 F = np.float32
 
 
@@ -204,23 +202,7 @@ def test_refined_hit_lies_between_the_samples_and_reaches_iso():
 
 
 def test_iso_kernels_use_no_scratch(tmp_path):
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
-        pytest.skip("no hipcc")
-    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    assert re.search(r"^SRCS\s*:=.*\biso\.hip\b", text, flags=re.M)
-    m = re.search(r"^FLAGS\s*:=\s*(.*)$", text, flags=re.M)
-    flags = [f.replace("$(ARCH)", "gfx950") for f in m.group(1).split() if not f.startswith("$(")]
-    out = str(tmp_path / "iso.s")
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc"] + flags + ["--offload-arch=gfx950", "-S", "--cuda-device-only", os.path.join(CSRC, "iso.hip"), "-o", out]
-    subprocess.run(cmd, check=True, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    kernels, name = {}, None
-    for line in open(out):
-        mm = re.match(r"^(_Z\w+):", line)
-        if mm:
-            name = mm.group(1)
-        mm = re.match(r";\s*ScratchSize:\s*(\d+)", line)
-        if mm and name:
-            kernels[name] = int(mm.group(1))
+    kernels = {k: v["ScratchSize"] for k, v in T.kernel_listing("iso.hip", tmp_path / "iso.s").items()}
     iso = {k: v for k, v in kernels.items() if "k_iso" in k}
     assert len(iso) == 4, kernels
     assert all(v == 0 for v in iso.values()), kernels

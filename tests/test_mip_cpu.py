@@ -8,18 +8,16 @@ renderers (tests/test_max_map_skip_cpu.py, tests/test_gpu_max_map_sweep.py)."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import helpers as T
 from vkvolume_amd import abi, lib
 from vkvolume_amd.abi import MipOptions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vkvolume_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 F = np.float32
 INV255 = F(1.0) / F(255.0)
 
@@ -470,22 +468,7 @@ def test_mip_np_on_analytic_volumes():
 
 
 def test_mip_kernels_use_no_scratch(tmp_path):
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
-        pytest.skip("no hipcc")
-    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    m = re.search(r"^FLAGS\s*:=\s*(.*)$", text, flags=re.M)
-    flags = [f.replace("$(ARCH)", "gfx950") for f in m.group(1).split() if not f.startswith("$(")]
-    out = str(tmp_path / "mip.s")
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc"] + flags + ["--offload-arch=gfx950", "-S", "--cuda-device-only", os.path.join(CSRC, "mip.hip"), "-o", out]
-    subprocess.run(cmd, check=True, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    kernels, name = {}, None
-    for line in open(out):
-        mm = re.match(r"^(_Z\w+):", line)
-        if mm:
-            name = mm.group(1)
-        mm = re.match(r";\s*ScratchSize:\s*(\d+)", line)
-        if mm and name:
-            kernels[name] = int(mm.group(1))
+    kernels = {k: v["ScratchSize"] for k, v in T.kernel_listing("mip.hip", tmp_path / "mip.s").items()}
     mip = {k: v for k, v in kernels.items() if "k_mip" in k}
     assert len(mip) == 4, kernels
     assert any("k_max_map" in k for k in kernels), kernels

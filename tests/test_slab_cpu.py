@@ -7,18 +7,16 @@ slab_np and slab_skip_np are the references tests/test_gpu_slab.py compares the 
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import helpers as T
 from tests.test_mip_cpu import INV255, KMAX_SAMPLE, _fma, max_map_np, max_map_skip_np, sample_linear_np
 from vkvolume_amd import abi, camera, lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vkvolume_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 F = np.float32
 MODES = (abi.SLAB_MAX, abi.SLAB_MIN, abi.SLAB_MEAN)
 
@@ -414,24 +412,7 @@ def test_slab_plane_frames():
 
 
 def test_slab_kernels_use_no_scratch(tmp_path):
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
-        pytest.skip("no hipcc")
-    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    srcs = re.search(r"^SRCS\s*:=\s*(.*)$", text, flags=re.M).group(1).split()
-    assert "slab.hip" in srcs
-    m = re.search(r"^FLAGS\s*:=\s*(.*)$", text, flags=re.M)
-    flags = [f.replace("$(ARCH)", "gfx950") for f in m.group(1).split() if not f.startswith("$(")]
-    out = str(tmp_path / "slab.s")
-    cmd = [HIPCC if os.path.exists(HIPCC) else "hipcc"] + flags + ["--offload-arch=gfx950", "-S", "--cuda-device-only", os.path.join(CSRC, "slab.hip"), "-o", out]
-    subprocess.run(cmd, check=True, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    kernels, name = {}, None
-    for line in open(out):
-        mm = re.match(r"^(_Z\w+):", line)
-        if mm:
-            name = mm.group(1)
-        mm = re.match(r";\s*ScratchSize:\s*(\d+)", line)
-        if mm and name:
-            kernels[name] = int(mm.group(1))
+    kernels = {k: v["ScratchSize"] for k, v in T.kernel_listing("slab.hip", tmp_path / "slab.s").items()}
     slab = {k: v for k, v in kernels.items() if "k_slab" in k}
     # the launcher selects: two layouts x (MAX dense, MAX skipping, MIN, MEAN)
     assert len(slab) == 8 and len(kernels) == 8, kernels

@@ -297,11 +297,6 @@ int check_launch(vkv_ctx *ctx, const char *what)
 	return VKV_OK;
 }
 
-static bool extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
-
-// ceil(volume / map) must reproduce a valid block size (src/compute_distance_map.cpp:110-113)
-static bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
-
 int check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box)
 {
 	if (!box)
@@ -815,9 +810,9 @@ int vkv_build_uniforms(const float *view, const float *proj, const float *node_t
 	rc->plane_tex[0] = plane_tex.x, rc->plane_tex[1] = plane_tex.y, rc->plane_tex[2] = plane_tex.z, rc->plane_tex[3] = plane_tex.w;
 	rc->camera_pos_tex[0] = cam_pos_tex.x, rc->camera_pos_tex[1] = cam_pos_tex.y, rc->camera_pos_tex[2] = cam_pos_tex.z, rc->camera_pos_tex[3] = cam_pos_tex.w;
 	rc->front_index   = (plane_tex.x < 0 ? 1 : 0) + (plane_tex.y < 0 ? 2 : 0) + (plane_tex.z < 0 ? 4 : 0);
-	rc->block_size[0] = (float) ((ve.width + me.width - 1) / me.width);
-	rc->block_size[1] = (float) ((ve.height + me.height - 1) / me.height);
-	rc->block_size[2] = (float) ((ve.depth + me.depth - 1) / me.depth);
+	rc->block_size[0] = (float) block_of(ve.width, me.width);
+	rc->block_size[1] = (float) block_of(ve.height, me.height);
+	rc->block_size[2] = (float) block_of(ve.depth, me.depth);
 	rc->block_size[3] = 0.0f;
 
 	// Ray generator (replaces the rasteriser): in double precision from the same float matrices.  Unproject pixel-space
@@ -1281,25 +1276,9 @@ static int check_render_params(vkv_ctx *ctx, const VkvRenderParams *P)
 			if (!P->d_distance_maps[i])
 				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: distance map %d is null", i);
 	}
-	const VkvTileSchedule &t = P->tiles;
-	if (t.tile_width == 0 || t.tile_height == 0 || (t.tile_width % 16) || (t.tile_height % 16) || t.tile_stride == 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: tile size must be a positive multiple of 16 and tile_stride > 0");
-	{
-		const uint64_t tiles_x = (P->image_width + t.tile_width - 1) / t.tile_width, tiles_y = (P->image_height + t.tile_height - 1) / t.tile_height;
-		const bool     whole   = t.rect.w == 0 || t.rect.h == 0;
-		if (!whole && ((uint64_t) t.rect.x0 + t.rect.w > tiles_x || (uint64_t) t.rect.y0 + t.rect.h > tiles_y))
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: the schedule's tile rectangle runs past the image");
-		if (t.fill_outside && !whole && (t.compact || t.tile_first != 0 || t.tile_stride != 1 || (uint64_t) t.tile_count != (uint64_t) t.rect.w * t.rect.h))
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: fill_outside needs image-indexed outputs and the whole rectangle in one launch (tile_first 0, tile_stride 1)");
-		const uint64_t scheduled = whole ? tiles_x * tiles_y : (uint64_t) t.rect.w * t.rect.h;
-		if (t.tile_count && (uint64_t) t.tile_first + (uint64_t) (t.tile_count - 1) * t.tile_stride >= scheduled)
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: tile schedule runs past the %s", whole ? "image" : "tile rectangle");
-	}
-	if (P->d_packed_volume && ((uintptr_t) P->d_packed_volume & 255u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: d_packed_volume must be 256-byte aligned");
-	if (!P->d_out_color && !P->d_out_rgba8 && !P->d_out_counts && !P->d_out_depth)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: no output buffer");
-	return VKV_OK;
+	if (const int rc = check_tile_schedule(ctx, "render", P))
+		return rc;
+	return check_render_buffers(ctx, "render", P, false);
 }
 
 // opacity-correction table keyed by the TF alpha byte (frag:283):

@@ -283,7 +283,7 @@ namespace vkv
 bool cells_launch_ok(VkvExtent3D e, VkvExtent3D me)
 {
 	const uint64_t n_cells = (uint64_t) me.width * me.height * me.depth;
-	const uint64_t bx = (e.width + me.width - 1) / me.width, by = (e.height + me.height - 1) / me.height, bz = (e.depth + me.depth - 1) / me.depth;
+	const uint64_t bx = block_of(e.width, me.width), by = block_of(e.height, me.height), bz = block_of(e.depth, me.depth);
 	return me.height <= 65535u && me.depth <= 65535u && (n_cells + kCellsPerGroup - 1) / kCellsPerGroup <= 0x7fffffffull &&
 	       (bx + 3) / 4 * by * bz * kCellsPerGroup <= 0xffffffffull;        // (the classify kernel's 32-bit evaluation units)
 }
@@ -295,7 +295,7 @@ int launch_cell_summary(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gra
 	SummaryArgs a;
 	a.vol = d_vol, a.grad = d_grad, a.out = reinterpret_cast<uint4 *>(d_summary);
 	a.W = (int) e.width, a.H = (int) e.height, a.D = (int) e.depth, a.mw = (int) me.width, a.mh = (int) me.height;
-	a.bx = (int) ((e.width + me.width - 1) / me.width), a.by = (int) ((e.height + me.height - 1) / me.height), a.bz = (int) ((e.depth + me.depth - 1) / me.depth);
+	a.bx = (int) block_of(e.width, me.width), a.by = (int) block_of(e.height, me.height), a.bz = (int) block_of(e.depth, me.depth);
 	int ncz;
 	if (b)
 	{
@@ -333,7 +333,7 @@ int launch_occupancy_from_summary(vkv_ctx *ctx, const void *d_summary, const uin
 	a.summary = reinterpret_cast<const uint4 *>(d_summary), a.vol = d_vol, a.grad = d_grad, a.bits = d_bits, a.ranges = d_ranges, a.map = d_map;
 	a.unresolved = unresolved, a.n_cells = (uint64_t) me.width * me.height * me.depth;
 	a.W = (int) e.width, a.H = (int) e.height, a.D = (int) e.depth, a.mw = (int) me.width, a.mh = (int) me.height;
-	a.bx = (int) ((e.width + me.width - 1) / me.width), a.by = (int) ((e.height + me.height - 1) / me.height), a.bz = (int) ((e.depth + me.depth - 1) / me.depth);
+	a.bx = (int) block_of(e.width, me.width), a.by = (int) block_of(e.height, me.height), a.bz = (int) block_of(e.depth, me.depth);
 	a.use_gradient = use_gradient ? 1 : 0;
 	a.nd = (a.bx + 3) / 4, a.upc = a.nd * a.by * a.bz;
 	const uint64_t groups = (a.n_cells + kCellsPerGroup - 1) / kCellsPerGroup;

@@ -1,14 +1,67 @@
-// max_map_skip.hpp — the sample path of the maximum-intensity projection (k_mip) that the isosurface (k_iso, §5.10) and the slab (k_slab, §5.11) share:
-// the filtered intensity of one sample or of a group of samples, the grown-cell test, the exact skip step over the per-cell max map
-// (vkv_max_map) as a helper, and the host-side checks and arguments of both entry points.  k_mip keeps its own inline copy of the skip step:
-// calling max_map_skip cost its skipping variant 1-2 % (§5.10).  Included after raymarch_core.hpp.
+// direct_render.hpp — what the direct renderers share: the maximum-intensity projection (k_mip), the isosurface (k_iso, §5.10) and
+// the slab (k_slab, §5.11).  Device side: the deal of a launch's workgroups and lanes to pixels, the filtered intensity of one sample or of a
+// group of samples, the max map's geometry, the grown-cell test and the exact skip step over the per-cell max map (vkv_max_map), the first-hit
+// depth and the stores every kernel ends with.  Host side: the checks and the arguments of the three entry points.  k_mip keeps its own inline
+// copy of the skip step: calling max_map_skip cost its skipping variant 1-2 % (§5.10).
 #pragma once
 
 #include <cmath>
 
+#include "launchers.hpp"
+#include "render_args.hpp"
+
 // everything here is internal to the translation unit that includes it (no exported symbols)
 namespace
 {
+
+// The deal of workgroups and lanes to pixels, the integrator's (lean_block): XCD x = id & 7 takes the schedule's tiles x, x + 8, ..., whose blocks
+// are neighbouring ids on that XCD (L2 locality); a schedule that holds every tile of its rectangle starts them ring by ring from the middle
+// (start_entry), so the long rays through the volume start first.  A workgroup is a 16x16 block of a tile, a wave the (1 << pw) pixels wide
+// 64-pixel patch of it (pw = 2, 3, 4: 4x16, 8x8, 16x4).  false: this lane has no pixel; else pixel (px, py) and its output index o (compact:
+// inside the launch's own tile buffer).  k_iso holds a written-out copy (iso.hip says why): keep the two in step.
+__device__ __forceinline__ bool pixel_deal(const RayMarchArgs &A, uint32_t pw, uint32_t &px, uint32_t &py, uint32_t &o)
+{
+	const uint32_t x = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
+	if (rank >= A.tile_count)
+		return false;
+	const uint32_t k_tile = A.order_h ? start_entry(A, rank) : rank;
+	if (k_tile >= A.tile_count)
+		return false;
+	const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+	const uint32_t bx = (w & ((16u >> pw) - 1u)) << pw, by = (w >> (4u - pw)) * (64u >> pw);
+	const uint32_t t  = A.tile_first + k_tile * A.tile_stride;
+	const uint32_t lx = (sb % A.blocks_per_tile_x) * 16u + bx + (lane & ((1u << pw) - 1u)), ly = (sb / A.blocks_per_tile_x) * 16u + by + (lane >> pw);
+	px = A.org_x + (t % A.tiles_x) * A.tile_w + lx, py = A.org_y + (t / A.tiles_x) * A.tile_h + ly;
+	o  = A.compact ? (k_tile * A.tile_h + ly) * A.tile_w + lx : py * A.img_w + px;
+	return px < A.img_w && py < A.img_h;
+}
+
+// workgroups of a launch that pixel_deal serves: the schedule's tile count rounded up to a multiple of 8 (host)
+uint32_t deal_grid(const RayMarchArgs &a) { return (a.tile_count + 7u) / 8u * 8u * a.blocks_per_tile; }
+
+// the integrator's first_hit depth (ray_finish, frag:315-321) of the texture-space point (x, y, z): proj view model (p - 0.5, 1), z / w
+__device__ __forceinline__ float first_hit_depth(const RayMarchArgs &A, float x, float y, float z)
+{
+	const float p[4] = {x - 0.5f, y - 0.5f, z - 0.5f, 1.0f};
+	float       a4[4], b4[4], c4[4];
+	mat4_mul_vec4(A.model, p, a4);
+	mat4_mul_vec4(A.view, a4, b4);
+	mat4_mul_vec4(A.proj, b4, c4);
+	return c4[2] / c4[3];
+}
+
+// pixel o of an RGBA8 target (one non-temporal dword), and of the three counters of d_out_counts
+__device__ __forceinline__ void store_rgba8_nt(uint8_t *base, size_t o, float r, float g, float b, float a)
+{
+	__builtin_nontemporal_store((uint32_t) quantise_rgba8(r) | ((uint32_t) quantise_rgba8(g) << 8) | ((uint32_t) quantise_rgba8(b) << 16) |
+	                                ((uint32_t) quantise_rgba8(a) << 24),
+	                            reinterpret_cast<uint32_t *>(base) + o);
+}
+__device__ __forceinline__ void store_counts(uint32_t *base, size_t o, uint32_t n_filt, uint32_t n_probe, uint32_t n_skip)
+{
+	base[o * 3 + 0] = n_filt, base[o * 3 + 1] = n_probe, base[o * 3 + 2] = n_skip;
+}
 
 template <bool PACKED>
 __device__ __forceinline__ float mip_sample(const RayMarchArgs &A, float posx, float posy, float posz)
@@ -67,14 +120,22 @@ constexpr float kMaxSample = 255.0f * kInv255;
 // cell [lo, lo + b) grown by one voxel
 __device__ __forceinline__ bool in_grown(float c, int lo, int b) { return c >= (float) (lo - 1) && c < (float) (lo + b); }
 
+// the max map and its geometry in a kernel's arguments (fill_max_map_geometry); block 1 and cell 0 without a map
+struct MaxMapGeometry
+{
+	const uint8_t *max_map;         // skipping variants only
+	int            bx, by, bz;      // voxels per map cell per axis
+	int            lcx, lcy, lcz;   // last map cell per axis that holds a voxel: (extent - 1) / block
+	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
+};
+
 // One probe of the skip step at sample i of n (position pos*).  When sample i enters a map cell other than `last_cell`, the cell's byte B is
 // read (++n_probe); when B * kInv255 cannot reach `bound` (STRICT: B * kInv255 < bound; else B * kInv255 <= bound) and the sample lies in the
 // grown cell, the result is the last index i + kk (kk >= 0, never past sample n - 1) of the samples i .. i + kk that lie in the grown cell,
-// and last_cell is reset.  -1: filter sample i.  MM holds the max map and its geometry: max_map; bx, by, bz (voxels per cell); lcx, lcy, lcz
-// (last cell per axis that holds a voxel); rbx, rby, rbz (1 / block: finding the cell only, the skip itself is checked exactly).
-template <bool STRICT, typename MM>
-__device__ __forceinline__ int max_map_skip(const RayMarchArgs &A, const MM &M, const Ray &R, int i, int n, float posx, float posy, float posz, float bound,
-                                            uint32_t &last_cell, uint32_t &n_probe)
+// and last_cell is reset.  -1: filter sample i.
+template <bool STRICT>
+__device__ __forceinline__ int max_map_skip(const RayMarchArgs &A, const MaxMapGeometry &M, const Ray &R, int i, int n, float posx, float posy, float posz,
+                                            float bound, uint32_t &last_cell, uint32_t &n_probe)
 {
 	const float fW = (float) A.W, fH = (float) A.H, fD = (float) A.D;
 	// the sampler's own voxel coordinates of this sample (sample_linear / packed_footprint)
@@ -114,10 +175,6 @@ __device__ __forceinline__ int max_map_skip(const RayMarchArgs &A, const MM &M, 
 
 // ---- host side: the checks and arguments vkv_render_mip, vkv_render_isosurface and vkv_render_slab share --------------------------------------------------
 
-bool     extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
-bool     map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
-uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
-
 // the checks of the fields of P a MIP / isosurface call reads (`what`: the entry point's name in the messages), with the max map d_max_map
 // (or null) and `has_output`: an output of the call's own options is set; VKV_OK or the code (nothing is enqueued before they pass).
 // rays = false (vkv_render_slab): the call casts no rays, so it has no depth (options.depth_attachment and d_out_depth are unsupported) and
@@ -147,76 +204,34 @@ int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams
 		if ((uint64_t) P->map_extent.width * P->map_extent.height * P->map_extent.depth > 0xffffffffull)
 			return set_error(ctx, VKV_E_UNSUPPORTED, "%s: max maps with more than 2^32 cells are not supported", what);
 	}
+	if (const int rc = check_tile_schedule(ctx, what, P))
+		return rc;
+	if (const int rc = check_render_buffers(ctx, what, P, has_output))
+		return rc;
 	const VkvTileSchedule &t = P->tiles;
-	if (t.tile_width == 0 || t.tile_height == 0 || (t.tile_width % 16) || (t.tile_height % 16) || t.tile_stride == 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: tile size must be a positive multiple of 16 and tile_stride > 0", what);
-	const uint64_t tiles_x = (P->image_width + t.tile_width - 1) / t.tile_width, tiles_y = (P->image_height + t.tile_height - 1) / t.tile_height;
-	const bool     whole   = t.rect.w == 0 || t.rect.h == 0;
-	if (!whole && ((uint64_t) t.rect.x0 + t.rect.w > tiles_x || (uint64_t) t.rect.y0 + t.rect.h > tiles_y))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: the schedule's tile rectangle runs past the image", what);
-	const uint64_t scheduled = whole ? tiles_x * tiles_y : (uint64_t) t.rect.w * t.rect.h;
-	if (t.tile_count && (uint64_t) t.tile_first + (uint64_t) (t.tile_count - 1) * t.tile_stride >= scheduled)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: tile schedule runs past the %s", what, whole ? "image" : "tile rectangle");
-	if (P->d_packed_volume && ((uintptr_t) P->d_packed_volume & 255u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_packed_volume must be 256-byte aligned", what);
-	if (!P->d_out_color && !P->d_out_rgba8 && !P->d_out_counts && !P->d_out_depth && !has_output)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: no output buffer", what);
 	const uint64_t nb = (uint64_t) (t.tile_width / 16) * (t.tile_height / 16) * t.tile_count;
 	if (nb > 0x3fffffffull || (uint64_t) P->image_width * P->image_height > 0xffffffffull / 4 || nb * 256 > 0xffffffffull / 4)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: frame too large for one launch", what);
 	return VKV_OK;
 }
 
-// VkvRenderParams -> the fields of RayMarchArgs the MIP and isosurface kernels read (the rest stays zero)
-void fill_mip_args(const VkvRenderParams *P, RayMarchArgs &a)
+// VkvRenderParams -> the fields of RayMarchArgs the direct renderers' kernels read (the rest stays zero)
+void fill_direct_args(const VkvRenderParams *P, RayMarchArgs &a)
 {
-	a = RayMarchArgs{};
-	for (int i = 0; i < 3; ++i)
-		a.dir00[i] = P->ray_gen.dir00[i], a.ddx[i] = P->ray_gen.ddx[i], a.ddy[i] = P->ray_gen.ddy[i], a.cam[i] = P->ray_cast.camera_pos_tex[i];
-	for (int i = 0; i < 4; ++i)
-		a.plane_tex[i] = P->ray_cast.plane_tex[i];
-	for (int i = 0; i < 16; ++i)
-		a.model[i] = P->camera.model[i], a.view[i] = P->camera.camera_view[i], a.proj[i] = P->camera.camera_proj[i],
-		a.view_proj_inv[i] = P->camera.camera_view_proj_inv[i], a.model_inv[i] = P->camera.model_inv[i];
-	a.sampling_factor = P->transfer_function.sampling_factor;
-	a.W = (int) P->volume_extent.width, a.H = (int) P->volume_extent.height, a.D = (int) P->volume_extent.depth;
-	a.mw = (int) P->map_extent.width, a.mh = (int) P->map_extent.height, a.md = (int) P->map_extent.depth;
-	a.vol    = P->d_volume;
-	a.packed = static_cast<const uint8_t *>(P->d_packed_volume);
-	{
-		const PackedDims pd = packed_dims(a.W, a.H, a.D);
-		a.pmx = pd.mx, a.pmy = pd.my;
-	}
-	a.out_color = P->d_out_color, a.out_rgba8 = P->d_out_rgba8, a.out_counts = P->d_out_counts, a.out_depth = P->d_out_depth;
-	a.in_depth         = P->options.depth_attachment ? P->d_in_depth : nullptr;
-	a.depth_attachment = P->options.depth_attachment != 0;
-	a.img_w = P->image_width, a.img_h = P->image_height;
-	a.tile_w = P->tiles.tile_width, a.tile_h = P->tiles.tile_height;
-	a.tile_first = P->tiles.tile_first, a.tile_stride = P->tiles.tile_stride, a.tile_count = P->tiles.tile_count, a.compact = P->tiles.compact;
-	const VkvTileRect &r     = P->tiles.rect;
-	const bool         whole = r.w == 0 || r.h == 0;
-	a.tiles_x                = whole ? (a.img_w + a.tile_w - 1) / a.tile_w : r.w;
-	a.org_x = whole ? 0u : r.x0 * a.tile_w, a.org_y = whole ? 0u : r.y0 * a.tile_h;
-	a.blocks_per_tile_x = a.tile_w / 16;
-	a.blocks_per_tile   = a.blocks_per_tile_x * (a.tile_h / 16);
-	a.nblocks           = a.blocks_per_tile * a.tile_count;
-	a.test              = VKV_TEST_NONE;
-	{        // shape of a wave's pixel patch, as the integrator picks it: voxels per pixel step in x against y
-		double vx = 0.0, vy = 0.0;
-		const double dim[3] = {(double) a.W, (double) a.H, (double) a.D};
-		for (int k = 0; k < 3; ++k)
-			vx += (double) a.ddx[k] * dim[k] * (double) a.ddx[k] * dim[k], vy += (double) a.ddy[k] * dim[k] * (double) a.ddy[k] * dim[k];
-		const double q = (vx > 0.0 && vy > 0.0) ? std::sqrt(vx / vy) : 1.0;
-		a.wave_pw_log2 = q >= 1.6 ? 2u : (q <= 1.0 / 1.6 ? 4u : 3u);        // 4x16, 16x4 or 8x8 pixels
-	}
-	// a schedule over every tile of its rectangle (the whole image or VkvTileSchedule.rect) starts in the integrator's ring order
-	const uint32_t rows = whole ? (a.img_h + a.tile_h - 1) / a.tile_h : r.h;
+	a                = RayMarchArgs{};
+	const bool whole = fill_shared_args(P, a);
+	a.in_depth       = P->options.depth_attachment ? P->d_in_depth : nullptr;        // null unless the attachment is on (the integrator passes it as it comes)
+	a.nblocks        = a.blocks_per_tile * a.tile_count;        // (within the limits of check_first_hit_params, whose message a too large frame gets)
+	a.test           = VKV_TEST_NONE;
+	a.wave_pw_log2   = wave_patch_log2(a.ddx, a.ddy, a.W, a.H, a.D);        // the integrator's shape, without its VkvTuning.wave_shape override
+	// a schedule over every tile of its rectangle starts in the integrator's ring order, computed (start_entry) for the whole image too: the
+	// integrator reads its cached table there
+	const uint32_t rows = whole ? (a.img_h + a.tile_h - 1) / a.tile_h : P->tiles.rect.h;
 	a.order_h           = (a.tile_first == 0 && a.tile_stride == 1 && (uint64_t) a.tile_count == (uint64_t) a.tiles_x * rows) ? rows : 0u;
 }
 
-// the max-map fields of a kernel's arguments (MipArgs, IsoArgs: what max_map_skip reads); block 1 and cell 0 without a map
-template <typename MM>
-void fill_max_map_geometry(const VkvRenderParams *P, const uint8_t *d_max_map, MM &m)
+// the max map d_max_map (or null) of a call as its kernel reads it
+void fill_max_map_geometry(const VkvRenderParams *P, const uint8_t *d_max_map, MaxMapGeometry &m)
 {
 	m.max_map = d_max_map;
 	m.bx = m.by = m.bz = 1, m.lcx = m.lcy = m.lcz = 0, m.rbx = m.rby = m.rbz = 1.0f;

@@ -10,23 +10,20 @@
 #include <cmath>
 
 #include "raymarch_core.hpp"
-#include "max_map_skip.hpp"
+#include "direct_render.hpp"
 
 namespace
 {
 
 struct IsoArgs
 {
-	RayMarchArgs   A;               // the fields ray_setup, start_entry and the samplers read (fill_mip_args)
+	RayMarchArgs   A;               // the fields ray_setup, start_entry and the samplers read (fill_direct_args)
 	float          iso;
 	int            refine_steps;    // 0 .. 16
 	float          base[3], ambient, diffuse, specular;
 	uint32_t       shininess;       // 1 .. 1024
 	float *        out_normal;      // or null
-	const uint8_t *max_map;         // skipping variant only
-	int            bx, by, bz;      // voxels per map cell per axis
-	int            lcx, lcy, lcz;   // last map cell per axis that holds a voxel: (extent - 1) / block
-	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
+	MaxMapGeometry mm;              // skipping variant only
 };
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz)
@@ -38,8 +35,8 @@ template <bool PACKED, bool SKIP>
 __global__ void __launch_bounds__(256) k_iso(const IsoArgs I)
 {
 	const RayMarchArgs &A = I.A;
-	// the integrator's deal of workgroups, as k_mip: XCD x = id & 7 takes the schedule's tiles x, x + 8, ...; a schedule that holds every tile of
-	// its rectangle starts them ring by ring from the middle (start_entry)
+	// pixel_deal (direct_render.hpp), written out: keep the two in step.  Calling it cost the skipping variant 0.4-0.95 % on C4
+	// (profiles/r9_direct_renderer_refactor.txt), the precedent being k_mip's skip step
 	const uint32_t x = blockIdx.x & 7u, idx = blockIdx.x >> 3;
 	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
 	if (rank >= A.tile_count)
@@ -104,7 +101,7 @@ __global__ void __launch_bounds__(256) k_iso(const IsoArgs I)
 			const float fi   = (float) i;
 			const float posx = __builtin_fmaf(fi, R.sx, R.ex), posy = __builtin_fmaf(fi, R.sy, R.ey), posz = __builtin_fmaf(fi, R.sz, R.ez);
 			// a cell whose byte cannot reach iso: jump over its samples
-			const int last = max_map_skip<true>(A, I, R, i, n, posx, posy, posz, iso, last_cell, n_probe);
+			const int last = max_map_skip<true>(A, I.mm, R, i, n, posx, posy, posz, iso, last_cell, n_probe);
 			if (last >= 0)
 			{
 				n_skip += (uint32_t) (last + 1 - i);
@@ -142,14 +139,7 @@ __global__ void __launch_bounds__(256) k_iso(const IsoArgs I)
 		}
 		const float hx = __builtin_fmaf(th, R.sx, R.ex), hy = __builtin_fmaf(th, R.sy, R.ey), hz = __builtin_fmaf(th, R.sz, R.ez);
 		if (A.out_depth)
-		{        // the integrator's first_hit depth (ray_finish), at the hit point
-			const float p[4] = {hx - 0.5f, hy - 0.5f, hz - 0.5f, 1.0f};
-			float       a4[4], b4[4], c4[4];
-			mat4_mul_vec4(A.model, p, a4);
-			mat4_mul_vec4(A.view, a4, b4);
-			mat4_mul_vec4(A.proj, b4, c4);
-			depth = c4[2] / c4[3];
-		}
+			depth = first_hit_depth(A, hx, hy, hz);
 		// gradient: the integrator's tetrahedron taps (raymarch_core.hpp, GRAD == 2), in texture space
 		const float dix = 1.0f / (float) A.W, diy = 1.0f / (float) A.H, diz = 1.0f / (float) A.D;
 		const float t1  = mip_sample<PACKED>(A, hx + dix, hy - diy, hz - diz);
@@ -194,13 +184,11 @@ __global__ void __launch_bounds__(256) k_iso(const IsoArgs I)
 	if (A.out_color)
 		store_float4_nt(A.out_color, po, cr, cg, cb, ca);
 	if (A.out_rgba8)
-		__builtin_nontemporal_store((uint32_t) quantise_rgba8(cr) | ((uint32_t) quantise_rgba8(cg) << 8) | ((uint32_t) quantise_rgba8(cb) << 16) |
-		                                ((uint32_t) quantise_rgba8(ca) << 24),
-		                            reinterpret_cast<uint32_t *>(A.out_rgba8) + po);
+		store_rgba8_nt(A.out_rgba8, po, cr, cg, cb, ca);
 	if (I.out_normal)
 		store_float4_nt(I.out_normal, po, nx, ny, nz, nw);
 	if (A.out_counts)
-		A.out_counts[po * 3 + 0] = n_filt, A.out_counts[po * 3 + 1] = n_probe, A.out_counts[po * 3 + 2] = n_skip;
+		store_counts(A.out_counts, po, n_filt, n_probe, n_skip);
 	if (A.out_depth)
 		__builtin_nontemporal_store(depth, A.out_depth + po);
 }
@@ -226,6 +214,15 @@ int check_iso(vkv_ctx *ctx, const VkvRenderParams *P, const VkvIsoOptions *I)
 	return check_first_hit_params(ctx, "render_isosurface", P, I->d_max_map, I->d_out_normal != nullptr);
 }
 
+template <bool PACKED>
+void launch_iso(const IsoArgs &a, hipStream_t s)
+{
+	if (a.mm.max_map)
+		hipLaunchKernelGGL((k_iso<PACKED, true>), dim3(deal_grid(a.A)), dim3(256), 0, s, a);
+	else
+		hipLaunchKernelGGL((k_iso<PACKED, false>), dim3(deal_grid(a.A)), dim3(256), 0, s, a);
+}
+
 }        // namespace
 
 extern "C" {
@@ -239,24 +236,17 @@ int vkv_render_isosurface(vkv_ctx *ctx, const VkvRenderParams *P, const VkvIsoOp
 	if (rc != VKV_OK)
 		return rc;
 	IsoArgs a;
-	fill_mip_args(P, a.A);
+	fill_direct_args(P, a.A);
 	if (a.A.nblocks == 0)
 		return VKV_OK;
 	a.iso = I->iso, a.refine_steps = (int) I->refine_steps, a.shininess = I->shininess, a.out_normal = I->d_out_normal;
 	a.base[0] = I->base_color[0], a.base[1] = I->base_color[1], a.base[2] = I->base_color[2];
 	a.ambient = I->ambient, a.diffuse = I->diffuse, a.specular = I->specular;
-	fill_max_map_geometry(P, I->d_max_map, a);
-	const hipStream_t s      = (hipStream_t) stream;
-	const dim3        grid((a.A.tile_count + 7u) / 8u * 8u * a.A.blocks_per_tile), block(256);
-	const bool        packed = a.A.packed != nullptr;
-	if (I->d_max_map && packed)
-		hipLaunchKernelGGL((k_iso<true, true>), grid, block, 0, s, a);
-	else if (I->d_max_map)
-		hipLaunchKernelGGL((k_iso<false, true>), grid, block, 0, s, a);
-	else if (packed)
-		hipLaunchKernelGGL((k_iso<true, false>), grid, block, 0, s, a);
+	fill_max_map_geometry(P, I->d_max_map, a.mm);
+	if (a.A.packed)
+		launch_iso<true>(a, (hipStream_t) stream);
 	else
-		hipLaunchKernelGGL((k_iso<false, false>), grid, block, 0, s, a);
+		launch_iso<false>(a, (hipStream_t) stream);
 	return check_launch(ctx, "render_isosurface");
 }
 

@@ -13,7 +13,7 @@
 #include <cmath>
 
 #include "raymarch_core.hpp"
-#include "max_map_skip.hpp"
+#include "direct_render.hpp"
 #include "row_loads.hpp"
 
 namespace
@@ -60,40 +60,23 @@ __global__ void __launch_bounds__(256) k_max_map(const MaxMapArgs a)
 
 struct MipArgs
 {
-	RayMarchArgs   A;               // the fields ray_setup, start_entry and the samplers read (fill_mip_args)
+	RayMarchArgs   A;               // the fields ray_setup, start_entry and the samplers read (fill_direct_args)
 	float          threshold, window_max;
-	const uint8_t *max_map;         // skipping variant only
 	float *        out_intensity;   // or null
-	int            bx, by, bz;      // voxels per map cell per axis
-	int            lcx, lcy, lcz;   // last map cell per axis that holds a voxel: (extent - 1) / block
-	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
+	MaxMapGeometry mm;              // skipping variant only
 };
 
-// (kMaxSample, mip_sample, mip_samples and in_grown are in max_map_skip.hpp, shared with k_iso.  The skip step below is written out here rather than
-// calling max_map_skip: the shared helper's control flow cost the skipping variant 1-2 %)
+// (the deal, the samplers, in_grown, the depth and the stores are in direct_render.hpp, shared with k_iso and k_slab.  The skip step below is written
+// out here rather than calling max_map_skip: the shared helper's control flow cost the skipping variant 1-2 %)
 
 template <bool PACKED, bool SKIP>
 __global__ void __launch_bounds__(256) k_mip(const MipArgs M)
 {
 	const RayMarchArgs &A = M.A;
-	// the integrator's deal of workgroups (lean_block): XCD x = id & 7 takes the schedule's tiles x, x + 8, ..., whose blocks are neighbouring
-	// ids on that XCD (L2 locality); a schedule that holds every tile of its rectangle starts them ring by ring from the middle (start_entry),
-	// so the long rays through the volume start first
-	const uint32_t x = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
-	if (rank >= A.tile_count)
-		return;
-	const uint32_t k_tile = A.order_h ? start_entry(A, rank) : rank;
-	if (k_tile >= A.tile_count)
-		return;
-	// the wave's 64 pixels: a (1 << wave_pw_log2)-wide patch of the 16x16 block, the shape the integrator picks for the view (fill_render_args)
-	const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u, pw = A.wave_pw_log2;
-	const uint32_t bx = (w & ((16u >> pw) - 1u)) << pw, by = (w >> (4u - pw)) * (64u >> pw);
-	const uint32_t t  = A.tile_first + k_tile * A.tile_stride;
-	const uint32_t lx = (sb % A.blocks_per_tile_x) * 16u + bx + (lane & ((1u << pw) - 1u)), ly = (sb / A.blocks_per_tile_x) * 16u + by + (lane >> pw);
-	const uint32_t px = A.org_x + (t % A.tiles_x) * A.tile_w + lx, py = A.org_y + (t / A.tiles_x) * A.tile_h + ly;
-	const uint32_t o  = A.compact ? (k_tile * A.tile_h + ly) * A.tile_w + lx : py * A.img_w + px;
-	if (px >= A.img_w || py >= A.img_h)
+	const MaxMapGeometry &G = M.mm;
+	// a wave's patch: the shape the integrator picks for the view (wave_patch_log2)
+	uint32_t px, py, o;
+	if (!pixel_deal(A, A.wave_pw_log2, px, py, o))
 		return;
 	Ray R;
 	R.o                = o;
@@ -127,7 +110,7 @@ __global__ void __launch_bounds__(256) k_mip(const MipArgs M)
 	}
 	if (SKIP && marched)
 	{
-		// the skip step of max_map_skip<false> (max_map_skip.hpp), written out: keep the two in step
+		// the skip step of max_map_skip<false> (direct_render.hpp), written out: keep the two in step
 		const int   n  = R.n_steps;
 		const float fW = (float) A.W, fH = (float) A.H, fD = (float) A.D;
 		uint32_t    last_cell = ~0u;
@@ -140,24 +123,24 @@ __global__ void __launch_bounds__(256) k_mip(const MipArgs M)
 			{
 				// the sampler's own voxel coordinates of this sample (sample_linear / packed_footprint)
 				const float cx = __builtin_fmaf(posx, fW, -0.5f), cy = __builtin_fmaf(posy, fH, -0.5f), cz = __builtin_fmaf(posz, fD, -0.5f);
-				const int   mx = i_clamp((int) __builtin_floorf((cx + 0.5f) * M.rbx), 0, M.lcx);
-				const int   my = i_clamp((int) __builtin_floorf((cy + 0.5f) * M.rby), 0, M.lcy);
-				const int   mz = i_clamp((int) __builtin_floorf((cz + 0.5f) * M.rbz), 0, M.lcz);
+				const int   mx = i_clamp((int) __builtin_floorf((cx + 0.5f) * G.rbx), 0, G.lcx);
+				const int   my = i_clamp((int) __builtin_floorf((cy + 0.5f) * G.rby), 0, G.lcy);
+				const int   mz = i_clamp((int) __builtin_floorf((cz + 0.5f) * G.rbz), 0, G.lcz);
 				const uint32_t cell = ((uint32_t) mz * (uint32_t) A.mh + (uint32_t) my) * (uint32_t) A.mw + (uint32_t) mx;
 				if (cell != last_cell)
 				{
 					++n_probe;
 					last_cell = cell;
-					const int lx = mx * M.bx, ly = my * M.by, lz = mz * M.bz;
-					if ((float) M.max_map[cell] * kInv255 <= best && in_grown(cx, lx, M.bx) && in_grown(cy, ly, M.by) && in_grown(cz, lz, M.bz))
+					const int lx = mx * G.bx, ly = my * G.by, lz = mz * G.bz;
+					if ((float) G.max_map[cell] * kInv255 <= best && in_grown(cx, lx, G.bx) && in_grown(cy, ly, G.by) && in_grown(cz, lz, G.bz))
 					{
 						// samples i .. i + kk: the estimate aims a quarter voxel past the cell's edge (inside the half-voxel margin); the last one is
 						// checked exactly below, and the sampler's coordinates are monotone in the sample index, so every sample between lies in the
 						// grown cell too
 						const float sx = R.sx * fW, sy = R.sy * fH, sz = R.sz * fD;
-						const float tx = sx > 0.0f ? ((float) (lx + M.bx) - 0.25f - cx) / sx : (sx < 0.0f ? ((float) lx - 0.75f - cx) / sx : INFINITY);
-						const float ty = sy > 0.0f ? ((float) (ly + M.by) - 0.25f - cy) / sy : (sy < 0.0f ? ((float) ly - 0.75f - cy) / sy : INFINITY);
-						const float tz = sz > 0.0f ? ((float) (lz + M.bz) - 0.25f - cz) / sz : (sz < 0.0f ? ((float) lz - 0.75f - cz) / sz : INFINITY);
+						const float tx = sx > 0.0f ? ((float) (lx + G.bx) - 0.25f - cx) / sx : (sx < 0.0f ? ((float) lx - 0.75f - cx) / sx : INFINITY);
+						const float ty = sy > 0.0f ? ((float) (ly + G.by) - 0.25f - cy) / sy : (sy < 0.0f ? ((float) ly - 0.75f - cy) / sy : INFINITY);
+						const float tz = sz > 0.0f ? ((float) (lz + G.bz) - 0.25f - cz) / sz : (sz < 0.0f ? ((float) lz - 0.75f - cz) / sz : INFINITY);
 						const float tm = g_min(g_min(tx, ty), g_min(tz, (float) (n - 1 - i)));
 						int         kk = tm > 0.0f ? (int) tm : 0;
 						if (kk > 0)
@@ -166,7 +149,7 @@ __global__ void __launch_bounds__(256) k_mip(const MipArgs M)
 							const float qx = __builtin_fmaf(__builtin_fmaf(fl, R.sx, R.ex), fW, -0.5f);
 							const float qy = __builtin_fmaf(__builtin_fmaf(fl, R.sy, R.ey), fH, -0.5f);
 							const float qz = __builtin_fmaf(__builtin_fmaf(fl, R.sz, R.ez), fD, -0.5f);
-							if (!(in_grown(qx, lx, M.bx) && in_grown(qy, ly, M.by) && in_grown(qz, lz, M.bz)))
+							if (!(in_grown(qx, lx, G.bx) && in_grown(qy, ly, G.by) && in_grown(qz, lz, G.bz)))
 								kk = 0;
 						}
 						i += kk + 1;
@@ -197,27 +180,19 @@ __global__ void __launch_bounds__(256) k_mip(const MipArgs M)
 		g         = M.window_max <= M.threshold ? 1.0f : g_clamp((best - M.threshold) / (M.window_max - M.threshold), 0.0f, 1.0f);
 		a         = 1.0f;
 		if (A.out_depth)
-		{        // the integrator's first_hit depth (ray_finish), at sample k
-			const float fk   = (float) k;
-			const float p[4] = {__builtin_fmaf(fk, R.sx, R.ex) - 0.5f, __builtin_fmaf(fk, R.sy, R.ey) - 0.5f, __builtin_fmaf(fk, R.sz, R.ez) - 0.5f, 1.0f};
-			float       a4[4], b4[4], c4[4];
-			mat4_mul_vec4(A.model, p, a4);
-			mat4_mul_vec4(A.view, a4, b4);
-			mat4_mul_vec4(A.proj, b4, c4);
-			depth = c4[2] / c4[3];
+		{        // at sample k
+			const float fk = (float) k;
+			depth          = first_hit_depth(A, __builtin_fmaf(fk, R.sx, R.ex), __builtin_fmaf(fk, R.sy, R.ey), __builtin_fmaf(fk, R.sz, R.ez));
 		}
 	}
 	if (A.out_color)
 		store_float4_nt(A.out_color, po, g, g, g, a);
 	if (A.out_rgba8)
-	{
-		const uint32_t q = (uint32_t) quantise_rgba8(g);
-		__builtin_nontemporal_store(q | (q << 8) | (q << 16) | ((uint32_t) quantise_rgba8(a) << 24), reinterpret_cast<uint32_t *>(A.out_rgba8) + po);
-	}
+		store_rgba8_nt(A.out_rgba8, po, g, g, g, a);
 	if (M.out_intensity)
 		__builtin_nontemporal_store(intensity, M.out_intensity + po);
 	if (A.out_counts)
-		A.out_counts[po * 3 + 0] = n_filt, A.out_counts[po * 3 + 1] = n_probe, A.out_counts[po * 3 + 2] = n_skip;
+		store_counts(A.out_counts, po, n_filt, n_probe, n_skip);
 	if (A.out_depth)
 		__builtin_nontemporal_store(depth, A.out_depth + po);
 }
@@ -232,6 +207,15 @@ int check_mip(vkv_ctx *ctx, const VkvRenderParams *P, const VkvMipOptions *M)
 	if (!std::isfinite(M->threshold) || std::isnan(M->window_max))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_mip: threshold must be finite and window_max not NaN");
 	return check_first_hit_params(ctx, "render_mip", P, M->d_max_map, M->d_out_intensity != nullptr);
+}
+
+template <bool PACKED>
+void launch_mip(const MipArgs &m, hipStream_t s)
+{
+	if (m.mm.max_map)
+		hipLaunchKernelGGL((k_mip<PACKED, true>), dim3(deal_grid(m.A)), dim3(256), 0, s, m);
+	else
+		hipLaunchKernelGGL((k_mip<PACKED, false>), dim3(deal_grid(m.A)), dim3(256), 0, s, m);
 }
 
 }        // namespace
@@ -285,22 +269,15 @@ int vkv_render_mip(vkv_ctx *ctx, const VkvRenderParams *P, const VkvMipOptions *
 	if (rc != VKV_OK)
 		return rc;
 	MipArgs m;
-	fill_mip_args(P, m.A);
+	fill_direct_args(P, m.A);
 	if (m.A.nblocks == 0)
 		return VKV_OK;
 	m.threshold = M->threshold, m.window_max = M->window_max, m.out_intensity = M->d_out_intensity;
-	fill_max_map_geometry(P, M->d_max_map, m);
-	const hipStream_t s      = (hipStream_t) stream;
-	const dim3        grid((m.A.tile_count + 7u) / 8u * 8u * m.A.blocks_per_tile), block(256);
-	const bool        packed = m.A.packed != nullptr;
-	if (M->d_max_map && packed)
-		hipLaunchKernelGGL((k_mip<true, true>), grid, block, 0, s, m);
-	else if (M->d_max_map)
-		hipLaunchKernelGGL((k_mip<false, true>), grid, block, 0, s, m);
-	else if (packed)
-		hipLaunchKernelGGL((k_mip<true, false>), grid, block, 0, s, m);
+	fill_max_map_geometry(P, M->d_max_map, m.mm);
+	if (m.A.packed)
+		launch_mip<true>(m, (hipStream_t) stream);
 	else
-		hipLaunchKernelGGL((k_mip<false, false>), grid, block, 0, s, m);
+		launch_mip<false>(m, (hipStream_t) stream);
 	return check_launch(ctx, "render_mip");
 }
 

@@ -419,7 +419,7 @@ static int fill_empty(vkv_ctx *ctx, uint8_t *d_map, size_t n, hipStream_t s, boo
 // what the occupancy pass (whole map or a region update's) can take in one launch: the grid of k_occupancy_map
 bool occupancy_launch_ok(VkvExtent3D e, VkvExtent3D me)
 {
-	const int bx = (int) ((e.width + me.width - 1) / me.width), cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
+	const int bx = (int) block_of(e.width, me.width), cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
 	return (uint64_t) ((me.width + cells_per_block - 1) / cells_per_block) * me.height <= 0xffffffull && me.depth <= 65535u;
 }
 
@@ -437,8 +437,7 @@ int launch_occupancy_map(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gr
 		hipLaunchKernelGGL(k_tf_columns, dim3(1), dim3(256), 0, s, d_bits);        // words 2048..2055 of the scratch's table area
 	}
 	// src/compute_distance_map.cpp:110-113
-	const int bx = (int) ((e.width + me.width - 1) / me.width), by = (int) ((e.height + me.height - 1) / me.height),
-	          bz = (int) ((e.depth + me.depth - 1) / me.depth);
+	const int bx = (int) block_of(e.width, me.width), by = (int) block_of(e.height, me.height), bz = (int) block_of(e.depth, me.depth);
 	const int      cells_per_block = 256 / bx > 0 ? 256 / bx : 1;
 	const uint32_t blocks_x        = (me.width + cells_per_block - 1) / cells_per_block;
 	const dim3 grid(blocks_x * me.height, me.depth);
@@ -530,8 +529,7 @@ int launch_occupancy_map_cells(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t
 		hipLaunchKernelGGL(k_occupancy_of_distance, dim3((uint32_t) blocks), dim3(256), 0, s, d_map, n_cells);
 	}
 	// src/compute_distance_map.cpp:110-113
-	const int bx = (int) ((e.width + me.width - 1) / me.width), by = (int) ((e.height + me.height - 1) / me.height),
-	          bz = (int) ((e.depth + me.depth - 1) / me.depth);
+	const int bx = (int) block_of(e.width, me.width), by = (int) block_of(e.height, me.height), bz = (int) block_of(e.depth, me.depth);
 	const int      cpb      = 256 / bx > 0 ? 256 / bx : 1;
 	const uint32_t blocks_x = (c1[0] - c0[0] + cpb - 1) / cpb;
 	const dim3     grid(blocks_x * (c1[1] - c0[1]), c1[2] - c0[2]);

@@ -10,6 +10,7 @@
 
 #include "raymarch_inst.hpp"
 #include "launchers.hpp"
+#include "render_args.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
 // Start order from measured costs: one workgroup per frame sorts the schedule entries 0 .. count - 1 by the cost the previous frame
@@ -326,59 +327,36 @@ void screen_tile_rect(const VkvRayCastUniform *rc, const VkvRayGen *rg, uint32_t
 // VkvRenderParams -> kernel arguments.  Returns VKV_OK with a.nblocks == 0 when the schedule is empty.
 int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, RayMarchArgs &a, hipStream_t s, const VkvTuning &T, bool setup, bool batch)
 {
+	bool whole_schedule = fill_shared_args(P, a);        // every tile of the image is scheduled (no rectangle, or a fill_outside rectangle rewritten below)
 	for (int i = 0; i < 3; ++i)
-	{
-		a.dir00[i] = P->ray_gen.dir00[i], a.ddx[i] = P->ray_gen.ddx[i], a.ddy[i] = P->ray_gen.ddy[i];
-		a.cam[i]        = P->ray_cast.camera_pos_tex[i];
 		a.block_size[i] = P->ray_cast.block_size[i];
-	}
-	for (int i = 0; i < 4; ++i)
-		a.plane_tex[i] = P->ray_cast.plane_tex[i];
-	for (int i = 0; i < 16; ++i)
-		a.model[i] = P->camera.model[i], a.view[i] = P->camera.camera_view[i], a.proj[i] = P->camera.camera_proj[i],
-		a.view_proj_inv[i] = P->camera.camera_view_proj_inv[i], a.model_inv[i] = P->camera.model_inv[i];
-	a.sampling_factor = P->transfer_function.sampling_factor;
-	a.grad_modifier   = P->transfer_function.grad_magnitude_modifier;
-	a.W = (int) P->volume_extent.width, a.H = (int) P->volume_extent.height, a.D = (int) P->volume_extent.depth;
-	a.mw = (int) P->map_extent.width, a.mh = (int) P->map_extent.height, a.md = (int) P->map_extent.depth;
-	a.vol = P->d_volume, a.grad = P->d_gradient, a.tf = P->d_transfer_function;
-	a.packed  = static_cast<const uint8_t *>(P->d_packed_volume);
+	a.grad_modifier = P->transfer_function.grad_magnitude_modifier;
+	a.grad = P->d_gradient, a.tf = P->d_transfer_function;
 	a.tf_bits = P->d_transfer_function_bits;
-	{
-		const PackedDims pd = packed_dims(a.W, a.H, a.D);
-		a.pmx = pd.mx, a.pmy = pd.my;
-	}
 	for (int i = 0; i < 8; ++i)
 		a.maps[i] = P->d_distance_maps[i];
-	a.out_color = P->d_out_color, a.out_rgba8 = P->d_out_rgba8, a.out_counts = P->d_out_counts, a.out_depth = P->d_out_depth;
-	a.in_depth         = P->d_in_depth;
-	a.depth_attachment = P->options.depth_attachment != 0, a.blend = P->blend_over_target != 0;
-	a.img_w = P->image_width, a.img_h = P->image_height;
-	a.tile_w = P->tiles.tile_width, a.tile_h = P->tiles.tile_height;
-	a.tile_first = P->tiles.tile_first, a.tile_stride = P->tiles.tile_stride, a.tile_count = P->tiles.tile_count, a.compact = P->tiles.compact;
+	a.in_depth = P->d_in_depth;        // whatever options.depth_attachment says (the direct renderers pass it only when that is set)
+	a.blend    = P->blend_over_target != 0;
 	a.fill_rgba8_rows = (a.out_rgba8 && !a.out_color && !a.out_counts && !a.out_depth && !a.blend && (a.img_w & 3u) == 0 && (((uintptr_t) a.out_rgba8) & 15u) == 0) ? 1u : 0u;
-	bool whole_schedule;        // every tile of the image is scheduled (no rectangle, or a fill_outside rectangle handed to a resident-wave scheduler)
-	{        // the schedule's tile rectangle (all zero: the whole image); tiles are numbered row-major inside it
+	{
 		const VkvTileRect &r = P->tiles.rect;
 		const uint32_t     full_x = (a.img_w + a.tile_w - 1) / a.tile_w, full_y = (a.img_h + a.tile_h - 1) / a.tile_h;
-		bool               whole  = r.w == 0 || r.h == 0;
 		a.fill_tiles = 0, a.img_tiles_x = full_x, a.rect_tx0 = a.rect_ty0 = a.rect_th = 0;
-		if (!whole && P->tiles.fill_outside)
+		if (!whole_schedule && P->tiles.fill_outside)
 		{
-			// fill_outside (checked by check_render_params: the whole rectangle, image-indexed outputs): the workgroups of a vkv_render_batch launch
-			// fill the tiles outside the rectangle themselves; vkv_render (argument block by value: lean_block) and the resident-wave schedulers
-			// (A/B switches) simply render the whole-image schedule - the same frame either way
+			// fill_outside (the integrator's alone; checked by check_render_params: the whole rectangle, image-indexed outputs): the workgroups of a
+			// vkv_render_batch launch fill the tiles outside the rectangle themselves; vkv_render (argument block by value: lean_block) and the
+			// resident-wave schedulers (A/B switches) simply render the whole-image schedule - the same frame either way
 			if (!batch || T.scheduler == 1 || T.batch_mode == 1 || (uint64_t) full_x * full_y - (uint64_t) r.w * r.h > (uint64_t) kFillPerTile * r.w * r.h)
-				whole = true, a.tile_count = full_x * full_y;        // (also a rectangle so small that its tiles could not fill the rest: a cheap frame anyway)
+			{        // (also a rectangle so small that its tiles could not fill the rest: a cheap frame anyway)
+				whole_schedule = true;
+				a.tile_count = full_x * full_y, a.tiles_x = full_x, a.org_x = a.org_y = 0u;
+			}
 			else
 				a.fill_tiles = full_x * full_y - r.w * r.h, a.rect_tx0 = r.x0, a.rect_ty0 = r.y0, a.rect_th = r.h;
 		}
-		a.tiles_x = whole ? full_x : r.w;
-		a.org_x = whole ? 0u : r.x0 * a.tile_w, a.org_y = whole ? 0u : r.y0 * a.tile_h;
-		whole_schedule = whole;
 	}
-	a.blocks_per_tile_x = a.tile_w / 16;
-	a.blocks_per_tile   = a.blocks_per_tile_x * (a.tile_h / 16);
+	// the limits below and their messages are the integrator's own (the direct renderers' come from check_first_hit_params)
 	const uint64_t nb   = (uint64_t) a.blocks_per_tile * a.tile_count;
 	a.nblocks           = 0;
 	if (nb == 0)
@@ -395,14 +373,8 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 	a.trace       = reinterpret_cast<unsigned long long *>(ctx->d_trace);
 	a.back        = (int) std::ceil(P->transfer_function.sampling_factor);
 	a.clamp_always = T.clamp_always != 0 ? 1u : 0u;
-	{        // shape of a wave's pixel patch: voxels per pixel step in x against y (texture-space ray increments x the extent)
-		double vx = 0.0, vy = 0.0;
-		const double dim[3] = {(double) a.W, (double) a.H, (double) a.D};
-		for (int k = 0; k < 3; ++k)
-			vx += (double) a.ddx[k] * dim[k] * (double) a.ddx[k] * dim[k], vy += (double) a.ddy[k] * dim[k] * (double) a.ddy[k] * dim[k];
-		const double r = (vx > 0.0 && vy > 0.0) ? std::sqrt(vx / vy) : 1.0;
-		a.wave_pw_log2 = T.wave_shape == 4 ? 2u : (T.wave_shape == 8 ? 3u : (T.wave_shape == 16 ? 4u : (r >= 1.6 ? 2u : (r <= 1.0 / 1.6 ? 4u : 3u))));
-	}
+	// shape of a wave's pixel patch: VkvTuning.wave_shape (A/B switch), or what the view asks for
+	a.wave_pw_log2 = T.wave_shape == 4 ? 2u : (T.wave_shape == 8 ? 3u : (T.wave_shape == 16 ? 4u : wave_patch_log2(a.ddx, a.ddy, a.W, a.H, a.D)));
 	{
 		const float m[3] = {(float) a.mw, (float) a.mh, (float) a.md};
 		for (int k = 0; k < 3; ++k)

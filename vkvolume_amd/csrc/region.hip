@@ -37,7 +37,7 @@ int launch_update_volume_region(vkv_ctx *ctx, const void *d_src, int type, bool 
 		const uint32_t mext[3] = {me.width, me.height, me.depth};
 		for (int a = 0; a < 3; ++a)        // src/compute_distance_map.cpp:110-113; the cells that meet the grown box
 		{
-			const uint32_t blk = (ext[a] + mext[a] - 1) / mext[a];
+			const uint32_t blk = block_of(ext[a], mext[a]);
 			c0[a] = g0[a] / blk, c1[a] = (g1[a] - 1) / blk + 1;
 		}
 		if (!(scratch = stream_scratch(ctx, s)).p)

@@ -6,27 +6,24 @@
 // j = 0 .. samples - 1; a sample counts when q_j lies in [0, 1]^3.  fma is monotone in j, so per axis the counted indices are one range,
 // found by bisection over the very test that defines it.  One lane per pixel, a workgroup = 16x16 pixels dealt to the XCDs and started as
 // k_mip's are (mip.hip), a wave = an 8x8 pixel patch whatever the plane: the footprints of a thin slice then fall in neighbouring voxel rows
-// and bricks.  A sample is the integrator's filtered intensity (mip_sample / mip_samples of max_map_skip.hpp); the skipping variant walks the
+// and bricks.  A sample is the integrator's filtered intensity (mip_sample / mip_samples of direct_render.hpp); the skipping variant walks the
 // column like a MIP ray with entry p and step dn (max_map_skip, bound = the best so far).
 #include <cmath>
 
 #include "raymarch_core.hpp"
-#include "max_map_skip.hpp"
+#include "direct_render.hpp"
 
 namespace
 {
 
 struct SlabArgs
 {
-	RayMarchArgs   A;               // the fields start_entry and the samplers read (fill_mip_args); no ray is set up
+	RayMarchArgs   A;               // the fields start_entry and the samplers read (fill_direct_args); no ray is set up
 	float          origin[3], du[3], dv[3], dn[3];
 	int            samples;         // 1 .. 4096
 	float          window_min, window_max;
 	float *        out_value;       // or null
-	const uint8_t *max_map;         // skipping variant only
-	int            bx, by, bz;      // voxels per map cell per axis
-	int            lcx, lcy, lcz;   // last map cell per axis that holds a voxel: (extent - 1) / block
-	float          rbx, rby, rbz;   // 1 / block (finding the cell only; the skip itself is checked exactly)
+	MaxMapGeometry mm;              // skipping variant only
 };
 
 // the first j in [0, n] for which pred(fma(j, d, p)) holds (n: none); pred must turn from false to true once as j rises
@@ -62,23 +59,11 @@ __global__ void __launch_bounds__(256) k_slab(const SlabArgs S)
 {
 	static_assert(!SKIP || MODE == VKV_SLAB_MAX, "the max map bounds a maximum only");
 	const RayMarchArgs &A = S.A;
-	// k_mip's deal of workgroups: XCD x = id & 7 takes the schedule's tiles x, x + 8, ...; a schedule that holds every tile of its rectangle
-	// starts them ring by ring from the middle (start_entry)
-	const uint32_t x = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
-	if (rank >= A.tile_count)
+	// a wave's patch: 8x8 pixels whatever the plane
+	uint32_t px, py, o;
+	if (!pixel_deal(A, 3u, px, py, o))
 		return;
-	const uint32_t k_tile = A.order_h ? start_entry(A, rank) : rank;
-	if (k_tile >= A.tile_count)
-		return;
-	// the wave's 64 pixels: an 8x8 patch of the 16x16 block
-	const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-	const uint32_t t  = A.tile_first + k_tile * A.tile_stride;
-	const uint32_t lx = (sb % A.blocks_per_tile_x) * 16u + (w & 1u) * 8u + (lane & 7u), ly = (sb / A.blocks_per_tile_x) * 16u + (w >> 1) * 8u + (lane >> 3);
-	const uint32_t px = A.org_x + (t % A.tiles_x) * A.tile_w + lx, py = A.org_y + (t / A.tiles_x) * A.tile_h + ly;
-	const size_t   po = A.compact ? (k_tile * A.tile_h + ly) * A.tile_w + lx : py * A.img_w + px;
-	if (px >= A.img_w || py >= A.img_h)
-		return;
+	const size_t po = o;
 	// the column of this pixel as a ray: entry p, step dn
 	Ray         R;
 	const float fx = (float) px, fy = (float) py;
@@ -129,7 +114,7 @@ __global__ void __launch_bounds__(256) k_slab(const SlabArgs S)
 		{
 			const float fi   = (float) i;
 			const float posx = __builtin_fmaf(fi, R.sx, R.ex), posy = __builtin_fmaf(fi, R.sy, R.ey), posz = __builtin_fmaf(fi, R.sz, R.ez);
-			const int   last = max_map_skip<false>(A, S, R, i, hi, posx, posy, posz, best, last_cell, n_probe);
+			const int   last = max_map_skip<false>(A, S.mm, R, i, hi, posx, posy, posz, best, last_cell, n_probe);
 			if (last >= 0)
 			{
 				n_skip += (uint32_t) (last + 1 - i);
@@ -156,14 +141,11 @@ __global__ void __launch_bounds__(256) k_slab(const SlabArgs S)
 	if (A.out_color)
 		store_float4_nt(A.out_color, po, g, g, g, a);
 	if (A.out_rgba8)
-	{
-		const uint32_t q = (uint32_t) quantise_rgba8(g);
-		__builtin_nontemporal_store(q | (q << 8) | (q << 16) | ((uint32_t) quantise_rgba8(a) << 24), reinterpret_cast<uint32_t *>(A.out_rgba8) + po);
-	}
+		store_rgba8_nt(A.out_rgba8, po, g, g, g, a);
 	if (S.out_value)
 		__builtin_nontemporal_store(value, S.out_value + po);
 	if (A.out_counts)
-		A.out_counts[po * 3 + 0] = n_filt, A.out_counts[po * 3 + 1] = n_probe, A.out_counts[po * 3 + 2] = n_skip;
+		store_counts(A.out_counts, po, n_filt, n_probe, n_skip);
 }
 
 // the checks of vkv_render_slab; VKV_OK or the code (nothing is enqueued before they pass)
@@ -214,15 +196,15 @@ int vkv_render_slab(vkv_ctx *ctx, const VkvRenderParams *P, const VkvSlabOptions
 	if (rc != VKV_OK)
 		return rc;
 	SlabArgs a;
-	fill_mip_args(P, a.A);
+	fill_direct_args(P, a.A);
 	if (a.A.nblocks == 0)
 		return VKV_OK;
 	a.A.out_depth = nullptr, a.A.in_depth = nullptr, a.A.depth_attachment = 0;        // (rejected when set)
 	for (int c = 0; c < 3; ++c)
 		a.origin[c] = S->origin[c], a.du[c] = S->du[c], a.dv[c] = S->dv[c], a.dn[c] = S->dn[c];
 	a.samples = (int) S->samples, a.window_min = S->window_min, a.window_max = S->window_max, a.out_value = S->d_out_value;
-	fill_max_map_geometry(P, S->d_max_map, a);
-	const dim3 grid((a.A.tile_count + 7u) / 8u * 8u * a.A.blocks_per_tile);
+	fill_max_map_geometry(P, S->d_max_map, a.mm);
+	const dim3 grid(deal_grid(a.A));
 	if (a.A.packed)
 		launch_slab<true>(a, S->mode, S->d_max_map != nullptr, grid, (hipStream_t) stream);
 	else

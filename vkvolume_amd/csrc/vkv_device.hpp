@@ -316,6 +316,11 @@ namespace vkv
 int  set_error(vkv_ctx *ctx, int code, const char *fmt, ...);
 int  check_launch(vkv_ctx *ctx, const char *what);
 int  check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box);        // VKV_OK for null (the whole volume) or a box inside extent
+static inline bool extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
+// ceil(volume / map) must reproduce a valid block size (src/compute_distance_map.cpp:110-113)
+static inline bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
+// voxels per map cell on one axis: ceil(extent / map extent)
+static inline uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
 VkvStreamKey stream_key(hipStream_t stream);
 // this stream's scratch block (out of the arena on first use, kept until vkv_release_stream / vkv_destroy), LOCKED until the object goes:
 // an entry point keeps it from its first write into the block to its last enqueue.  p == nullptr + error set when there is no room.
