@@ -322,7 +322,7 @@ RING_RECTS = [(0, 0, 1, 1), (3, 2, 1, 5), (2, 3, 7, 1), (1, 0, 2, 7), (0, 1, 9, 
 @pytest.mark.parametrize("rect", RING_RECTS, ids=lambda r: "%dx%d@%d,%d" % (r[2], r[3], r[0], r[1]))
 def test_computed_start_order_reaches_every_tile_of_a_rectangle(ctx, rect):
     """A schedule that holds every tile of a tile rectangle starts its tiles ring by ring from the rectangle's middle (start_entry in
-    raymarch_core.hpp: computed in the kernel, no table).  Every rectangle shape - one tile, one row, one column, two rows, odd and even sides,
+    ray_setup.hpp: computed in the kernel, no table).  Every rectangle shape - one tile, one row, one column, two rows, odd and even sides,
     the whole image - renders exactly its tiles: inside equal to the whole-image frame, outside untouched (image-indexed) / every slot of the
     compact buffer written; the plain order (VkvTuning.tile_order_linear) gives the same bytes."""
     from tests.test_gpu_parity import fuzz_case

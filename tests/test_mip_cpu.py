@@ -65,13 +65,13 @@ def _gmax(x, y):
 
 
 def _mat4_mul(m, v):
-    """mat4_mul_vec4 of raymarch_core.hpp: m column-major float[16], v four arrays"""
+    """mat4_mul_vec4 of volume_sampling.hpp: m column-major float[16], v four arrays"""
     m = np.asarray(m, F)
     return [_fma(m[12 + i], v[3], _fma(m[8 + i], v[2], _fma(m[4 + i], v[1], F(m[i]) * v[0]))) for i in range(4)]
 
 
 def sample_linear_np(vol, px, py, pz):
-    """sample_linear of raymarch_core.hpp: clamp-to-edge trilinear filter, lerps as fma(w, b - a, a), times kInv255"""
+    """sample_linear of volume_sampling.hpp: clamp-to-edge trilinear filter, lerps as fma(w, b - a, a), times kInv255"""
     D, H, W = vol.shape
     cx, cy, cz = _fma(px, F(W), F(-0.5)), _fma(py, F(H), F(-0.5)), _fma(pz, F(D), F(-0.5))
     fx, fy, fz = np.floor(cx), np.floor(cy), np.floor(cz)

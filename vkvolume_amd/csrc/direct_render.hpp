@@ -8,7 +8,10 @@
 #include <cmath>
 
 #include "launchers.hpp"
+#include "raymarch_args.hpp"
+#include "ray_setup.hpp"
 #include "render_args.hpp"
+#include "volume_sampling.hpp"
 
 // everything here is internal to the translation unit that includes it (no exported symbols)
 namespace

@@ -9,7 +9,8 @@
 // refine_steps filters on the bisection and four on the tetrahedron gradient (the integrator's GRAD == 2 taps, frag:92-97).
 #include <cmath>
 
-#include "raymarch_core.hpp"
+#include "ray_setup.hpp"
+#include "volume_sampling.hpp"
 #include "direct_render.hpp"
 
 namespace
@@ -140,7 +141,7 @@ __global__ void __launch_bounds__(256) k_iso(const IsoArgs I)
 		const float hx = __builtin_fmaf(th, R.sx, R.ex), hy = __builtin_fmaf(th, R.sy, R.ey), hz = __builtin_fmaf(th, R.sz, R.ez);
 		if (A.out_depth)
 			depth = first_hit_depth(A, hx, hy, hz);
-		// gradient: the integrator's tetrahedron taps (raymarch_core.hpp, GRAD == 2), in texture space
+		// gradient: the integrator's tetrahedron taps (raymarch_persistent.hpp, ray_event, GRAD == 2), in texture space
 		const float dix = 1.0f / (float) A.W, diy = 1.0f / (float) A.H, diz = 1.0f / (float) A.D;
 		const float t1  = mip_sample<PACKED>(A, hx + dix, hy - diy, hz - diz);
 		const float t2  = mip_sample<PACKED>(A, hx - dix, hy - diy, hz + diz);

@@ -12,7 +12,8 @@
 #include <algorithm>
 #include <cmath>
 
-#include "raymarch_core.hpp"
+#include "ray_setup.hpp"
+#include "volume_sampling.hpp"
 #include "direct_render.hpp"
 #include "row_loads.hpp"
 

@@ -1,4 +1,4 @@
-// raymarch.hip — launchers of the ray-march integrator (device code: raymarch_core.hpp).
+// raymarch.hip — launchers of the ray-march integrator (device code: raymarch_core.hpp and the headers it includes).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -1,11 +1,15 @@
 // render_args.hpp — VkvRenderParams -> the fields of RayMarchArgs that the integrator (fill_render_args, raymarch.hip) and the direct renderers
 // (fill_direct_args, direct_render.hpp) fill alike, and the shape of a wave's pixel patch.  It
-// defines host functions only; raymarch_core.hpp is included for RayMarchArgs.
+// defines host functions only: RayMarchArgs comes from raymarch_args.hpp (no device code), VkvRenderParams and packed_dims from vkv_device.hpp.
+// Included by raymarch.hip and direct_render.hpp.
 #pragma once
 
 #include <cmath>
 
-#include "raymarch_core.hpp"
+#include "vkv_device.hpp"
+#include "raymarch_args.hpp"
+
+using namespace vkv;
 
 // everything here is internal to the translation unit that includes it (no exported symbols)
 namespace

@@ -10,7 +10,8 @@
 // column like a MIP ray with entry p and step dn (max_map_skip, bound = the best so far).
 #include <cmath>
 
-#include "raymarch_core.hpp"
+#include "raymarch_args.hpp"
+#include "volume_sampling.hpp"
 #include "direct_render.hpp"
 
 namespace

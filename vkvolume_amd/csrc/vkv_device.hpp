@@ -65,7 +65,7 @@ __device__ __forceinline__ float gradient_on_the_fly(const uint8_t *__restrict__
 	return gradient_from_taps(v1, v2, v3, v4, modifier);
 }
 
-// ---- correctly rounded fp32 division out of v_rcp_f32 (the ray set-up's 22 divisions per ray; see raymarch_core.hpp, ray_setup) ----
+// ---- correctly rounded fp32 division out of v_rcp_f32 (the ray set-up's 22 divisions per ray; see ray_setup.hpp) ----
 __device__ __forceinline__ bool div_ordinary(float x)
 {
 	const float m = __builtin_fabsf(x);
