@@ -21,15 +21,35 @@
 // the dispatch itself with numerators +0 and -0).
 // Operands outside the ordinary range (axis-parallel rays: 1 / 0; NaNs of a degenerate camera) send the whole wave through the
 // plain IEEE set-up (ray_setup below), so the fast path never has to be right about them.
+//
+// The range test (round 10).  Both paths give the same bits wherever the fast one is valid, so the predicate that chooses between them only
+// has to be SUFFICIENT: true only where every operand of every division is ordinary.  It is not kept per operand (28 times two compares and
+// the scalar mask operations that fold them into a flag) but as one accumulated range per lane, OrdRange (vkv_device.hpp): the smallest and
+// the largest magnitude of the operands as integers, two compares behind the last one, the ballot as before.  Its bounds are 2^-39 and 2^39,
+// one binade inside div_ordinary's, and that slack is what lets operands be left out:
+//   * the two lengths len = sqrt(fma(z, z, fma(y, y, x * x))).  With 2^-39 <= |x|, |y|, |z| <= 2^39 nothing under- or overflows, every term
+//     is >= 0 and rounding is monotone, so x^2 (1 - 2^-24) <= fl(x * x) <= the sum <= 3 * 2^78 (1 + 2^-24)^3 and
+//     2^-39 (1 - 2^-24) <= len <= 1.74 * 2^39: inside [2^-40, 2^40].
+//   * the upper bound of a component of a normalised vector, q = a / len with len as above: |a| <= len (1 + 2^-23), so |q| < 2 and q is
+//     neither inf nor NaN; only its lower bound can fail (ord_low).
+//   * the three block sizes: the same for every ray of a launch, tested once on the host (RayMarchArgs.ord_lo0, fill_render_args).
+// Everything else goes in: the numerators dx..dz, Bp and Ap, vx..vz, the step numerators (their denominator is a step count, 1 .. 2^24),
+// the numerators and the quotients of the divisions by the block size.  The host program of tests/test_ray_setup_range_cpu.py checks
+// "new implies old" for one operand over all 2^32 floats, for tuples with every special value in every position, and the two arguments above.
+//
+// Divisions by a block size that is a power of two (the application's and the benchmark's is 4): n / block is n * (1 / block) exactly, one
+// multiplication instead of the eight instructions of recip_refined + div_by; RayMarchArgs.block_rcp holds the reciprocal per axis (0 for an
+// axis that has none) and block_pow2 says that all three axes have one: one wave-uniform branch, three multiplications behind it, the
+// divisions on its other side.  The IEEE path keeps `a / b`.
 // ---------------------------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------------------------
 // Ray generation + frag:147-210.  Returns true when the ray has to be marched; false when the pixel is finished
 // already (not covered, grazing-ray early-out, or a RayEntry / RayExit test output) with its result in R.
-// FAST: divisions through div_by / recip_exact; `ok` comes back false when an operand was outside their range (the caller then
+// FAST: divisions through div_by / recip_exact; `ord` comes back as the range of their operands' magnitudes (when it is not ord_ok the caller
 // repeats the set-up with FAST = false for the whole wave).
 // ---------------------------------------------------------------------------------------------------------------
 template <int SKIP, bool FAST>
-__device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t px, uint32_t py, Ray &R, bool &ok)
+__device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t px, uint32_t py, Ray &R, OrdRange &ord)
 {
 	R.r = R.g = R.b = R.a = 0.0f;        // out_color = vec4(0) (frag:120)
 	R.depth = 0.0f;                      // gl_FragDepth = 0 (frag:140)
@@ -47,7 +67,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 		const float len = __builtin_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
 		if (FAST)
 		{
-			ok = ok && div_ordinary(len) && div_ordinary_num(dx) && div_ordinary_num(dy) && div_ordinary_num(dz);
+			ord_both(ord, dx, dy, dz);        // (len follows from them)
 			const float r = recip_refined(len);
 			dx = div_by(dx, len, r), dy = div_by(dy, len, r), dz = div_by(dz, len, r);
 		}
@@ -72,7 +92,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 				float inv;
 				if (FAST)
 				{
-					ok  = ok && div_ordinary(dv[a]);
+					ord_low(ord, dv[a]);
 					inv = recip_exact(dv[a]);
 				}
 				else
@@ -92,7 +112,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 	float t_plane;
 	if (FAST)
 	{
-		ok      = ok && div_ordinary(Bp) && div_ordinary_num(0.0f - Ap);
+		ord_both(ord, Bp), ord_both(ord, Ap);        // (|0 - Ap| = |Ap|)
 		t_plane = div_by(0.0f - Ap, Bp, recip_refined(Bp));
 	}
 	else
@@ -129,7 +149,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 		const float len = __builtin_sqrtf(__builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx)));
 		if (FAST)
 		{
-			ok = ok && div_ordinary(len) && div_ordinary_num(vx) && div_ordinary_num(vy) && div_ordinary_num(vz);
+			ord_both(ord, vx, vy, vz);        // (len follows from them)
 			const float r = recip_refined(len);
 			rdx = div_by(vx, len, r), rdy = div_by(vy, len, r), rdz = div_by(vz, len, r);
 		}
@@ -141,7 +161,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 		float ix, iy, iz;
 		if (FAST)
 		{
-			ok = ok && div_ordinary(rdx) && div_ordinary(rdy) && div_ordinary(rdz);
+			ord_low(ord, rdx, rdy, rdz);
 			ix = recip_exact(rdx), iy = recip_exact(rdy), iz = recip_exact(rdz);
 		}
 		else
@@ -192,7 +212,7 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 		const float den = nf - 1.0f, nx = rdx * ray_distance, ny = rdy * ray_distance, nz = rdz * ray_distance;
 		if (FAST)
 		{
-			ok = ok && div_ordinary_num(nx) && div_ordinary_num(ny) && div_ordinary_num(nz);        // den is 1 .. 2^24
+			ord_both(ord, nx, ny, nz);        // den is 1 .. 2^24
 			const float r = recip_refined(den);
 			sx = div_by(nx, den, r), sy = div_by(ny, den, r), sz = div_by(nz, den, r);
 		}
@@ -215,12 +235,19 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 		if (FAST)
 		{
 			const float nx = sx * (float) W, ny = sy * (float) H, nz = sz * (float) D;
-			ok = ok && div_ordinary(A.block_size[0]) && div_ordinary(A.block_size[1]) && div_ordinary(A.block_size[2]) && div_ordinary_num(nx) &&
-			     div_ordinary_num(ny) && div_ordinary_num(nz);
-			const float tx = div_by(nx, A.block_size[0], recip_refined(A.block_size[0]));
-			const float ty = div_by(ny, A.block_size[1], recip_refined(A.block_size[1]));
-			const float tz = div_by(nz, A.block_size[2], recip_refined(A.block_size[2]));
-			ok    = ok && div_ordinary(tx) && div_ordinary(ty) && div_ordinary(tz);
+			ord.lo = ord_min(ord.lo, A.ord_lo0);        // the block sizes: 0 when one of them is not ordinary
+			ord_both(ord, nx, ny, nz);
+			// (a power-of-two block: the product is the IEEE quotient, and it stays a normal number - nx is at least 2^-39 here, or `ord` fails)
+			float tx, ty, tz;
+			if (A.block_pow2 != 0u)        // (one wave-uniform branch for the three axes: a branch per axis costs what its multiplication saves)
+				tx = nx * A.block_rcp[0], ty = ny * A.block_rcp[1], tz = nz * A.block_rcp[2];
+			else
+			{
+				tx = div_by(nx, A.block_size[0], recip_refined(A.block_size[0]));
+				ty = div_by(ny, A.block_size[1], recip_refined(A.block_size[1]));
+				tz = div_by(nz, A.block_size[2], recip_refined(A.block_size[2]));
+			}
+			ord_both(ord, tx, ty, tz);
 			R.six = recip_exact(tx), R.siy = recip_exact(ty), R.siz = recip_exact(tz);
 		}
 		else
@@ -245,11 +272,11 @@ __device__ __forceinline__ bool ray_setup_impl(const RayMarchArgs &A, uint32_t p
 template <int SKIP>
 __device__ __forceinline__ bool ray_setup(const RayMarchArgs &A, uint32_t px, uint32_t py, Ray &R)
 {
-	bool       ok      = true;
-	const bool marched = ray_setup_impl<SKIP, true>(A, px, py, R, ok);
-	if (__builtin_amdgcn_ballot_w64(!ok) == 0ull)
+	OrdRange   ord     = {~0u, 0u};
+	const bool marched = ray_setup_impl<SKIP, true>(A, px, py, R, ord);
+	if (__builtin_amdgcn_ballot_w64(!ord_ok(ord)) == 0ull)
 		return marched;
-	bool unused = true;
+	OrdRange unused = {~0u, 0u};
 	return ray_setup_impl<SKIP, false>(A, px, py, R, unused);
 }
 

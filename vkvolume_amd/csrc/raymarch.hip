@@ -329,7 +329,9 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 {
 	bool whole_schedule = fill_shared_args(P, a);        // every tile of the image is scheduled (no rectangle, or a fill_outside rectangle rewritten below)
 	for (int i = 0; i < 3; ++i)
-		a.block_size[i] = P->ray_cast.block_size[i];
+		a.block_size[i] = P->ray_cast.block_size[i], a.block_rcp[i] = pow2_reciprocal(a.block_size[i]);
+	a.block_pow2 = (a.block_rcp[0] != 0.0f && a.block_rcp[1] != 0.0f && a.block_rcp[2] != 0.0f) ? 1u : 0u;
+	a.ord_lo0 = (div_ordinary(a.block_size[0]) && div_ordinary(a.block_size[1]) && div_ordinary(a.block_size[2])) ? ~0u : 0u;
 	a.grad_modifier = P->transfer_function.grad_magnitude_modifier;
 	a.grad = P->d_gradient, a.tf = P->d_transfer_function;
 	a.tf_bits = P->d_transfer_function_bits;

@@ -15,6 +15,11 @@ struct RayMarchArgs
 	float cam[3];
 	float plane_tex[4];
 	float block_size[3];
+	// the ray set-up's divisions by the block size (ray_setup.hpp): 1 / block_size per axis where that is exact (a power of two in range), else 0,
+	// and block_pow2 != 0 when all three are; ord_lo0 = the start value of a lane's smallest operand magnitude - ~0u, or 0 when a block size is
+	// outside the fast divisions' range
+	float    block_rcp[3];
+	uint32_t block_pow2, ord_lo0;
 	// CameraUniform matrices needed for gl_FragDepth (frag:319)
 	float model[16], view[16], proj[16];
 	float view_proj_inv[16], model_inv[16];        // DEPTH_ATTACHMENT only (frag:154-156)

@@ -45,7 +45,7 @@ struct RmLds
 		{
 			float    alpha[256];        // opacity correction keyed by the alpha byte (frag:283)
 			uint32_t bits[2048];
-			float    unorm[256];        // byte / 255 (exact IEEE division)
+			float    unorm[256];        // byte / 255 (the IEEE quotient: unorm8_staged)
 		} g;
 		struct
 		{
@@ -79,10 +79,10 @@ __device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L,
 			L.s.ai[i] = ai, L.s.ag[i] = ag;
 			if (i == 255)
 				L.s.ai[256] = ai, L.s.ag[256] = ag;
-			L.s.pair[i] = i == 0 ? make_float2(0.0f, 0.0f) : make_float2(a, unorm8(i) * a);        // (alpha byte 0 blends nothing: lean_march relies on it)
+			L.s.pair[i] = i == 0 ? make_float2(0.0f, 0.0f) : make_float2(a, unorm8_staged(i) * a);        // (alpha byte 0 blends nothing: lean_march relies on it)
 		}
 		else
-			L.g.unorm[i] = unorm8(i);
+			L.g.unorm[i] = unorm8_staged(i);
 	}
 	if (!sep && A.tf_bits)
 		for (int i = threadIdx.x; i < 2048; i += blockDim.x)
@@ -273,18 +273,23 @@ __device__ __forceinline__ void lean_lds_check()
 		__builtin_trap();
 }
 
-// workgroup-wide "any": one flag word per wave at the start of the segment (before the tables are staged there), two barriers
+// workgroup-wide "any", once per workgroup: one flag word per wave in the segment's first 16 bytes, which nothing else uses (the tables start at
+// kLdsBase), and ONE barrier - no wave has to wait until the others have read the flags before it stages the tables.  (The address is 0 at run
+// time only, through an empty asm: as a constant it would be a null pointer to the compiler.)
 __device__ __forceinline__ bool wg_any(bool pred)
 {
-	uint32_t *flags = (uint32_t *) (lds_u32_ptr) kLdsBase;
-	const bool mine = __builtin_amdgcn_ballot_w64(pred) != 0ull;
+	static_assert(kLdsBase >= 16, "the flag words of wg_any sit in front of the tables");
+	uint32_t zero = 0u;
+	asm volatile("" : "+v"(zero));
+	const lds_u32_ptr flags = (lds_u32_ptr) (uintptr_t) zero;
+	const bool        mine  = __builtin_amdgcn_ballot_w64(pred) != 0ull;
 	if ((threadIdx.x & 63u) == 0u)
 		flags[threadIdx.x >> 6] = mine ? 1u : 0u;
 	__syncthreads();
 	const uint32_t nw  = blockDim.x >> 6;        // 4 in the product; the lab builds workgroups of 1 and 2 waves
-	const uint4    f   = *reinterpret_cast<const uint4 *>(flags);
-	const bool     any = (f.x | (nw > 1u ? f.y : 0u) | (nw > 2u ? f.z : 0u) | (nw > 3u ? f.w : 0u)) != 0u;
-	__syncthreads();
+	typedef uint32_t flags_v4u __attribute__((ext_vector_type(4)));
+	const flags_v4u f   = *reinterpret_cast<const __attribute__((address_space(3))) flags_v4u *>(flags);
+	const bool      any = (f.x | (nw > 1u ? f.y : 0u) | (nw > 2u ? f.z : 0u) | (nw > 3u ? f.w : 0u)) != 0u;
 	return any;
 }
 

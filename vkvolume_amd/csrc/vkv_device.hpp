@@ -66,15 +66,42 @@ __device__ __forceinline__ float gradient_on_the_fly(const uint8_t *__restrict__
 }
 
 // ---- correctly rounded fp32 division out of v_rcp_f32 (the ray set-up's 22 divisions per ray; see ray_setup.hpp) ----
-__device__ __forceinline__ bool div_ordinary(float x)
+__host__ __device__ __forceinline__ bool div_ordinary(float x)
 {
 	const float m = __builtin_fabsf(x);
 	return m >= 0x1p-40f && m <= 0x1p40f;        // false for 0, denormals, huge values, inf and NaN
 }
-__device__ __forceinline__ bool div_ordinary_num(float x)
+__host__ __device__ __forceinline__ bool div_ordinary_num(float x)
 {        // (a zero numerator is NOT ordinary: the refinement loses the sign of -0 / d)
 	return div_ordinary(x);
 }
+// The set-up's form of the same test: instead of one div_ordinary per operand (two compares and the mask bookkeeping that folds them into a
+// flag), the smallest and the largest MAGNITUDE of all operands of a lane, as bit patterns without the sign - for those the integer order is
+// the order of the magnitudes, with +-0 and the denormals at the bottom (below 0x00800000) and +-inf and every NaN at the top (from
+// 0x7f800000) - and two compares at the end (ord_ok).  The bounds are one binade INSIDE div_ordinary's on either side, 2^-39 and 2^39: ord_ok
+// then implies div_ordinary of every operand that went in, and of the few that are left out because they follow from operands that did (the
+// length of a vector whose components went in: ray_setup.hpp gives the argument; tests/test_ray_setup_range_cpu.py checks all of it on the host).
+struct OrdRange
+{
+	uint32_t lo, hi;        // smallest / largest magnitude so far; the host starts lo (RayMarchArgs.ord_lo0: ~0u, or 0 = "never ordinary")
+};
+constexpr uint32_t kOrdLoBits = 0x2c000000u, kOrdHiBits = 0x53000000u;        // 2^-39, 2^39
+__host__ __device__ __forceinline__ uint32_t ord_mag(float x) { return __builtin_bit_cast(uint32_t, x) & 0x7fffffffu; }
+__host__ __device__ __forceinline__ uint32_t ord_min(uint32_t a, uint32_t b) { return b < a ? b : a; }
+__host__ __device__ __forceinline__ uint32_t ord_max(uint32_t a, uint32_t b) { return b > a ? b : a; }
+// operands whose magnitude has to be tested on both sides
+__host__ __device__ __forceinline__ void ord_both(OrdRange &r, float a)
+{
+	const uint32_t m = ord_mag(a);
+	r.lo = ord_min(r.lo, m), r.hi = ord_max(r.hi, m);
+}
+__host__ __device__ __forceinline__ void ord_both(OrdRange &r, float a, float b, float c) { ord_both(r, a), ord_both(r, b), ord_both(r, c); }
+// operands that are bounded above by construction (a component of a normalised vector: ray_setup.hpp): only the lower bound can fail.  NOT for
+// an operand that can be inf or NaN.
+__host__ __device__ __forceinline__ void ord_low(OrdRange &r, float a) { r.lo = ord_min(r.lo, ord_mag(a)); }
+__host__ __device__ __forceinline__ void ord_low(OrdRange &r, float a, float b, float c) { ord_low(r, a), ord_low(r, b), ord_low(r, c); }
+__host__ __device__ __forceinline__ bool ord_ok(const OrdRange &r) { return r.lo >= kOrdLoBits && r.hi <= kOrdHiBits; }
+
 __device__ __forceinline__ float recip_refined(float d)
 {
 	const float r0 = __builtin_amdgcn_rcpf(d);
@@ -82,7 +109,7 @@ __device__ __forceinline__ float recip_refined(float d)
 	return __builtin_fmaf(e, r0, r0);
 }
 // a / d given r = recip_refined(d)
-__device__ __forceinline__ float div_by(float a, float d, float r)
+__host__ __device__ __forceinline__ float div_by(float a, float d, float r)
 {
 	const float q0 = a * r;
 	const float q1 = __builtin_fmaf(__builtin_fmaf(-d, q0, a), r, q0);
@@ -95,7 +122,21 @@ __device__ __forceinline__ float recip_exact(float d)
 	const float q1 = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
 	return __builtin_fmaf(__builtin_fmaf(-d, q1, 1.0f), r, q1);
 }
+// byte / 255 with the IEEE quotient's bits and without the division: div_by with the correctly rounded reciprocal as r (a constant; checked
+// against the division for all 256 bytes on the host, tests/test_ray_setup_range_cpu.py, and 0 * r = 0 needs no special case: the byte is unsigned).
+// For the tables a workgroup stages in front of its march loop (stage_tables_er); unorm8 stays the definition.
+__host__ __device__ __forceinline__ float unorm8_staged(uint32_t b) { return div_by((float) b, 255.0f, kInv255); }
 
+// A block size that is a power of two (the application's is 4): 1 / block is a float, and n * (1 / block) is the correctly rounded n / block -
+// the IEEE quotient - for every n.  The host half of the set-up's divisions by the block size (fill_render_args): the exact reciprocal, or 0 when
+// the block size is no power of two in [2^-39, 2^39] (the kernel then divides: ray_setup_impl).
+__host__ __device__ __forceinline__ float pow2_reciprocal(float block)
+{
+	const uint32_t u = __builtin_bit_cast(uint32_t, block);
+	if ((u & 0x807fffffu) != 0u || u < kOrdLoBits || u > kOrdHiBits)        // negative, a mantissa bit set, or outside the range (0, denormal, inf, NaN)
+		return 0.0f;
+	return __builtin_bit_cast(float, 0x7f000000u - u);        // 2^-(e - 127): exponent field 254 - e
+}
 
 // R8_UNORM store: round to nearest even.
 __device__ __forceinline__ uint8_t store_unorm8(float g) { return (uint8_t) __builtin_rintf(g * 255.0f); }
