@@ -40,6 +40,17 @@
  *     passed by const pointer and copied at call time;
  *   - volumes are dense uint8, x fastest: index = (z*height + y)*width + x
  *     (raw file order, src/volume_component.cpp:47-52); distance / occupancy maps the same;
+ *   - ALIGNMENT: byte buffers may start at ANY byte - volumes, gradient maps, occupancy, distance and
+ *     octant maps (each of the eight on its own), swap buffers, the 8-bit sources and the destinations
+ *     of vkv_convert_volume / vkv_update_volume_region - so a caller may keep them all in one arena.
+ *     RGBA8 render targets (d_out_rgba8) and the images and gathered tiles of vkv_scatter_tiles need
+ *     the alignment of one pixel only (4 bytes, 16 for 16-byte pixels).  The launchers pick their
+ *     vector variants from the pointers as well as from the extents; the results are the same bytes,
+ *     and nothing before the first or past the last byte of a buffer is read or written
+ *     (tests/test_gpu_pointer_alignment.py).  The exceptions are stated at the entry points:
+ *     16-bit sources 2 bytes, d_transfer_function and d_tables of the transfer-function updates 4,
+ *     counters, d_unresolved and d_histogram 8, d_summary 16, the packed image
+ *     (vkv_pack_volume) 256;
  *   - matrices are column-major float[16] (glm::mat4 byte layout).
  */
 #ifndef VKVOLUME_AMD_H

@@ -158,3 +158,51 @@ def wave_patch_log2(p):
     vx, vy = (float(np.sum((np.array(list(d)[:3], np.float64) * dim) ** 2)) for d in (p.ray_gen.ddx, p.ray_gen.ddy))
     q = np.sqrt(vx / vy) if vx > 0.0 and vy > 0.0 else 1.0
     return 2 if q >= 1.6 else (4 if q <= 1.0 / 1.6 else 3)
+
+
+GUARD_BYTES = 256
+
+
+class Guarded:
+    """Handle of a guarded() buffer: `buf` is the whole allocation (uint8), bytes [start, stop) of it are the payload, every other byte
+    is a guard that was filled with `fill`."""
+
+    def __init__(self, buf, start, stop, fill):
+        self.buf, self.start, self.stop, self.fill = buf, start, stop, fill
+
+    def check(self):
+        """Indices (into the allocation) of the guard bytes that no longer hold the fill; empty when nothing strayed."""
+        whole = self.buf.cpu().numpy()
+        bad = np.flatnonzero(whole != self.fill)
+        return [int(i) for i in bad if not self.start <= i < self.stop]
+
+
+def guarded(array_or_shape, offset=0, fill=0, device="cpu", dtype=np.uint8):
+    """A buffer inside ONE allocation laid out as [256 guard bytes + offset | payload | 256 guard bytes], the payload starting `offset` bytes
+    past a 256-byte boundary; the whole allocation, payload included, is pre-filled with the byte `fill`.  `array_or_shape`: a numpy array or
+    torch tensor (copied into the payload) or a shape of `dtype` elements (the payload keeps the fill: an output that every byte of which
+    must be written).  Returns (payload view, Guarded handle).  A kernel that strays by a few bytes lands in memory the test owns and
+    shows in handle.check(); nothing relies on a fault."""
+    import torch
+    src = None
+    if isinstance(array_or_shape, torch.Tensor):
+        src = array_or_shape.contiguous()
+        shape, tdtype = tuple(src.shape), src.dtype
+    elif isinstance(array_or_shape, np.ndarray):
+        src = torch.from_numpy(np.ascontiguousarray(array_or_shape))
+        shape, tdtype = tuple(src.shape), src.dtype
+    else:
+        shape = (array_or_shape,) if isinstance(array_or_shape, int) else tuple(array_or_shape)
+        tdtype = torch.from_numpy(np.zeros(1, dtype)).dtype
+    item = torch.empty(0, dtype=tdtype).element_size()
+    nbytes = item * int(np.prod(shape, dtype=np.int64))
+    assert 0 <= offset and offset % item == 0, "offset %d is no multiple of the element size %d" % (offset, item)
+    # 255 spare bytes: the allocator promises less than 256-byte alignment on some devices (the CPU: 64)
+    buf = torch.full((255 + GUARD_BYTES + offset + nbytes + GUARD_BYTES,), fill, dtype=torch.uint8, device=device)
+    start = (-buf.data_ptr()) % 256 + GUARD_BYTES + offset
+    view = buf[start:start + nbytes].view(tdtype).view(shape)
+    if src is not None:
+        view.copy_(src)
+    assert view.data_ptr() % 256 == offset % 256 and view.data_ptr() == buf.data_ptr() + start
+    assert start >= GUARD_BYTES and buf.numel() - (start + nbytes) >= GUARD_BYTES
+    return view, Guarded(buf, start, start + nbytes, fill)
