@@ -720,6 +720,28 @@ typedef struct VkvSlabOptions
  * allocation, no host wait; the kernels use no scratch memory), so after one direct call on `stream` it can be captured into a hipGraph. */
 int vkv_render_slab(vkv_ctx *ctx, const VkvRenderParams *params, const VkvSlabOptions *slab, void *stream);
 
+/* ---- 3x3x3 filters of the uint8 volume --------------------------------------------------------------------------- */
+enum VkvFilterKind { VKV_FILTER_BINOMIAL3 = 0, VKV_FILTER_MEDIAN3 = 1 };
+
+/* d_dst = d_src filtered over each voxel's 3x3x3 neighbourhood; the result is an ordinary volume for every other entry point.
+ * Neighbourhood: for a voxel (x, y, z) of a W x H x D volume, N is the 27 bytes src[clamp(z + dz, 0, D - 1)][clamp(y + dy, 0, H - 1)]
+ * [clamp(x + dx, 0, W - 1)], dx, dy, dz in {-1, 0, 1}: clamp-to-edge, as the samplers do.  On a face a clamped neighbour counts as often as
+ * it occurs; an axis of extent 1 gives three copies.
+ * VKV_FILTER_BINOMIAL3: S = sum of w(dx) w(dy) w(dz) N with w = (1, 2, 1) (the weights sum to 64, S <= 16320), dst = (S + 32) >> 6: integer
+ * arithmetic with ONE rounding at the end, not one per axis.  A constant volume is a fixed point.
+ * VKV_FILTER_MEDIAN3: dst = the 14th smallest of the 27 bytes of N (index 13 after sorting).
+ * box == NULL: every voxel of d_dst is written.  With a box exactly its voxels are written, at their volume positions in d_dst, from d_src's
+ * box grown by one voxel and clamped; every other byte of d_dst is untouched.
+ * Keeping a filtered copy current across vkv_update_volume_region(box) on the raw volume: after the update, vkv_filter_volume over that box
+ * grown by one voxel per side and clipped to the volume, on the same stream, leaves the copy byte-equal to a full refilter.
+ * d_src and d_dst may start at any byte; every extent is accepted, widths below 4 and axes of length 1 included; nothing before the first or
+ * past the last byte of either buffer is read or written.  Every argument is checked before anything is enqueued, and a rejected call writes
+ * nothing.  VKV_E_INVALID_ARGUMENT: a null ctx or pointer, a zero extent, an unknown kind, an empty box or one not inside `extent`, byte
+ * ranges [d_src, d_src + n) and [d_dst, d_dst + n) (n = W H D) that overlap (an in-place stencil would read its own output).
+ * VKV_E_UNSUPPORTED: a volume too large for one launch.  One kernel launch and nothing else (no memset or copy node, no allocation, no host
+ * wait, no scratch block; the kernels use no scratch memory), so after one direct call on `stream` it can be captured into a hipGraph. */
+int vkv_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, int32_t kind, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

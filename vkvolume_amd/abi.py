@@ -141,6 +141,7 @@ class IsoOptions(C.Structure):
 
 
 SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2  # VkvSlabMode
+FILTER_BINOMIAL3, FILTER_MEDIAN3 = 0, 1  # VkvFilterKind
 
 
 class SlabOptions(C.Structure):

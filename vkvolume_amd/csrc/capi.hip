@@ -1149,6 +1149,27 @@ int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, cons
 	return launch_histogram_occupied_count(ctx, d_histogram, tf, d_count, (hipStream_t) stream);
 }
 
+// every argument is checked before the first launch (and before the device is touched)
+int vkv_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, int32_t kind, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_src || !d_dst || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "filter_volume: null pointer or zero extent");
+	if (kind != VKV_FILTER_BINOMIAL3 && kind != VKV_FILTER_MEDIAN3)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "filter_volume: unknown kind %d", (int) kind);
+	if (const int rc = check_box(ctx, "filter_volume", extent, box))
+		return rc;
+	if (!filter_launch_ok(extent))        // also: the byte count below fits 64 bits
+		return set_error(ctx, VKV_E_UNSUPPORTED, "filter_volume: volume too large for one launch");
+	const uint64_t  n = (uint64_t) extent.width * extent.height * extent.depth;
+	const uintptr_t a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
+	if (a < b ? b - a < n : a - b < n)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "filter_volume: d_src and d_dst overlap (the filter does not run in place)");
+	DeviceGuard guard(ctx->device);
+	return launch_filter_volume(ctx, d_src, d_dst, extent, box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth}, kind, (hipStream_t) stream);
+}
+
 // every argument is checked before the first launch
 int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
                      void *d_summary, void *stream)

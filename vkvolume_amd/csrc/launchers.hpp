@@ -92,8 +92,14 @@ int launch_cell_summary(vkv_ctx *ctx, const uint8_t *d_vol, const uint8_t *d_gra
 int launch_occupancy_from_summary(vkv_ctx *ctx, const void *d_summary, const uint8_t *d_vol, const uint8_t *d_grad, bool use_gradient, uint8_t *scratch,
                                   VkvExtent3D e, uint8_t *d_map, VkvExtent3D me, uint64_t *d_unresolved, hipStream_t s);
 
+// ---- filter.hip
+// what the filter launch can take
+bool filter_launch_ok(VkvExtent3D e);
+// vkv_filter_volume after the entry point's argument checks: the voxels of b (inside e) of d_dst from d_src, kind a VkvFilterKind
+int launch_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, int kind, hipStream_t s);
+
 // ---- raymarch.hip
-// vkv_render / vkv_render_batch (n frames in one launch) after the entry point's argument checks
+// vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);
 int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, const float *alpha_luts, hipStream_t s);
 // vkv_prepare_render: everything a later launch of these n parameter blocks on s takes from the context, created now

@@ -23,7 +23,7 @@ EXPORTS = [
     "vkv_transfer_function_texture_device", "vkv_update_transfer_function", "vkv_update_volume_region",
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
-    "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab",
+    "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab", "vkv_filter_volume",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -112,6 +112,7 @@ def load():
     L.vkv_render_mip.argtypes = [vp, P(abi.RenderParams), P(abi.MipOptions), vp]
     L.vkv_render_isosurface.argtypes = [vp, P(abi.RenderParams), P(abi.IsoOptions), vp]
     L.vkv_render_slab.argtypes = [vp, P(abi.RenderParams), P(abi.SlabOptions), vp]
+    L.vkv_filter_volume.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), i32, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -339,6 +340,14 @@ class Context:
 
     def render_slab_rc(self, params, slab, stream=0):
         return self._lib.vkv_render_slab(self.handle, None if params is None else C.byref(params), None if slab is None else C.byref(slab), stream)
+
+    def filter_volume(self, d_src, d_dst, extent, box, kind, stream=0):
+        """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""
+        self.check(self.filter_volume_rc(d_src, d_dst, extent, box, kind, stream))
+
+    def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
+        """Like filter_volume() but returns the status code (error-path tests)."""
+        return self._lib.vkv_filter_volume(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), int(kind), stream)
 
     def occupancy_map_from_summary(self, d_summary, d_volume, d_gradient, d_tf, tf, extent, d_map, map_extent, d_unresolved=None, stream=0):
         """vkv_occupancy_map_from_summary: vkv_occupancy_map's map, decided from the cell summaries where they are certain; d_unresolved

@@ -229,6 +229,39 @@ class Volume:
         self.ctx.volume_histogram(_ptr(self.volume), _ptr(grad), self.extent, box, mode, _ptr(out), _stream())
         return out
 
+    _FILTER_KINDS = (abi.FILTER_BINOMIAL3, abi.FILTER_MEDIAN3)
+
+    def filter(self, kind, passes=1, out=None, box=None):
+        """The volume filtered over each voxel's clamp-to-edge 3x3x3 neighbourhood on the current stream (vkv_filter_volume): a uint8 tensor
+        of the volume's shape.  ``kind``: abi.FILTER_BINOMIAL3 (weights (1, 2, 1)^3 / 64, one rounding) or abi.FILTER_MEDIAN3.  ``passes`` > 1
+        applies the filter that many times, ping-ponging between ``out`` and one temporary buffer.  ``out``: a contiguous uint8 tensor of
+        the volume's shape on its device that does not alias it.  ``box`` (an abi.Box, or ((x0, y0, z0), (width, height, depth))): only the
+        box's voxels of ``out`` are written, which keeps a filtered copy current after update_region(); it needs ``out`` and passes == 1.
+        ``self.volume`` and the derived buffers are not touched: loading the result as a volume is the caller's decision."""
+        if kind not in self._FILTER_KINDS:
+            raise ValueError("Volume.filter: unknown kind %r" % (kind,))
+        if int(passes) != passes or passes < 1:
+            raise ValueError("Volume.filter: passes must be a positive integer")
+        if out is None:
+            if box is not None:
+                raise ValueError("Volume.filter: a box needs `out` (the bytes outside the box are kept)")
+            out = torch.empty_like(self.volume)
+        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
+            raise ValueError("Volume.filter: `out` must be a contiguous uint8 tensor of shape %s on %s" % (tuple(self.volume.shape), self.volume.device))
+        if box is not None:
+            if passes != 1:
+                raise ValueError("Volume.filter: a box takes one pass")
+            if not isinstance(box, abi.Box):
+                (x0, y0, z0), (w, h, d) = box
+                box = abi.Box(x0, y0, z0, w, h, d)
+        tmp = torch.empty_like(self.volume) if passes > 1 else None
+        src = self.volume
+        for i in range(1, passes + 1):
+            dst = out if (passes - i) % 2 == 0 else tmp
+            self.ctx.filter_volume(_ptr(src), _ptr(dst), self.extent, box, kind, _stream())
+            src = dst
+        return out
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
