@@ -2,7 +2,7 @@
  * vkv_oracle.c — CPU restatement of the reference's ray-caster hot path (see vkv_oracle.h).
  *
  * TEST INFRASTRUCTURE ONLY — never linked into, called from, or shipped with the product.
- * PARITY UNPINNED — the reference has no golden vectors and cannot run here (vkv_oracle.h).
+ * PARITY — pinned to the reference's shader text where oracle/_ref was built; host code unpinned (vkv_oracle.h).
  *
  * Every function cites the reference file:line it follows.  Where the reference relies on
  * Vulkan fixed-function behaviour with implementation latitude (trilinear filtering, UNORM

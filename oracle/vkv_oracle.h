@@ -5,9 +5,11 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it, and only as the checker
  * or as the timed CPU baseline.  The product (vkvolume_amd/) never links or calls it.
  *
- * PARITY UNPINNED: the reference (LDeakin/VkVolume) has no tests, golden vectors or fixtures for
- * this path, and it cannot be built or run in this environment (GLSL + Vulkan + an un-vendored
- * Vulkan-Samples submodule).  This oracle is therefore pinned by
+ * PARITY: the reference (LDeakin/VkVolume) has no tests, golden vectors or fixtures for this path and
+ * its application cannot be built without Vulkan, but its shaders compile as C++ (oracle/glsl_host/,
+ * `make ref`): where that library was built, tests/test_reference_text_cpu.py holds this oracle to the
+ * shader text itself, bit for bit.  The host formulas and the ray generator stay unpinned
+ * (DESIGN.md section 2).  The oracle is also pinned by
  *   (1) brute-force mathematical known-answer tests for the distance maps (tests/test_oracle_*.py),
  *   (2) closed-form checks (sphere entry/exit, ESS invariance, monotonicity), and
  *   (3) self-generated golden vectors under tests/golden/ (regression only).

@@ -1,7 +1,7 @@
 """ctypes/numpy front-end of the CPU oracle (``oracle/vkv_oracle.c``).
 
 TEST INFRASTRUCTURE ONLY: imported by ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of
-``bench.py`` — never by the product package.  PARITY UNPINNED (see ``vkv_oracle.h``).
+``bench.py`` — never by the product package.  Parity: see ``vkv_oracle.h`` and ``vkv_ref.py``.
 """
 import ctypes as C
 import os

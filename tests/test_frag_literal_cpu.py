@@ -45,23 +45,35 @@ def literal_counts(scene, p, entry, pins):
     return out
 
 
+_FRAMES = {}
+
+
+def frame(mode, ert, sf):
+    """One configuration's scene, parameters, oracle frame, ray entries and the literal's counters under "plain" arithmetic (by far the slowest
+    part: pure Python).  Kept, unchanged, for tests/test_reference_text_cpu.py, which holds the compiled shader text to the same literal."""
+    key = (mode, ert, sf)
+    if key not in _FRAMES:
+        scene = scene_for(sf)
+        view, proj = T.orbit(33.0 + 40.0 * mode, image_size=IMAGE)
+        ro = abi.RenderOptions(skipping_type=mode, clip_distance=1.0, early_ray_termination=ert)
+        p = scene.params(view, proj, IMAGE, ro)
+        ref = scene.render(p)
+        pe = scene.params(view, proj, IMAGE, abi.RenderOptions(skipping_type=mode, clip_distance=1.0, early_ray_termination=ert, test=abi.TEST_RAY_ENTRY))
+        entry = scene.render(pe).color  # rgb = ray_entry, a = 1 where the pixel has a fragment
+        _FRAMES[key] = (scene, p, ref, entry, literal_counts(scene, p, entry, "plain"))
+    return _FRAMES[key]
+
+
 @pytest.mark.parametrize("sf", [0.5, 1.0, 2.0])
 @pytest.mark.parametrize("ert", [True, False])
 @pytest.mark.parametrize("mode", [abi.SKIP_NONE, abi.SKIP_BLOCK, abi.SKIP_DISTANCE, abi.SKIP_ANISOTROPIC_DISTANCE])
 def test_oracle_counters_equal_the_literal_transliteration(mode, ert, sf, capsys):
-    scene = scene_for(sf)
-    view, proj = T.orbit(33.0 + 40.0 * mode, image_size=IMAGE)
-    ro = abi.RenderOptions(skipping_type=mode, clip_distance=1.0, early_ray_termination=ert)
-    p = scene.params(view, proj, IMAGE, ro)
-    ref = scene.render(p)
-    pe = scene.params(view, proj, IMAGE, abi.RenderOptions(skipping_type=mode, clip_distance=1.0, early_ray_termination=ert, test=abi.TEST_RAY_ENTRY))
-    entry = scene.render(pe).color  # rgb = ray_entry, a = 1 where the pixel has a fragment
+    scene, p, ref, entry, plain = frame(mode, ert, sf)
     assert ref.counts[..., 0].sum() > 100
     build = literal_counts(scene, p, entry, "build")
     bad = np.argwhere((build != ref.counts).any(-1))
     assert len(bad) == 0, "build-pinned literal differs from the oracle at pixels %r: literal %r oracle %r" % (
         bad[:5].tolist(), [build[y, x].tolist() for y, x in bad[:5]], [ref.counts[y, x].tolist() for y, x in bad[:5]])
-    plain = literal_counts(scene, p, entry, "plain")
     diff = np.argwhere((plain != ref.counts).any(-1))
     covered = int((entry[..., 3] > 0).sum())
     with capsys.disabled():
