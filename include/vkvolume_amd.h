@@ -742,6 +742,41 @@ enum VkvFilterKind { VKV_FILTER_BINOMIAL3 = 0, VKV_FILTER_MEDIAN3 = 1 };
  * wait, no scratch block; the kernels use no scratch memory), so after one direct call on `stream` it can be captured into a hipGraph. */
 int vkv_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, int32_t kind, void *stream);
 
+/* ---- isosurface meshes: marching tetrahedra ------------------------------------------------------------------------
+ * The isosurface of the uint8 volume as a triangle list in a defined order, every step fp32 IEEE.  f(x, y, z) = (float) byte * kInv255; a
+ * voxel is inside if f >= iso (the hit rule of vkv_render_isosurface).  Coordinates are voxel indices: voxel centres lie at integers.
+ * Cubes: origins (x, y, z), 0 <= x < W - 1, 0 <= y < H - 1, 0 <= z < D - 1 (an axis of length 1 gives none); with a box only the cubes whose
+ * eight voxels all lie in it.  Corner j = dx + 2 dy + 4 dz.  A cube's six tetrahedra, in this order, are the corners T0 = (0, 1, 3, 7),
+ * T1 = (0, 1, 5, 7), T2 = (0, 2, 3, 7), T3 = (0, 2, 6, 7), T4 = (0, 4, 5, 7), T5 = (0, 4, 6, 7): the paths from corner 0 to corner 7 that add
+ * the axes in a permutation's order; T1, T2, T5 come from odd permutations.  Neighbouring cubes cut their shared face alike.
+ * Triangles of a tetrahedron: its local vertices are 0 .. 3 in the order listed; mask m has bit i set if local vertex i is inside; m = 0
+ * and m = 15 give nothing.  With `ins` and `out` the inside and outside local vertices in rising order and an edge written as a pair:
+ *   one inside vertex p:   [(p, out0), (p, out1), (p, out2)];        one outside vertex p:   [(ins0, p), (ins1, p), (ins2, p)];
+ *   two and two, a, b = ins, c, d = out:  A = (a, c), B = (a, d), C = (b, d), D = (b, c);  [A, B, C] and [A, C, D].
+ * The second and third vertex of each triangle are swapped iff (the tetrahedron is odd) XOR (m in {2, 5, 8, 10, 11, 14}); then
+ * (v1 - v0) x (v2 - v0) points from the inside vertices towards the outside ones in all 6 x 14 cases.
+ * Vertex on an edge (i, j): a = the voxel of the LOWER local index, b = the other (b - a is 0 or 1 per axis); t = (iso - f_a) / (f_b - f_a),
+ * one subtraction each and a correctly rounded division, no clamp; component c is (float) a_c + t where b_c != a_c, else (float) a_c.  It
+ * depends on the edge alone, so shared vertices are bit-equal and the mesh is watertight under exact comparison.  A voxel with f == iso gives
+ * t = 0 or 1 and triangles of zero area; they are kept.
+ * Order: by cube (x fastest, then y, then z), then tetrahedron 0 .. 5, then triangle; at most 12 per cube.  9 floats per triangle:
+ * v0.xyz v1.xyz v2.xyz.
+ * d_counts[0] = the exact total, whatever the capacity; d_counts[1] = min(total, capacity_triangles); d_triangles receives exactly the first
+ * d_counts[1] triangles of the list and not one float beyond them.  capacity_triangles == 0 (d_triangles may be NULL) is the counting call:
+ * no emit work is enqueued.  d_max_map (NULL: dense): vkv_max_map of d_volume with map_extent; a tile of cubes whose cells all hold a byte B
+ * with B * kInv255 < iso is counted as empty without reading a voxel: the same bits.  d_scratch: vkv_isosurface_mesh_scratch_bytes(extent,
+ * box) bytes (at least 16; 0 for an extent or box this call rejects), 8-byte aligned, the per-row-segment counts and their scan; its
+ * contents mean nothing between calls.  d_counts must be 8-byte aligned, d_triangles 4-byte aligned; d_volume may start at any byte.
+ * Kernels only (no allocation, no memset or copy node, no host wait, no atomics; the kernels use no scratch memory): after one direct call on
+ * `stream` it can be captured into a hipGraph.  Two runs give the same bytes.  Nothing in the context is written.  Every argument is checked
+ * before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_volume, d_scratch or d_counts, a
+ * zero extent, a non-finite iso, an empty box or one not inside `extent`, a max map without a valid map_extent, a non-zero capacity with a
+ * NULL d_triangles, a misaligned d_scratch, d_counts or d_triangles.  VKV_E_UNSUPPORTED: a volume too large for the launches.  Every extent
+ * is accepted; nothing outside any buffer is read or written. */
+size_t vkv_isosurface_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
+                        VkvExtent3D map_extent, void *d_scratch, float *d_triangles, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

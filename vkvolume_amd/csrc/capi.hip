@@ -1170,6 +1170,33 @@ int vkv_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExt
 	return launch_filter_volume(ctx, d_src, d_dst, extent, box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth}, kind, (hipStream_t) stream);
 }
 
+size_t vkv_isosurface_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return mesh_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
+                        VkvExtent3D map_extent, void *d_scratch, float *d_triangles, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_volume || !d_scratch || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: null pointer or zero extent");
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: iso must be finite");
+	if (const int rc = check_box(ctx, "isosurface_mesh", extent, box))
+		return rc;
+	if (d_max_map && !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: the max map needs a valid map_extent");
+	if (capacity_triangles != 0 && !d_triangles)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: a capacity of %llu triangles needs d_triangles", (unsigned long long) capacity_triangles);
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || ((uintptr_t) d_triangles & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: d_scratch and d_counts must be 8-byte aligned, d_triangles 4-byte aligned");
+	if (!mesh_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh: volume too large for the launches");
+	DeviceGuard guard(ctx->device);
+	return launch_isosurface_mesh(ctx, d_volume, extent, box ? *box : VkvBox{0, 0, 0, extent.width, extent.height, extent.depth}, iso, d_max_map, map_extent,
+	                              d_scratch, d_triangles, capacity_triangles, d_counts, (hipStream_t) stream);
+}
+
 // every argument is checked before the first launch
 int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
                      void *d_summary, void *stream)

@@ -98,6 +98,14 @@ bool filter_launch_ok(VkvExtent3D e);
 // vkv_filter_volume after the entry point's argument checks: the voxels of b (inside e) of d_dst from d_src, kind a VkvFilterKind
 int launch_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, int kind, hipStream_t s);
 
+// ---- mesh.hip
+// vkv_isosurface_mesh_scratch_bytes: 0 for an extent or box that is not accepted; what the launches can take (box null: the whole volume)
+size_t mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+bool   mesh_launch_ok(VkvExtent3D e, const VkvBox *box);
+// vkv_isosurface_mesh after the entry point's argument checks (b inside e; me is read with a max map only)
+int launch_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, const uint8_t *d_max_map, VkvExtent3D me,
+                           void *d_scratch, float *d_triangles, uint64_t capacity, uint64_t *d_counts, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

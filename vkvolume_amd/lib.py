@@ -24,6 +24,7 @@ EXPORTS = [
     "vkv_volume_histogram", "vkv_histogram_occupied_count",
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
     "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab", "vkv_filter_volume",
+    "vkv_isosurface_mesh_scratch_bytes", "vkv_isosurface_mesh",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -113,6 +114,9 @@ def load():
     L.vkv_render_isosurface.argtypes = [vp, P(abi.RenderParams), P(abi.IsoOptions), vp]
     L.vkv_render_slab.argtypes = [vp, P(abi.RenderParams), P(abi.SlabOptions), vp]
     L.vkv_filter_volume.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), i32, vp]
+    L.vkv_isosurface_mesh_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
+    L.vkv_isosurface_mesh_scratch_bytes.restype = C.c_size_t
+    L.vkv_isosurface_mesh.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, vp, abi.Extent3D, vp, vp, C.c_uint64, vp, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -341,6 +345,18 @@ class Context:
     def render_slab_rc(self, params, slab, stream=0):
         return self._lib.vkv_render_slab(self.handle, None if params is None else C.byref(params), None if slab is None else C.byref(slab), stream)
 
+    def isosurface_mesh(self, d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_triangles, capacity, d_counts, stream=0):
+        """vkv_isosurface_mesh: the marching-tetrahedra triangles of `box` (None: the whole volume) at `iso` in their defined order; d_counts
+        (2 x uint64) = the total and min(total, capacity); d_triangles the first min(total, capacity) triangles, 9 floats each.  d_max_map /
+        map_extent None: dense.  d_scratch: mesh_scratch_bytes(extent, box) bytes."""
+        self.check(self.isosurface_mesh_rc(d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_triangles, capacity, d_counts, stream))
+
+    def isosurface_mesh_rc(self, d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_triangles, capacity, d_counts, stream=0):
+        """Like isosurface_mesh() but returns the status code (error-path tests)."""
+        return self._lib.vkv_isosurface_mesh(self.handle, d_volume, extent, None if box is None else C.byref(box), float(iso), d_max_map,
+                                             abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_triangles, int(capacity),
+                                             d_counts, stream)
+
     def filter_volume(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""
         self.check(self.filter_volume_rc(d_src, d_dst, extent, box, kind, stream))
@@ -442,3 +458,9 @@ def load_data(path, header):
     if rc != 0:
         raise RuntimeError("load_data failed (%d)" % rc)
     return out
+
+
+def mesh_scratch_bytes(extent, box=None):
+    """vkv_isosurface_mesh_scratch_bytes: the scratch vkv_isosurface_mesh needs for `box` (None: the whole volume) of `extent`; 0 for an extent
+    or box the call rejects"""
+    return int(load().vkv_isosurface_mesh_scratch_bytes(extent, None if box is None else C.byref(box)))

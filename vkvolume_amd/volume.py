@@ -262,6 +262,43 @@ class Volume:
             src = dst
         return out
 
+    def extract_isosurface(self, iso, box=None, use_max_map=False, capacity=None):
+        """The isosurface of the volume at ``iso`` as triangles on the current stream (vkv_isosurface_mesh: marching tetrahedra in a defined
+        order, voxel-index coordinates): returns ``(triangles, total)``, an [n, 3, 3] float32 device tensor and the surface's triangle count.
+        ``capacity`` None: a counting call, ONE host read of the total, then the emit into a tensor of exactly that size; total is an int.
+        With a capacity it is one call and no host read: n = capacity, the rows past min(total, capacity) are not written, and total is the
+        call's two-element int64 device tensor (the total, the rows written).  ``box`` (an abi.Box, or ((x0, y0, z0), (width, height,
+        depth))): only the cubes inside it.  ``use_max_map``: skip empty tiles through the volume's max map (build_max_map() first; the
+        same bits).  vkvolume_amd.mesh turns the result into texture or model space, welds it and writes STL."""
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if use_max_map and self.max_map is None:
+            raise RuntimeError("Volume.extract_isosurface: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError("Volume.extract_isosurface: capacity must be a non-negative integer or None")
+        nbytes = lib.mesh_scratch_bytes(self.extent, box)
+        if nbytes == 0:
+            raise ValueError("Volume.extract_isosurface: the box is empty or outside the volume, or the volume is too large")
+        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        counts = torch.empty((2,), dtype=torch.int64, device=self.device)
+        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
+
+        def call(tri, n):
+            self.ctx.isosurface_mesh(_ptr(self.volume), self.extent, box, iso, _ptr(max_map), map_extent, _ptr(scratch), _ptr(tri), n, _ptr(counts),
+                                     _stream())
+
+        if capacity is not None:
+            tri = torch.empty((int(capacity), 3, 3), dtype=torch.float32, device=self.device)
+            call(tri if capacity else None, int(capacity))
+            return tri, counts
+        call(None, 0)
+        total = int(counts[0].item())
+        tri = torch.empty((total, 3, 3), dtype=torch.float32, device=self.device)
+        if total:
+            call(tri, total)
+        return tri, total
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
