@@ -29,6 +29,8 @@ PROGRAM = r"""
 #include <cstdio>
 #include <cstring>
 #include <random>
+#include <thread>
+#include <vector>
 
 using namespace vkv;
 

@@ -9,6 +9,7 @@
 // Every variant must render the product's frames bit for bit (tools/lab/run_lab.py checks before it times).
 #pragma once
 
+#include "../../vkvolume_amd/csrc/context.hpp"
 #include "../../vkvolume_amd/csrc/raymarch_core.hpp"
 
 // round 3's flag values (the product's kLean* are a different, smaller set)

@@ -1,4 +1,4 @@
-// addr_tables.hpp — host-only builder of the address tables of the packed sampling image (packed_addr_lut, capi.hip).  Plain C++: no HIP
+// addr_tables.hpp — host-only builder of the address tables of the packed sampling image (packed_addr_lut, context.hip).  Plain C++: no HIP
 // header, so that a test driver built with the host compiler can include it (tests/test_addr_tables_cpu.py).
 //
 // Two-level tables (uint32 words): in-macro-brick terms of x, y, z at words 0, 32, 64 (padded index b & 31); macro-brick terms (b >> 5) of x

@@ -1,10 +1,11 @@
-// launchers.hpp — every function of the library that crosses a translation unit on the host side: the kernel launchers, the limits the
-// entry points check before they enqueue anything, and the few helpers of raymarch.hip that capi.hip calls.  capi.hip and every file that
-// defines one of them include it, so a changed signature is a compile error, not a link error.  All of them return VKV_OK or an error code
-// with the context's error text set; `s` is the stream the work is enqueued on; device pointers are named d_*.
+// launchers.hpp — every function of the library that crosses a translation unit on the host side: the kernel launchers, the limits the entry
+// points check before they enqueue anything, the helpers of raymarch.hip that capi.hip and context.hip call, and the argument checks of capi.hip
+// that other files share.  The entry points' files (capi.hip, context.hip, exchange.hip) and every file that defines one of them include it, so a
+// changed signature is a compile error, not a link error.  All of them return VKV_OK or an error code with the context's error text set; `s` is
+// the stream the work is enqueued on; device pointers are named d_*.  The context: context.hpp; host arithmetic without HIP: ../host/host_arith.hpp.
 #pragma once
 
-#include "vkv_device.hpp"
+#include "context.hpp"
 
 namespace vkv
 {
@@ -112,38 +113,13 @@ int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut
 int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, const float *alpha_luts, hipStream_t s);
 // vkv_prepare_render: everything a later launch of these n parameter blocks on s takes from the context, created now
 int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream_t s);
-// vkv_screen_tile_rect: the screen bound of the volume's box in whole tiles
-void screen_tile_rect(const VkvRayCastUniform *rc, const VkvRayGen *rg, uint32_t iw, uint32_t ih, uint32_t tw, uint32_t th, uint32_t align, VkvTileRect *out);
 // loads the start-order kernels' code object on the current device (vkv_register_target)
 void load_feedback_code();
 
-// ---- checks of a VkvRenderParams that vkv_render / vkv_render_batch (capi.hip) and the direct renderers (direct_render.hpp) share.  Defined here
-// (static: no symbol) because their callers are in different translation units; `what` is the entry point's name in the messages.
-// The tile schedule: tile size a multiple of 16 and tile_stride > 0, the rectangle inside the image, the schedule inside the image or the
-// rectangle.  (The fill_outside check sits between them, where vkv_render has always had it; the direct renderers reject fill_outside before.)
-static int check_tile_schedule(vkv_ctx *ctx, const char *what, const VkvRenderParams *P)
-{
-	const VkvTileSchedule &t = P->tiles;
-	if (t.tile_width == 0 || t.tile_height == 0 || (t.tile_width % 16) || (t.tile_height % 16) || t.tile_stride == 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: tile size must be a positive multiple of 16 and tile_stride > 0", what);
-	const uint64_t tiles_x = (P->image_width + t.tile_width - 1) / t.tile_width, tiles_y = (P->image_height + t.tile_height - 1) / t.tile_height;
-	const bool     whole   = t.rect.w == 0 || t.rect.h == 0;
-	if (!whole && ((uint64_t) t.rect.x0 + t.rect.w > tiles_x || (uint64_t) t.rect.y0 + t.rect.h > tiles_y))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: the schedule's tile rectangle runs past the image", what);
-	if (t.fill_outside && !whole && (t.compact || t.tile_first != 0 || t.tile_stride != 1 || (uint64_t) t.tile_count != (uint64_t) t.rect.w * t.rect.h))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: fill_outside needs image-indexed outputs and the whole rectangle in one launch (tile_first 0, tile_stride 1)", what);
-	const uint64_t scheduled = whole ? tiles_x * tiles_y : (uint64_t) t.rect.w * t.rect.h;
-	if (t.tile_count && (uint64_t) t.tile_first + (uint64_t) (t.tile_count - 1) * t.tile_stride >= scheduled)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: tile schedule runs past the %s", what, whole ? "image" : "tile rectangle");
-	return VKV_OK;
-}
-// The buffers: the packed image's alignment, and at least one output (own_output: an output of the entry point's own options is set)
-static int check_render_buffers(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, bool own_output)
-{
-	if (P->d_packed_volume && ((uintptr_t) P->d_packed_volume & 255u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_packed_volume must be 256-byte aligned", what);
-	if (!P->d_out_color && !P->d_out_rgba8 && !P->d_out_counts && !P->d_out_depth && !own_output)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: no output buffer", what);
-	return VKV_OK;
-}
+// ---- capi.hip: argument checks that entry points of several files share; `what` is the entry point's name in the messages
+// VKV_OK for null (the whole volume) or a box inside extent
+int check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box);
+// a VkvRenderParams' tile schedule and buffers (vkv_render / vkv_render_batch and the direct renderers, direct_render.hpp)
+int check_tile_schedule(vkv_ctx *ctx, const char *what, const VkvRenderParams *P);
+int check_render_buffers(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, bool own_output);
 }        // namespace vkv

@@ -1,11 +1,8 @@
 // raymarch.hip — launchers of the ray-march integrator (device code: raymarch_core.hpp and the headers it includes).
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <new>
 #include <vector>
 
 #include "raymarch_inst.hpp"
@@ -143,147 +140,29 @@ LeanChoice choose_lean(const RayMarchArgs &a, const VkvTuning &T)
 	return {1, lean_lds_bytes(1, a.lut_words, a.W, a.H, a.D)};
 }
 
-// (skipping type, early ray termination) -> the translation unit that holds the kernels of that pair
-static int launch_single(vkv_ctx *ctx, int skip, bool ert, int sched, const VkvTuning &T, int grad, RayMarchArgs &a, hipStream_t s)
+// (skipping type, early ray termination) -> the translation unit that holds the kernels of that pair: f(RayMarchLaunchers<SKIP, ERT>{});
+// false for a bad skipping type
+template <class F>
+static bool with_launchers(int skip, bool ert, F &&f)
 {
 	switch (skip)
 	{
-		case VKV_SKIP_NONE: return ert ? RayMarchLaunchers<VKV_SKIP_NONE, true>::single(ctx, sched, T, grad, a, s) : RayMarchLaunchers<VKV_SKIP_NONE, false>::single(ctx, sched, T, grad, a, s);
-		case VKV_SKIP_BLOCK: return ert ? RayMarchLaunchers<VKV_SKIP_BLOCK, true>::single(ctx, sched, T, grad, a, s) : RayMarchLaunchers<VKV_SKIP_BLOCK, false>::single(ctx, sched, T, grad, a, s);
-		case VKV_SKIP_DISTANCE: return ert ? RayMarchLaunchers<VKV_SKIP_DISTANCE, true>::single(ctx, sched, T, grad, a, s) : RayMarchLaunchers<VKV_SKIP_DISTANCE, false>::single(ctx, sched, T, grad, a, s);
-		case VKV_SKIP_ANISOTROPIC_DISTANCE:
-			return ert ? RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, true>::single(ctx, sched, T, grad, a, s) : RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, false>::single(ctx, sched, T, grad, a, s);
-		default: return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: bad skipping_type %d", skip);
-	}
-}
-
-static void load_render_code(int skip, bool ert)
-{
-	switch (skip)
-	{
-		case VKV_SKIP_NONE: ert ? RayMarchLaunchers<VKV_SKIP_NONE, true>::load() : RayMarchLaunchers<VKV_SKIP_NONE, false>::load(); break;
-		case VKV_SKIP_BLOCK: ert ? RayMarchLaunchers<VKV_SKIP_BLOCK, true>::load() : RayMarchLaunchers<VKV_SKIP_BLOCK, false>::load(); break;
-		case VKV_SKIP_DISTANCE: ert ? RayMarchLaunchers<VKV_SKIP_DISTANCE, true>::load() : RayMarchLaunchers<VKV_SKIP_DISTANCE, false>::load(); break;
-		case VKV_SKIP_ANISOTROPIC_DISTANCE: ert ? RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, true>::load() : RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, false>::load(); break;
-		default: break;
+		case VKV_SKIP_NONE: ert ? f(RayMarchLaunchers<VKV_SKIP_NONE, true>{}) : f(RayMarchLaunchers<VKV_SKIP_NONE, false>{}); return true;
+		case VKV_SKIP_BLOCK: ert ? f(RayMarchLaunchers<VKV_SKIP_BLOCK, true>{}) : f(RayMarchLaunchers<VKV_SKIP_BLOCK, false>{}); return true;
+		case VKV_SKIP_DISTANCE: ert ? f(RayMarchLaunchers<VKV_SKIP_DISTANCE, true>{}) : f(RayMarchLaunchers<VKV_SKIP_DISTANCE, false>{}); return true;
+		case VKV_SKIP_ANISOTROPIC_DISTANCE: ert ? f(RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, true>{}) : f(RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, false>{}); return true;
+		default: return false;
 	}
 }
 
 // the start-order kernels of this file (vkv_register_target: the first launch into a registered target would load them otherwise)
 void load_feedback_code()
 {
-
 	hipFuncAttributes at;
 	(void) hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_tile_order_from_cost));
 }
 
-static bool launch_batch(int skip, bool ert, int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t grid, uint32_t gpf, LeanChoice c, bool no_counts, hipStream_t s)
-{
-	switch (skip)
-	{
-		case VKV_SKIP_NONE: ert ? RayMarchLaunchers<VKV_SKIP_NONE, true>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s) : RayMarchLaunchers<VKV_SKIP_NONE, false>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s); return true;
-		case VKV_SKIP_BLOCK: ert ? RayMarchLaunchers<VKV_SKIP_BLOCK, true>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s) : RayMarchLaunchers<VKV_SKIP_BLOCK, false>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s); return true;
-		case VKV_SKIP_DISTANCE: ert ? RayMarchLaunchers<VKV_SKIP_DISTANCE, true>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s) : RayMarchLaunchers<VKV_SKIP_DISTANCE, false>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s); return true;
-		case VKV_SKIP_ANISOTROPIC_DISTANCE:
-			ert ? RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, true>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s) : RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, false>::batch(grad, d_frames, n, grid, gpf, c, no_counts, s);
-			return true;
-		default: return false;
-	}
-}
-
-static bool launch_pull(vkv_ctx *ctx, int skip, bool ert, int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, LeanChoice c, uint64_t units, hipStream_t s)
-{
-	switch (skip)
-	{
-		case VKV_SKIP_NONE: ert ? RayMarchLaunchers<VKV_SKIP_NONE, true>::pull(ctx, grad, d_frames, n, d_heads, c, units, s) : RayMarchLaunchers<VKV_SKIP_NONE, false>::pull(ctx, grad, d_frames, n, d_heads, c, units, s); return true;
-		case VKV_SKIP_BLOCK: ert ? RayMarchLaunchers<VKV_SKIP_BLOCK, true>::pull(ctx, grad, d_frames, n, d_heads, c, units, s) : RayMarchLaunchers<VKV_SKIP_BLOCK, false>::pull(ctx, grad, d_frames, n, d_heads, c, units, s); return true;
-		case VKV_SKIP_DISTANCE: ert ? RayMarchLaunchers<VKV_SKIP_DISTANCE, true>::pull(ctx, grad, d_frames, n, d_heads, c, units, s) : RayMarchLaunchers<VKV_SKIP_DISTANCE, false>::pull(ctx, grad, d_frames, n, d_heads, c, units, s); return true;
-		case VKV_SKIP_ANISOTROPIC_DISTANCE:
-			ert ? RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, true>::pull(ctx, grad, d_frames, n, d_heads, c, units, s) : RayMarchLaunchers<VKV_SKIP_ANISOTROPIC_DISTANCE, false>::pull(ctx, grad, d_frames, n, d_heads, c, units, s);
-			return true;
-		default: return false;
-	}
-}
-
-// Conservative pixel bound of what a frame's fragments can see: the unit box [0,1]^3 (texture space) cut by the clipping plane (kept side:
-// dot(plane_tex.xyz, p) + plane_tex.w >= 0 - ray_setup_impl starts a ray at t0 = max(t_box_near, t_plane) and needs t0 < t_box_far, so every
-// fragment's ray holds a point of that clipped box), as seen through the ray generator of the kernel: pixel (px, py) looks along
-// dir00 + (px + 0.5) ddx + (py + 0.5) ddy from cam, so a point c is seen at the (fx, fy) with c - cam = g (dir00 + fx ddx + fy ddy), g > 0.
-// The clipped box is convex and the map to (fx, fy) keeps convexity in front of the camera: the bound is the min / max over its VERTICES - the
-// box corners on the kept side and the points where the plane cuts an edge (the plane is moved outwards by 1e-4 of its normal's length
-// first: the device evaluates in fp32) -, widened by two pixels (the device evaluates the direction in fp32: it can disagree with this
-// double-precision solve by a tiny fraction of a pixel).  A vertex at or behind the camera plane, or a degenerate generator, disables it
-// (kScreenBoundNone); no vertex at all = nothing can be seen (kScreenBoundEmpty).  With the application's plane (through a point in front of the
-// camera, facing away from it) every vertex lies in front of the camera, also for a camera inside the box: round 6 - the bound of the
-// un-clipped box (rounds 2-5) gave up there.  Pixels outside cannot have a fragment, whatever the depth test does afterwards.
-enum
-{
-	kScreenBoundNone  = 0,
-	kScreenBoundEmpty = 1,
-	kScreenBoundRect  = 2
-};
-int screen_bound(const float cam[3], const float dir00[3], const float ddx[3], const float ddy[3], const float plane_tex[4], double out[4])
-{
-	// inverse of M = [ddx ddy dir00] (columns) by the adjugate
-	const double M[3][3] = {{ddx[0], ddy[0], dir00[0]}, {ddx[1], ddy[1], dir00[1]}, {ddx[2], ddy[2], dir00[2]}};
-	double       inv[3][3], scale = 0.0;
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j)
-		{
-			const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-			inv[j][i]    = M[i1][j1] * M[i2][j2] - M[i1][j2] * M[i2][j1];        // cofactor (i, j) -> adjugate (j, i)
-			scale        = std::max(scale, std::fabs(M[i][j]));
-		}
-	const double det = M[0][0] * inv[0][0] + M[0][1] * inv[1][0] + M[0][2] * inv[2][0];
-	if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale * scale * scale))
-		return kScreenBoundNone;
-	// vertices of the clipped box
-	double    vert[8 + 12][3];
-	int       n_vert = 0;
-	double    sd[8];        // signed plane values of the corners (+ the outward shift)
-	bool      clip = plane_tex != nullptr;
-	if (clip)
-	{
-		const double pn = std::sqrt((double) plane_tex[0] * plane_tex[0] + (double) plane_tex[1] * plane_tex[1] + (double) plane_tex[2] * plane_tex[2]);
-		if (!std::isfinite(pn) || !(pn > 0.0) || !std::isfinite((double) plane_tex[3]))
-			clip = false;        // no usable plane: the whole box
-		for (int c = 0; c < 8 && clip; ++c)
-			sd[c] = (double) plane_tex[0] * (c & 1) + (double) plane_tex[1] * ((c >> 1) & 1) + (double) plane_tex[2] * ((c >> 2) & 1) + (double) plane_tex[3] + 1e-4 * pn;
-	}
-	for (int c = 0; c < 8; ++c)
-		if (!clip || sd[c] >= 0.0)
-			vert[n_vert][0] = (double) (c & 1), vert[n_vert][1] = (double) ((c >> 1) & 1), vert[n_vert][2] = (double) ((c >> 2) & 1), ++n_vert;
-	if (clip)
-		for (int c = 0; c < 8; ++c)
-			for (int axis = 0; axis < 3; ++axis)
-			{
-				const int d = c | (1 << axis);
-				if (d == c || (sd[c] >= 0.0) == (sd[d] >= 0.0))
-					continue;        // (each edge once: from its corner with the axis bit clear) the plane does not cut this edge
-				const double u = sd[c] / (sd[c] - sd[d]);
-				for (int k = 0; k < 3; ++k)
-					vert[n_vert][k] = (double) ((c >> k) & 1) + u * ((double) ((d >> k) & 1) - (double) ((c >> k) & 1));
-				++n_vert;
-			}
-	if (n_vert == 0)
-		return kScreenBoundEmpty;
-	double lo_x = 1e300, hi_x = -1e300, lo_y = 1e300, hi_y = -1e300;
-	for (int i = 0; i < n_vert; ++i)
-	{
-		const double v[3] = {vert[i][0] - cam[0], vert[i][1] - cam[1], vert[i][2] - cam[2]};
-		const double fa = (inv[0][0] * v[0] + inv[0][1] * v[1] + inv[0][2] * v[2]) / det, fb = (inv[1][0] * v[0] + inv[1][1] * v[1] + inv[1][2] * v[2]) / det;
-		const double g  = (inv[2][0] * v[0] + inv[2][1] * v[1] + inv[2][2] * v[2]) / det;
-		if (!(g > 1e-6) || !std::isfinite(fa) || !std::isfinite(fb))
-			return kScreenBoundNone;        // a vertex beside or behind the camera: its projection says nothing
-		lo_x = std::min(lo_x, fa / g), hi_x = std::max(hi_x, fa / g), lo_y = std::min(lo_y, fb / g), hi_y = std::max(hi_y, fb / g);
-	}
-	// pixel p is sampled at p + 0.5
-	out[0] = std::floor(lo_x - 0.5) - 2.0, out[1] = std::ceil(hi_x - 0.5) + 2.0, out[2] = std::floor(lo_y - 0.5) - 2.0, out[3] = std::ceil(hi_y - 0.5) + 2.0;
-	if (out[1] < 0.0 || out[3] < 0.0 || out[0] > 4.0e9 || out[2] > 4.0e9)
-		return kScreenBoundEmpty;        // off screen
-	return kScreenBoundRect;
-}
-
+// the conservative pixel bound of the clipped box (screen_bound: ../host/host_arith.cpp) as the kernel's cull rectangle
 static void screen_bound_of_box(RayMarchArgs &a, const VkvTuning &T)
 {
 	a.cull_x0 = 0u, a.cull_x1 = ~0u, a.cull_y0 = 0u, a.cull_y1 = ~0u;
@@ -300,28 +179,6 @@ static void screen_bound_of_box(RayMarchArgs &a, const VkvTuning &T)
 	}
 	a.cull_x0 = b[0] <= 0.0 ? 0u : (uint32_t) b[0], a.cull_y0 = b[2] <= 0.0 ? 0u : (uint32_t) b[2];
 	a.cull_x1 = b[1] >= 4.0e9 ? ~0u : (uint32_t) b[1], a.cull_y1 = b[3] >= 4.0e9 ? ~0u : (uint32_t) b[3];
-}
-
-// vkv_screen_tile_rect: the same bound in whole tiles
-void screen_tile_rect(const VkvRayCastUniform *rc, const VkvRayGen *rg, uint32_t iw, uint32_t ih, uint32_t tw, uint32_t th, uint32_t align, VkvTileRect *out)
-{
-	const uint32_t tiles_x = (iw + tw - 1) / tw, tiles_y = (ih + th - 1) / th;
-	*out = VkvTileRect{0u, 0u, tiles_x, tiles_y};
-	double    b[4];
-	const int kind = screen_bound(rc->camera_pos_tex, rg->dir00, rg->ddx, rg->ddy, rc->plane_tex, b);
-	if (kind == kScreenBoundNone)
-		return;
-	if (kind == kScreenBoundEmpty || b[0] >= (double) iw || b[2] >= (double) ih)
-	{
-		*out = VkvTileRect{0u, 0u, 1u, 1u};
-		return;
-	}
-	const uint32_t x0 = b[0] <= 0.0 ? 0u : (uint32_t) b[0], y0 = b[2] <= 0.0 ? 0u : (uint32_t) b[2];
-	const uint32_t x1 = b[1] >= (double) (iw - 1) ? iw - 1 : (uint32_t) b[1], y1 = b[3] >= (double) (ih - 1) ? ih - 1 : (uint32_t) b[3];        // inclusive
-	const uint32_t q = align > 1 ? align : 1u;
-	uint32_t       tx0 = (x0 / tw) / q * q, ty0 = (y0 / th) / q * q;
-	uint32_t       tx1 = std::min(tiles_x, (x1 / tw + q) / q * q), ty1 = std::min(tiles_y, (y1 / th + q) / q * q);        // exclusive
-	*out = VkvTileRect{tx0, ty0, tx1 - tx0, ty1 - ty0};
 }
 
 // VkvRenderParams -> kernel arguments.  Returns VKV_OK with a.nblocks == 0 when the schedule is empty.
@@ -419,11 +276,11 @@ static bool apply_feedback(vkv_ctx *ctx, RayMarchArgs &a, hipStream_t s)
 	const uint32_t              period = ctx->tuning.feedback_period < 1u ? 1u : ctx->tuning.feedback_period;
 	if (!ctx->tuning.feedback || !target || a.tile_count < 64 || ctx->d_debug_orders)
 		return false;
-	for (auto *e : ctx->feedback)
+	for (auto &e : ctx->feedback)
 		if (e->target == target && e->img_w == a.img_w && e->img_h == a.img_h && e->tile_w == a.tile_w && e->tile_h == a.tile_h && e->first == a.tile_first &&
 		    e->stride == a.tile_stride && e->count == a.tile_count && e->org_x == a.org_x && e->org_y == a.org_y && e->tiles_x == a.tiles_x)
 		{
-			f = e;
+			f = e.get();
 			break;
 		}
 	if (!f)
@@ -476,15 +333,15 @@ static bool apply_feedback(vkv_ctx *ctx, RayMarchArgs &a, hipStream_t s)
 	++f->frames;
 	if (f->has_cost && !stale)
 	{
-		a.tile_order = f->d_order;        // the order the last sort behind a frame into this target left
+		a.tile_order = f->d_order.get();        // the order the last sort behind a frame into this target left
 		++f->used;
 	}
 	if (!measure)
 		return false;
 	for (int i = 0; i < 3; ++i)
 		f->view_dir[i] = dir[i], f->view_pos[i] = a.cam[i];
-	a.tile_cost = f->d_cost;
-	a.order_out = f->d_order;        // written by the sort that FOLLOWS this frame's render on the stream
+	a.tile_cost = f->d_cost.get();
+	a.order_out = f->d_order.get();        // written by the sort that FOLLOWS this frame's render on the stream
 	f->has_cost = true;
 	return true;
 }
@@ -506,7 +363,9 @@ int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut
 	// start-order feedback as in vkv_render_batch (with early ray termination only; the sort runs BEHIND the render on the stream): a
 	// frame that runs alone also ends earlier when its long tiles start first (C3: 0.256 -> 0.246 ms)
 	const bool sort = sched == (int) kSchedLean && ert && apply_feedback(ctx, a, s);
-	int        rc2 = launch_single(ctx, P->options.skipping_type, ert, sched, T, grad, a, s);
+	int        rc2 = VKV_OK;
+	if (!with_launchers(P->options.skipping_type, ert, [&](auto l) { rc2 = decltype(l)::single(ctx, sched, T, grad, a, s); }))
+		rc2 = set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: bad skipping_type %d", P->options.skipping_type);
 	if (rc2 == VKV_OK && sort)
 	{
 		hipLaunchKernelGGL(k_tile_order_from_cost, dim3(1), dim3(256), 0, s, a.tile_cost, a.order_out, a.tile_count);
@@ -528,7 +387,7 @@ int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream
 			rc = fill_render_args(ctx, &P[i], lut, a, s, T, true, true);
 		if (rc != VKV_OK)
 			return rc;
-		load_render_code(P[i].options.skipping_type, P[i].options.early_ray_termination != 0);
+		(void) with_launchers(P[i].options.skipping_type, P[i].options.early_ray_termination != 0, [](auto l) { decltype(l)::load(); });
 	}
 	load_feedback_code();
 	if (!stream_scratch(ctx, s, true).p)
@@ -562,7 +421,7 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 		vkv_ctx::UploadSlot &u = scratch.block->upload[(scratch.block->upload_next + k) % vkv_ctx::kUploadRing];
 		if (!u.pinned)
 			continue;
-		if (u.pending && hipEventQuery(u.done) == hipSuccess)
+		if (u.pending && hipEventQuery(u.done.get()) == hipSuccess)
 			u.pending = false;
 		if (!u.pending)
 		{
@@ -659,7 +518,8 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 				if (failed)
 					return set_error(ctx, VKV_E_UNSUPPORTED, "render_batch: no argument block for a captured launch: %s", hipGetErrorString(ea != hipSuccess ? ea : eb));
 				c.pinned = static_cast<uint8_t *>(hp), c.device = static_cast<uint8_t *>(dp);
-				ctx->capture_slots.push_back(c);
+				c.own_pinned.reset(c.pinned), c.own_device.reset(c.device);        // the context's from here on
+				ctx->capture_slots.push_back(std::move(c));
 				slot = &ctx->capture_slots.back();
 			}
 			slot->in_use = true, slot->owner = stream_key(s);
@@ -675,7 +535,7 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 		return set_error(ctx, (int) e, "render_batch: argument upload: %s", hipGetErrorString(e));
 	if (ring_slot)
 	{        // the slot is the copy's source until this event has completed; if it cannot be recorded, wait for the copy here
-		if (hipEventRecord(ring_slot->done, s) == hipSuccess)
+		if (hipEventRecord(ring_slot->done.get(), s) == hipSuccess)
 			ring_slot->pending = true;
 		else
 			(void) hipStreamSynchronize(s);
@@ -714,17 +574,12 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 		pull = a.packed == b.packed && a.tf_bits == b.tf_bits && a.tf == b.tf && a.addr_lut == b.addr_lut && a.W == b.W && a.H == b.H && a.D == b.D &&
 		       std::memcmp(a.alpha_lut, b.alpha_lut, sizeof(a.alpha_lut)) == 0;
 	}
-	if (pull)
-	{
-		if (!launch_pull(ctx, P[0].options.skipping_type, ert, grad, d_frames, n, d_heads, choice, units, s))
-			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: bad skipping_type %d", P[0].options.skipping_type);
-		if (any_sort)
-			hipLaunchKernelGGL(k_tile_orders_from_cost, dim3(n), dim3(256), 0, s, d_frames);
-		const int rc_pull = check_launch(ctx, "render_batch");
-		slot_guard.armed = slot_guard.armed && rc_pull != VKV_OK;
-		return rc_pull;
-	}
-	if (!launch_batch(P[0].options.skipping_type, ert, grad, d_frames, n, (uint32_t) grid, gpf, choice, no_counts, s))
+	if (!with_launchers(P[0].options.skipping_type, ert, [&](auto l) {
+		    if (pull)
+			    decltype(l)::pull(ctx, grad, d_frames, n, d_heads, choice, units, s);
+		    else
+			    decltype(l)::batch(grad, d_frames, n, (uint32_t) grid, gpf, choice, no_counts, s);
+	    }))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: bad skipping_type %d", P[0].options.skipping_type);
 	// behind the render, on the same stream: the costs it measured become the start order of the next frames into these targets (the
 	// sort is not in front of anybody's render this way; in front it cost 70 us per 20-frame block of three launches)

@@ -51,7 +51,7 @@ struct RayMarchArgs
 	uint32_t        clamp_always;   // k_raymarch_lean: 1 = no clamp-free march loop (VkvTuning.clamp_always: A/B switch, same bits)
 	float           mapf[3], mapb[3];        // k_raymarch_lean, clamp-free loop: the map extent as floats, and the largest floats below them
 	uint32_t        wave_pw_log2;            // k_raymarch_lean: log2 of the width in pixels of a wave's 64-pixel patch (2, 3, 4: 4x16, 8x8, 16x4)
-	const uint32_t *addr_lut;       // k_raymarch_lean: per-axis byte offsets of the packed image (packed_addr_lut, vkv_device.hpp), or null
+	const uint32_t *addr_lut;       // k_raymarch_lean: per-axis byte offsets of the packed image (packed_addr_lut, context.hpp), or null
 	uint32_t        lut_y, lut_z, lut_words;        // word offsets of the y and z tables inside addr_lut and the length of the two-level tables
 	uint32_t        lut_full;       // word offset inside addr_lut of the prebuilt per-voxel-index tables (16-byte aligned, zero-padded to 16 bytes), 0 = none
 	uint32_t        cull_x0, cull_x1, cull_y0, cull_y1;        // k_raymarch_lean: pixels outside [x0, x1] x [y0, y1] cannot see the volume's box

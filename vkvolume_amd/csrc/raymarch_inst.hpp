@@ -4,6 +4,7 @@
 // side), and by raymarch.hip, which only sees the declarations (extern template) and dispatches on the two run-time options.
 #pragma once
 
+#include "context.hpp"
 #include "raymarch_core.hpp"
 
 namespace vkv

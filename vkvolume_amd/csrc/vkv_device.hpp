@@ -9,13 +9,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <map>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
 #include "../../include/vkvolume_amd.h"
 
 namespace vkv
@@ -218,210 +211,5 @@ __host__ __device__ __forceinline__ size_t packed_brick_offset(int bx, int by, i
 	return (macro * 512 + sub) * 256;
 }
 
-}        // namespace vkv
-
-// Host-side context (capi.hip owns it).
-// Device scratch is handed out PER STREAM (stream_scratch): calls on different streams never touch the same bytes.  Calls on one stream are
-// ordered on the device, but an entry point enqueues several operations that pass data through the block (a bit table, argument blocks,
-// queue heads), and two host threads enqueueing on the same stream could interleave them: each block has a lock, held by the entry point
-// from its first write into the block to its last enqueue (stream_scratch returns the block locked).  hipStreamPerThread is one handle for
-// a different stream in every thread: per-stream state is keyed by (handle, calling thread) for it (stream_key).  Lock order: a block's
-// lock, then ctx->mutex briefly; ctx->mutex is never held while a block's lock is being taken.
-//
-// Device memory policy (include/vkvolume_amd.h, "Conventions"): vkv_create allocates one ARENA with two regions - the scratch blocks of
-// up to kScratchReserve streams, and the small immutable tables a launch needs (tile start orders, address tables) - plus a pinned host
-// mirror of the table region.  A table is written into the mirror and uploaded from there asynchronously on the stream of the launch that
-// first needs it; launches on other streams are ordered behind that upload with an event until it has completed.  Nothing is freed or
-// re-used while a launch could read it: tables stay until vkv_trim (a set-up call that waits for the device, then empties the region) or
-// vkv_destroy; when the region is full a launch runs without the table.  Only set-up calls (vkv_prepare_render, vkv_register_target) fall
-// back to hipMalloc when a region is full.
-// the key of a stream's state in the context: the handle, and for hipStreamPerThread also the calling thread
-struct VkvStreamKey
-{
-	hipStream_t     stream = nullptr;
-	std::thread::id thread;
-	bool operator<(const VkvStreamKey &o) const { return stream != o.stream ? stream < o.stream : thread < o.thread; }
-	bool operator==(const VkvStreamKey &o) const { return stream == o.stream && thread == o.thread; }
-};
-
-struct vkv_ctx
-{
-	int   device;
-	int   cu_count;        // compute units of the device (grid of the resident-workgroup kernels)
-	char  error[512];
-	void *d_trace;        // diagnostic wave timeline buffer (vkv_debug_trace), normally null
-	const uint32_t *d_debug_orders;        // diagnostic per-frame tile start orders of vkv_render_batch (vkv_debug_tile_orders), normally null
-	uint32_t        debug_order_frames, debug_order_count;
-	std::mutex      mutex;
-	VkvTuning       tuning;        // vkv_create: defaults + environment; vkv_set_tuning replaces it (read under the mutex, copied per call)
-	// ---- device arena ----
-	uint8_t *           arena = nullptr;
-	size_t              arena_bytes = 0;
-	size_t              table_base = 0;          // the arena's first table_base bytes are scratch blocks, the rest holds tables
-	size_t              scratch_used = 0, table_used = 0;
-	uint8_t *           table_mirror = nullptr;  // pinned host twin of the table region: the source of every asynchronous table upload
-	std::vector<void *> overflow;                // hipMalloc blocks set-up calls took for tables when the region was full; freed by vkv_trim / vkv_destroy
-	std::vector<void *> overflow_scratch;        // ... for scratch blocks beyond the reserve; freed by vkv_destroy
-	// Argument blocks of vkv_render_batch launches captured into hipGraphs.  A captured launch owns a SLOT: a pinned host block (the graph's copy
-	// node reads its source at every replay) and a device block of its own (the copy's target and the kernels' argument pointer: a graph may be
-	// replayed on any stream, next to other graphs and to live launches, so it must not share the capture stream's scratch block).  kCaptureSlots
-	// slots are set aside by vkv_create; later ones are allocated during the capture.  A slot belongs to the stream it was captured on until
-	// vkv_release_captured(stream), vkv_trim or vkv_destroy.
-	struct CaptureSlot
-	{
-		uint8_t *   pinned = nullptr, *device = nullptr;
-		VkvStreamKey owner;
-		bool         in_use = false, pooled = false;
-	};
-	uint8_t *                capture_pool = nullptr, *capture_pool_device = nullptr;
-	std::vector<CaptureSlot> capture_slots;
-	// a stream's scratch block: kScratchBytes of device memory and the lock of the entry point that is passing data through it
-	// upload: a small ring of pinned host slots (carved out of upload_pool by vkv_create, for the arena's blocks) in which vkv_render_batch
-	// assembles the argument blocks it uploads into the block; a slot is taken again only after the event recorded behind the copy that read
-	// it has completed (claimed under the block's lock).  A block without slots (beyond the reserve), or with every slot still being read,
-	// uploads from pageable memory.
-	struct UploadSlot
-	{
-		uint8_t *  pinned = nullptr;
-		hipEvent_t done = nullptr;
-		bool       pending = false;        // `done` has been recorded and not yet seen complete
-	};
-	static constexpr uint32_t kUploadRing = 4;
-	struct ScratchBlock
-	{
-		uint8_t *  p = nullptr;
-		std::mutex lock;
-		UploadSlot upload[kUploadRing];
-		uint32_t   upload_next = 0;
-	};
-	uint8_t *upload_pool = nullptr;        // pinned, kScratchReserve x kUploadRing x kUploadSlotBytes; freed by vkv_destroy
-	// opacity-correction tables by the two floats they depend on (bit compare): a camera move re-uses them, a slider move adds one
-	struct AlphaLut
-	{
-		uint32_t factor_bits, sampling_bits;
-		float    lut[256];
-	};
-	std::vector<AlphaLut> alpha_luts;        // at most kAlphaLuts, replaced round robin
-	uint32_t              alpha_next = 0;
-	std::vector<std::unique_ptr<ScratchBlock>> scratch_blocks;        // every block the context has handed out (stable addresses)
-	std::map<VkvStreamKey, ScratchBlock *>     scratch;               // stream -> its block
-	std::vector<ScratchBlock *>                free_scratch;          // blocks given back by vkv_release_stream
-	// an immutable device table with its host copy (the source of the asynchronous upload: it must outlive the call)
-	struct Table
-	{
-		std::vector<uint32_t> host;
-		uint32_t *            d = nullptr;
-		hipEvent_t            uploaded = nullptr;        // recorded behind the upload
-		hipStream_t           upload_stream = nullptr;
-		bool                  ready = false;            // the upload is known to have completed: no more waits
-	};
-	// start orders of tile schedules (centre of the image first), built on first use and kept (heap objects: stable addresses)
-	struct TileOrder
-	{
-		uint32_t tiles_x, tiles_y, tile_w, tile_h, img_w, img_h, first, stride, count;
-		float    mix_heavy, mix_spread;
-		Table    table;
-	};
-	std::vector<TileOrder *> tile_orders;
-	// per-axis address tables of the packed sampling image, per volume extent
-	struct AddrLut
-	{
-		int      W, H, D;
-		uint32_t lut_y, lut_z, words;
-		uint32_t full;        // word offset of the per-voxel-index tables behind the two-level ones (addr_tables.hpp), 0 = none
-		Table    table;
-	};
-	std::vector<AddrLut *> addr_luts;
-	// start-order feedback of the targets registered with vkv_register_target: the tile costs the last measured frame into the target left
-	// behind and the buffer its longest-first order is written to (raymarch.hip, apply_feedback); heap objects, so their addresses stay valid
-	struct TileFeedback
-	{
-		const void *target;
-		uint32_t    img_w, img_h, tile_w, tile_h, first, stride, count;
-		uint32_t    org_x, org_y, tiles_x;        // the schedule's tile rectangle as the launcher sees it (pixels of its first tile, tile columns)
-		uint32_t *  d_cost, *d_order;
-		bool        has_cost;        // a frame has been rendered into this target with the cost buffer attached
-		uint32_t    frames;          // frames rendered into this target so far (costs are measured and sorted every few frames)
-		uint32_t    measured_at = 0; // value of `frames` at the last measured frame
-		uint32_t    period = 8;      // frames until the next measurement (doubles while no frame can use the measured order)
-		uint32_t    used = 0;        // frames since the last measurement that started in its order
-		float       view_dir[3] = {0, 0, 0}, view_pos[3] = {0, 0, 0};        // central ray and camera position (texture space) of the measured frame
-		float       prev_dir[3] = {0, 0, 0}, prev_pos[3] = {0, 0, 0};        // ... of the previous frame into the target (measured or not)
-		bool        has_prev = false;
-	};
-	std::vector<TileFeedback *> feedback;
-};
-
-namespace vkv
-{
-int  set_error(vkv_ctx *ctx, int code, const char *fmt, ...);
-int  check_launch(vkv_ctx *ctx, const char *what);
-int  check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box);        // VKV_OK for null (the whole volume) or a box inside extent
-static inline bool extent_ok(VkvExtent3D e) { return e.width > 0 && e.height > 0 && e.depth > 0; }
-// ceil(volume / map) must reproduce a valid block size (src/compute_distance_map.cpp:110-113)
-static inline bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_ok(me) && me.width <= e.width && me.height <= e.height && me.depth <= e.depth; }
-// voxels per map cell on one axis: ceil(extent / map extent)
-static inline uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
-VkvStreamKey stream_key(hipStream_t stream);
-// this stream's scratch block (out of the arena on first use, kept until vkv_release_stream / vkv_destroy), LOCKED until the object goes:
-// an entry point keeps it from its first write into the block to its last enqueue.  p == nullptr + error set when there is no room.
-struct StreamScratch
-{
-	uint8_t *                    p = nullptr;
-	std::unique_lock<std::mutex> lock;
-	vkv_ctx::ScratchBlock *      block = nullptr;        // its pinned upload ring (used under `lock`)
-};
-StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = false);
-// start order of a tile schedule: entry indices sorted by the distance of the tile's centre from the image centre (device array of
-// `count` uint32, cached per schedule shape); nullptr when the table cannot be allocated (the kernel then takes the tiles in order)
-// Per-axis byte offsets of the packed sampling image: the offset of the footprint whose padded base texel is (bx, by, bz) is
-// X(bx) + Y(by) + Z(bz) (the brick index and the position inside the brick are sums of per-axis terms), each in two levels:
-// in-macro-brick term of b & 31 + macro-brick term of b >> 5.  Layout of the device array (uint32 words): in-macro tables of x, y, z
-// at 0, 32, 64; macro terms of x at 96, of y at *lut_y, of z as 64-bit values at *lut_z (even), *words in all; behind them, at word *full
-// (16-byte aligned; 0 = not built), the sums X[W + 2], Y[H + 2], Z[D + 2] per padded voxel index in units of two bytes, zero-padded to a multiple
-// of 16 bytes: what a workgroup's LDS holds (stage_full_lut), built once per extent.  nullptr if it cannot be allocated.
-// Both tables come out of the context's arena and are uploaded on `stream` when new (see vkv_ctx); `setup` = called from a set-up entry
-// point: may fall back to hipMalloc when the arena is full.  nullptr when there is no room: the launch then runs without the table.
-const uint32_t *packed_addr_lut(vkv_ctx *ctx, int W, int H, int D, uint32_t *lut_y, uint32_t *lut_z, uint32_t *words, uint32_t *full, hipStream_t stream, bool setup = false);
-const uint32_t *tile_start_order(vkv_ctx *ctx, uint32_t img_w, uint32_t img_h, uint32_t tile_w, uint32_t tile_h, uint32_t first, uint32_t stride, uint32_t count,
-                                 hipStream_t stream, bool setup = false);
-VkvTuning tuning_of(vkv_ctx *ctx);        // a copy of the context's tuning block (taken under its mutex)
-constexpr size_t kScratchBytes     = 128 * 1024;
-constexpr size_t kScratchReserve   = 16;          // scratch blocks the arena keeps for streams (2 MiB of the default 8 MiB)
-constexpr uint32_t kCaptureSlots   = 32;          // vkv_render_batch launches one context may have captured into hipGraphs
-constexpr size_t   kUploadSlotBytes = 64 * 1024;   // pinned slot of a scratch block's upload ring: the pull heads + VKV_MAX_BATCH argument blocks
-constexpr size_t   kAlphaLuts = 8;
-constexpr size_t   kCaptureSlotBytes = 96 * 1024;  // >= the pull heads + VKV_MAX_BATCH argument blocks (= the scratch block's argument area)
-constexpr uint32_t kMaxDynamicLds  = 64 * 1024 - 1024;        // what a lean kernel may ask for as dynamic LDS (its tables; no hipFuncSetAttribute is called)
-constexpr size_t kTfBitsOffset     = 0;           // 256*256 bits = 8 KiB: TF bit table of the map update / the voxel count (+ 8 words behind it: its column mask)
-constexpr size_t kQueueHeadsOffset = 8192 + 64;       // 8 x u32 tile-queue heads of the persistent ray-march scheduler
-constexpr size_t kTfRangesOffset   = 16 * 1024;       // 64 KiB: row-range ORs / ANDs of the bit table (cells.hip, k_tf_ranges), written and read
-                                                      // within one occupancy-from-summary launch pair; shares bytes with the batch argument
-                                                      // blocks below, which only a later launch on the same stream writes (stream order)
-constexpr size_t kPullHeadsBytes   = 2048;        // 8 ticket counters of k_raymarch_lean_pull, 256 bytes apart (one memory channel each), directly in
-                                                  // front of the argument blocks: one upload zeroes the counters and brings the arguments
-constexpr uint32_t kPullHeadStride = 64;         // in uint32 words
-constexpr size_t kBatchArgsOffset  = 32 * 1024 + kPullHeadsBytes;        // vkv_render_batch: kMaxBatch argument blocks
-constexpr uint32_t kMaxBatch       = VKV_MAX_BATCH;
-static_assert(kTfRangesOffset >= kQueueHeadsOffset + 32 && kTfRangesOffset + 4 * 2048 * 8 <= kScratchBytes, "the range table must fit the scratch block");
-
-// Every device entry point runs on the context's device whatever the calling thread's current device is, and leaves the
-// caller's current device as it found it.
-struct DeviceGuard
-{
-	int  prev = -1;
-	bool switched = false;
-	explicit DeviceGuard(int device)
-	{
-		if (hipGetDevice(&prev) == hipSuccess && prev != device)
-			switched = hipSetDevice(device) == hipSuccess;
-	}
-	~DeviceGuard()
-	{
-		if (switched)
-			(void) hipSetDevice(prev);
-	}
-	DeviceGuard(const DeviceGuard &) = delete;
-	DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+constexpr uint32_t kPullHeadStride = 64;        // uint32 words between two ticket counters of k_raymarch_lean_pull (256 bytes: one memory channel each; context.hpp)
 }        // namespace vkv
