@@ -777,6 +777,43 @@ size_t vkv_isosurface_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
 int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
                         VkvExtent3D map_extent, void *d_scratch, float *d_triangles, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
 
+/* ---- indexed isosurface meshes with vertex normals ---------------------------------------------------------------------
+ * The same surface as a vertex list and three vertex numbers per triangle.  Everything not restated here is as for vkv_isosurface_mesh: f,
+ * the inside rule, cubes, tetrahedra, case rules, winding, coordinates, the box rule, the max-map rule (a tile of VOXELS whose cells all stay
+ * below iso owns no vertex and starts no triangle: the same bits), and that every argument is checked before anything is enqueued.
+ * Vertex list.  An EDGE is a pair (voxel v, direction d = dx + 2 dy + 4 dz, 1 <= d <= 7; v + d means v + (dx, dy, dz)) with both v and v + d
+ * inside the box, and every axis of the box at least 2 voxels long (an axis of length 1 gives no cubes and no edges).  These are exactly the
+ * tetrahedron edges of the box's cubes: every such edge runs from a cube corner a to a corner b with a & b == a.  An edge is CROSSING if
+ * inside(v) != inside(v + d).  The vertex list is the crossing edges ordered by v (x fastest, then y, then z), then by d rising: one vertex
+ * per crossing edge.  Position: a = v, b = v + d, t = (iso - f_a) / (f_b - f_a), component c is (float) a_c + t where d has that axis, else
+ * (float) a_c: the vertex rule above, so positions are bit-equal to the triangle list's.  Where a voxel equals iso exactly, several edges
+ * give bit-equal positions; they stay separate vertices, as the triangle list keeps its triangles of zero area.  3 floats per vertex.
+ * Normals (d_normals may be NULL: none are computed).  For a voxel p of the VOLUME, G_c(p) = (int) vol[p + e_c] - (int) vol[p - e_c], both
+ * neighbours clamped to the volume (not to the box: a box's normals equal the whole volume's).  n_c = -((float) G_c(a) + t * (float) (G_c(b)
+ * - G_c(a))) with a, b, t of the vertex: both integers are exact in fp32, then one multiplication, one addition (no FMA) and the sign flip.
+ * Not normalised (the length is in bytes per two voxels), may be zero, points from the inside to the outside on a smooth field.  3 floats
+ * per vertex, parallel to d_vertices.
+ * Indices.  The triangles of vkv_isosurface_mesh in the same order, 3 x uint32 each (v0 v1 v2): the edge (a, b) of the cube with origin o is
+ * the edge (o + a, a ^ b), and its index is that edge's position in the FULL vertex list, reduced mod 2^32; it depends on neither capacity.
+ * d_counts holds four values: [0] = the total number of triangles, [1] = min([0], capacity_triangles), [2] = the total number of vertices,
+ * [3] = min([2], capacity_vertices).  Exactly the first [1] triangles' indices and the first [3] vertices (and their normals, if asked for)
+ * are written, and not one element beyond them.  A capacity of zero for either list (its pointers NULL or not) enqueues no emit for that
+ * list; both zero is the counting call.  capacity_vertices may not exceed 0xffffffff, so a call with [2] == [3] has exact indices; a larger
+ * surface is extracted box by box.  d_scratch: vkv_isosurface_mesh_indexed_scratch_bytes(extent, box) bytes (at least 16, a multiple of 8;
+ * 0 for an extent or box this call rejects; 16 bytes per 256 x-adjacent voxels of a row of the box), 8-byte aligned; its contents mean
+ * nothing between calls.  d_volume may start at any byte; every extent is accepted; nothing outside any buffer is read or written.
+ * Kernels only (no allocation, no memset or copy node, no host wait, no atomics; the kernels use no scratch memory): two runs give the same
+ * bytes, and after one direct call on `stream` it can be captured into a hipGraph.  Nothing in the context is written.  A rejected call
+ * writes nothing.  VKV_E_INVALID_ARGUMENT: everything vkv_isosurface_mesh rejects (a null ctx, d_volume, d_scratch or d_counts, a zero
+ * extent, a non-finite iso, an empty box or one not inside `extent`, a max map without a valid map_extent), capacity_vertices > 0xffffffff,
+ * a non-zero capacity_vertices with a NULL d_vertices or capacity_triangles with a NULL d_indices, d_normals with capacity_vertices == 0, a
+ * d_vertices, d_normals or d_indices that is not 4-byte aligned, a d_counts or d_scratch that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a
+ * volume too large for the launches. */
+size_t vkv_isosurface_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
+                                VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
+                                uint32_t *d_indices, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

@@ -378,6 +378,42 @@ int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exten
 	                              d_scratch, d_triangles, capacity_triangles, d_counts, (hipStream_t) stream);
 }
 
+size_t vkv_isosurface_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return mesh_indexed_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
+                                VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
+                                uint32_t *d_indices, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_volume || !d_scratch || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: null pointer or zero extent");
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: iso must be finite");
+	if (const int rc = check_box(ctx, "isosurface_mesh_indexed", extent, box))
+		return rc;
+	if (d_max_map && !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: the max map needs a valid map_extent");
+	if (capacity_vertices > 0xffffffffull)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu vertices is past 32-bit indices; split the surface by boxes",
+		                 (unsigned long long) capacity_vertices);
+	if (capacity_vertices != 0 && !d_vertices)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu vertices needs d_vertices", (unsigned long long) capacity_vertices);
+	if (capacity_vertices == 0 && d_normals)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: d_normals needs a capacity of vertices");
+	if (capacity_triangles != 0 && !d_indices)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu triangles needs d_indices", (unsigned long long) capacity_triangles);
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || (((uintptr_t) d_vertices | (uintptr_t) d_normals | (uintptr_t) d_indices) & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
+		                 "isosurface_mesh_indexed: d_scratch and d_counts must be 8-byte aligned, d_vertices, d_normals and d_indices 4-byte aligned");
+	if (!mesh_indexed_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh_indexed: volume too large for the launches");
+	DeviceGuard guard(ctx->device);
+	return launch_isosurface_mesh_indexed(ctx, d_volume, extent, box_or_whole(box, extent), iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals,
+	                                      capacity_vertices, d_indices, capacity_triangles, d_counts, (hipStream_t) stream);
+}
+
 // every argument is checked before the first launch
 int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
                      void *d_summary, void *stream)

@@ -107,6 +107,14 @@ bool   mesh_launch_ok(VkvExtent3D e, const VkvBox *box);
 int launch_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, const uint8_t *d_max_map, VkvExtent3D me,
                            void *d_scratch, float *d_triangles, uint64_t capacity, uint64_t *d_counts, hipStream_t s);
 
+// ---- mesh_indexed.hip
+// vkv_isosurface_mesh_indexed_scratch_bytes, what its launches can take, and the call after the entry point's argument checks
+size_t mesh_indexed_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+bool   mesh_indexed_launch_ok(VkvExtent3D e, const VkvBox *box);
+int launch_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, const uint8_t *d_max_map, VkvExtent3D me,
+                                   void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices, uint32_t *d_indices,
+                                   uint64_t capacity_triangles, uint64_t *d_counts, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

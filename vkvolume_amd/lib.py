@@ -25,6 +25,7 @@ EXPORTS = [
     "vkv_cell_summary", "vkv_occupancy_map_from_summary", "vkv_update_transfer_function_from_summary",
     "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab", "vkv_filter_volume",
     "vkv_isosurface_mesh_scratch_bytes", "vkv_isosurface_mesh",
+    "vkv_isosurface_mesh_indexed_scratch_bytes", "vkv_isosurface_mesh_indexed",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -117,6 +118,9 @@ def load():
     L.vkv_isosurface_mesh_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
     L.vkv_isosurface_mesh_scratch_bytes.restype = C.c_size_t
     L.vkv_isosurface_mesh.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, vp, abi.Extent3D, vp, vp, C.c_uint64, vp, vp]
+    L.vkv_isosurface_mesh_indexed_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
+    L.vkv_isosurface_mesh_indexed_scratch_bytes.restype = C.c_size_t
+    L.vkv_isosurface_mesh_indexed.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, vp, abi.Extent3D, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -357,6 +361,21 @@ class Context:
                                              abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_triangles, int(capacity),
                                              d_counts, stream)
 
+    def isosurface_mesh_indexed(self, d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals, capacity_vertices,
+                                d_indices, capacity_triangles, d_counts, stream=0):
+        """vkv_isosurface_mesh_indexed: the surface of isosurface_mesh() as a vertex list (one vertex per crossing edge, 3 floats; d_normals
+        None or as many gradient normals) and 3 x uint32 vertex numbers per triangle; d_counts (4 x uint64) = the triangles, those written,
+        the vertices, those written.  d_scratch: mesh_indexed_scratch_bytes(extent, box) bytes."""
+        self.check(self.isosurface_mesh_indexed_rc(d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals,
+                                                   capacity_vertices, d_indices, capacity_triangles, d_counts, stream))
+
+    def isosurface_mesh_indexed_rc(self, d_volume, extent, box, iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals, capacity_vertices,
+                                   d_indices, capacity_triangles, d_counts, stream=0):
+        """Like isosurface_mesh_indexed() but returns the status code (error-path tests)."""
+        return self._lib.vkv_isosurface_mesh_indexed(self.handle, d_volume, extent, None if box is None else C.byref(box), float(iso), d_max_map,
+                                                     abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_vertices, d_normals,
+                                                     int(capacity_vertices), d_indices, int(capacity_triangles), d_counts, stream)
+
     def filter_volume(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""
         self.check(self.filter_volume_rc(d_src, d_dst, extent, box, kind, stream))
@@ -464,3 +483,9 @@ def mesh_scratch_bytes(extent, box=None):
     """vkv_isosurface_mesh_scratch_bytes: the scratch vkv_isosurface_mesh needs for `box` (None: the whole volume) of `extent`; 0 for an extent
     or box the call rejects"""
     return int(load().vkv_isosurface_mesh_scratch_bytes(extent, None if box is None else C.byref(box)))
+
+
+def mesh_indexed_scratch_bytes(extent, box=None):
+    """vkv_isosurface_mesh_indexed_scratch_bytes: the scratch vkv_isosurface_mesh_indexed needs for `box` (None: the whole volume) of `extent`;
+    0 for an extent or box the call rejects"""
+    return int(load().vkv_isosurface_mesh_indexed_scratch_bytes(extent, None if box is None else C.byref(box)))

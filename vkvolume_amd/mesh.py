@@ -1,7 +1,10 @@
 """What to do with the triangles of Volume.extract_isosurface / vkv_isosurface_mesh on the host: numpy only, nothing here is pinned to the bit.
 
 ``tri`` is always an [n, 3, 3] float32 array (triangle, vertex, xyz) in voxel-index coordinates, voxel centres at integers (a device tensor's
-``.cpu().numpy()``).  Triangles wind so that (v1 - v0) x (v2 - v0) points from the inside (f >= iso) to the outside.
+``.cpu().numpy()``).  Triangles wind so that (v1 - v0) x (v2 - v0) points from the inside (f >= iso) to the outside.  The indexed form of
+Volume.extract_isosurface_indexed / vkv_isosurface_mesh_indexed is ``vertices`` [v, 3] float32 and ``faces`` [n, 3] of vertex numbers (any
+integer type; a torch.uint32 tensor's ``.cpu().numpy()``): unindex() turns it into ``tri``, write_ply() stores it, and the coordinate maps take
+a vertex array as well.
 """
 import struct
 
@@ -21,14 +24,22 @@ def _whd(extent):
     return np.asarray(extent, np.float32).reshape(3)
 
 
+def _points(p):
+    """triangles [n, 3, 3] or vertices [v, 3]"""
+    p = np.ascontiguousarray(p, np.float32)
+    return p if p.ndim == 2 and p.shape[1] == 3 else _tri(p)
+
+
 def to_texture(tri, extent):
-    """voxel-index coordinates -> texture coordinates ([0, 1]^3 = the volume): (p + 0.5) / extent, ``extent`` = (W, H, D) or an abi.Extent3D"""
-    return (_tri(tri) + np.float32(0.5)) / _whd(extent)
+    """voxel-index coordinates -> texture coordinates ([0, 1]^3 = the volume): (p + 0.5) / extent, ``extent`` = (W, H, D) or an abi.Extent3D;
+    ``tri``: triangles [n, 3, 3] or vertices [v, 3]"""
+    return (_points(tri) + np.float32(0.5)) / _whd(extent)
 
 
 def to_model(tri, extent, matrix):
     """voxel-index coordinates -> the space ``matrix`` maps the volume's centred unit cube into: matrix * (texture - 0.5).  ``matrix``: a
-    column-major 4 x 4 as vkvolume_amd.camera builds them (memory order m[col][row]), e.g. Volume.image_transform or node * image."""
+    column-major 4 x 4 as vkvolume_amd.camera builds them (memory order m[col][row]), e.g. Volume.image_transform or node * image.
+    ``tri``: triangles [n, 3, 3] or vertices [v, 3]."""
     local = to_texture(tri, extent).astype(np.float64) - 0.5
     m = np.asarray(matrix, np.float64).reshape(4, 4)
     return (local @ m[:3, :3] + m[3, :3]).astype(np.float32)
@@ -45,6 +56,15 @@ def weld(tri):
     rank = np.empty_like(order)
     rank[order] = np.arange(len(order))
     return tri.reshape(-1, 3)[first[order]].copy(), rank[inverse.reshape(-1)].reshape(-1, 3).astype(np.int64)
+
+
+def unindex(vertices, faces):
+    """the triangle list [n, 3, 3] float32 of an indexed mesh: vertices[faces]"""
+    vertices = np.ascontiguousarray(vertices, np.float32)
+    faces = np.asarray(faces)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices must have the shape [v, 3] and faces [n, 3], not %s and %s" % (vertices.shape, faces.shape))
+    return np.ascontiguousarray(vertices[faces.astype(np.int64)])
 
 
 def drop_degenerate(tri):
@@ -71,4 +91,29 @@ def write_stl(path, tri, header=b"vkvolume_amd isosurface"):
     with open(path, "wb") as f:
         f.write(bytes(header)[:80].ljust(80, b"\0"))
         f.write(struct.pack("<I", len(tri)))
+        f.write(rec.tobytes())
+
+
+def write_ply(path, vertices, faces, normals=None):
+    """binary little-endian PLY: per vertex x y z (and nx ny nz with ``normals`` [v, 3]) as float32, per face a uchar 3 and three uint32"""
+    vertices = np.ascontiguousarray(vertices, np.float32)
+    faces = np.asarray(faces)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices must have the shape [v, 3] and faces [n, 3], not %s and %s" % (vertices.shape, faces.shape))
+    names = ["x", "y", "z"]
+    columns = [vertices]
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, np.float32)
+        if normals.shape != vertices.shape:
+            raise ValueError("normals must have the vertices' shape %s, not %s" % (vertices.shape, normals.shape))
+        names += ["nx", "ny", "nz"]
+        columns.append(normals)
+    header = ["ply", "format binary_little_endian 1.0", "comment vkvolume_amd isosurface", "element vertex %d" % len(vertices)]
+    header += ["property float %s" % n for n in names]
+    header += ["element face %d" % len(faces), "property list uchar uint vertex_indices", "end_header"]
+    rec = np.zeros(len(faces), np.dtype([("n", "u1"), ("v", "<u4", 3)]))
+    rec["n"], rec["v"] = 3, faces
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(np.concatenate(columns, axis=1).astype("<f4").tobytes())
         f.write(rec.tobytes())

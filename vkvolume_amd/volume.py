@@ -299,6 +299,50 @@ class Volume:
             call(tri, total)
         return tri, total
 
+    def extract_isosurface_indexed(self, iso, box=None, use_max_map=False, normals=False, capacity=None):
+        """The isosurface of extract_isosurface() as an indexed mesh on the current stream (vkv_isosurface_mesh_indexed): returns ``(vertices,
+        faces, normals)``: [nv, 3] float32, [nt, 3] torch.uint32 and, with ``normals``, [nv, 3] float32 gradient normals (not normalised,
+        pointing from the inside out), else None.  One vertex per crossing edge: ``vertices[faces]`` is extract_isosurface()'s triangle list
+        bit for bit.  ``capacity`` None: a counting call, ONE host read of the four counts, then the emit into tensors of exactly those sizes.
+        ``capacity=(vertices, triangles)``: one call and no host read; the tensors have those sizes, the rows past the written counts are not
+        written, and a fourth result is the call's int64 device tensor (triangles, triangles written, vertices, vertices written).  ``box``
+        and ``use_max_map`` as for extract_isosurface().  vkvolume_amd.mesh unindexes the result and writes PLY."""
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if use_max_map and self.max_map is None:
+            raise RuntimeError("Volume.extract_isosurface_indexed: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
+        if capacity is not None:
+            cap_v, cap_t = capacity
+            if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
+                raise ValueError("Volume.extract_isosurface_indexed: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32")
+        nbytes = lib.mesh_indexed_scratch_bytes(self.extent, box)
+        if nbytes == 0:
+            raise ValueError("Volume.extract_isosurface_indexed: the box is empty or outside the volume, or the volume is too large")
+        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        counts = torch.empty((4,), dtype=torch.int64, device=self.device)
+        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
+
+        def call(nv, nt):
+            vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+            faces = torch.empty((nt, 3), dtype=torch.uint32, device=self.device)
+            nrm = torch.empty((nv, 3), dtype=torch.float32, device=self.device) if normals else None
+            self.ctx.isosurface_mesh_indexed(_ptr(self.volume), self.extent, box, iso, _ptr(max_map), map_extent, _ptr(scratch),
+                                             _ptr(vertices) if nv else None, _ptr(nrm) if nv else None, nv, _ptr(faces) if nt else None, nt,
+                                             _ptr(counts), _stream())
+            return vertices, faces, nrm
+
+        if capacity is not None:
+            return call(int(cap_v), int(cap_t)) + (counts,)
+        call(0, 0)
+        total = counts.cpu().tolist()
+        if total[2] > 0xffffffff:
+            raise ValueError("Volume.extract_isosurface_indexed: %d vertices are past 32-bit indices; extract the surface box by box" % total[2])
+        if total[0] == 0 and total[2] == 0:
+            return (torch.empty((0, 3), dtype=torch.float32, device=self.device), torch.empty((0, 3), dtype=torch.uint32, device=self.device),
+                    torch.empty((0, 3), dtype=torch.float32, device=self.device) if normals else None)
+        return call(total[2], total[0])
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
