@@ -814,6 +814,56 @@ int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent
                                 VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
                                 uint32_t *d_indices, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
 
+/* ---- connected components and island removal ---------------------------------------------------------------------------
+ * vkv_label_components numbers the connected components of the inside voxels of a box; vkv_select_components keeps or fills them by size.
+ * Inside rule: the mesh's.  f = (float) byte * kInv255, and a voxel is inside iff f >= iso.
+ * Voxels and connections.  Only the voxels of `box` take part (NULL: the whole volume), and connections run only through voxels of the box.
+ * Two inside voxels are adjacent if their offset (dx, dy, dz) lies in the neighbourhood `connectivity`:
+ *   VKV_CONNECT_6:  the six unit offsets;
+ *   VKV_CONNECT_14: +-(dx, dy, dz) with dx, dy, dz in {0, 1}, not all zero.  These are exactly the tetrahedron edges of vkv_isosurface_mesh
+ *                   (cube corners a, b with a & b == a), so the components are precisely the bodies that the mesh's surface separates;
+ *   VKV_CONNECT_26: every offset in {-1, 0, 1}^3 except zero.
+ * A component is a class of the transitive closure of adjacency.
+ * Labels.  d_labels has the box's shape, box.width x box.height x box.depth with x fastest (NULL box: the volume's shape); every element is
+ * written.  0: an outside voxel; k in 1 .. K: component k.  Components are numbered in the order of their first voxel, i.e. their smallest
+ * box-linear index i = ((z - z0) bh + (y - y0)) bw + (x - x0): the numbering of scipy.ndimage.label with the matching structure.
+ * Sizes.  d_sizes[k - 1] = the voxel count of component k for k <= d_counts[1]; not one element beyond that is written.  With
+ * capacity_components == 0 d_sizes may be NULL and no size work is enqueued.
+ * Counts.  d_counts[0] = K, exact whatever the capacity; d_counts[1] = min(K, capacity_components); d_counts[2] = the number of inside voxels.
+ * d_max_map (NULL: dense): vkv_max_map of d_volume with map_extent; the voxels of a cell that holds a byte B with B * kInv255 < iso get label
+ * 0 without being read: the same bits as the dense path.  The map is consulted per voxel, so all it saves is the voxel's own byte read, one
+ * of the five bytes per voxel the call moves; it is measured to be no faster than the dense path.
+ * d_scratch: vkv_label_components_scratch_bytes(extent, box) bytes, 8-byte aligned: 24 bytes per 64 voxels of the box (rounded up) plus 16
+ * bytes per 262144 voxels (rounded up), three eighths of a byte per voxel; 0 for an extent or box this call rejects.  Its contents mean
+ * nothing between calls.
+ * Kernels only (no allocation, no memset or copy node, no host wait; the kernels use no scratch memory, and none waits for another lane, wave
+ * or workgroup): after one direct call on `stream` it can be captured into a hipGraph.  Integer atomics (minimum, addition) are used where the
+ * result does not depend on their order: two runs give the same bytes in d_labels, d_sizes and d_counts.  Nothing in the context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_volume,
+ * d_scratch, d_labels or d_counts, a zero extent, a non-finite iso, an unknown connectivity, an empty box or one not inside `extent`, a max
+ * map without a valid map_extent, a non-zero capacity with a NULL d_sizes, a d_labels or d_sizes that is not 4-byte aligned, a d_counts or
+ * d_scratch that is not 8-byte aligned, a capacity_components above 0xffffffff.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels
+ * (labels are uint32; a larger volume goes box by box).  d_volume may start at any byte; every extent is accepted, widths below 4 and axes
+ * of length 1 included; nothing outside any buffer is read or written.
+ *
+ * vkv_select_components: pointwise, one kernel launch.  For every voxel v of the box, at its volume position in d_dst, with L = d_labels[v]
+ * (the box's shape, as written by vkv_label_components for the same box): L == 0: dst = src; L > d_counts[1] (its size is not known): dst =
+ * src, what is not known is not removed; otherwise dst = src if min_voxels <= d_sizes[L - 1] <= max_voxels, else dst = fill.  Bytes of d_dst
+ * outside the box are untouched.  d_counts is read on the device: no host wait.  d_sizes may be NULL where d_counts[1] is 0 (nothing is
+ * removed then).  d_dst == d_src is allowed (in place); any other overlap of [d_src, d_src + W H D) and [d_dst, d_dst + W H D) is
+ * VKV_E_INVALID_ARGUMENT, as are a null ctx, d_src, d_dst, d_labels or d_counts, a zero extent, an empty box or one not inside `extent`,
+ * fill > 255, min_voxels > max_voxels, a d_labels or d_sizes that is not 4-byte aligned and a d_counts that is not 8-byte aligned.
+ * VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels.  The result is an ordinary volume for every other entry point. */
+#define VKV_CONNECT_6 6
+#define VKV_CONNECT_14 14
+#define VKV_CONNECT_26 26
+size_t vkv_label_components_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_label_components(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t connectivity,
+                         const uint8_t *d_max_map, VkvExtent3D map_extent, void *d_scratch, uint32_t *d_labels, uint32_t *d_sizes,
+                         uint64_t capacity_components, uint64_t *d_counts, void *stream);
+int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
+                          const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

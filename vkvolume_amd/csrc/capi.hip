@@ -414,6 +414,67 @@ int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent
 	                                      capacity_vertices, d_indices, capacity_triangles, d_counts, (hipStream_t) stream);
 }
 
+size_t vkv_label_components_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return components_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_label_components(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t connectivity,
+                         const uint8_t *d_max_map, VkvExtent3D map_extent, void *d_scratch, uint32_t *d_labels, uint32_t *d_sizes,
+                         uint64_t capacity_components, uint64_t *d_counts, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_volume || !d_scratch || !d_labels || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: null pointer or zero extent");
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: iso must be finite");
+	if (connectivity != VKV_CONNECT_6 && connectivity != VKV_CONNECT_14 && connectivity != VKV_CONNECT_26)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: unknown connectivity %d (6, 14 or 26)", (int) connectivity);
+	if (const int rc = check_box(ctx, "label_components", extent, box))
+		return rc;
+	if (d_max_map && !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: the max map needs a valid map_extent");
+	if (capacity_components > 0xffffffffull)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: a capacity of %llu components is past 32-bit labels", (unsigned long long) capacity_components);
+	if (capacity_components != 0 && !d_sizes)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: a capacity of %llu components needs d_sizes", (unsigned long long) capacity_components);
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || (((uintptr_t) d_labels | (uintptr_t) d_sizes) & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_components: d_scratch and d_counts must be 8-byte aligned, d_labels and d_sizes 4-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "label_components: a box of more than 2^32 - 1 voxels; label it box by box");
+	DeviceGuard guard(ctx->device);
+	return launch_label_components(ctx, d_volume, extent, box_or_whole(box, extent), iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes,
+	                               capacity_components, d_counts, (hipStream_t) stream);
+}
+
+// every argument is checked before the launch (and before the device is touched)
+int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
+                          const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_src || !d_dst || !d_labels || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: null pointer or zero extent");
+	if (const int rc = check_box(ctx, "select_components", extent, box))
+		return rc;
+	if (fill > 255u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: fill %u is no byte", fill);
+	if (min_voxels > max_voxels)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: min_voxels %llu above max_voxels %llu", (unsigned long long) min_voxels,
+		                 (unsigned long long) max_voxels);
+	if ((((uintptr_t) d_labels | (uintptr_t) d_sizes) & 3u) != 0 || ((uintptr_t) d_counts & 7u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: d_labels and d_sizes must be 4-byte aligned, d_counts 8-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "select_components: a box of more than 2^32 - 1 voxels");
+	const unsigned __int128 bytes = (unsigned __int128) extent.width * extent.height * extent.depth;
+	const uint64_t          n     = bytes > ~0ull ? ~0ull : (uint64_t) bytes;
+	const uintptr_t         a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
+	if (a != b && (a < b ? b - a < n : a - b < n))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: d_src and d_dst overlap without being equal");
+	DeviceGuard guard(ctx->device);
+	return launch_select_components(ctx, d_src, d_dst, extent, box_or_whole(box, extent), d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill,
+	                                (hipStream_t) stream);
+}
+
 // every argument is checked before the first launch
 int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
                      void *d_summary, void *stream)

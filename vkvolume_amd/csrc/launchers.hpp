@@ -115,6 +115,16 @@ int launch_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent
                                    void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices, uint32_t *d_indices,
                                    uint64_t capacity_triangles, uint64_t *d_counts, hipStream_t s);
 
+// ---- components.hip
+// vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (at most 2^32 - 1 voxels in the
+// box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)
+size_t components_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+bool   components_launch_ok(VkvExtent3D e, const VkvBox *box);
+int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int connectivity, const uint8_t *d_max_map,
+                            VkvExtent3D me, void *d_scratch, uint32_t *d_labels, uint32_t *d_sizes, uint64_t capacity, uint64_t *d_counts, hipStream_t s);
+int launch_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels,
+                             const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

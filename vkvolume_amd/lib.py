@@ -26,6 +26,7 @@ EXPORTS = [
     "vkv_max_map", "vkv_render_mip", "vkv_render_isosurface", "vkv_render_slab", "vkv_filter_volume",
     "vkv_isosurface_mesh_scratch_bytes", "vkv_isosurface_mesh",
     "vkv_isosurface_mesh_indexed_scratch_bytes", "vkv_isosurface_mesh_indexed",
+    "vkv_label_components_scratch_bytes", "vkv_label_components", "vkv_select_components",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -121,6 +122,10 @@ def load():
     L.vkv_isosurface_mesh_indexed_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
     L.vkv_isosurface_mesh_indexed_scratch_bytes.restype = C.c_size_t
     L.vkv_isosurface_mesh_indexed.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, vp, abi.Extent3D, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+    L.vkv_label_components_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
+    L.vkv_label_components_scratch_bytes.restype = C.c_size_t
+    L.vkv_label_components.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, i32, vp, abi.Extent3D, vp, vp, vp, C.c_uint64, vp, vp]
+    L.vkv_select_components.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), vp, vp, vp, C.c_uint64, C.c_uint64, u32, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -376,6 +381,32 @@ class Context:
                                                      abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_vertices, d_normals,
                                                      int(capacity_vertices), d_indices, int(capacity_triangles), d_counts, stream)
 
+    def label_components(self, d_volume, extent, box, iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes, capacity_components,
+                         d_counts, stream=0):
+        """vkv_label_components: d_labels (uint32, the shape of `box`; None: of the volume) = 0 for an outside voxel, else the number 1 .. K of
+        its connected component under `connectivity` (abi.CONNECT_*), numbered by first voxel; d_sizes[k - 1] = the voxels of component k for
+        the first min(K, capacity_components); d_counts (3 x uint64) = K, the sizes written, the inside voxels.  d_scratch:
+        components_scratch_bytes(extent, box) bytes."""
+        self.check(self.label_components_rc(d_volume, extent, box, iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes,
+                                            capacity_components, d_counts, stream))
+
+    def label_components_rc(self, d_volume, extent, box, iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes, capacity_components,
+                            d_counts, stream=0):
+        """Like label_components() but returns the status code (error-path tests)."""
+        return self._lib.vkv_label_components(self.handle, d_volume, extent, None if box is None else C.byref(box), float(iso), int(connectivity),
+                                              d_max_map, abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_labels, d_sizes,
+                                              int(capacity_components), d_counts, stream)
+
+    def select_components(self, d_src, d_dst, extent, box, d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill=0, stream=0):
+        """vkv_select_components: the voxels of `box` of d_dst = d_src, but `fill` where the voxel's component (d_labels, d_sizes, d_counts of
+        label_components() for the same box) has fewer than min_voxels or more than max_voxels voxels; d_dst may be d_src"""
+        self.check(self.select_components_rc(d_src, d_dst, extent, box, d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill, stream))
+
+    def select_components_rc(self, d_src, d_dst, extent, box, d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill=0, stream=0):
+        """Like select_components() but returns the status code (error-path tests)."""
+        return self._lib.vkv_select_components(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), d_labels, d_sizes, d_counts,
+                                               int(min_voxels), int(max_voxels), int(fill), stream)
+
     def filter_volume(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""
         self.check(self.filter_volume_rc(d_src, d_dst, extent, box, kind, stream))
@@ -483,6 +514,12 @@ def mesh_scratch_bytes(extent, box=None):
     """vkv_isosurface_mesh_scratch_bytes: the scratch vkv_isosurface_mesh needs for `box` (None: the whole volume) of `extent`; 0 for an extent
     or box the call rejects"""
     return int(load().vkv_isosurface_mesh_scratch_bytes(extent, None if box is None else C.byref(box)))
+
+
+def components_scratch_bytes(extent, box=None):
+    """vkv_label_components_scratch_bytes: the scratch vkv_label_components needs for `box` (None: the whole volume) of `extent`; 0 for an
+    extent or box the call rejects (a box of more than 2^32 - 1 voxels included)"""
+    return int(load().vkv_label_components_scratch_bytes(extent, None if box is None else C.byref(box)))
 
 
 def mesh_indexed_scratch_bytes(extent, box=None):

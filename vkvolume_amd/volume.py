@@ -343,6 +343,74 @@ class Volume:
                     torch.empty((0, 3), dtype=torch.float32, device=self.device) if normals else None)
         return call(total[2], total[0])
 
+    _CONNECTIVITIES = (abi.CONNECT_6, abi.CONNECT_14, abi.CONNECT_26)
+
+    def label_components(self, iso, connectivity=6, box=None, sizes=True, use_max_map=False):
+        """The connected components of the voxels with value >= ``iso`` (the mesh's inside rule) on the current stream
+        (vkv_label_components): returns ``(labels, sizes, counts)``.  ``labels``: a torch.uint32 tensor of the box's shape [depth, height,
+        width] (the volume's without a box), 0 for outside voxels and 1 .. K for the components in the order of their first voxel, the
+        numbering of scipy.ndimage.label.  ``sizes``: a torch.uint32 tensor of K voxel counts, or None with ``sizes=False``.  ``counts``: the
+        call's int64 device tensor (K, the sizes written, the inside voxels).  ``connectivity``: 6, 14 (the marching-tetrahedra edges: the
+        bodies extract_isosurface() separates) or 26.  With ``sizes`` a counting call runs first and K is read back to size the tensor
+        exactly: ONE host wait.  ``box`` and ``use_max_map`` as for extract_isosurface()."""
+        if connectivity not in self._CONNECTIVITIES:
+            raise ValueError("Volume.label_components: connectivity must be 6, 14 or 26")
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if use_max_map and self.max_map is None:
+            raise RuntimeError("Volume.label_components: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
+        nbytes = lib.components_scratch_bytes(self.extent, box)
+        if nbytes == 0:
+            raise ValueError("Volume.label_components: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
+        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
+        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        counts = torch.empty((3,), dtype=torch.int64, device=self.device)
+        labels = torch.empty(shape, dtype=torch.uint32, device=self.device)
+        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
+
+        def call(d_sizes, n):
+            self.ctx.label_components(_ptr(self.volume), self.extent, box, iso, connectivity, _ptr(max_map), map_extent, _ptr(scratch), _ptr(labels),
+                                      _ptr(d_sizes), n, _ptr(counts), _stream())
+
+        call(None, 0)
+        if not sizes:
+            return labels, None, counts
+        k = int(counts[0].item())
+        d_sizes = torch.empty((k,), dtype=torch.uint32, device=self.device)
+        if k:
+            call(d_sizes, k)
+        return labels, d_sizes, counts
+
+    def remove_islands(self, iso, min_voxels=None, keep_largest=False, connectivity=6, fill=0, out=None, box=None):
+        """The volume without its small connected components at ``iso`` on the current stream (vkv_label_components, then
+        vkv_select_components): a uint8 tensor of the volume's shape in which every inside voxel (value >= iso) of a component with fewer
+        than ``min_voxels`` voxels holds ``fill``; everything else is the volume's byte.  ``keep_largest=True`` keeps only the largest
+        component: the sizes are read back to find it, which is one more host wait, and min_voxels = max(sizes), so ties are all kept.
+        Exactly one of ``min_voxels`` and ``keep_largest`` must be given.  ``fill`` should lie below iso (the default 0 does for every iso >
+        0).  ``out``: a contiguous uint8 tensor of the volume's shape on its device (``out=self.volume`` works in place); without it a copy
+        is made.  ``box``: only the box's voxels take part and are written; components are those of the box alone.  ``self.volume`` and the
+        derived buffers are not touched unless ``out`` is the volume: loading the result is the caller's decision."""
+        if (min_voxels is None) == (not keep_largest):
+            raise ValueError("Volume.remove_islands: give exactly one of min_voxels and keep_largest")
+        if min_voxels is not None and (int(min_voxels) != min_voxels or min_voxels < 0):
+            raise ValueError("Volume.remove_islands: min_voxels must be a non-negative integer")
+        if int(fill) != fill or not 0 <= fill <= 255:
+            raise ValueError("Volume.remove_islands: fill must be a byte")
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if out is None:
+            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
+        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
+            raise ValueError("Volume.remove_islands: `out` must be a contiguous uint8 tensor of shape %s on %s" % (tuple(self.volume.shape), self.volume.device))
+        labels, sizes, counts = self.label_components(iso, connectivity=connectivity, box=box)
+        if keep_largest:
+            min_voxels = int(sizes.to(torch.int64).max().item()) if sizes.numel() else 0
+        self.ctx.select_components(_ptr(self.volume), _ptr(out), self.extent, box, _ptr(labels), _ptr(sizes) if sizes.numel() else None, _ptr(counts),
+                                   int(min_voxels), 0xffffffffffffffff, int(fill), _stream())
+        return out
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
