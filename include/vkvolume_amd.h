@@ -864,6 +864,46 @@ int vkv_label_components(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exte
 int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
                           const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, void *stream);
 
+/* ---- exact Euclidean distance transform and ball morphology ---------------------------------------------------------------
+ * vkv_distance_transform writes the exact squared Euclidean distance of every voxel of a box to the nearest TARGET voxel of the box;
+ * vkv_select_by_distance fills the voxels whose distance lies in a range: ball erosion and dilation (hence opening and closing), shells,
+ * margins.  (vkv_distance_map is something else: the Chebyshev transform of the occupancy CELLS that the ray-march skips by.)
+ * Inside rule: the mesh's.  f = (float) byte * kInv255, and a voxel is inside iff f >= iso.
+ * Voxels.  Only the voxels of `box` exist (NULL: the whole volume): nothing beyond the box counts as inside or as outside.
+ * Targets.  VKV_DISTANCE_TO_INSIDE: the inside voxels of the box; VKV_DISTANCE_TO_OUTSIDE: its outside voxels.
+ * Output.  d_dist2 has the box's shape, box.width x box.height x box.depth with x fastest (NULL box: the volume's shape); every element is
+ * written: d_dist2[v] = min(limit, min over the target voxels u of the box of |v - u|^2), |v - u|^2 = dx^2 + dy^2 + dz^2 in voxel units, an
+ * integer: 0 on a target voxel, and `limit` everywhere where the box holds no target voxel.  limit == VKV_DISTANCE_NONE (0xffffffff) means
+ * unlimited (a true distance is at most 3 x 32767^2 < 0xffffffff); limit == 0 is invalid.  All arithmetic is integer and compares squares:
+ * no square root, no float, so the result is unique and two runs give the same bytes.  A limited transform costs less: the work per voxel
+ * grows with the distance found, and the limit cuts it (morphology by radius^2 r2 needs limit = r2 + 1 only).
+ * d_scratch: vkv_distance_transform_scratch_bytes(extent, box) bytes, 8-byte aligned: 8 bytes per 64 voxels of the box (rounded up), the
+ * target bits, plus 4 bytes per voxel of the box, the second distance buffer: 4 B and one bit per voxel; 0 for an extent or box this call
+ * rejects.  Its contents mean nothing between calls.
+ * Kernels only (no allocation, no memset or copy node, no host wait, no atomics; the kernels use no scratch memory, and none waits for another
+ * lane, wave or workgroup): after one direct call on `stream` it can be captured into a hipGraph.  Nothing in the context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_volume,
+ * d_scratch or d_dist2, a zero extent, a non-finite iso, an unknown target, limit == 0, an empty box or one not inside `extent`, a d_dist2
+ * that is not 4-byte aligned, a d_scratch that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels or with an axis
+ * above 32768 (a larger volume goes box by box).  d_volume may start at any byte; every extent is accepted, widths below 4 and axes of
+ * length 1 included; nothing outside any buffer is read or written.
+ *
+ * vkv_select_by_distance: pointwise, one kernel launch.  For every voxel v of the box, at its volume position in d_dst: dst = fill if lo <=
+ * d_dist2[v] <= hi (d_dist2: the box's shape, as written by vkv_distance_transform for the same box), else dst = src.  Bytes of d_dst outside
+ * the box are untouched.  Erosion by a ball of radius^2 r2: VKV_DISTANCE_TO_OUTSIDE, then (lo, hi, fill) = (1, r2, a byte below iso);
+ * dilation: VKV_DISTANCE_TO_INSIDE, then (1, r2, a byte at or above iso); an opening is an erosion and a dilation of its result, a closing the
+ * reverse.  Since nothing exists beyond the box, an erosion does not eat at the box's faces (scipy's border_value=1).  d_dst == d_src is
+ * allowed (in place); any other overlap of [d_src, d_src + W H D) and [d_dst, d_dst + W H D) is VKV_E_INVALID_ARGUMENT, as are a null ctx,
+ * d_src, d_dst or d_dist2, a zero extent, an empty box or one not inside `extent`, fill > 255, lo > hi and a d_dist2 that is not 4-byte
+ * aligned.  VKV_E_UNSUPPORTED: as above.  The result is an ordinary volume for every other entry point. */
+#define VKV_DISTANCE_NONE 0xffffffffu
+enum VkvDistanceTarget { VKV_DISTANCE_TO_INSIDE = 0, VKV_DISTANCE_TO_OUTSIDE = 1 };
+size_t vkv_distance_transform_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_distance_transform(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
+                           uint32_t limit, void *d_scratch, uint32_t *d_dist2, void *stream);
+int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box,
+                           const uint32_t *d_dist2, uint32_t lo, uint32_t hi, uint32_t fill, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

@@ -475,6 +475,59 @@ int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, Vk
 	                                (hipStream_t) stream);
 }
 
+size_t vkv_distance_transform_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return edt_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_distance_transform(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target, uint32_t limit,
+                           void *d_scratch, uint32_t *d_dist2, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_volume || !d_scratch || !d_dist2 || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: null pointer or zero extent");
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: iso must be finite");
+	if (target != VKV_DISTANCE_TO_INSIDE && target != VKV_DISTANCE_TO_OUTSIDE)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: unknown target %d", (int) target);
+	if (limit == 0u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: limit 0 (VKV_DISTANCE_NONE: unlimited)");
+	if (const int rc = check_box(ctx, "distance_transform", extent, box))
+		return rc;
+	if (((uintptr_t) d_scratch & 7u) != 0 || ((uintptr_t) d_dist2 & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: d_scratch must be 8-byte aligned, d_dist2 4-byte aligned");
+	if (!edt_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768; transform it box by box");
+	DeviceGuard guard(ctx->device);
+	return launch_distance_transform(ctx, d_volume, extent, box_or_whole(box, extent), iso, target, limit, d_scratch, d_dist2, (hipStream_t) stream);
+}
+
+// every argument is checked before the launch (and before the device is touched)
+int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_dist2, uint32_t lo,
+                           uint32_t hi, uint32_t fill, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_src || !d_dst || !d_dist2 || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: null pointer or zero extent");
+	if (const int rc = check_box(ctx, "select_by_distance", extent, box))
+		return rc;
+	if (fill > 255u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: fill %u is no byte", fill);
+	if (lo > hi)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: lo %u above hi %u", lo, hi);
+	if (((uintptr_t) d_dist2 & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: d_dist2 must be 4-byte aligned");
+	if (!edt_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "select_by_distance: a box of more than 2^32 - 1 voxels or an axis above 32768");
+	const unsigned __int128 bytes = (unsigned __int128) extent.width * extent.height * extent.depth;
+	const uint64_t          n     = bytes > ~0ull ? ~0ull : (uint64_t) bytes;
+	const uintptr_t         a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
+	if (a != b && (a < b ? b - a < n : a - b < n))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: d_src and d_dst overlap without being equal");
+	DeviceGuard guard(ctx->device);
+	return launch_select_by_distance(ctx, d_src, d_dst, extent, box_or_whole(box, extent), d_dist2, lo, hi, fill, (hipStream_t) stream);
+}
+
 // every argument is checked before the first launch
 int vkv_cell_summary(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d_gradient, VkvExtent3D extent, VkvExtent3D map_extent, const VkvBox *box,
                      void *d_summary, void *stream)

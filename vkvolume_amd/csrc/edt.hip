@@ -1,0 +1,265 @@
+// edt.hip — the exact squared Euclidean distance transform of the thresholded voxels of a box (vkv_distance_transform) and the pointwise
+// select on it (vkv_select_by_distance): ball erosion, dilation, shells and margins; DESIGN.md §5.16.  (distance.hip is the Chebyshev
+// transform of the occupancy CELLS, another metric on another grid.)  Integer work only: no MFMA, no floating point after the threshold, no
+// square root.
+//
+// A voxel is a TARGET iff (byte >= thr) == (target == VKV_DISTANCE_TO_INSIDE), thr being mesh_common.hpp's derivation from iso: the mesh's
+// inside rule.  Every kernel is one-dimensional over the box-linear index i = ((z - z0) bh + (y - y0)) bw + (x - x0), one voxel per lane, so
+// every access of every pass is coalesced along x; a wave's 64 voxels are one ENTRY, as in components.hip.  All values are squared distances
+// CAPPED at `limit` (0xffffffff = VKV_DISTANCE_NONE when unlimited): min(limit, min_u (a_u + b)) = min(limit, min_u (min(limit, a_u) + b))
+// for b >= 0, so capping after every pass gives the capped result, and the cap doubles as "no target in this row / column".
+//   k_edt_bits   target bits by wave ballot, one 64-bit word per entry (scratch).  Reads the volume, 1 B per voxel.
+//   k_edt_x      g(i) = min(limit, dx^2), dx = the distance along the voxel's own row to the nearest target bit: clz / ctz in the lane's own
+//                word, then whole words outward.  Reads the bits, writes buffer P0.
+//   k_edt_axis   out(p) = min over p' of the line of (g(p') + (p - p')^2), for y (stride bw) and then for z (stride bw bh): from best = g(p)
+//                it looks at p - d and p + d for d = 1, 2, ... while d^2 < best, four offsets at a time.  Reads one buffer, writes the OTHER (a line's outputs need
+//                its inputs: not in place).  A pass over an axis of length 1 is not launched.
+// BUFFERS.  The two 4-byte buffers are d_dist2 and the scratch block's; the x pass writes the one that makes the last pass land in d_dist2:
+// passes = 1 + (bh > 1) + (bd > 1), P0 = d_dist2 when that is odd.  Every pass writes every element of its output, so nothing depends on what
+// the buffers held before, and two runs give the same bytes.
+// LOOP BOUNDS.  k_edt_x walks words from the lane's own to the word of the window's end, the window being the row cut to +-reach, reach =
+// ceil(sqrt(limit)) (65536 when unlimited): at most min(bw, reach) / 64 + 2 words per side.  k_edt_axis ends at the latest when neither p - d
+// nor p + d lies in the line: d < len <= 32768 rounds.  No lane waits for another lane, wave or workgroup; no atomics.
+// NO OVERFLOW.  Offsets along an axis are at most 32767, their squares at most 2^30 - 2^16 + 1; a true distance is at most 3 x 32767^2 =
+// 3221028867 < 2^32 - 1.  No sum is formed before it is known to fit: a candidate g + d^2 replaces best only after g < best - d^2 was seen,
+// with d^2 < best, so the difference does not wrap, a "none" g (the cap) never passes, and g + d^2 < best <= 2^32 - 1.  Box-linear
+// indices: i - d stride and i + d stride lie in the line, hence in [0, n), n <= 2^32 - 1.
+// No kernel uses scratch memory (tests/test_distance_cpu.py reads the listing).
+#include <utility>
+
+#include "launchers.hpp"
+#include "mesh_common.hpp"
+
+using namespace vkv;
+
+struct EdtGeom
+{
+	const uint8_t *vol;
+	uint32_t       W, H;              // the volume's row and slice
+	uint32_t       x0, y0, z0;        // the box's first voxel
+	uint32_t       bw, bh, n;         // the box's row, slice height and voxels
+	uint32_t       thr;               // the smallest inside byte; 256: none
+	uint32_t       outside;           // 1: the targets are the outside voxels
+};
+
+struct EdtVoxel
+{
+	uint32_t i, lane, x, y, z;
+	bool     valid;
+};
+
+__device__ __forceinline__ EdtVoxel edt_voxel(const EdtGeom &G)
+{
+	EdtVoxel v;
+	v.i     = blockIdx.x * 256u + threadIdx.x;        // at most 2^32 - 1: the grid has at most 2^24 workgroups
+	v.lane  = threadIdx.x & 63u;
+	v.valid = v.i < G.n;
+	const uint32_t t = v.i / G.bw;
+	v.x = v.i - t * G.bw, v.y = t % G.bh, v.z = t / G.bh;
+	return v;
+}
+
+__device__ __forceinline__ size_t edt_address(const EdtGeom &G, const EdtVoxel &v)
+{
+	return ((size_t) (G.z0 + v.z) * (size_t) G.H + (size_t) (G.y0 + v.y)) * (size_t) G.W + (size_t) (G.x0 + v.x);
+}
+
+__global__ void __launch_bounds__(256) k_edt_bits(EdtGeom G, uint64_t *__restrict__ bits)
+{
+	const EdtVoxel v = edt_voxel(G);
+	bool           t = false;
+	if (v.valid)
+		t = (G.vol[edt_address(G, v)] >= G.thr) != (G.outside != 0u);
+	const uint64_t m = __ballot(t);        // lanes past the box give 0: the last word's upper bits are no targets
+	if (v.valid && v.lane == 0)
+		bits[v.i >> 6] = m;
+}
+
+// the squared distance along the row, capped: the row's bits are [i - x, i - x + bw), of which [i - min(x, reach), i + min(bw - 1 - x, reach)]
+// is searched; a target further than reach = ceil(sqrt(limit)) away gives the cap anyway
+__global__ void __launch_bounds__(256) k_edt_x(EdtGeom G, const uint64_t *__restrict__ bits, uint32_t *__restrict__ out, uint32_t limit, uint32_t reach)
+{
+	const EdtVoxel v = edt_voxel(G);
+	if (!v.valid)        // no wave-wide operation below
+		return;
+	const uint32_t lo = v.i - min(v.x, reach), hi = v.i + min(G.bw - 1u - v.x, reach);        // lo <= i <= hi < n
+	uint32_t       dx = 0xffffffffu;
+	{        // the highest target bit in [lo, i]
+		uint32_t w = v.i >> 6;
+		uint64_t m = bits[w] & (~0ull >> (63u - (v.i & 63u)));
+		for (;;)        // w falls to lo >> 6 at the latest
+		{
+			const bool last = w == lo >> 6;
+			if (last)
+				m &= ~0ull << (lo & 63u);
+			if (m)
+			{
+				dx = v.i - (w * 64u + 63u - (uint32_t) __clzll((long long) m));
+				break;
+			}
+			if (last)
+				break;
+			m = bits[--w];
+		}
+	}
+	if (dx != 0u)
+	{        // the lowest target bit in [i, end]: nothing further than dx - 1 can win.  end <= hi < n: no wrap
+		const uint32_t end = v.i + min(hi - v.i, dx - 1u);
+		uint32_t       w   = v.i >> 6;
+		uint64_t       m   = bits[w] & (~0ull << (v.i & 63u));
+		for (;;)        // w rises to end >> 6 at the latest
+		{
+			const bool last = w == end >> 6;
+			if (last)
+				m &= ~0ull >> (63u - (end & 63u));
+			if (m)
+			{
+				dx = w * 64u + (uint32_t) __builtin_ctzll(m) - v.i;
+				break;
+			}
+			if (last)
+				break;
+			m = bits[++w];
+		}
+	}
+	// dx <= 32767 where a target was found: dx^2 < 2^30
+	out[v.i] = dx == 0xffffffffu ? limit : min(dx * dx, limit);
+}
+
+constexpr uint32_t kEdtBatch = 4;
+
+// one axis pass: p = the voxel's position on its line of `len` voxels `stride` apart
+__global__ void __launch_bounds__(256) k_edt_axis(uint32_t n, uint32_t stride, uint32_t len, const uint32_t *__restrict__ src, uint32_t *__restrict__ dst)
+{
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n)
+		return;
+	const uint32_t p = (i / stride) % len, below = p, above = len - 1u - p;
+	uint32_t       best = src[i];        // <= limit
+	const uint32_t far  = max(below, above);
+	// kEdtBatch offsets at a time, so that their loads are in flight together: of d .. d + 3 those are loaded that lie in the line and
+	// whose d^2 is below best as it stands; best only falls, so what is not loaded could not have won, and what is loaded is a voxel of the line
+	for (uint32_t d = 1; d <= far && d * d < best; d += kEdtBatch)        // d < len <= 32768: (d + 3)^2 < 2^31
+	{
+		uint32_t g[kEdtBatch];
+#pragma unroll
+		for (uint32_t k = 0; k < kEdtBatch; ++k)
+		{
+			const uint32_t dd = d + k;
+			const uint64_t o  = (uint64_t) dd * stride;
+			const bool     in = dd * dd < best, lo = in && dd <= below, hi = in && dd <= above;
+			// without a branch, so that nothing waits between the loads: an offset that is not wanted reads the voxel itself
+			const uint32_t a = src[i - (lo ? o : 0ull)], b = src[i + (hi ? o : 0ull)];
+			g[k]             = min(lo ? a : 0xffffffffu, hi ? b : 0xffffffffu);
+		}
+#pragma unroll
+		for (uint32_t k = 0; k < kEdtBatch; ++k)
+		{
+			const uint32_t d2 = (d + k) * (d + k);
+			if (d2 < best && g[k] < best - d2)        // every voxel from d2 >= best on is at least that far away
+				best = g[k] + d2;
+		}
+	}
+	dst[i] = best;
+}
+
+__global__ void __launch_bounds__(256) k_edt_select(const uint8_t *src, uint8_t *dst, EdtGeom G, const uint32_t *__restrict__ dist2, uint32_t lo, uint32_t hi,
+                                                    uint32_t fill)
+{
+	const EdtVoxel v = edt_voxel(G);
+	if (!v.valid)
+		return;
+	const size_t   a = edt_address(G, v);
+	const uint32_t d = dist2[v.i];
+	dst[a]           = d >= lo && d <= hi ? (uint8_t) fill : src[a];        // in place: a lane reads and writes its own byte only
+}
+
+struct EdtPlan
+{
+	uint32_t n, entries, wgs;
+};
+
+static bool edt_plan(VkvExtent3D e, const VkvBox *box, EdtPlan &p)
+{
+	if (!mesh_extent_and_box_ok(e, box))
+		return false;
+	const VkvBox b = whole_or(e, box);
+	if (b.width > 32768u || b.height > 32768u || b.depth > 32768u)
+		return false;
+	if ((uint64_t) b.width * b.height * b.depth > 0xffffffffull)        // the product of three factors <= 2^15 fits 64 bits
+		return false;
+	p.n       = b.width * b.height * b.depth;
+	p.entries = p.n / 64u + (p.n % 64u != 0u);        // n + 63 may wrap
+	p.wgs     = (p.entries + 3u) / 4u;
+	return true;
+}
+
+static EdtGeom edt_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, const EdtPlan &p, float iso, int target)
+{
+	EdtGeom G{};
+	G.vol = d_vol, G.W = e.width, G.H = e.height, G.x0 = b.x0, G.y0 = b.y0, G.z0 = b.z0, G.bw = b.width, G.bh = b.height, G.n = p.n;
+	G.thr     = mesh_geom(d_vol, e, b, iso, nullptr, VkvExtent3D{}, MeshPlan{}).thr;        // the mesh's own derivation
+	G.outside = target == VKV_DISTANCE_TO_OUTSIDE ? 1u : 0u;
+	return G;
+}
+
+namespace vkv
+{
+
+// [target bits: u64 x entries][the second distance buffer: u32 x voxels], an entry = 64 voxels: 4 bytes and one bit per voxel, the bits
+// rounded up to 8 bytes; 0: the extent and box are not accepted
+size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box)
+{
+	EdtPlan p;
+	if (!edt_plan(e, box, p))
+		return 0;
+	return 8 * (size_t) p.entries + 4 * (size_t) p.n;
+}
+
+bool edt_launch_ok(VkvExtent3D e, const VkvBox *box)
+{
+	EdtPlan p;
+	return edt_plan(e, box, p);
+}
+
+int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, uint32_t limit, void *d_scratch,
+                              uint32_t *d_dist2, hipStream_t s)
+{
+	EdtPlan p;
+	if (!edt_plan(e, &b, p))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768");
+	uint64_t     *bits  = static_cast<uint64_t *>(d_scratch);
+	uint32_t     *other = reinterpret_cast<uint32_t *>(bits + p.entries);
+	const EdtGeom G     = edt_geom(d_vol, e, b, p, iso, target);
+	uint32_t      reach = 0;        // the smallest r with r^2 >= limit: at most 65536
+	while ((uint64_t) reach * reach < limit)
+		++reach;
+	const bool y = b.height > 1u, z = b.depth > 1u;
+	uint32_t  *cur = (y != z) ? other : d_dist2, *nxt = (y != z) ? d_dist2 : other;        // one further pass: it starts in the scratch block
+	hipLaunchKernelGGL(k_edt_bits, dim3(p.wgs), dim3(256), 0, s, G, bits);
+	hipLaunchKernelGGL(k_edt_x, dim3(p.wgs), dim3(256), 0, s, G, bits, cur, limit, reach);
+	if (y)
+	{
+		hipLaunchKernelGGL(k_edt_axis, dim3(p.wgs), dim3(256), 0, s, p.n, b.width, b.height, cur, nxt);
+		std::swap(cur, nxt);
+	}
+	if (z)
+	{
+		hipLaunchKernelGGL(k_edt_axis, dim3(p.wgs), dim3(256), 0, s, p.n, b.width * b.height, b.depth, cur, nxt);
+		std::swap(cur, nxt);
+	}
+	return check_launch(ctx, "distance_transform");        // cur == d_dist2
+}
+
+int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_dist2, uint32_t lo,
+                              uint32_t hi, uint32_t fill, hipStream_t s)
+{
+	EdtPlan p;
+	if (!edt_plan(e, &b, p))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "select_by_distance: a box of more than 2^32 - 1 voxels or an axis above 32768");
+	const EdtGeom G = edt_geom(d_src, e, b, p, 0.0f, VKV_DISTANCE_TO_INSIDE);
+	hipLaunchKernelGGL(k_edt_select, dim3(p.wgs), dim3(256), 0, s, d_src, d_dst, G, d_dist2, lo, hi, fill);
+	return check_launch(ctx, "select_by_distance");
+}
+
+}        // namespace vkv

@@ -125,6 +125,16 @@ int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, c
 int launch_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels,
                              const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, hipStream_t s);
 
+// ---- edt.hip
+// vkv_distance_transform_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (at most 2^32 - 1 voxels in the
+// box, no box axis above 32768), and vkv_distance_transform / vkv_select_by_distance after the entry points' argument checks (b inside e)
+size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+bool   edt_launch_ok(VkvExtent3D e, const VkvBox *box);
+int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, uint32_t limit, void *d_scratch,
+                              uint32_t *d_dist2, hipStream_t s);
+int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_dist2, uint32_t lo,
+                              uint32_t hi, uint32_t fill, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

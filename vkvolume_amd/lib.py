@@ -27,6 +27,7 @@ EXPORTS = [
     "vkv_isosurface_mesh_scratch_bytes", "vkv_isosurface_mesh",
     "vkv_isosurface_mesh_indexed_scratch_bytes", "vkv_isosurface_mesh_indexed",
     "vkv_label_components_scratch_bytes", "vkv_label_components", "vkv_select_components",
+    "vkv_distance_transform_scratch_bytes", "vkv_distance_transform", "vkv_select_by_distance",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
 DEBUG_EXPORTS = ["vkv_debug_trace", "vkv_debug_tile_orders", "vkv_debug_check", "vkv_debug_tf_scratch"]
@@ -126,6 +127,10 @@ def load():
     L.vkv_label_components_scratch_bytes.restype = C.c_size_t
     L.vkv_label_components.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, i32, vp, abi.Extent3D, vp, vp, vp, C.c_uint64, vp, vp]
     L.vkv_select_components.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), vp, vp, vp, C.c_uint64, C.c_uint64, u32, vp]
+    L.vkv_distance_transform_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
+    L.vkv_distance_transform_scratch_bytes.restype = C.c_size_t
+    L.vkv_distance_transform.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, i32, u32, vp, vp, vp]
+    L.vkv_select_by_distance.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), vp, u32, u32, u32, vp]
     L.vkv_debug_tf_scratch.argtypes = [vp, vp, vp]
     L.vkv_convert_volume.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.vkv_load_header.argtypes = [C.c_char_p, P(abi.VolumeHeader)]
@@ -407,6 +412,28 @@ class Context:
         return self._lib.vkv_select_components(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), d_labels, d_sizes, d_counts,
                                                int(min_voxels), int(max_voxels), int(fill), stream)
 
+    def distance_transform(self, d_volume, extent, box, iso, target, limit, d_scratch, d_dist2, stream=0):
+        """vkv_distance_transform: d_dist2 (uint32, the shape of `box`; None: of the volume) = min(limit, the squared Euclidean distance to
+        the nearest target voxel of the box), the targets being the voxels at or above `iso` (abi.DISTANCE_TO_INSIDE) or below it
+        (abi.DISTANCE_TO_OUTSIDE); limit None or abi.DISTANCE_NONE: unlimited.  d_scratch: distance_transform_scratch_bytes(extent, box)
+        bytes."""
+        self.check(self.distance_transform_rc(d_volume, extent, box, iso, target, limit, d_scratch, d_dist2, stream))
+
+    def distance_transform_rc(self, d_volume, extent, box, iso, target, limit, d_scratch, d_dist2, stream=0):
+        """Like distance_transform() but returns the status code (error-path tests)."""
+        return self._lib.vkv_distance_transform(self.handle, d_volume, extent, None if box is None else C.byref(box), float(iso), int(target),
+                                                abi.DISTANCE_NONE if limit is None else int(limit), d_scratch, d_dist2, stream)
+
+    def select_by_distance(self, d_src, d_dst, extent, box, d_dist2, lo, hi, fill, stream=0):
+        """vkv_select_by_distance: the voxels of `box` of d_dst = `fill` where lo <= d_dist2 <= hi (distance_transform() of the same box),
+        else d_src; d_dst may be d_src"""
+        self.check(self.select_by_distance_rc(d_src, d_dst, extent, box, d_dist2, lo, hi, fill, stream))
+
+    def select_by_distance_rc(self, d_src, d_dst, extent, box, d_dist2, lo, hi, fill, stream=0):
+        """Like select_by_distance() but returns the status code (error-path tests)."""
+        return self._lib.vkv_select_by_distance(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), d_dist2, int(lo), int(hi),
+                                                int(fill), stream)
+
     def filter_volume(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""
         self.check(self.filter_volume_rc(d_src, d_dst, extent, box, kind, stream))
@@ -520,6 +547,12 @@ def components_scratch_bytes(extent, box=None):
     """vkv_label_components_scratch_bytes: the scratch vkv_label_components needs for `box` (None: the whole volume) of `extent`; 0 for an
     extent or box the call rejects (a box of more than 2^32 - 1 voxels included)"""
     return int(load().vkv_label_components_scratch_bytes(extent, None if box is None else C.byref(box)))
+
+
+def distance_transform_scratch_bytes(extent, box=None):
+    """vkv_distance_transform_scratch_bytes: the scratch vkv_distance_transform needs for `box` (None: the whole volume) of `extent`: 4 bytes
+    per voxel and 8 per 64 voxels; 0 for an extent or box the call rejects (more than 2^32 - 1 voxels or an axis above 32768 included)"""
+    return int(load().vkv_distance_transform_scratch_bytes(extent, None if box is None else C.byref(box)))
 
 
 def mesh_indexed_scratch_bytes(extent, box=None):

@@ -411,6 +411,96 @@ class Volume:
                                    int(min_voxels), 0xffffffffffffffff, int(fill), _stream())
         return out
 
+    _DISTANCE_TARGETS = {"inside": abi.DISTANCE_TO_INSIDE, "outside": abi.DISTANCE_TO_OUTSIDE}
+
+    def _distance_transform(self, src, iso, target, limit, box):
+        """vkv_distance_transform of the uint8 tensor `src` (the volume's shape) on the current stream; box: an abi.Box or None"""
+        nbytes = lib.distance_transform_scratch_bytes(self.extent, box)
+        if nbytes == 0:
+            raise ValueError("Volume.distance_transform: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
+        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
+        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        dist2 = torch.empty(shape, dtype=torch.uint32, device=self.device)
+        self.ctx.distance_transform(_ptr(src), self.extent, box, iso, target, limit, _ptr(scratch), _ptr(dist2), _stream())
+        return dist2
+
+    def distance_transform(self, iso, to="inside", limit=None, box=None):
+        """The exact squared Euclidean distance transform on the current stream (vkv_distance_transform): a torch.uint32 tensor of the box's
+        shape [depth, height, width] (the volume's without a box) that holds, per voxel, the squared distance in voxel units to the nearest
+        voxel with value >= ``iso`` (``to="inside"``; the mesh's inside rule) or below it (``to="outside"``), 0 on such a voxel.  ``limit``:
+        values are capped at it (cheaper: the work grows with the distance found); None: unlimited, and 0xffffffff everywhere where the box
+        holds no such voxel.  Only the box's voxels exist: nothing beyond it counts as inside or outside.  No host wait."""
+        if to not in self._DISTANCE_TARGETS:
+            raise ValueError("Volume.distance_transform: `to` must be 'inside' or 'outside'")
+        if limit is not None and (int(limit) != limit or not 1 <= limit <= abi.DISTANCE_NONE):
+            raise ValueError("Volume.distance_transform: limit must be an integer in 1 .. 0xffffffff or None")
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        return self._distance_transform(self.volume, iso, self._DISTANCE_TARGETS[to], limit, box)
+
+    @staticmethod
+    def ball_radius2(radius=None, radius2=None):
+        """The squared radius of a morphology call: ``radius2`` itself, or floor(radius * radius) in doubles (so sqrt(2) gives 2); the ball
+        holds the offsets with dx^2 + dy^2 + dz^2 <= radius2.  At least 1: radius2 = 1 is the 6-neighbourhood, 2 the 18, 3 the 26."""
+        if (radius is None) == (radius2 is None):
+            raise ValueError("give exactly one of radius and radius2")
+        if radius2 is None:
+            if not radius >= 0:
+                raise ValueError("radius must be a non-negative number")
+            r2 = int(np.floor(float(radius) * float(radius)))
+        else:
+            if int(radius2) != radius2:
+                raise ValueError("radius2 must be an integer")
+            r2 = int(radius2)
+        if not 1 <= r2 <= abi.DISTANCE_NONE - 1:
+            raise ValueError("the squared radius must lie in 1 .. 0xfffffffe")
+        return r2
+
+    def _morphology(self, name, steps, iso, radius, radius2, inside_fill, outside_fill, out, box):
+        """steps: "erode" / "dilate" in order; the first reads the volume, each further one the result before it (in place in `out`)"""
+        r2 = self.ball_radius2(radius, radius2)
+        for f in (inside_fill, outside_fill):
+            if int(f) != f or not 0 <= f <= 255:
+                raise ValueError("Volume.%s: inside_fill and outside_fill must be bytes" % name)
+        if box is not None and not isinstance(box, abi.Box):
+            (x0, y0, z0), (w, h, d) = box
+            box = abi.Box(x0, y0, z0, w, h, d)
+        if out is None:
+            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
+        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
+            raise ValueError("Volume.%s: `out` must be a contiguous uint8 tensor of shape %s on %s" % (name, tuple(self.volume.shape), self.volume.device))
+        src = self.volume
+        for step in steps:
+            erode = step == "erode"
+            dist2 = self._distance_transform(src, iso, abi.DISTANCE_TO_OUTSIDE if erode else abi.DISTANCE_TO_INSIDE, r2 + 1, box)
+            self.ctx.select_by_distance(_ptr(src), _ptr(out), self.extent, box, _ptr(dist2), 1, r2, int(outside_fill if erode else inside_fill), _stream())
+            src = out
+        return out
+
+    def erode(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+        """The volume eroded by a ball on the current stream (vkv_distance_transform to the outside with limit radius2 + 1, then
+        vkv_select_by_distance): a uint8 tensor of the volume's shape in which every inside voxel (value >= ``iso``) within the ball of an
+        outside voxel holds ``outside_fill``; everything else is the volume's byte.  Give ``radius`` (radius2 = floor(radius * radius)) or
+        ``radius2``.  ``outside_fill`` should lie below iso and ``inside_fill`` at or above it (dilate(), open() and close() write it).
+        ``out``: a contiguous uint8 tensor of the volume's shape on its device (``out=self.volume`` works in place); without it a copy is
+        made.  ``box``: only the box's voxels exist, take part and are written; nothing beyond the box is outside, so the erosion does not
+        eat at the box's faces (scipy's border_value=1).  ``self.volume`` is not touched unless ``out`` is the volume."""
+        return self._morphology("erode", ("erode",), iso, radius, radius2, inside_fill, outside_fill, out, box)
+
+    def dilate(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+        """The volume dilated by a ball: every outside voxel within the ball of an inside voxel holds ``inside_fill``; see erode()."""
+        return self._morphology("dilate", ("dilate",), iso, radius, radius2, inside_fill, outside_fill, out, box)
+
+    def open(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+        """The opening by a ball: erode(), then dilate() of the result.  It cuts bridges and removes parts thinner than the ball, after which
+        remove_islands() can drop what they held on by; see erode()."""
+        return self._morphology("open", ("erode", "dilate"), iso, radius, radius2, inside_fill, outside_fill, out, box)
+
+    def close(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+        """The closing by a ball: dilate(), then erode() of the result.  It fills pores and cracks thinner than the ball; see erode()."""
+        return self._morphology("close", ("dilate", "erode"), iso, radius, radius2, inside_fill, outside_fill, out, box)
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
