@@ -10,7 +10,8 @@ lock-free union-find; a workgroup holds four entries; a scan chunk holds 4096 en
   64x1x1, 64x2x1, 64x3x1, 64x1x2, 64x1x3, 64x2x3   at, one past and two past one tile in y and z (a tile is one row and one slice);
   255, 256, 257 x 2 x 2                  around one workgroup along x;
   5x7x67, 9x33x5                        narrow boxes: an entry spans many rows and several slices;
-  64x65x64 (266240 voxels)              crosses a scan chunk: the second chunk's components take the first chunk's total.
+  64x65x64 (266240 voxels)              crosses a scan chunk: the second chunk's components take the first chunk's total;
+  64x1024x1025 (67174400 voxels)        257 chunk sums, one more than a round of the scan of the chunk sums holds (closed-form references).
 Contents: below and above (nothing, one component), random densities 0.1, 0.31 (the cubic site-percolation threshold: large tortuous
 components) and 0.6, the 3-D checkerboard (all singletons under 6, one component under 14 and 26), a ball, a serpentine (ONE
 one-voxel-wide path through every row and slice: one component over every seam, with long find chains), two slabs joined by one voxel.
@@ -104,9 +105,10 @@ def test_the_contents_are_what_the_docstring_says():
 
 
 # ---- one call ---------------------------------------------------------------------------------------------------------------------------
-def run(ctx, vol, iso, connectivity, cap, box=None, block=0, vol_offset=0, vol_fill=0x00, null_sizes=False, what=""):
+def run(ctx, vol, iso, connectivity, cap, box=None, block=0, vol_offset=0, vol_fill=0x00, null_sizes=False, map_extent=None, max_map=None, what=""):
     """(labels: the whole buffer, the box's shape, uint32; sizes: the whole buffer [max(cap, 1)] uint32; counts [3] uint64) of ONE
-    vkv_label_components call on guarded buffers, every output pre-filled with FILL; with `block` through the max map of that block size"""
+    vkv_label_components call on guarded buffers, every output pre-filled with FILL; with `block` through the max map of that block size, with
+    `map_extent` (w, h, d) through the map of that extent (built here, or the bytes `max_map`)"""
     abox = None if box is None else abi.Box(*box)
     shape = vol.shape if box is None else (box[5], box[4], box[3])
     d_vol, h_vol = T.guarded(vol, vol_offset, vol_fill, "cuda")
@@ -118,10 +120,14 @@ def run(ctx, vol, iso, connectivity, cap, box=None, block=0, vol_offset=0, vol_f
     d_sizes, h_sizes = T.guarded((max(cap, 1),), 0, FILL, "cuda", dtype=np.int32)
     handles = [("d_volume", h_vol), ("d_scratch", h_scratch), ("d_counts", h_counts), ("d_labels", h_labels), ("d_sizes", h_sizes)]
     d_map = me = None
-    if block:
-        me = block_extent(vol, block)
-        d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
-        ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+    if block or map_extent is not None:
+        me = block_extent(vol, block) if map_extent is None else abi.Extent3D(*map_extent)
+        if max_map is None:
+            d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
+            ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+        else:
+            assert max_map.shape == (me.depth, me.height, me.width) and max_map.dtype == np.uint8
+            d_map, h_map = T.guarded(max_map, 0, FILL, "cuda")
         handles.append(("d_max_map", h_map))
     ctx.label_components(d_vol.data_ptr(), ext_of(vol), abox, iso, connectivity, None if d_map is None else d_map.data_ptr(), me, d_scratch.data_ptr(),
                          d_labels.data_ptr(), None if null_sizes else d_sizes.data_ptr(), cap, d_counts.data_ptr(), st())
@@ -191,6 +197,51 @@ def test_more_entries_than_one_scan_chunk(ctx, chunk_extent, content):
         if content.startswith("random") and c == 6:
             assert want[0].reshape(-1)[262144:].max() > want[0].reshape(-1)[:262144].max() > 0        # components begin in both chunks
         check(ctx, vol, ISO, c, want, what="%s %s, %d" % (content, chunk_extent, c))
+
+
+# ---- more chunk sums than one round of the scan -------------------------------------------------------------------------------------------
+ROUNDS_EXTENT = (64, 1024, 1025)        # 67 174 400 voxels = 1 049 600 entries of 64 = 257 chunks of 4096: one more than a round of the scan holds
+
+
+@pytest.fixture(scope="module")
+def lattice():
+    """inside exactly where x, y and z are all even: every component is one voxel under 6, 14 and 26, so K = 32 x 512 x 513, the label of an
+    inside voxel is its running count in memory order and every size is 1 (closed forms: components_np does not run at this size)"""
+    w, h, d = ROUNDS_EXTENT
+    vol = np.zeros((d, h, w), np.uint8)
+    vol[::2, ::2, ::2] = 255
+    inside = vol.reshape(-1) != 0
+    k = 32 * 512 * 513
+    labels = np.where(inside, np.cumsum(inside, dtype=np.uint32), np.uint32(0)).reshape(vol.shape)
+    assert int(labels.max()) == k == 8404992 and labels[d - 1, h - 2, w - 2] == k
+    return vol, (labels, np.ones(k, np.uint32), np.array([k, k, k], np.uint64))
+
+
+@pytest.mark.parametrize("connectivity", [6, 26])
+def test_more_chunk_sums_than_one_round_of_the_scan_lattice(ctx, lattice, connectivity):
+    """257 chunk sums: k_cc_scan_total carries a total into a second round, and the last chunk's components are ranked behind 8 388 608 others;
+    with capacity K - 1 the exact prefix of the sizes is written and nothing behind it"""
+    vol, want = lattice
+    k = int(want[2][0])
+    check(ctx, vol, ISO, connectivity, want, cap=k, what="lattice %s, %d, capacity K" % (ROUNDS_EXTENT, connectivity))
+    check(ctx, vol, ISO, connectivity, want, cap=k - 1, what="lattice %s, %d, capacity K - 1" % (ROUNDS_EXTENT, connectivity))
+
+
+@pytest.mark.parametrize("connectivity", [6, 26])
+def test_more_chunk_sums_than_one_round_of_the_scan_sparse_rows(ctx, connectivity):
+    """five full rows far apart, the last one the last entry of the 257th chunk: five components of 64 voxels, and the last one's label, 5,
+    is the total that the scan carried over 256 chunk sums plus one"""
+    w, h, d = ROUNDS_EXTENT
+    vol = np.zeros((d, h, w), np.uint8)
+    labels = np.zeros((d, h, w), np.uint32)
+    rows = ((0, 0), (3, 1000), (512, 513), (1023, 0), (1024, 1023))
+    for k, (z, y) in enumerate(rows):
+        vol[z, y, :] = 255
+        labels[z, y, :] = k + 1
+    assert (rows[-1][0] * h + rows[-1][1]) // 4096 == 256 and (rows[-2][0] * h + rows[-2][1]) // 4096 < 256
+    want = (labels, np.full(5, 64, np.uint32), np.array([5, 5, 320], np.uint64))
+    check(ctx, vol, ISO, connectivity, want, what="sparse rows %s, %d" % (ROUNDS_EXTENT, connectivity))
+    check(ctx, vol, ISO, connectivity, want, cap=4, what="sparse rows %s, %d, capacity 4" % (ROUNDS_EXTENT, connectivity))
 
 
 # ---- boxes ------------------------------------------------------------------------------------------------------------------------------

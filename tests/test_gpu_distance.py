@@ -8,7 +8,8 @@ look d voxels up and down their line while d^2 is below the best value so far; a
                                           either buffer), fewer voxels than a wave, one short of, at and one past one and two words along
                                           x, around one workgroup, narrow boxes whose entries wrap rows and slices;
   200x3x2, 3x200x2, 2x3x200             long walks along each axis, over several words along x;
-  70x66x65                              every axis longer than a word, several workgroups per slice.
+  70x66x65                              every axis longer than a word, several workgroups per slice;
+  32768x2x2, 2x32768x2, 2x2x32768       the longest axis the call accepts, with the limits around 32767^2 (closed-form references).
 Contents: no target and all target; ONE target voxel at each corner and at the centre (most rows and columns then carry "none", the cap,
 and every offset up to the full diagonal is added to it: the overflow case); one full slice per axis; random at 0.001, 0.1, 0.5 and 0.9; a
 ball; the 3-D checkerboard.  Both targets; limits NONE, 1, 2, 9, 10 and 100000.  The reference of a limited call is min(limit, the unlimited
@@ -133,6 +134,39 @@ def test_every_axis_longer_than_a_word(ctx, content):
     w, h, d = 70, 66, 65
     vol = contents(content, (d, h, w), seed=41)
     check_all_limits(ctx, vol, what="%s 70x66x65" % content)
+
+
+# ---- the longest axis -------------------------------------------------------------------------------------------------------------------
+LONGEST = 32768        # edt.hip: axes up to 32768, dx * dx < 2^30, (d + 3)^2 < 2^31, reach <= 65536
+FARTHEST = (LONGEST - 1) ** 2        # 1 073 676 289: the farthest row distance
+LONG_LIMITS = (None, FARTHEST, FARTHEST + 1, FARTHEST + 2, 0xfffffffe)        # reach 32767: the row's end equals the cap; reach 32768; the far corner's
+LONG_CONTENTS = {"corner 0": (0,), "corner 7": (7,), "corners 0 and 7": (0, 7), "no target": ()}        # distance 32767^2 + 1 + 1; the largest limit
+
+
+@pytest.mark.parametrize("content", sorted(LONG_CONTENTS), ids=lambda c: c.replace(" ", "_"))
+@pytest.mark.parametrize("extent", [(LONGEST, 2, 2), (2, LONGEST, 2), (2, 2, LONGEST)], ids=lambda e: "%dx%dx%d" % e)
+def test_an_axis_of_32768_voxels(ctx, extent, content):
+    """the longest axis the call accepts, along each axis in turn: targets at the two far corners, so that the largest offsets and their
+    squares occur (and, without a target, every line is walked to its end); the reference is the definition in 64-bit integers: the minimum over
+    the targets of the sum of the squared coordinate differences, capped.  To the outside, the volume is the inverted one"""
+    w, h, d = extent
+    corners = [((d - 1) * (k >> 2 & 1), (h - 1) * (k >> 1 & 1), (w - 1) * (k & 1)) for k in LONG_CONTENTS[content]]
+    z, y, x = (a.astype(np.uint64) for a in np.indices((d, h, w), sparse=True))
+    sq = lambda a, c: np.where(a > c, a - np.uint64(c), np.uint64(c) - a) ** 2  # noqa: E731
+    exact = np.full((d, h, w), 2 ** 64 - 1, np.uint64)
+    for cz, cy, cx in corners:
+        exact = np.minimum(exact, sq(z, cz) + sq(y, cy) + sq(x, cx))
+    if len(corners) == 1:
+        assert int(exact.max()) == FARTHEST + 2        # the far corner
+    for target in TARGETS:
+        vol = np.full((d, h, w), 17 if target == TO_INSIDE else 200, np.uint8)
+        for c in corners:
+            vol[c] = 200 if target == TO_INSIDE else 17
+        device_volume = upload(vol)
+        for limit in LONG_LIMITS:
+            want = np.minimum(exact, np.uint64(NONE if limit is None else limit)).astype(np.uint32)
+            what = "%s %s, to %s, limit %s" % (content, extent, ("inside", "outside")[target], limit)
+            same(run(ctx, vol, ISO, target, limit, device_volume=device_volume, what=what), want, what)
 
 
 # ---- boxes ------------------------------------------------------------------------------------------------------------------------------
@@ -399,6 +433,57 @@ def test_volume_morphology_against_scipy(ctx, blobs):
     inplace = make_volume(ctx, blobs, block=2, packed=False)
     assert inplace.open(ISO, radius2=4, out=inplace.volume) is inplace.volume
     same(inplace.volume.cpu().numpy(), dilate_np(erode_np(blobs, ISO, 4), ISO, 4), "Volume.open in place")
+
+
+IN_PLACE = ("dilate", "close", "open", "erode", "remove_islands")
+
+
+@pytest.mark.parametrize("call", IN_PLACE)
+def test_in_place_results_keep_the_max_map_current(ctx, blobs, call):
+    """out=v.volume: dilate and close raise voxels to inside_fill, so the map built before the call is no upper bound any more and everything
+    that skips through it would drop geometry; the others lower voxels.  After the call the map is max_map_np of the new bytes, and the
+    consumers that skip through it give what the dense ones give"""
+    from tests.test_gpu_mip import assert_same_bits, draw, subpass
+    from tests.test_mesh_cpu import mesh_np, same_bits
+    from tests.test_mip_cpu import max_map_np
+    r2, block = 4, 2
+    base = blobs
+    if call == "remove_islands":
+        base = erode_np(blobs, ISO, r2)        # (the blobs are one component; eroded they fall apart)
+        wl, ws, wc = components_np(base, ISO, 6)
+        assert wc[0] >= 10
+        want = select_np(base, wl, ws, len(ws), int(ws.max()), 2 ** 64 - 1, 0)
+    else:
+        want = {"dilate": lambda: dilate_np(blobs, ISO, r2), "erode": lambda: erode_np(blobs, ISO, r2), "open": lambda: dilate_np(erode_np(blobs, ISO, r2), ISO, r2),
+                "close": lambda: erode_np(dilate_np(blobs, ISO, r2), ISO, r2)}[call]()
+    me = tuple(-(-e // block) for e in base.shape[::-1])
+    before, after = max_map_np(base, me), max_map_np(want, me)
+    assert (want != base).any() and (after != before).any(), "the premise: the call changes voxels and the map"
+    if call in ("dilate", "close"):
+        assert ((before < 128) & (after >= 128)).any(), "the premise: a cell below iso holds inside voxels after the call"
+    v = make_volume(ctx, base, block=block, packed=False)
+    same(v.max_map.cpu().numpy(), before, "the map before the call")
+    if call == "remove_islands":
+        assert v.remove_islands(ISO, keep_largest=True, out=v.volume) is v.volume
+    else:
+        assert getattr(v, call)(ISO, radius2=r2, out=v.volume) is v.volume
+    same(v.volume.cpu().numpy(), want, "Volume.%s in place" % call)
+    same(v.max_map.cpu().numpy(), after, "Volume.%s in place: the max map" % call)
+    mesh = mesh_np(want, ISO)
+    assert len(mesh) > 100
+    for use_max_map in (True, False):
+        tri, total = v.extract_isosurface(ISO, use_max_map=use_max_map)
+        assert total == len(mesh)
+        same_bits(tri.cpu().numpy(), mesh, "extract_isosurface(use_max_map=%s) after Volume.%s in place" % (use_max_map, call))
+    labels, sizes, counts = v.label_components(ISO, connectivity=6, use_max_map=True)
+    wl, ws, wc = components_np(want, ISO, 6)
+    same(labels.cpu().numpy(), wl, "label_components(use_max_map=True): labels")
+    same(sizes.cpu().numpy(), ws, "label_components(use_max_map=True): sizes")
+    assert counts.cpu().tolist() == wc.tolist()
+    sp, p = subpass(v)
+    dense, fast = draw(sp, p, 0.5, 1.0, skip=False), draw(sp, p, 0.5, 1.0, skip=True)
+    assert (dense["rgba8"][:, 3] == 255).sum() > 20
+    assert_same_bits(fast, dense, "draw_mip(skip=True) after Volume.%s in place" % call)
 
 
 def test_an_opening_cuts_the_bridge_that_island_removal_cannot(ctx):

@@ -4,7 +4,10 @@ kinds of content, an anisotropic / rotated voxel grid, a camera outside, inside 
 odd image, a sampling factor, bounds on and beside the map's bytes, packed or linear sampling and, on some draws, a depth attachment
 (tests/test_max_map_skip_cpu.py: draw_geometry).  For every draw: vkv_max_map equals max_map_np; the skipping MIP / isosurface equal the
 dense ones bit for bit on every output; the dense ones equal mip_np / iso_np bit for bit; the skipping path's three counters equal the
-restated walk's (max_map_skip_np) pixel by pixel; and the draw skipped samples."""
+restated walk's (max_map_skip_np) pixel by pixel; and the draw skipped samples.  The other entry points that skip over the map
+(vkv_isosurface_mesh, vkv_isosurface_mesh_indexed, vkv_label_components, the MAX mode of vkv_render_slab) have cell arithmetic of their own and
+are swept in tests/test_gpu_max_map_consumers.py, with wider volumes (tiles of 256 cubes) and the draw recipe of
+tests/test_max_map_consumers_cpu.py."""
 import os
 
 import numpy as np

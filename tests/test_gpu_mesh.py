@@ -45,9 +45,10 @@ def block_extent(vol, block):
     return abi.Extent3D((w + block - 1) // block, (h + block - 1) // block, (d + block - 1) // block)
 
 
-def run(ctx, vol, iso, capacity, box=None, block=0, vol_offset=0, vol_fill=0x00, null_triangles=False, what=""):
+def run(ctx, vol, iso, capacity, box=None, block=0, vol_offset=0, vol_fill=0x00, null_triangles=False, map_extent=None, max_map=None, what=""):
     """(counts [2] uint64, the whole triangle buffer [capacity, 3, 3] float32) of ONE vkv_isosurface_mesh call on guarded buffers, every output
-    pre-filled with FILL; with `block` the call goes through the max map of that block size (built here by vkv_max_map)"""
+    pre-filled with FILL; with `block` the call goes through the max map of that block size (built here by vkv_max_map), with `map_extent` (w, h, d)
+    through the map of that extent: built here, or the bytes `max_map` (md, mh, mw)"""
     abox = None if box is None else abi.Box(*box)
     d_vol, h_vol = T.guarded(vol, vol_offset, vol_fill, "cuda")
     nbytes = lib.mesh_scratch_bytes(ext_of(vol), abox)
@@ -57,10 +58,14 @@ def run(ctx, vol, iso, capacity, box=None, block=0, vol_offset=0, vol_fill=0x00,
     d_tri, h_tri = T.guarded((max(capacity, 1), 3, 3), 0, FILL, "cuda", dtype=np.float32)
     handles = [("d_volume", h_vol), ("d_scratch", h_scratch), ("d_counts", h_counts), ("d_triangles", h_tri)]
     d_map = me = None
-    if block:
-        me = block_extent(vol, block)
-        d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
-        ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+    if block or map_extent is not None:
+        me = block_extent(vol, block) if map_extent is None else abi.Extent3D(*map_extent)
+        if max_map is None:
+            d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
+            ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+        else:
+            assert max_map.shape == (me.depth, me.height, me.width) and max_map.dtype == np.uint8
+            d_map, h_map = T.guarded(max_map, 0, FILL, "cuda")
         handles.append(("d_max_map", h_map))
     ctx.isosurface_mesh(d_vol.data_ptr(), ext_of(vol), abox, iso, None if d_map is None else d_map.data_ptr(), me, d_scratch.data_ptr(),
                         None if null_triangles else d_tri.data_ptr(), capacity, d_counts.data_ptr(), st())

@@ -39,9 +39,11 @@ def guard_damage(h):
     return np.flatnonzero(changed).tolist()
 
 
-def run(ctx, vol, iso, cap_v, cap_t, box=None, block=0, vol_offset=0, vol_fill=0x00, normals=True, null_vertices=False, null_indices=False, what=""):
+def run(ctx, vol, iso, cap_v, cap_t, box=None, block=0, vol_offset=0, vol_fill=0x00, normals=True, null_vertices=False, null_indices=False, map_extent=None,
+        max_map=None, what=""):
     """(counts [4] uint64, the whole vertex buffer [cap_v, 3] float32, the whole normal buffer, the whole index buffer [cap_t, 3] uint32) of ONE
-    vkv_isosurface_mesh_indexed call on guarded buffers, every output pre-filled with FILL; with `block` through the max map of that block size"""
+    vkv_isosurface_mesh_indexed call on guarded buffers, every output pre-filled with FILL; with `block` through the max map of that block size, with `map_extent` (w, h, d)
+    through the map of that extent (built here, or the bytes `max_map`)"""
     abox = None if box is None else abi.Box(*box)
     d_vol, h_vol = T.guarded(vol, vol_offset, vol_fill, "cuda")
     nbytes = lib.mesh_indexed_scratch_bytes(ext_of(vol), abox)
@@ -53,10 +55,14 @@ def run(ctx, vol, iso, cap_v, cap_t, box=None, block=0, vol_offset=0, vol_fill=0
     d_idx, h_idx = T.guarded((max(cap_t, 1), 3), 0, FILL, "cuda", dtype=np.int32)
     handles = [("d_volume", h_vol), ("d_scratch", h_scratch), ("d_counts", h_counts), ("d_vertices", h_vert), ("d_normals", h_norm), ("d_indices", h_idx)]
     d_map = me = None
-    if block:
-        me = block_extent(vol, block)
-        d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
-        ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+    if block or map_extent is not None:
+        me = block_extent(vol, block) if map_extent is None else abi.Extent3D(*map_extent)
+        if max_map is None:
+            d_map, h_map = T.guarded((me.depth, me.height, me.width), 0, FILL, "cuda")
+            ctx.max_map(d_vol.data_ptr(), ext_of(vol), me, None, d_map.data_ptr(), st())
+        else:
+            assert max_map.shape == (me.depth, me.height, me.width) and max_map.dtype == np.uint8
+            d_map, h_map = T.guarded(max_map, 0, FILL, "cuda")
         handles.append(("d_max_map", h_map))
     ctx.isosurface_mesh_indexed(d_vol.data_ptr(), ext_of(vol), abox, iso, None if d_map is None else d_map.data_ptr(), me, d_scratch.data_ptr(),
                                 None if null_vertices else d_vert.data_ptr(), d_norm.data_ptr() if normals and not null_vertices else None, cap_v,

@@ -47,6 +47,18 @@ def bound_candidates(mm):
     return vals
 
 
+def place_bright_voxels(rng, vol, shape, blocks):
+    """1 .. 11 bright voxels (100 .. 255) written into vol (d, h, w): on the faces, edges and corners of cells of `blocks` voxels, at their
+    centres, and one voxel outside a cell's own box (clamped to the volume)"""
+    for _ in range(int(rng.integers(1, 12))):
+        c = [int(rng.integers(0, -(-e // b))) for e, b in zip(shape, blocks)]
+        pos = []
+        for ci, b, e in zip(c, blocks, shape):
+            lo = ci * b
+            pos.append(min(max(int(rng.choice([lo, lo + b - 1, lo - 1, lo + b, lo + b // 2])), 0), e - 1))
+        vol[pos[2], pos[1], pos[0]] = int(rng.integers(100, 256))
+
+
 def draw_geometry(rng, family, max_extent=64):
     """one draw of the sweep: dict shape (w, h, d), vol (d, h, w) uint8, map_extent (w, h, d), voxel_size, axis_angle, camera (azimuth,
     elevation, radius, clip), axis_parallel, sampling_factor, and plateau (the plateau's byte, or None)"""
@@ -68,13 +80,7 @@ def draw_geometry(rng, family, max_extent=64):
     elif family == "bright_voxels":
         # a dim background, bright voxels on the faces, edges and corners of cells and one voxel outside a cell's own box
         vol = rng.integers(0, 24, (d, h, w), dtype=np.uint8)
-        for _ in range(int(rng.integers(1, 12))):
-            c = [int(rng.integers(0, -(-e // b))) for e, b in zip(shape, (bx, by, bz))]
-            pos = []
-            for ci, b, e in zip(c, (bx, by, bz), shape):
-                lo = ci * b
-                pos.append(min(max(int(rng.choice([lo, lo + b - 1, lo - 1, lo + b, lo + b // 2])), 0), e - 1))
-            vol[pos[2], pos[1], pos[0]] = int(rng.integers(100, 256))
+        place_bright_voxels(rng, vol, shape, (bx, by, bz))
     elif family == "plateau":
         plateau = int(rng.integers(1, 255))
         vol = rng.integers(0, plateau, (d, h, w), dtype=np.uint8) // 2

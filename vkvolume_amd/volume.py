@@ -390,7 +390,9 @@ class Volume:
         Exactly one of ``min_voxels`` and ``keep_largest`` must be given.  ``fill`` should lie below iso (the default 0 does for every iso >
         0).  ``out``: a contiguous uint8 tensor of the volume's shape on its device (``out=self.volume`` works in place); without it a copy
         is made.  ``box``: only the box's voxels take part and are written; components are those of the box alone.  ``self.volume`` and the
-        derived buffers are not touched unless ``out`` is the volume: loading the result is the caller's decision."""
+        derived buffers are not touched unless ``out`` is the volume: loading the result is the caller's decision.  In place, a max map built
+        with build_max_map() is rebuilt over the box on the same stream, without a host wait, and stays current; the gradient map, the packed
+        image, the cell summary and the occupancy and distance maps are the caller's to re-derive."""
         if (min_voxels is None) == (not keep_largest):
             raise ValueError("Volume.remove_islands: give exactly one of min_voxels and keep_largest")
         if min_voxels is not None and (int(min_voxels) != min_voxels or min_voxels < 0):
@@ -409,7 +411,14 @@ class Volume:
             min_voxels = int(sizes.to(torch.int64).max().item()) if sizes.numel() else 0
         self.ctx.select_components(_ptr(self.volume), _ptr(out), self.extent, box, _ptr(labels), _ptr(sizes) if sizes.numel() else None, _ptr(counts),
                                    int(min_voxels), 0xffffffffffffffff, int(fill), _stream())
+        self._written_in_place(out, box)
         return out
+
+    def _written_in_place(self, out, box):
+        """after a call that wrote the voxels of `box` (an abi.Box; None: all) into `out`: where `out` is the volume's own storage, the max
+        map (if built) is rebuilt over the box on the current stream, as update_region() does; no host wait"""
+        if self.max_map is not None and out.untyped_storage().data_ptr() == self.volume.untyped_storage().data_ptr():
+            self.build_max_map(box)
 
     _DISTANCE_TARGETS = {"inside": abi.DISTANCE_TO_INSIDE, "outside": abi.DISTANCE_TO_OUTSIDE}
 
@@ -476,6 +485,7 @@ class Volume:
             dist2 = self._distance_transform(src, iso, abi.DISTANCE_TO_OUTSIDE if erode else abi.DISTANCE_TO_INSIDE, r2 + 1, box)
             self.ctx.select_by_distance(_ptr(src), _ptr(out), self.extent, box, _ptr(dist2), 1, r2, int(outside_fill if erode else inside_fill), _stream())
             src = out
+        self._written_in_place(out, box)
         return out
 
     def erode(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
@@ -485,7 +495,10 @@ class Volume:
         ``radius2``.  ``outside_fill`` should lie below iso and ``inside_fill`` at or above it (dilate(), open() and close() write it).
         ``out``: a contiguous uint8 tensor of the volume's shape on its device (``out=self.volume`` works in place); without it a copy is
         made.  ``box``: only the box's voxels exist, take part and are written; nothing beyond the box is outside, so the erosion does not
-        eat at the box's faces (scipy's border_value=1).  ``self.volume`` is not touched unless ``out`` is the volume."""
+        eat at the box's faces (scipy's border_value=1).  ``self.volume`` is not touched unless ``out`` is the volume.  In place, a max map
+        built with build_max_map() is rebuilt over the box after the last step, on the same stream and without a host wait, so
+        extract_isosurface / label_components(use_max_map=True) and draw_mip / draw_iso / draw_slab(skip=True) see the new voxels; the gradient
+        map, the packed image, the cell summary and the occupancy and distance maps are the caller's to re-derive."""
         return self._morphology("erode", ("erode",), iso, radius, radius2, inside_fill, outside_fill, out, box)
 
     def dilate(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
