@@ -4,6 +4,8 @@
 //         ../vkvolume_amd/host/host_arith.cpp ../vkvolume_amd/host/load_volume.cpp
 // exit status 0 = every check passed (a sanitizer report aborts the process).  Expected values are worked out here from the definitions
 // (tile centres, the pinhole projection, the opacity formula, the documented ranges), not by calling the code under test a second time.
+// With the argument "iso_threshold" it instead prints kInv255's bits and, for every float32 bit pattern on stdin (hexadecimal, one per
+// line), iso_threshold() of it: the test holds those against numpy.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -451,8 +453,27 @@ static void resolve_rect_tests()
 		CHECK(!resolve_rect(&past, iw, ih, t, t, out));
 }
 
-int main()
+// "kInv255 <bits>", then one threshold per bit pattern read
+static int iso_threshold_mode()
 {
+	uint32_t bits;
+	std::memcpy(&bits, &kInv255, sizeof(bits));
+	std::printf("kInv255 %08x\n", (unsigned) bits);
+	unsigned in;
+	while (std::scanf("%x", &in) == 1)
+	{
+		float iso;
+		bits = in;
+		std::memcpy(&iso, &bits, sizeof(iso));
+		std::printf("%u\n", (unsigned) iso_threshold(iso));
+	}
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc > 1 && std::strcmp(argv[1], "iso_threshold") == 0)
+		return iso_threshold_mode();
 	for (uint32_t stride_case = 0; stride_case < 2; ++stride_case)
 	{        // whole schedules, and a rank's strided share of them
 		const uint32_t first = stride_case ? 1u : 0u, stride = stride_case ? 3u : 1u;

@@ -5,21 +5,18 @@
 #include <cstring>
 #include <vector>
 
-#include "launchers.hpp"
+#include "box_domain.hpp"
 
 namespace vkv
 {
 int check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box)
 {
-	if (!box)
+	if (!box || extent_and_box_ok(extent, box))
 		return VKV_OK;
 	const VkvBox b = *box;
 	if (b.width == 0 || b.height == 0 || b.depth == 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: empty box", what);
-	if ((uint64_t) b.x0 + b.width > extent.width || (uint64_t) b.y0 + b.height > extent.height || (uint64_t) b.z0 + b.depth > extent.depth)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: box (%u, %u, %u) + (%u, %u, %u) outside the volume", what, b.x0, b.y0, b.z0, b.width, b.height,
-		                 b.depth);
-	return VKV_OK;
+	return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: box (%u, %u, %u) + (%u, %u, %u) outside the volume", what, b.x0, b.y0, b.z0, b.width, b.height, b.depth);
 }
 
 // skipping_type's maps: 8 for ANISOTROPIC_DISTANCE, else 1, and for the distance transforms a swap buffer that is none of them
@@ -82,7 +79,17 @@ int check_render_buffers(vkv_ctx *ctx, const char *what, const VkvRenderParams *
 	return VKV_OK;
 }
 
-static VkvBox box_or_whole(const VkvBox *box, VkvExtent3D e) { return box ? *box : VkvBox{0, 0, 0, e.width, e.height, e.depth}; }
+// d_src and d_dst, each of extent's bytes, do not overlap, or (allow_equal: the call works in place) are the same buffer
+static int check_in_place_or_disjoint(vkv_ctx *ctx, const char *what, const void *d_src, const void *d_dst, VkvExtent3D extent, bool allow_equal)
+{
+	const unsigned __int128 bytes = (unsigned __int128) extent.width * extent.height * extent.depth;
+	const uint64_t          n     = bytes > ~0ull ? ~0ull : (uint64_t) bytes;
+	const uintptr_t         a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
+	if ((allow_equal && a == b) || (a < b ? b - a : a - b) >= n)
+		return VKV_OK;
+	return set_error(ctx, VKV_E_INVALID_ARGUMENT,
+	                 allow_equal ? "%s: d_src and d_dst overlap without being equal" : "%s: d_src and d_dst overlap (the filter does not run in place)", what);
+}
 // the transfer-function texture and its tables are read and written as dwords
 static bool tf_pointers_aligned(const void *d_tf, const void *d_tables) { return (((uintptr_t) d_tf | (uintptr_t) d_tables) & 3u) == 0; }
 
@@ -315,7 +322,7 @@ int vkv_volume_histogram(vkv_ctx *ctx, const uint8_t *d_volume, const uint8_t *d
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: bad mode %d", (int) mode);
 	if (((uintptr_t) d_histogram & 7u) != 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "volume_histogram: d_histogram must be 8-byte aligned");
-	return launch_volume_histogram(ctx, d_volume, d_gradient, extent, box_or_whole(box, extent), mode, d_histogram, (hipStream_t) stream);
+	return launch_volume_histogram(ctx, d_volume, d_gradient, extent, whole_or(extent, box), mode, d_histogram, (hipStream_t) stream);
 }
 
 int vkv_histogram_occupied_count(vkv_ctx *ctx, const uint64_t *d_histogram, const VkvTransferFunctionUniform *tf, uint64_t *d_count, void *stream)
@@ -341,14 +348,12 @@ int vkv_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExt
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "filter_volume: unknown kind %d", (int) kind);
 	if (const int rc = check_box(ctx, "filter_volume", extent, box))
 		return rc;
-	if (!filter_launch_ok(extent))        // also: the byte count below fits 64 bits
+	if (!filter_launch_ok(extent))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "filter_volume: volume too large for one launch");
-	const uint64_t  n = (uint64_t) extent.width * extent.height * extent.depth;
-	const uintptr_t a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
-	if (a < b ? b - a < n : a - b < n)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "filter_volume: d_src and d_dst overlap (the filter does not run in place)");
+	if (const int rc = check_in_place_or_disjoint(ctx, "filter_volume", d_src, d_dst, extent, false))
+		return rc;
 	DeviceGuard guard(ctx->device);
-	return launch_filter_volume(ctx, d_src, d_dst, extent, box_or_whole(box, extent), kind, (hipStream_t) stream);
+	return launch_filter_volume(ctx, d_src, d_dst, extent, whole_or(extent, box), kind, (hipStream_t) stream);
 }
 
 size_t vkv_isosurface_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return mesh_scratch_bytes(extent, box); }
@@ -374,7 +379,7 @@ int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exten
 	if (!mesh_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh: volume too large for the launches");
 	DeviceGuard guard(ctx->device);
-	return launch_isosurface_mesh(ctx, d_volume, extent, box_or_whole(box, extent), iso, d_max_map, map_extent,
+	return launch_isosurface_mesh(ctx, d_volume, extent, whole_or(extent, box), iso, d_max_map, map_extent,
 	                              d_scratch, d_triangles, capacity_triangles, d_counts, (hipStream_t) stream);
 }
 
@@ -410,7 +415,7 @@ int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent
 	if (!mesh_indexed_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh_indexed: volume too large for the launches");
 	DeviceGuard guard(ctx->device);
-	return launch_isosurface_mesh_indexed(ctx, d_volume, extent, box_or_whole(box, extent), iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals,
+	return launch_isosurface_mesh_indexed(ctx, d_volume, extent, whole_or(extent, box), iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals,
 	                                      capacity_vertices, d_indices, capacity_triangles, d_counts, (hipStream_t) stream);
 }
 
@@ -442,7 +447,7 @@ int vkv_label_components(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exte
 	if (!components_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "label_components: a box of more than 2^32 - 1 voxels; label it box by box");
 	DeviceGuard guard(ctx->device);
-	return launch_label_components(ctx, d_volume, extent, box_or_whole(box, extent), iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes,
+	return launch_label_components(ctx, d_volume, extent, whole_or(extent, box), iso, connectivity, d_max_map, map_extent, d_scratch, d_labels, d_sizes,
 	                               capacity_components, d_counts, (hipStream_t) stream);
 }
 
@@ -465,13 +470,10 @@ int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, Vk
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: d_labels and d_sizes must be 4-byte aligned, d_counts 8-byte aligned");
 	if (!components_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "select_components: a box of more than 2^32 - 1 voxels");
-	const unsigned __int128 bytes = (unsigned __int128) extent.width * extent.height * extent.depth;
-	const uint64_t          n     = bytes > ~0ull ? ~0ull : (uint64_t) bytes;
-	const uintptr_t         a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
-	if (a != b && (a < b ? b - a < n : a - b < n))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components: d_src and d_dst overlap without being equal");
+	if (const int rc = check_in_place_or_disjoint(ctx, "select_components", d_src, d_dst, extent, true))
+		return rc;
 	DeviceGuard guard(ctx->device);
-	return launch_select_components(ctx, d_src, d_dst, extent, box_or_whole(box, extent), d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill,
+	return launch_select_components(ctx, d_src, d_dst, extent, whole_or(extent, box), d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill,
 	                                (hipStream_t) stream);
 }
 
@@ -498,7 +500,7 @@ int vkv_distance_transform(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D ex
 	if (!edt_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768; transform it box by box");
 	DeviceGuard guard(ctx->device);
-	return launch_distance_transform(ctx, d_volume, extent, box_or_whole(box, extent), iso, target, limit, d_scratch, d_dist2, (hipStream_t) stream);
+	return launch_distance_transform(ctx, d_volume, extent, whole_or(extent, box), iso, target, limit, d_scratch, d_dist2, (hipStream_t) stream);
 }
 
 // every argument is checked before the launch (and before the device is touched)
@@ -519,13 +521,10 @@ int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, V
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: d_dist2 must be 4-byte aligned");
 	if (!edt_launch_ok(extent, box))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "select_by_distance: a box of more than 2^32 - 1 voxels or an axis above 32768");
-	const unsigned __int128 bytes = (unsigned __int128) extent.width * extent.height * extent.depth;
-	const uint64_t          n     = bytes > ~0ull ? ~0ull : (uint64_t) bytes;
-	const uintptr_t         a = (uintptr_t) d_src, b = (uintptr_t) d_dst;
-	if (a != b && (a < b ? b - a < n : a - b < n))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_by_distance: d_src and d_dst overlap without being equal");
+	if (const int rc = check_in_place_or_disjoint(ctx, "select_by_distance", d_src, d_dst, extent, true))
+		return rc;
 	DeviceGuard guard(ctx->device);
-	return launch_select_by_distance(ctx, d_src, d_dst, extent, box_or_whole(box, extent), d_dist2, lo, hi, fill, (hipStream_t) stream);
+	return launch_select_by_distance(ctx, d_src, d_dst, extent, whole_or(extent, box), d_dist2, lo, hi, fill, (hipStream_t) stream);
 }
 
 // every argument is checked before the first launch

@@ -1,8 +1,8 @@
 // components.hip — connected components of the inside voxels of a box (vkv_label_components) and the size filter on them
 // (vkv_select_components); DESIGN.md §5.15.  Integer work on bytes and labels; no MFMA, no floating point after the threshold.
 //
-// A voxel is inside iff byte >= thr (mesh_common.hpp's derivation of thr from iso: the mesh's inside rule).  Every kernel is one-dimensional
-// over the box-linear index i = ((z - z0) bh + (y - y0)) bw + (x - x0), one voxel per lane; a wave's 64 voxels are one ENTRY (the tile:
+// A voxel is inside iff byte >= thr (iso_threshold(iso): the mesh's inside rule).  Every kernel is one-dimensional over the box-linear index
+// of box_domain.hpp, i = ((z - z0) bh + (y - y0)) bw + (x - x0), one voxel per lane; a wave's 64 voxels are one ENTRY (the tile:
 // 64 x 1 x 1, wrapping over rows where the box is narrower).  d_labels doubles as the union-find's parent array until the last two kernels:
 // parent[i] is the box-linear index of an ancestor of i in i's component; an outside voxel's cell holds its final 0 from the first kernel on and
 // is never read: who is inside is told by the inside bits.
@@ -13,7 +13,7 @@
 //                     and v + o ~ v - ex + o already hold along x, so that pair's union covers this one.  Lock-free union-find with atomicMin.
 //   k_cc_flatten      parent[i] = find(i) for inside voxels; the root bits (parent[i] == i) by ballot, one more word per entry; per entry the
 //                     number of roots and of inside voxels.
-//   k_cc_scan_*       the fixed-tree scans of mesh_common.hpp over the entries' root counts; K, min(K, capacity) and the inside count.
+//   k_cc_scan_*       the fixed-tree scans of fixed_scan.hpp over the entries' root counts; K, min(K, capacity) and the inside count.
 //   k_cc_rank_roots   a root's label is 1 + the roots before it: its entry's scan + the root bits below its lane.  Also zeroes the sizes.
 //   k_cc_relabel      inside non-roots (by the two bit words) read their root's cell; sizes: a wave walks 32 entries, carries one pending
 //                     (label, count) across them and adds the other labels once per entry: integer atomicAdd, far fewer than voxels or
@@ -33,21 +33,10 @@
 // No kernel uses scratch memory (tests/test_components_cpu.py reads the listing).
 #include <algorithm>
 
-#include "launchers.hpp"
-#include "mesh_common.hpp"
+#include "box_domain.hpp"
+#include "fixed_scan.hpp"
 
 using namespace vkv;
-
-struct CcGeom
-{
-	const uint8_t *vol;
-	uint32_t       W, H;              // the volume's row and slice
-	uint32_t       x0, y0, z0;        // the box's first voxel
-	uint32_t       bw, bh, bd, n;        // the box's shape and its voxels
-	uint32_t       thr;               // the smallest inside byte; 256: none
-	const uint8_t *map;               // the max map or null
-	uint32_t       bx, by, bz, mw, mh;
-};
 
 __device__ __forceinline__ uint32_t cc_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void     cc_store(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -98,37 +87,19 @@ __device__ __forceinline__ void cc_union(uint32_t *parent, uint32_t a, uint32_t 
 	}
 }
 
-struct CcVoxel
-{
-	uint32_t i, lane, x, y, z;
-	bool     valid;
-};
-
-__device__ __forceinline__ CcVoxel cc_voxel(const CcGeom &G)
-{
-	CcVoxel v;
-	v.i     = blockIdx.x * 256u + threadIdx.x;        // at most 2^32 - 1: the grid has at most 2^24 workgroups
-	v.lane  = threadIdx.x & 63u;
-	v.valid = v.i < G.n;
-	const uint32_t t = v.i / G.bw;
-	v.x = v.i - t * G.bw, v.y = t % G.bh, v.z = t / G.bh;
-	return v;
-}
-
 __device__ __forceinline__ bool cc_bit(const uint64_t *bits, uint32_t j) { return (bits[j >> 6] >> (j & 63u)) & 1ull; }
 
-__global__ void __launch_bounds__(256) k_cc_init(CcGeom G, uint32_t *__restrict__ parent, uint64_t *__restrict__ bits)
+__global__ void __launch_bounds__(256) k_cc_init(BoxLinear G, MaxMap M, uint32_t *__restrict__ parent, uint64_t *__restrict__ bits)
 {
-	const CcVoxel v  = cc_voxel(G);
-	bool          in = false;
+	const BoxVoxel v  = box_voxel(G);
+	bool           in = false;
 	if (v.valid)
 	{
-		const uint32_t X = G.x0 + v.x, Y = G.y0 + v.y, Z = G.z0 + v.z;
-		bool           look = true;
-		if (G.map)        // a cell whose maximum stays below thr holds no inside voxel: none of its voxels is read
-			look = G.map[((size_t) (Z / G.bz) * (size_t) G.mh + (size_t) (Y / G.by)) * (size_t) G.mw + (size_t) (X / G.bx)] >= G.thr;
+		bool look = true;
+		if (M.map)        // a cell whose maximum stays below thr holds no inside voxel: none of its voxels is read
+			look = M.map[M.cell_of(G.x0 + v.x, G.y0 + v.y, G.z0 + v.z)] >= G.thr;
 		if (look)
-			in = G.vol[((size_t) Z * (size_t) G.H + (size_t) Y) * (size_t) G.W + (size_t) X] >= G.thr;
+			in = G.vol[box_address(G, v)] >= G.thr;
 	}
 	const uint64_t m      = __ballot(in);
 	const uint64_t starts = (m & ~(m << 1)) | __ballot(in && v.x == 0);        // a run ends with its row
@@ -161,9 +132,9 @@ __device__ __forceinline__ constexpr bool cc_offset(int dx, int dy, int dz)
 }
 
 template <int CONN>
-__global__ void __launch_bounds__(256) k_cc_merge(CcGeom G, uint32_t *parent, const uint64_t *__restrict__ bits)
+__global__ void __launch_bounds__(256) k_cc_merge(BoxLinear G, uint32_t *parent, const uint64_t *__restrict__ bits)
 {
-	const CcVoxel v = cc_voxel(G);
+	const BoxVoxel v = box_voxel(G);
 	if (!v.valid || !cc_bit(bits, v.i))        // no wave-wide operation below
 		return;
 	if (v.lane == 0 && v.x > 0 && cc_bit(bits, v.i - 1u))        // the x seam: the run goes on in the entry before
@@ -216,29 +187,7 @@ __global__ void __launch_bounds__(256) k_cc_flatten(uint32_t n, uint32_t *parent
 __global__ void __launch_bounds__(256) k_cc_scan_chunks(const uint32_t *__restrict__ counts, uint32_t *__restrict__ local, uint64_t *__restrict__ sums,
                                                         uint64_t *__restrict__ insums, uint32_t n_entries)
 {
-	__shared__ uint32_t lds[256];
-	constexpr uint32_t  kPer  = kMeshScanChunk / 256;
-	const uint32_t      first = blockIdx.x * kMeshScanChunk + threadIdx.x * kPer;
-	uint32_t            c[kPer], mine = 0, mine_in = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < kPer; ++k)
-	{
-		const uint32_t both = first + k < n_entries ? counts[first + k] : 0u;
-		c[k]                = both & 0xffffu;
-		mine += c[k], mine_in += both >> 16;
-	}
-	uint32_t total, total_in;
-	uint32_t before = block_exclusive_scan(mine, lds, total);
-	(void) block_exclusive_scan(mine_in, lds, total_in);
-#pragma unroll
-	for (uint32_t k = 0; k < kPer; ++k)
-	{
-		if (first + k < n_entries)
-			local[first + k] = before;
-		before += c[k];
-	}
-	if (threadIdx.x == 0)
-		sums[blockIdx.x] = total, insums[blockIdx.x] = total_in;
+	scan_chunk<true>(counts, local, sums, n_entries, insums);
 }
 
 // one workgroup: sums[c] becomes the roots of the chunks before c; d_counts = K, min(K, capacity), the inside voxels
@@ -246,7 +195,7 @@ __global__ void __launch_bounds__(256) k_cc_scan_total(uint64_t *__restrict__ su
                                                        uint64_t *__restrict__ d_counts)
 {
 	__shared__ uint64_t lds[256];
-	mesh_scan_total(sums, n_chunks, capacity, d_counts);
+	scan_total(sums, n_chunks, capacity, d_counts);
 	uint64_t mine = 0, total;
 	for (uint32_t c = threadIdx.x; c < n_chunks; c += 256)
 		mine += insums[c];
@@ -267,7 +216,7 @@ __global__ void __launch_bounds__(256) k_cc_rank_roots(uint32_t n, uint32_t *__r
 	const uint32_t e = i >> 6;
 	const uint64_t w = root_bits[e];
 	if ((w >> lane) & 1ull)
-		labels[i] = (uint32_t) chunk_before[e / kMeshScanChunk] + local[e] + (uint32_t) __builtin_popcountll(w & ((1ull << lane) - 1ull)) + 1u;
+		labels[i] = (uint32_t) chunk_before[e / kScanChunk] + local[e] + (uint32_t) __builtin_popcountll(w & ((1ull << lane) - 1ull)) + 1u;
 }
 
 // A wave walks kCcSpan consecutive entries and carries ONE pending (label, count) pair across them, so the label that dominates its 2048
@@ -319,51 +268,17 @@ __global__ void __launch_bounds__(256) k_cc_relabel(uint32_t n, uint32_t n_entri
 		atomicAdd(sizes + (pend - 1u), pend_n);
 }
 
-__global__ void __launch_bounds__(256) k_cc_select(const uint8_t *src, uint8_t *dst, CcGeom G, const uint32_t *__restrict__ labels,
+__global__ void __launch_bounds__(256) k_cc_select(const uint8_t *src, uint8_t *dst, BoxLinear G, const uint32_t *__restrict__ labels,
                                                    const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ d_counts, uint64_t min_voxels,
                                                    uint64_t max_voxels, uint32_t fill)
 {
-	const CcVoxel v = cc_voxel(G);
-	if (!v.valid)
-		return;
-	const size_t   a = ((size_t) (G.z0 + v.z) * (size_t) G.H + (size_t) (G.y0 + v.y)) * (size_t) G.W + (size_t) (G.x0 + v.x);
-	const uint32_t L = labels[v.i];
-	uint8_t        b = src[a];
-	if (L != 0 && sizes && L <= d_counts[1])        // a size that is not known removes nothing
-	{
+	box_select(G, src, dst, fill, [&](uint32_t i) {
+		const uint32_t L = labels[i];
+		if (L == 0 || !sizes || L > d_counts[1])        // a size that is not known removes nothing
+			return false;
 		const uint64_t s = sizes[L - 1u];
-		if (s < min_voxels || s > max_voxels)
-			b = (uint8_t) fill;
-	}
-	dst[a] = b;
-}
-
-struct CcPlan
-{
-	uint32_t n, entries, chunks, wgs;
-};
-
-static bool cc_plan(VkvExtent3D e, const VkvBox *box, CcPlan &p)
-{
-	if (!mesh_extent_and_box_ok(e, box))
-		return false;
-	const VkvBox b = whole_or(e, box);
-	if ((uint64_t) b.width * b.height > 0xffffffffull || (uint64_t) b.width * b.height * b.depth > 0xffffffffull)
-		return false;
-	p.n       = b.width * b.height * b.depth;
-	p.entries = p.n / 64u + (p.n % 64u != 0u);        // n + 63 may wrap
-	p.chunks  = (p.entries + kMeshScanChunk - 1) / kMeshScanChunk;
-	p.wgs     = (p.entries + 3u) / 4u;
-	return true;
-}
-
-static CcGeom cc_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, const CcPlan &p, float iso, const uint8_t *d_max_map, VkvExtent3D me)
-{
-	const MeshGeom M = mesh_geom(d_vol, e, b, iso, d_max_map, me, MeshPlan{});        // thr and the map's blocks: the mesh's own derivation
-	CcGeom         G{};
-	G.vol = d_vol, G.W = e.width, G.H = e.height, G.x0 = b.x0, G.y0 = b.y0, G.z0 = b.z0, G.bw = b.width, G.bh = b.height, G.bd = b.depth, G.n = p.n;
-	G.thr = M.thr, G.map = d_max_map, G.bx = (uint32_t) M.bx, G.by = (uint32_t) M.by, G.bz = (uint32_t) M.bz, G.mw = (uint32_t) M.mw, G.mh = (uint32_t) M.mh;
-	return G;
+		return s < min_voxels || s > max_voxels;
+	});
 }
 
 namespace vkv
@@ -374,28 +289,29 @@ namespace vkv
 // 4096 entries, i.e. 3/8 byte per voxel; 0: the extent and box are not accepted
 size_t components_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
-	CcPlan p;
-	if (!cc_plan(e, box, p))
+	BoxLinearPlan p;
+	if (!box_linear_plan(e, box, p))
 		return 0;
-	return 16 * (size_t) p.chunks + 24 * (size_t) p.entries;
+	return 16 * (size_t) scan_chunks(p.entries) + 24 * (size_t) p.entries;
 }
 
 bool components_launch_ok(VkvExtent3D e, const VkvBox *box)
 {
-	CcPlan p;
-	return cc_plan(e, box, p);
+	BoxLinearPlan p;
+	return box_linear_plan(e, box, p);
 }
 
 int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int connectivity, const uint8_t *d_max_map,
                             VkvExtent3D me, void *d_scratch, uint32_t *d_labels, uint32_t *d_sizes, uint64_t capacity, uint64_t *d_counts, hipStream_t s)
 {
-	CcPlan p;
-	if (!cc_plan(e, &b, p))
+	BoxLinearPlan p;
+	if (!box_linear_plan(e, &b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "label_components: a box of more than 2^32 - 1 voxels; label it box by box");
-	uint64_t    *sums = static_cast<uint64_t *>(d_scratch), *insums = sums + p.chunks, *bits = insums + p.chunks, *root_bits = bits + p.entries;
-	uint32_t    *counts = reinterpret_cast<uint32_t *>(root_bits + p.entries), *local = counts + p.entries;
-	const CcGeom G      = cc_geom(d_vol, e, b, p, iso, d_max_map, me);
-	hipLaunchKernelGGL(k_cc_init, dim3(p.wgs), dim3(256), 0, s, G, d_labels, bits);
+	const uint32_t  chunks = scan_chunks(p.entries);
+	uint64_t       *sums = static_cast<uint64_t *>(d_scratch), *insums = sums + chunks, *bits = insums + chunks, *root_bits = bits + p.entries;
+	uint32_t       *counts = reinterpret_cast<uint32_t *>(root_bits + p.entries), *local = counts + p.entries;
+	const BoxLinear G      = box_linear(d_vol, e, b, p, iso);
+	hipLaunchKernelGGL(k_cc_init, dim3(p.wgs), dim3(256), 0, s, G, MaxMap(d_max_map, e, me), d_labels, bits);
 	if (connectivity == VKV_CONNECT_6)
 		hipLaunchKernelGGL(k_cc_merge<VKV_CONNECT_6>, dim3(p.wgs), dim3(256), 0, s, G, d_labels, bits);
 	else if (connectivity == VKV_CONNECT_14)
@@ -403,8 +319,8 @@ int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, c
 	else
 		hipLaunchKernelGGL(k_cc_merge<VKV_CONNECT_26>, dim3(p.wgs), dim3(256), 0, s, G, d_labels, bits);
 	hipLaunchKernelGGL(k_cc_flatten, dim3(p.wgs), dim3(256), 0, s, p.n, d_labels, bits, root_bits, counts);
-	hipLaunchKernelGGL(k_cc_scan_chunks, dim3(p.chunks), dim3(256), 0, s, counts, local, sums, insums, p.entries);
-	hipLaunchKernelGGL(k_cc_scan_total, dim3(1), dim3(256), 0, s, sums, insums, p.chunks, capacity, d_counts);
+	hipLaunchKernelGGL(k_cc_scan_chunks, dim3(chunks), dim3(256), 0, s, counts, local, sums, insums, p.entries);
+	hipLaunchKernelGGL(k_cc_scan_total, dim3(1), dim3(256), 0, s, sums, insums, chunks, capacity, d_counts);
 	uint32_t *sizes = capacity ? d_sizes : nullptr;        // no capacity: no size work
 	hipLaunchKernelGGL(k_cc_rank_roots, dim3(p.wgs), dim3(256), 0, s, p.n, d_labels, root_bits, local, sums, sizes, d_counts);
 	hipLaunchKernelGGL(k_cc_relabel, dim3((p.entries + 4 * kCcSpan - 1) / (4 * kCcSpan)), dim3(256), 0, s, p.n, p.entries, d_labels, bits, root_bits, sizes,
@@ -415,10 +331,10 @@ int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, c
 int launch_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels,
                              const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, hipStream_t s)
 {
-	CcPlan p;
-	if (!cc_plan(e, &b, p))
+	BoxLinearPlan p;
+	if (!box_linear_plan(e, &b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "select_components: a box of more than 2^32 - 1 voxels");
-	const CcGeom G = cc_geom(d_src, e, b, p, 0.0f, nullptr, VkvExtent3D{});
+	const BoxLinear G = box_linear(d_src, e, b, p, 0.0f);        // thr is not read
 	hipLaunchKernelGGL(k_cc_select, dim3(p.wgs), dim3(256), 0, s, d_src, d_dst, G, d_labels, d_sizes, d_counts, min_voxels, max_voxels, fill);
 	return check_launch(ctx, "select_components");
 }

@@ -3,8 +3,8 @@
 // transform of the occupancy CELLS, another metric on another grid.)  Integer work only: no MFMA, no floating point after the threshold, no
 // square root.
 //
-// A voxel is a TARGET iff (byte >= thr) == (target == VKV_DISTANCE_TO_INSIDE), thr being mesh_common.hpp's derivation from iso: the mesh's
-// inside rule.  Every kernel is one-dimensional over the box-linear index i = ((z - z0) bh + (y - y0)) bw + (x - x0), one voxel per lane, so
+// A voxel is a TARGET iff (byte >= thr) == (target == VKV_DISTANCE_TO_INSIDE), thr = iso_threshold(iso): the mesh's inside rule.  Every
+// kernel is one-dimensional over the box-linear index of box_domain.hpp, i = ((z - z0) bh + (y - y0)) bw + (x - x0), one voxel per lane, so
 // every access of every pass is coalesced along x; a wave's 64 voxels are one ENTRY, as in components.hip.  All values are squared distances
 // CAPPED at `limit` (0xffffffff = VKV_DISTANCE_NONE when unlimited): min(limit, min_u (a_u + b)) = min(limit, min_u (min(limit, a_u) + b))
 // for b >= 0, so capping after every pass gives the capped result, and the cap doubles as "no target in this row / column".
@@ -27,49 +27,16 @@
 // No kernel uses scratch memory (tests/test_distance_cpu.py reads the listing).
 #include <utility>
 
-#include "launchers.hpp"
-#include "mesh_common.hpp"
+#include "box_domain.hpp"
 
 using namespace vkv;
 
-struct EdtGeom
+__global__ void __launch_bounds__(256) k_edt_bits(BoxLinear G, uint32_t outside, uint64_t *__restrict__ bits)        // outside 1: the targets are the outside voxels
 {
-	const uint8_t *vol;
-	uint32_t       W, H;              // the volume's row and slice
-	uint32_t       x0, y0, z0;        // the box's first voxel
-	uint32_t       bw, bh, n;         // the box's row, slice height and voxels
-	uint32_t       thr;               // the smallest inside byte; 256: none
-	uint32_t       outside;           // 1: the targets are the outside voxels
-};
-
-struct EdtVoxel
-{
-	uint32_t i, lane, x, y, z;
-	bool     valid;
-};
-
-__device__ __forceinline__ EdtVoxel edt_voxel(const EdtGeom &G)
-{
-	EdtVoxel v;
-	v.i     = blockIdx.x * 256u + threadIdx.x;        // at most 2^32 - 1: the grid has at most 2^24 workgroups
-	v.lane  = threadIdx.x & 63u;
-	v.valid = v.i < G.n;
-	const uint32_t t = v.i / G.bw;
-	v.x = v.i - t * G.bw, v.y = t % G.bh, v.z = t / G.bh;
-	return v;
-}
-
-__device__ __forceinline__ size_t edt_address(const EdtGeom &G, const EdtVoxel &v)
-{
-	return ((size_t) (G.z0 + v.z) * (size_t) G.H + (size_t) (G.y0 + v.y)) * (size_t) G.W + (size_t) (G.x0 + v.x);
-}
-
-__global__ void __launch_bounds__(256) k_edt_bits(EdtGeom G, uint64_t *__restrict__ bits)
-{
-	const EdtVoxel v = edt_voxel(G);
+	const BoxVoxel v = box_voxel(G);
 	bool           t = false;
 	if (v.valid)
-		t = (G.vol[edt_address(G, v)] >= G.thr) != (G.outside != 0u);
+		t = (G.vol[box_address(G, v)] >= G.thr) != (outside != 0u);
 	const uint64_t m = __ballot(t);        // lanes past the box give 0: the last word's upper bits are no targets
 	if (v.valid && v.lane == 0)
 		bits[v.i >> 6] = m;
@@ -77,9 +44,9 @@ __global__ void __launch_bounds__(256) k_edt_bits(EdtGeom G, uint64_t *__restric
 
 // the squared distance along the row, capped: the row's bits are [i - x, i - x + bw), of which [i - min(x, reach), i + min(bw - 1 - x, reach)]
 // is searched; a target further than reach = ceil(sqrt(limit)) away gives the cap anyway
-__global__ void __launch_bounds__(256) k_edt_x(EdtGeom G, const uint64_t *__restrict__ bits, uint32_t *__restrict__ out, uint32_t limit, uint32_t reach)
+__global__ void __launch_bounds__(256) k_edt_x(BoxLinear G, const uint64_t *__restrict__ bits, uint32_t *__restrict__ out, uint32_t limit, uint32_t reach)
 {
-	const EdtVoxel v = edt_voxel(G);
+	const BoxVoxel v = box_voxel(G);
 	if (!v.valid)        // no wave-wide operation below
 		return;
 	const uint32_t lo = v.i - min(v.x, reach), hi = v.i + min(G.bw - 1u - v.x, reach);        // lo <= i <= hi < n
@@ -163,44 +130,22 @@ __global__ void __launch_bounds__(256) k_edt_axis(uint32_t n, uint32_t stride, u
 	dst[i] = best;
 }
 
-__global__ void __launch_bounds__(256) k_edt_select(const uint8_t *src, uint8_t *dst, EdtGeom G, const uint32_t *__restrict__ dist2, uint32_t lo, uint32_t hi,
+__global__ void __launch_bounds__(256) k_edt_select(const uint8_t *src, uint8_t *dst, BoxLinear G, const uint32_t *__restrict__ dist2, uint32_t lo, uint32_t hi,
                                                     uint32_t fill)
 {
-	const EdtVoxel v = edt_voxel(G);
-	if (!v.valid)
-		return;
-	const size_t   a = edt_address(G, v);
-	const uint32_t d = dist2[v.i];
-	dst[a]           = d >= lo && d <= hi ? (uint8_t) fill : src[a];        // in place: a lane reads and writes its own byte only
+	box_select(G, src, dst, fill, [&](uint32_t i) {
+		const uint32_t d = dist2[i];
+		return d >= lo && d <= hi;
+	});
 }
 
-struct EdtPlan
+// the shared plan and the transform's own limit: no box axis above 32768 (NO OVERFLOW above)
+static bool edt_plan(VkvExtent3D e, const VkvBox *box, BoxLinearPlan &p)
 {
-	uint32_t n, entries, wgs;
-};
-
-static bool edt_plan(VkvExtent3D e, const VkvBox *box, EdtPlan &p)
-{
-	if (!mesh_extent_and_box_ok(e, box))
+	if (!box_linear_plan(e, box, p))
 		return false;
 	const VkvBox b = whole_or(e, box);
-	if (b.width > 32768u || b.height > 32768u || b.depth > 32768u)
-		return false;
-	if ((uint64_t) b.width * b.height * b.depth > 0xffffffffull)        // the product of three factors <= 2^15 fits 64 bits
-		return false;
-	p.n       = b.width * b.height * b.depth;
-	p.entries = p.n / 64u + (p.n % 64u != 0u);        // n + 63 may wrap
-	p.wgs     = (p.entries + 3u) / 4u;
-	return true;
-}
-
-static EdtGeom edt_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, const EdtPlan &p, float iso, int target)
-{
-	EdtGeom G{};
-	G.vol = d_vol, G.W = e.width, G.H = e.height, G.x0 = b.x0, G.y0 = b.y0, G.z0 = b.z0, G.bw = b.width, G.bh = b.height, G.n = p.n;
-	G.thr     = mesh_geom(d_vol, e, b, iso, nullptr, VkvExtent3D{}, MeshPlan{}).thr;        // the mesh's own derivation
-	G.outside = target == VKV_DISTANCE_TO_OUTSIDE ? 1u : 0u;
-	return G;
+	return b.width <= 32768u && b.height <= 32768u && b.depth <= 32768u;
 }
 
 namespace vkv
@@ -210,7 +155,7 @@ namespace vkv
 // rounded up to 8 bytes; 0: the extent and box are not accepted
 size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
-	EdtPlan p;
+	BoxLinearPlan p;
 	if (!edt_plan(e, box, p))
 		return 0;
 	return 8 * (size_t) p.entries + 4 * (size_t) p.n;
@@ -218,25 +163,25 @@ size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 
 bool edt_launch_ok(VkvExtent3D e, const VkvBox *box)
 {
-	EdtPlan p;
+	BoxLinearPlan p;
 	return edt_plan(e, box, p);
 }
 
 int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, uint32_t limit, void *d_scratch,
                               uint32_t *d_dist2, hipStream_t s)
 {
-	EdtPlan p;
+	BoxLinearPlan p;
 	if (!edt_plan(e, &b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768");
 	uint64_t     *bits  = static_cast<uint64_t *>(d_scratch);
 	uint32_t     *other = reinterpret_cast<uint32_t *>(bits + p.entries);
-	const EdtGeom G     = edt_geom(d_vol, e, b, p, iso, target);
+	const BoxLinear G   = box_linear(d_vol, e, b, p, iso);
 	uint32_t      reach = 0;        // the smallest r with r^2 >= limit: at most 65536
 	while ((uint64_t) reach * reach < limit)
 		++reach;
 	const bool y = b.height > 1u, z = b.depth > 1u;
 	uint32_t  *cur = (y != z) ? other : d_dist2, *nxt = (y != z) ? d_dist2 : other;        // one further pass: it starts in the scratch block
-	hipLaunchKernelGGL(k_edt_bits, dim3(p.wgs), dim3(256), 0, s, G, bits);
+	hipLaunchKernelGGL(k_edt_bits, dim3(p.wgs), dim3(256), 0, s, G, target == VKV_DISTANCE_TO_OUTSIDE ? 1u : 0u, bits);
 	hipLaunchKernelGGL(k_edt_x, dim3(p.wgs), dim3(256), 0, s, G, bits, cur, limit, reach);
 	if (y)
 	{
@@ -254,10 +199,10 @@ int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e,
 int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_dist2, uint32_t lo,
                               uint32_t hi, uint32_t fill, hipStream_t s)
 {
-	EdtPlan p;
+	BoxLinearPlan p;
 	if (!edt_plan(e, &b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "select_by_distance: a box of more than 2^32 - 1 voxels or an axis above 32768");
-	const EdtGeom G = edt_geom(d_src, e, b, p, 0.0f, VKV_DISTANCE_TO_INSIDE);
+	const BoxLinear G = box_linear(d_src, e, b, p, 0.0f);        // thr is not read
 	hipLaunchKernelGGL(k_edt_select, dim3(p.wgs), dim3(256), 0, s, d_src, d_dst, G, d_dist2, lo, hi, fill);
 	return check_launch(ctx, "select_by_distance");
 }

@@ -2,7 +2,8 @@
 // points check before they enqueue anything, the helpers of raymarch.hip that capi.hip and context.hip call, and the argument checks of capi.hip
 // that other files share.  The entry points' files (capi.hip, context.hip, exchange.hip) and every file that defines one of them include it, so a
 // changed signature is a compile error, not a link error.  All of them return VKV_OK or an error code with the context's error text set; `s` is
-// the stream the work is enqueued on; device pointers are named d_*.  The context: context.hpp; host arithmetic without HIP: ../host/host_arith.hpp.
+// the stream the work is enqueued on; device pointers are named d_*.  The context: context.hpp; host arithmetic without HIP: ../host/host_arith.hpp;
+// what the box-of-voxels operations (mesh.hip .. edt.hip) share on both sides: box_domain.hpp (it includes this file) and fixed_scan.hpp.
 #pragma once
 
 #include "context.hpp"
@@ -100,7 +101,8 @@ bool filter_launch_ok(VkvExtent3D e);
 int launch_filter_volume(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, int kind, hipStream_t s);
 
 // ---- mesh.hip
-// vkv_isosurface_mesh_scratch_bytes: 0 for an extent or box that is not accepted; what the launches can take (box null: the whole volume)
+// vkv_isosurface_mesh_scratch_bytes: 0 for an extent or box that is not accepted (extent_and_box_ok, box_domain.hpp, as for the three files
+// below); what the launches can take (box null: the whole volume)
 size_t mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box);
 bool   mesh_launch_ok(VkvExtent3D e, const VkvBox *box);
 // vkv_isosurface_mesh after the entry point's argument checks (b inside e; me is read with a max map only)
@@ -116,8 +118,8 @@ int launch_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent
                                    uint64_t capacity_triangles, uint64_t *d_counts, hipStream_t s);
 
 // ---- components.hip
-// vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (at most 2^32 - 1 voxels in the
-// box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)
+// vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan: at most
+// 2^32 - 1 voxels in the box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)
 size_t components_scratch_bytes(VkvExtent3D e, const VkvBox *box);
 bool   components_launch_ok(VkvExtent3D e, const VkvBox *box);
 int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int connectivity, const uint8_t *d_max_map,
@@ -126,8 +128,8 @@ int launch_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst,
                              const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, hipStream_t s);
 
 // ---- edt.hip
-// vkv_distance_transform_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (at most 2^32 - 1 voxels in the
-// box, no box axis above 32768), and vkv_distance_transform / vkv_select_by_distance after the entry points' argument checks (b inside e)
+// vkv_distance_transform_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan and no box
+// axis above 32768), and vkv_distance_transform / vkv_select_by_distance after the entry points' argument checks (b inside e)
 size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box);
 bool   edt_launch_ok(VkvExtent3D e, const VkvBox *box);
 int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, uint32_t limit, void *d_scratch,
@@ -145,7 +147,7 @@ int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream
 void load_feedback_code();
 
 // ---- capi.hip: argument checks that entry points of several files share; `what` is the entry point's name in the messages
-// VKV_OK for null (the whole volume) or a box inside extent
+// VKV_OK for null (the whole volume) or a box inside extent (extent_and_box_ok, box_domain.hpp)
 int check_box(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box);
 // a VkvRenderParams' tile schedule and buffers (vkv_render / vkv_render_batch and the direct renderers, direct_render.hpp)
 int check_tile_schedule(vkv_ctx *ctx, const char *what, const VkvRenderParams *P);

@@ -13,7 +13,7 @@
 //   k_mesh_emit    a wave whose entries are all zero, or all start at or past the capacity, leaves at once; for every other entry it loads
 //                  the two slices again, prefixes its lanes' counts and stores the triangles whose index is below the capacity (the case table in LDS).
 // No kernel uses scratch memory (tests/test_mesh_cpu.py reads the listing).  The row loads, inside bits, corner mask, tile geometry, the
-// scans' bodies, the vertex rule and the plan live in mesh_common.hpp, which mesh_indexed.hip shares.
+// vertex rule and the plan live in mesh_common.hpp, which mesh_indexed.hip shares; the scans' bodies in fixed_scan.hpp.
 #include <algorithm>
 
 #include "launchers.hpp"
@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(256) k_mesh_count(MeshGeom G, uint32_t *__rest
 	__shared__ uint8_t lut[256];
 	const MeshTile     T    = mesh_tile(G, G.ny, G.nz);
 	const uint32_t     lane = threadIdx.x & 63u;
-	if (G.map && tile_is_empty(G, T, G.nx, G.ny))
+	if (G.mm.map && tile_is_empty(G, T, G.nx, G.ny))
 	{
 		if (threadIdx.x < 4 * kMeshSegment)
 		{
@@ -76,12 +76,12 @@ __global__ void __launch_bounds__(256) k_mesh_count(MeshGeom G, uint32_t *__rest
 __global__ void __launch_bounds__(256) k_mesh_scan_chunks(const uint32_t *__restrict__ counts, uint32_t *__restrict__ local, uint64_t *__restrict__ sums,
                                                           uint32_t n_entries)
 {
-	mesh_scan_chunk(counts, local, sums, n_entries);
+	scan_chunk(counts, local, sums, n_entries);
 }
 
 __global__ void __launch_bounds__(256) k_mesh_scan_total(uint64_t *__restrict__ sums, uint32_t n_chunks, uint64_t capacity, uint64_t *__restrict__ d_counts)
 {
-	mesh_scan_total(sums, n_chunks, capacity, d_counts);
+	scan_total(sums, n_chunks, capacity, d_counts);
 }
 
 template <bool WIDE>
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 	if (T.zc0 + (int) lane < T.zc1)
 	{
 		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kMeshScanChunk] + local[e];
+		start            = chunk_before[e / kScanChunk] + local[e];
 		work             = counts[e] != 0u && start < capacity;
 	}
 	uint64_t todo = __ballot(work);
@@ -129,14 +129,7 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 #pragma unroll
 		for (int i = 0; i < 4; ++i)
 			mine += i < nvalid ? (uint32_t) tab.count[corner_mask(q0, q1, i)] : 0u;
-		uint32_t incl = mine;        // inclusive prefix over the lanes: the cubes of a row lie in lane order
-#pragma unroll
-		for (int o = 1; o < 64; o <<= 1)
-		{
-			const uint32_t up = (uint32_t) __shfl_up((int) incl, o);
-			incl += lane >= (uint32_t) o ? up : 0u;
-		}
-		uint64_t idx = ((uint64_t) hi << 32 | lo) + (incl - mine);
+		uint64_t idx = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -177,7 +170,7 @@ namespace vkv
 size_t mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
-	if (!mesh_extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p))
+	if (!extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p))
 		return 0;
 	return std::max<size_t>(16, 8 * (size_t) p.chunks + 8 * (size_t) p.entries);
 }
@@ -200,20 +193,14 @@ int launch_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, co
 	const bool wide = e.width >= 4;        // the kernels' dword row loads
 	if (p.entries)
 	{
-		if (wide)
-			hipLaunchKernelGGL(k_mesh_count<true>, dim3(p.wgs), dim3(256), 0, s, G, counts);
-		else
-			hipLaunchKernelGGL(k_mesh_count<false>, dim3(p.wgs), dim3(256), 0, s, G, counts);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_mesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts); });
 		hipLaunchKernelGGL(k_mesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, counts, local, sums, p.entries);
 	}
 	hipLaunchKernelGGL(k_mesh_scan_total, dim3(1), dim3(256), 0, s, sums, p.chunks, capacity, d_counts);
 	if (p.entries && capacity)
-	{
-		if (wide)
-			hipLaunchKernelGGL(k_mesh_emit<true>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, iso, d_triangles, capacity);
-		else
-			hipLaunchKernelGGL(k_mesh_emit<false>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, iso, d_triangles, capacity);
-	}
+		dispatch_wide(wide, [&](auto w) {
+			hipLaunchKernelGGL(k_mesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, iso, d_triangles, capacity);
+		});
 	return check_launch(ctx, "isosurface_mesh");
 }
 

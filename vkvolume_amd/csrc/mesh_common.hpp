@@ -1,8 +1,10 @@
-// mesh_common.hpp — what the kernels of mesh.hip (vkv_isosurface_mesh) and mesh_indexed.hip (vkv_isosurface_mesh_indexed) share: the tile
-// geometry, the row loads and inside bits, the corner mask, the fixed-tree scans and the vertex rule.  Device code only; DESIGN.md §5.13, §5.14.
+// mesh_common.hpp — what only the kernels of mesh.hip (vkv_isosurface_mesh) and mesh_indexed.hip (vkv_isosurface_mesh_indexed) share: the tile
+// geometry, the row loads and inside bits, the corner mask, the vertex rule and the plan; DESIGN.md §5.13, §5.14.  The scans are
+// fixed_scan.hpp's; the box, the max map and the WIDE dispatch are box_domain.hpp's.
 #pragma once
 
-#include "launchers.hpp"
+#include "box_domain.hpp"
+#include "fixed_scan.hpp"
 #include "mtet_table.hpp"
 
 namespace vkv
@@ -10,7 +12,6 @@ namespace vkv
 
 constexpr int      kMeshTileX = 256, kMeshTileY = 4;        // cubes of a workgroup per slice: 64 lanes x 4 cubes, 4 rows
 constexpr int      kMeshSegment = 16;                       // slices of cubes a workgroup marches over (it loads one more)
-constexpr uint32_t kMeshScanChunk = 4096;                   // entries a scan workgroup takes: 256 threads x 16
 static_assert(kMeshSegment <= 64, "a wave tests its entries one per lane");
 
 // the middle corners of tetrahedron t (its local vertices 1 and 2; 0 and 3 are the cube's corners 0 and 7), one nibble per tetrahedron
@@ -31,9 +32,8 @@ struct MeshGeom
 	int            x0, y0, z0;        // the box's first voxel = the first cube's origin
 	int            nx, ny, nz;        // cubes of the box per axis: its extent - 1
 	uint32_t       segs_x, tiles_y, n_wgs;
-	uint32_t       thr;               // the smallest byte b with (float) b * kInv255 >= iso; 256: none
-	const uint8_t *map;               // the max map or null
-	int            bx, by, bz, mw, mh;
+	uint32_t       thr;               // the smallest inside byte (iso_threshold); 256: none
+	MaxMap         mm;                // the max map or none
 };
 
 // What a lane holds of one row: `d`, the voxels x .. x + 3 (zero past the row's end), and `e`, voxel x + 4: the first byte of the lane above
@@ -87,14 +87,6 @@ __device__ __forceinline__ uint32_t corner_mask(uint32_t q0, uint32_t q1, int i)
 	return (a & 3u) | ((a >> 6) & 0xcu) | (b & 3u) << 4 | ((b >> 6) & 0xcu) << 4;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t n)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-		n += (uint32_t) __shfl_xor((int) n, o);
-	return n;
-}
-
 struct MeshTile
 {
 	uint32_t xs;                 // x segment
@@ -125,86 +117,15 @@ __device__ __forceinline__ bool tile_is_empty(const MeshGeom &G, const MeshTile 
 	const int yt = T.yc - (int) (threadIdx.x >> 6);
 	const int ya = G.y0 + yt, yb = G.y0 + min(yt + kMeshTileY, rows) - 1;
 	const int za = G.z0 + T.zc0, zb = G.z0 + T.zc1 - 1;
-	const int cx = xa / G.bx, cy = ya / G.by, cz = za / G.bz;
-	const int ncx = xb / G.bx - cx + 1, ncy = yb / G.by - cy + 1, ncz = zb / G.bz - cz + 1;
+	const int cx = xa / G.mm.bx, cy = ya / G.mm.by, cz = za / G.mm.bz;
+	const int ncx = xb / G.mm.bx - cx + 1, ncy = yb / G.mm.by - cy + 1, ncz = zb / G.mm.bz - cz + 1;
 	int       any = 0;
 	for (int i = (int) threadIdx.x; i < ncx * ncy * ncz; i += 256)
 	{
 		const int ix = i % ncx, iy = (i / ncx) % ncy, iz = i / (ncx * ncy);
-		any |= G.map[((size_t) (cz + iz) * (size_t) G.mh + (size_t) (cy + iy)) * (size_t) G.mw + (size_t) (cx + ix)] >= G.thr;
+		any |= G.mm.map[G.mm.cell(cz + iz, cy + iy, cx + ix)] >= G.thr;
 	}
 	return !__syncthreads_or(any);
-}
-
-// exclusive scan of v over the workgroup's 256 threads (Hillis-Steele in LDS: a fixed tree), its total in `total`
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T *lds, T &total)
-{
-	const uint32_t i = threadIdx.x;
-	T              s = v;
-	lds[i]           = s;
-	__syncthreads();
-#pragma unroll
-	for (uint32_t o = 1; o < 256; o <<= 1)
-	{
-		const T add = i >= o ? lds[i - o] : T(0);
-		__syncthreads();
-		s += add;
-		lds[i] = s;
-		__syncthreads();
-	}
-	total = lds[255];
-	__syncthreads();
-	return s - v;
-}
-
-// chunk c = entries [4096 c, 4096 c + 4096): local[e] = the sum of the chunk's entries before e, sums[c] = the chunk's sum
-__device__ __forceinline__ void mesh_scan_chunk(const uint32_t *__restrict__ counts, uint32_t *__restrict__ local, uint64_t *__restrict__ sums,
-                                                uint32_t n_entries)
-{
-	__shared__ uint32_t lds[256];
-	constexpr uint32_t  kPer = kMeshScanChunk / 256;
-	const uint32_t      first = blockIdx.x * kMeshScanChunk + threadIdx.x * kPer;
-	uint32_t            c[kPer], mine = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < kPer; ++k)
-	{
-		c[k] = first + k < n_entries ? counts[first + k] : 0u;
-		mine += c[k];
-	}
-	uint32_t total;
-	uint32_t before = block_exclusive_scan(mine, lds, total);
-#pragma unroll
-	for (uint32_t k = 0; k < kPer; ++k)
-	{
-		if (first + k < n_entries)
-			local[first + k] = before;
-		before += c[k];
-	}
-	if (threadIdx.x == 0)
-		sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[c] becomes the sum of the chunks before c; counts[0] = the total, counts[1] = min(total, capacity)
-__device__ __forceinline__ void mesh_scan_total(uint64_t *__restrict__ sums, uint32_t n_chunks, uint64_t capacity, uint64_t *__restrict__ d_counts)
-{
-	__shared__ uint64_t lds[256];
-	uint64_t            carry = 0;
-	for (uint32_t c0 = 0; c0 < n_chunks; c0 += 256)
-	{
-		const uint32_t c = c0 + threadIdx.x;
-		const uint64_t v = c < n_chunks ? sums[c] : 0ull;
-		uint64_t       total;
-		const uint64_t before = block_exclusive_scan(v, lds, total);
-		if (c < n_chunks)
-			sums[c] = carry + before;
-		carry += total;
-	}
-	if (threadIdx.x == 0)
-	{
-		d_counts[0] = carry;
-		d_counts[1] = carry < capacity ? carry : capacity;
-	}
 }
 
 // the five voxels of row (j >> 1) & 3 = slice * 2 + row as one 64-bit value each; corner j of cube i is byte i + (j & 1) of it
@@ -256,19 +177,8 @@ inline bool mesh_plan(VkvExtent3D e, const VkvBox &b, MeshPlan &p, bool voxels =
 	if (entries > 0x7fffffffull || entries * cz > 0x7fffffffull || wgs * p.tiles_z > 0x7fffffffull)
 		return false;
 	p.entries = (uint32_t) (entries * cz), p.wgs = (uint32_t) (wgs * p.tiles_z);
-	p.chunks  = (p.entries + kMeshScanChunk - 1) / kMeshScanChunk;
+	p.chunks  = scan_chunks(p.entries);
 	return true;
-}
-
-inline VkvBox whole_or(VkvExtent3D e, const VkvBox *box) { return box ? *box : VkvBox{0, 0, 0, e.width, e.height, e.depth}; }
-
-// what the scratch-size functions accept: the entry points' own extent and box checks
-inline bool mesh_extent_and_box_ok(VkvExtent3D e, const VkvBox *box)
-{
-	if (!extent_ok(e))
-		return false;
-	return !(box && (box->width == 0 || box->height == 0 || box->depth == 0 || (uint64_t) box->x0 + box->width > e.width ||
-	                 (uint64_t) box->y0 + box->height > e.height || (uint64_t) box->z0 + box->depth > e.depth));
 }
 
 inline MeshGeom mesh_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, const uint8_t *d_max_map, VkvExtent3D me, const MeshPlan &p)
@@ -277,15 +187,7 @@ inline MeshGeom mesh_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, 
 	G.vol = d_vol, G.W = (int) e.width, G.H = (int) e.height, G.D = (int) e.depth;
 	G.x0 = (int) b.x0, G.y0 = (int) b.y0, G.z0 = (int) b.z0, G.nx = (int) p.nx, G.ny = (int) p.ny, G.nz = (int) p.nz;
 	G.segs_x = p.segs_x, G.tiles_y = p.tiles_y, G.n_wgs = p.wgs;
-	G.thr = 0;
-	while (G.thr < 256u && !((float) G.thr * kInv255 >= iso))        // the renderer's hit rule on a voxel's own value
-		++G.thr;
-	G.map = d_max_map, G.bx = G.by = G.bz = 1, G.mw = G.mh = 0;
-	if (d_max_map)
-	{
-		G.bx = (int) block_of(e.width, me.width), G.by = (int) block_of(e.height, me.height), G.bz = (int) block_of(e.depth, me.depth);
-		G.mw = (int) me.width, G.mh = (int) me.height;
-	}
+	G.thr = iso_threshold(iso), G.mm = MaxMap(d_max_map, e, me);
 	return G;
 }
 

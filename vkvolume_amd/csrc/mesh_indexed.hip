@@ -9,7 +9,7 @@
 // there (zero on the far faces) and the crossing edges they own.  Both lists lie in entry order.
 //   k_meshi_count          mesh.hip's count kernel with a second sum: a voxel's crossing mask is its cube's corner mask shifted down, flipped
 //                          where the voxel is inside, and cut to the directions that stay in the box; its vertices are a popcount.
-//   k_meshi_scan_*         the fixed-tree scans of mesh_common.hpp, both lists in one launch each (blockIdx.y / blockIdx.x picks the list).
+//   k_meshi_scan_*         the fixed-tree scans of fixed_scan.hpp, both lists in one launch each (blockIdx.y / blockIdx.x picks the list).
 //   k_meshi_emit_vertices  per entry with vertices below the capacity: the four rows again, the lanes' counts prefixed, then position and
 //                          (on request) normal of every crossing edge: twelve clamped byte gathers, for crossing edges only.
 //   k_meshi_emit_indices   per entry with triangles below the capacity: a triangle of cube o names owners in the rows (y, y + 1) x (z, z + 1)
@@ -53,19 +53,6 @@ __device__ __forceinline__ uint32_t owner_masks(const MeshGeom &G, uint32_t q0, 
 	return m;
 }
 
-// exclusive prefix of n over the wave's lanes
-__device__ __forceinline__ uint32_t wave_exclusive(uint32_t n, uint32_t lane)
-{
-	uint32_t incl = n;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t up = (uint32_t) __shfl_up((int) incl, o);
-		incl += lane >= (uint32_t) o ? up : 0u;
-	}
-	return incl - n;
-}
-
 // One pass, both counts: tri_counts[e] = the triangles of the cubes that start at entry e's voxels, vert_counts[e] = the crossing edges they own.
 template <bool WIDE>
 __global__ void __launch_bounds__(256) k_meshi_count(MeshGeom G, uint32_t *__restrict__ tri_counts, uint32_t *__restrict__ vert_counts)
@@ -74,7 +61,7 @@ __global__ void __launch_bounds__(256) k_meshi_count(MeshGeom G, uint32_t *__res
 	const int          vy = G.ny + 1, vz = G.nz + 1;
 	const MeshTile     T    = mesh_tile(G, vy, vz);
 	const uint32_t     lane = threadIdx.x & 63u;
-	if (G.map && tile_is_empty(G, T, G.nx + 1, vy))        // a cell below iso: its voxels and their neighbours are outside, no edge from them crosses
+	if (G.mm.map && tile_is_empty(G, T, G.nx + 1, vy))        // a cell below iso: its voxels and their neighbours are outside, no edge from them crosses
 	{
 		if (threadIdx.x < 4 * kMeshSegment)
 		{
@@ -129,7 +116,7 @@ __global__ void __launch_bounds__(256) k_meshi_scan_chunks(const uint32_t *__res
                                                            uint32_t n_entries, uint32_t n_chunks)
 {
 	const size_t list = blockIdx.y;
-	mesh_scan_chunk(counts + 2 * list * n_entries, local + 2 * list * n_entries, sums + list * n_chunks, n_entries);
+	scan_chunk(counts + 2 * list * n_entries, local + 2 * list * n_entries, sums + list * n_chunks, n_entries);
 }
 
 // workgroup 0: the triangles into d_counts[0, 1]; workgroup 1: the vertices into d_counts[2, 3]
@@ -137,7 +124,7 @@ __global__ void __launch_bounds__(256) k_meshi_scan_total(uint64_t *__restrict__
                                                           uint64_t capacity_vertices, uint64_t *__restrict__ d_counts)
 {
 	const size_t list = blockIdx.x;
-	mesh_scan_total(sums + list * n_chunks, n_chunks, list ? capacity_vertices : capacity_triangles, d_counts + 2 * list);
+	scan_total(sums + list * n_chunks, n_chunks, list ? capacity_vertices : capacity_triangles, d_counts + 2 * list);
 }
 
 // G_c of the volume's voxel (X, Y, Z): the byte after minus the byte before along each axis, both clamped to the volume
@@ -166,7 +153,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const u
 	if (T.zc0 + (int) lane < T.zc1)
 	{
 		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kMeshScanChunk] + local[e];
+		start            = chunk_before[e / kScanChunk] + local[e];
 		work             = counts[e] != 0u && start < capacity;
 	}
 	uint64_t todo = __ballot(work);
@@ -254,7 +241,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 	if (T.zc0 + (int) lane < min(T.zc1, G.nz))
 	{
 		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = tri_before[e / kMeshScanChunk] + tri_local[e];
+		start            = tri_before[e / kScanChunk] + tri_local[e];
 		work             = tri_counts[e] != 0u && start < capacity;
 	}
 	uint64_t todo = __ballot(work);
@@ -287,7 +274,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 			const uint32_t q0 = Q[oz][oy] | Q[oz][oy + 1] << 8, q1 = Q[oz + 1][oy] | Q[oz + 1][oy + 1] << 8;
 			const uint32_t m  = owner_masks(G, q0, q1, T.xc, T.yc + oy, zc + oz);
 			const uint32_t er = e + (uint32_t) oy * G.segs_x + (uint32_t) oz * T.e_step;
-			first[r]          = (uint32_t) vert_before[er / kMeshScanChunk] + vert_local[er] + wave_exclusive((uint32_t) __builtin_popcount(m), lane);
+			first[r]          = (uint32_t) vert_before[er / kScanChunk] + vert_local[er] + wave_exclusive((uint32_t) __builtin_popcount(m), lane);
 			uint32_t m4       = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) m, 0x130, 0xf, 0xf, false) & 0x7fu;        // wave_shl:1
 			above[r]          = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) first[r], 0x130, 0xf, 0xf, false);
 			if (lane == 63)        // voxel x + 4 opens the next entry
@@ -350,7 +337,7 @@ namespace vkv
 size_t mesh_indexed_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
-	if (!mesh_extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p, true))
+	if (!extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p, true))
 		return 0;
 	return std::max<size_t>(16, 16 * (size_t) p.chunks + 16 * (size_t) p.entries);
 }
@@ -375,31 +362,20 @@ int launch_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent
 	const bool     wide   = e.width >= 4;        // the kernels' dword row loads
 	if (p.entries)
 	{
-		if (wide)
-			hipLaunchKernelGGL(k_meshi_count<true>, dim3(p.wgs), dim3(256), 0, s, G, counts, counts + verts);
-		else
-			hipLaunchKernelGGL(k_meshi_count<false>, dim3(p.wgs), dim3(256), 0, s, G, counts, counts + verts);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_meshi_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, counts + verts); });
 		hipLaunchKernelGGL(k_meshi_scan_chunks, dim3(p.chunks, 2), dim3(256), 0, s, counts, local, sums, p.entries, p.chunks);
 	}
 	hipLaunchKernelGGL(k_meshi_scan_total, dim3(2), dim3(256), 0, s, sums, p.chunks, capacity_triangles, capacity_vertices, d_counts);
 	if (p.entries && capacity_vertices)
-	{
-		if (wide)
-			hipLaunchKernelGGL(k_meshi_emit_vertices<true>, dim3(p.wgs), dim3(256), 0, s, G, counts + verts, local + verts, sums + p.chunks, iso, d_vertices,
-			                   d_normals, capacity_vertices);
-		else
-			hipLaunchKernelGGL(k_meshi_emit_vertices<false>, dim3(p.wgs), dim3(256), 0, s, G, counts + verts, local + verts, sums + p.chunks, iso, d_vertices,
-			                   d_normals, capacity_vertices);
-	}
+		dispatch_wide(wide, [&](auto w) {
+			hipLaunchKernelGGL(k_meshi_emit_vertices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts + verts, local + verts, sums + p.chunks, iso,
+			                   d_vertices, d_normals, capacity_vertices);
+		});
 	if (p.entries && capacity_triangles)
-	{
-		if (wide)
-			hipLaunchKernelGGL(k_meshi_emit_indices<true>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, local + verts, sums + p.chunks, d_indices,
-			                   capacity_triangles);
-		else
-			hipLaunchKernelGGL(k_meshi_emit_indices<false>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, local + verts, sums + p.chunks, d_indices,
-			                   capacity_triangles);
-	}
+		dispatch_wide(wide, [&](auto w) {
+			hipLaunchKernelGGL(k_meshi_emit_indices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, local + verts, sums + p.chunks,
+			                   d_indices, capacity_triangles);
+		});
 	return check_launch(ctx, "isosurface_mesh_indexed");
 }
 

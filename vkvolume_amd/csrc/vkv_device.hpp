@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/vkvolume_amd.h"
+#include "../host/host_arith.hpp"        // kInv255: the host derives thresholds with the kernels' constant
 
 namespace vkv
 {
@@ -21,8 +22,6 @@ __device__ __forceinline__ float g_clamp(float x, float lo, float hi) { return g
 __device__ __forceinline__ float g_step(float edge, float x) { return (x < edge) ? 0.0f : 1.0f; }
 __device__ __forceinline__ float g_sign(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 __device__ __forceinline__ int   i_clamp(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
-constexpr float kInv255 = 1.0f / 255.0f;
 
 __device__ __forceinline__ size_t vidx(int x, int y, int z, int W, int H)
 {

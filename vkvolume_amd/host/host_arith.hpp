@@ -17,6 +17,18 @@ static inline bool map_extent_ok(VkvExtent3D e, VkvExtent3D me) { return extent_
 // voxels per map cell on one axis: ceil(extent / map extent)
 static inline uint32_t block_of(uint32_t e, uint32_t m) { return (e + m - 1) / m; }
 
+// a byte as a sample value: f = (float) byte * kInv255
+constexpr float kInv255 = 1.0f / 255.0f;
+// The inside threshold of iso: the smallest byte b with (float) b * kInv255 >= iso (the renderer's hit rule on a voxel's own value; the product
+// is monotone in b), 256 where there is none.  The meshes, the components and the distance transform all take their inside rule from here.
+static inline uint32_t iso_threshold(float iso)
+{
+	uint32_t thr = 0;
+	while (thr < 256u && !((float) thr * kInv255 >= iso))
+		++thr;
+	return thr;
+}
+
 // Range checks of a tuning block, shared by vkv_set_tuning (which rejects a bad block) and default_tuning (which falls back to the
 // built-in value of a field the environment set out of range).  Returns null when the block is fine, else what is wrong with it.
 const char *tuning_problem(const VkvTuning &t);

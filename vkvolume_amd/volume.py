@@ -25,6 +25,14 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _as_box(box):
+    """an abi.Box from an abi.Box or ((x0, y0, z0), (width, height, depth)); None stays None"""
+    if box is None or isinstance(box, abi.Box):
+        return box
+    (x0, y0, z0), (w, h, d) = box
+    return abi.Box(x0, y0, z0, w, h, d)
+
+
 class Volume:
     """Owns the volume / gradient / transfer-function / distance-map device buffers
     (Volume::Image members, src/volume_component.h:87-90)."""
@@ -112,14 +120,31 @@ class Volume:
     def _gradient_or_none(self):
         return self.gradient if self.options.use_precomputed_gradient else None
 
+    def _check_out(self, name, out):
+        """`out` of Volume.<name>: a contiguous uint8 tensor of the volume's shape on its device"""
+        if out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
+            raise ValueError("Volume.%s: `out` must be a contiguous uint8 tensor of shape %s on %s" % (name, tuple(self.volume.shape), self.volume.device))
+
+    def _scratch(self, nbytes, rejected):
+        """the scratch block of a call that needs `nbytes` (a *_scratch_bytes result; 0: ValueError(rejected)), 8-byte aligned"""
+        if nbytes == 0:
+            raise ValueError(rejected)
+        return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+
+    def _max_map_args(self, name, use_max_map):
+        """(max_map, map_extent) of Volume.<name>(use_max_map=...): the volume's max map, which must have been built, or (None, None)"""
+        if not use_max_map:
+            return None, None
+        if self.max_map is None:
+            raise RuntimeError("Volume.%s: use_max_map=True needs the volume's max map (call Volume.build_max_map first)" % name)
+        return self.max_map, self.map_extent
+
     def build_cell_summary(self, box=None):
         """The per-cell summaries of the occupancy map (vkv_cell_summary) on the current stream: of every cell (box None), or of the cells
         that meet ``box`` (an abi.Box or ((x0, y0, z0), (width, height, depth))).  The (cells, 16) uint8 buffer is allocated at the first
         call and kept in ``cell_summary``; it is built from the gradient map when use_precomputed_gradient is set.  update_region() keeps
         it current by rebuilding it over the update's box grown by one voxel per side."""
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         if self.cell_summary is None:
             if box is not None:
                 raise ValueError("Volume.build_cell_summary: build the whole summary (box=None) first")
@@ -133,9 +158,7 @@ class Volume:
         per side, for every cell (box None) or the cells whose grown box meets ``box`` (an abi.Box or ((x0, y0, z0), (width, height, depth))).
         The (map depth, height, width) uint8 buffer is allocated at the first call and kept in ``max_map``; update_region() keeps it current.
         VolumeRenderSubpass.draw_mip(skip=True) skips over it."""
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         if self.max_map is None:
             if box is not None:
                 raise ValueError("Volume.build_max_map: build the whole map (box=None) first")
@@ -222,9 +245,7 @@ class Volume:
             out = torch.empty((256, 256), dtype=torch.int64, device=self.device)
         elif out.dtype != torch.int64 or tuple(out.shape) != (256, 256) or not out.is_contiguous() or out.device != self.volume.device:
             raise ValueError("Volume.histogram: `out` must be a contiguous (256, 256) int64 tensor on %s" % (self.volume.device,))
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         grad = self.gradient if self.options.use_precomputed_gradient else None
         self.ctx.volume_histogram(_ptr(self.volume), _ptr(grad), self.extent, box, mode, _ptr(out), _stream())
         return out
@@ -246,14 +267,12 @@ class Volume:
             if box is not None:
                 raise ValueError("Volume.filter: a box needs `out` (the bytes outside the box are kept)")
             out = torch.empty_like(self.volume)
-        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
-            raise ValueError("Volume.filter: `out` must be a contiguous uint8 tensor of shape %s on %s" % (tuple(self.volume.shape), self.volume.device))
+        else:
+            self._check_out("filter", out)
         if box is not None:
             if passes != 1:
                 raise ValueError("Volume.filter: a box takes one pass")
-            if not isinstance(box, abi.Box):
-                (x0, y0, z0), (w, h, d) = box
-                box = abi.Box(x0, y0, z0, w, h, d)
+            box = _as_box(box)
         tmp = torch.empty_like(self.volume) if passes > 1 else None
         src = self.volume
         for i in range(1, passes + 1):
@@ -270,19 +289,13 @@ class Volume:
         call's two-element int64 device tensor (the total, the rows written).  ``box`` (an abi.Box, or ((x0, y0, z0), (width, height,
         depth))): only the cubes inside it.  ``use_max_map``: skip empty tiles through the volume's max map (build_max_map() first; the
         same bits).  vkvolume_amd.mesh turns the result into texture or model space, welds it and writes STL."""
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
-        if use_max_map and self.max_map is None:
-            raise RuntimeError("Volume.extract_isosurface: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
+        box = _as_box(box)
+        max_map, map_extent = self._max_map_args("extract_isosurface", use_max_map)
         if capacity is not None and (int(capacity) != capacity or capacity < 0):
             raise ValueError("Volume.extract_isosurface: capacity must be a non-negative integer or None")
-        nbytes = lib.mesh_scratch_bytes(self.extent, box)
-        if nbytes == 0:
-            raise ValueError("Volume.extract_isosurface: the box is empty or outside the volume, or the volume is too large")
-        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        scratch = self._scratch(lib.mesh_scratch_bytes(self.extent, box),
+                                "Volume.extract_isosurface: the box is empty or outside the volume, or the volume is too large")
         counts = torch.empty((2,), dtype=torch.int64, device=self.device)
-        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
 
         def call(tri, n):
             self.ctx.isosurface_mesh(_ptr(self.volume), self.extent, box, iso, _ptr(max_map), map_extent, _ptr(scratch), _ptr(tri), n, _ptr(counts),
@@ -307,21 +320,15 @@ class Volume:
         ``capacity=(vertices, triangles)``: one call and no host read; the tensors have those sizes, the rows past the written counts are not
         written, and a fourth result is the call's int64 device tensor (triangles, triangles written, vertices, vertices written).  ``box``
         and ``use_max_map`` as for extract_isosurface().  vkvolume_amd.mesh unindexes the result and writes PLY."""
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
-        if use_max_map and self.max_map is None:
-            raise RuntimeError("Volume.extract_isosurface_indexed: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
+        box = _as_box(box)
+        max_map, map_extent = self._max_map_args("extract_isosurface_indexed", use_max_map)
         if capacity is not None:
             cap_v, cap_t = capacity
             if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
                 raise ValueError("Volume.extract_isosurface_indexed: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32")
-        nbytes = lib.mesh_indexed_scratch_bytes(self.extent, box)
-        if nbytes == 0:
-            raise ValueError("Volume.extract_isosurface_indexed: the box is empty or outside the volume, or the volume is too large")
-        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
+        scratch = self._scratch(lib.mesh_indexed_scratch_bytes(self.extent, box),
+                                "Volume.extract_isosurface_indexed: the box is empty or outside the volume, or the volume is too large")
         counts = torch.empty((4,), dtype=torch.int64, device=self.device)
-        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
 
         def call(nv, nt):
             vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
@@ -355,19 +362,13 @@ class Volume:
         exactly: ONE host wait.  ``box`` and ``use_max_map`` as for extract_isosurface()."""
         if connectivity not in self._CONNECTIVITIES:
             raise ValueError("Volume.label_components: connectivity must be 6, 14 or 26")
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
-        if use_max_map and self.max_map is None:
-            raise RuntimeError("Volume.label_components: use_max_map=True needs the volume's max map (call Volume.build_max_map first)")
-        nbytes = lib.components_scratch_bytes(self.extent, box)
-        if nbytes == 0:
-            raise ValueError("Volume.label_components: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
+        box = _as_box(box)
+        max_map, map_extent = self._max_map_args("label_components", use_max_map)
+        scratch = self._scratch(lib.components_scratch_bytes(self.extent, box),
+                                "Volume.label_components: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
         shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
-        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
         counts = torch.empty((3,), dtype=torch.int64, device=self.device)
         labels = torch.empty(shape, dtype=torch.uint32, device=self.device)
-        max_map, map_extent = (self.max_map, self.map_extent) if use_max_map else (None, None)
 
         def call(d_sizes, n):
             self.ctx.label_components(_ptr(self.volume), self.extent, box, iso, connectivity, _ptr(max_map), map_extent, _ptr(scratch), _ptr(labels),
@@ -399,13 +400,11 @@ class Volume:
             raise ValueError("Volume.remove_islands: min_voxels must be a non-negative integer")
         if int(fill) != fill or not 0 <= fill <= 255:
             raise ValueError("Volume.remove_islands: fill must be a byte")
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         if out is None:
             out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
-        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
-            raise ValueError("Volume.remove_islands: `out` must be a contiguous uint8 tensor of shape %s on %s" % (tuple(self.volume.shape), self.volume.device))
+        else:
+            self._check_out("remove_islands", out)
         labels, sizes, counts = self.label_components(iso, connectivity=connectivity, box=box)
         if keep_largest:
             min_voxels = int(sizes.to(torch.int64).max().item()) if sizes.numel() else 0
@@ -424,11 +423,9 @@ class Volume:
 
     def _distance_transform(self, src, iso, target, limit, box):
         """vkv_distance_transform of the uint8 tensor `src` (the volume's shape) on the current stream; box: an abi.Box or None"""
-        nbytes = lib.distance_transform_scratch_bytes(self.extent, box)
-        if nbytes == 0:
-            raise ValueError("Volume.distance_transform: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
+        scratch = self._scratch(lib.distance_transform_scratch_bytes(self.extent, box),
+                                "Volume.distance_transform: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
         shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
-        scratch = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=self.device)
         dist2 = torch.empty(shape, dtype=torch.uint32, device=self.device)
         self.ctx.distance_transform(_ptr(src), self.extent, box, iso, target, limit, _ptr(scratch), _ptr(dist2), _stream())
         return dist2
@@ -443,9 +440,7 @@ class Volume:
             raise ValueError("Volume.distance_transform: `to` must be 'inside' or 'outside'")
         if limit is not None and (int(limit) != limit or not 1 <= limit <= abi.DISTANCE_NONE):
             raise ValueError("Volume.distance_transform: limit must be an integer in 1 .. 0xffffffff or None")
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         return self._distance_transform(self.volume, iso, self._DISTANCE_TARGETS[to], limit, box)
 
     @staticmethod
@@ -472,13 +467,11 @@ class Volume:
         for f in (inside_fill, outside_fill):
             if int(f) != f or not 0 <= f <= 255:
                 raise ValueError("Volume.%s: inside_fill and outside_fill must be bytes" % name)
-        if box is not None and not isinstance(box, abi.Box):
-            (x0, y0, z0), (w, h, d) = box
-            box = abi.Box(x0, y0, z0, w, h, d)
+        box = _as_box(box)
         if out is None:
             out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
-        elif out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
-            raise ValueError("Volume.%s: `out` must be a contiguous uint8 tensor of shape %s on %s" % (name, tuple(self.volume.shape), self.volume.device))
+        else:
+            self._check_out(name, out)
         src = self.volume
         for step in steps:
             erode = step == "erode"
