@@ -12,6 +12,7 @@ lock-free union-find; a workgroup holds four entries; a scan chunk holds 4096 en
   5x7x67, 9x33x5                        narrow boxes: an entry spans many rows and several slices;
   64x65x64 (266240 voxels)              crosses a scan chunk: the second chunk's components take the first chunk's total;
   64x1024x1025 (67174400 voxels)        257 chunk sums, one more than a round of the scan of the chunk sums holds (closed-form references).
+Sizes above one generation of workgroups, where merging workgroups are not all resident together: tests/test_gpu_components_scale.py.
 Contents: below and above (nothing, one component), random densities 0.1, 0.31 (the cubic site-percolation threshold: large tortuous
 components) and 0.6, the 3-D checkerboard (all singletons under 6, one component under 14 and 26), a ball, a serpentine (ONE
 one-voxel-wide path through every row and slice: one component over every seam, with long find chains), two slabs joined by one voxel.
