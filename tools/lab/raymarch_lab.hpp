@@ -507,6 +507,16 @@ __device__ __forceinline__ void er_march(const RayMarchArgs &A, Ray &R, bool mar
 	}
 }
 
+// block_pixel for the lab's kernels, which hold schedule entry k and block sb of its tile
+template <int W>
+__device__ __forceinline__ bool lab_block_pixel(const RayMarchArgs &A, uint32_t k, uint32_t sb, uint32_t rb, uint32_t &px, uint32_t &py, uint32_t &o)
+{
+	uint32_t tx, ty, sbx, sby;
+	entry_tile(A, k, tx, ty);
+	uniform_divmod(sb, A.blocks_per_tile_x, A.div_blocks_per_tile_x, sby, sbx);
+	return block_pixel<W>(A, k, sbx, sby, tx, ty, rb, px, py, o);
+}
+
 template <int SKIP, bool ERT, int GRAD, bool PACKED, int W, uint32_t FLAGS>
 __global__ void __launch_bounds__(256) k_raymarch_er(const RayMarchArgs A)
 {
@@ -527,7 +537,7 @@ __global__ void __launch_bounds__(256) k_raymarch_er(const RayMarchArgs A)
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	uint32_t       px, py, o;
 	// no lane leaves before the end: the brick cache is filled by all 64 lanes of a wave whatever their rays are doing
-	const bool inside = block_pixel<W>(A, k * A.blocks_per_tile + sb, (part * 4u + wave) * (64u / W) + lane / W, px, py, o);
+	const bool inside = lab_block_pixel<W>(A, k, sb, (part * 4u + wave) * (64u / W) + lane / W, px, py, o);
 	Ray        R;
 	R.o = o;
 	const unsigned long long t_start = A.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1104,7 +1114,7 @@ __device__ __forceinline__ void lab_lean_block(const RayMarchArgs &A, uint32_t b
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	uint32_t       px, py, o;
 	const uint32_t rb = (part * WPB + wave) * 64u + lane;
-	const bool     inside = block_pixel<1>(A, k * A.blocks_per_tile + sb, rb, px, py, o);
+	const bool     inside = lab_block_pixel<1>(A, k, sb, rb, px, py, o);
 	Ray R;
 	R.o = o;
 	const unsigned long long t_start = A.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;

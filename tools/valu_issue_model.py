@@ -88,7 +88,7 @@ def main():
         d = tempfile.mkdtemp()
         src = os.path.join(d, "k.hip")
         open(src, "w").write('#include "%s/vkvolume_amd/csrc/raymarch_inst.hpp"\n'
-                             "template __global__ void k_raymarch_lean_batch<VKV_SKIP_DISTANCE, true, 1, vkv::kLfFullNc>(const RayMarchArgs *__restrict__, uint32_t, uint32_t);\n" % ROOT)
+                             "template __global__ void k_raymarch_lean_batch<VKV_SKIP_DISTANCE, true, 1, vkv::kLfFullNc>(const RayMarchArgs *__restrict__, uint32_t, uint32_t, vkv::UniformDiv);\n" % ROOT)
         listing, name_filter = os.path.join(d, "k.s"), "k_raymarch_lean_batch"
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
                                "-fno-fast-math", "--cuda-device-only", "-S", src, "-o", listing], stderr=subprocess.DEVNULL)

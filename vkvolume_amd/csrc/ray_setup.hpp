@@ -386,7 +386,8 @@ __device__ __forceinline__ void ray_finish(const RayMarchArgs &A, Ray &R, bool m
 // ring clockwise from its top left tile.  The volume's silhouette and the empty corners of the rectangle start last, as with the centre-first
 // table of a whole-image schedule - but a rectangle's size changes with the camera, and a table per size does not pay (a camera that moves
 // gives every frame in flight its own: profiles/r6_rect_schedules.txt).  Launches of 2 - 4 frames on one stream: -11 % against the plain order.
-__device__ __forceinline__ uint32_t start_entry(const RayMarchArgs &A, uint32_t r)
+// Hands back the tile's column and row in the rectangle as well (tx, ty): the entry is ty * w + tx, and a caller that deals pixels needs them apart.
+__device__ __forceinline__ uint32_t start_entry(const RayMarchArgs &A, uint32_t r, uint32_t &tx_out, uint32_t &ty_out)
 {
 	const int w = (int) A.tiles_x, h = (int) A.order_h, rings = (min(w, h) + 1) >> 1;
 	auto      inner = [&](int j) { return (w - 2 * j > 0 && h - 2 * j > 0) ? (uint32_t) ((w - 2 * j) * (h - 2 * j)) : 0u; };        // tiles inside ring j - 1
@@ -411,5 +412,11 @@ __device__ __forceinline__ uint32_t start_entry(const RayMarchArgs &A, uint32_t 
 		tx = j + wj - 2 - q, ty = j + hj - 1;        // bottom edge, right to left
 	else
 		q -= wj - 1, tx = j, ty = j + hj - 2 - q;        // left edge, upwards
-	return (uint32_t) __builtin_amdgcn_readfirstlane(ty * w + tx);
+	tx_out = (uint32_t) __builtin_amdgcn_readfirstlane(tx), ty_out = (uint32_t) __builtin_amdgcn_readfirstlane(ty);
+	return ty_out * (uint32_t) w + tx_out;
+}
+__device__ __forceinline__ uint32_t start_entry(const RayMarchArgs &A, uint32_t r)
+{
+	uint32_t tx, ty;
+	return start_entry(A, r, tx, ty);
 }

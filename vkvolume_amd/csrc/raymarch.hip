@@ -215,6 +215,9 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 				a.fill_tiles = full_x * full_y - r.w * r.h, a.rect_tx0 = r.x0, a.rect_ty0 = r.y0, a.rect_th = r.h;
 		}
 	}
+	// what every wave of the launch would otherwise work out for itself: the divisors of the deal as multiply-and-shift (tiles_x is final here)
+	a.div_blocks_per_tile = uniform_div_of(a.blocks_per_tile), a.div_blocks_per_tile_x = uniform_div_of(a.blocks_per_tile_x);
+	a.div_tiles_x = uniform_div_of(a.tiles_x), a.div_img_tiles_x = uniform_div_of(a.img_tiles_x), a.div_per_row = uniform_div_of(a.img_tiles_x - a.tiles_x);
 	// the limits below and their messages are the integrator's own (the direct renderers' come from check_first_hit_params)
 	const uint64_t nb   = (uint64_t) a.blocks_per_tile * a.tile_count;
 	a.nblocks           = 0;
@@ -236,8 +239,13 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 	a.wave_pw_log2 = T.wave_shape == 4 ? 2u : (T.wave_shape == 8 ? 3u : (T.wave_shape == 16 ? 4u : wave_patch_log2(a.ddx, a.ddy, a.W, a.H, a.D)));
 	{
 		const float m[3] = {(float) a.mw, (float) a.mh, (float) a.md};
+		const int   e[3] = {a.W, a.H, a.D};
 		for (int k = 0; k < 3; ++k)
+		{
 			a.mapf[k] = m[k], a.mapb[k] = std::nextafterf(m[k], 0.0f);
+			a.cells_per_unit[k] = P->options.skipping_type != VKV_SKIP_NONE ? cells_per_unit(e[k], a.block_size[k]) : 0.0f;
+		}
+		a.free_margin = clamp_free_margin(a.W, a.H, a.D);
 	}
 	a.addr_lut = nullptr, a.lut_y = a.lut_z = a.lut_words = a.lut_full = 0;
 	if (a.packed && T.address_tables != 0)

@@ -5,6 +5,8 @@
 
 #include <stdint.h>
 
+#include "../host/host_arith.hpp"        // UniformDiv
+
 constexpr int kTraceWords = 10;        // u64 words per wave of the diagnostic trace buffer
 constexpr uint32_t kFillPerTile = 3;   // VkvTileSchedule.fill_outside: outside tiles a rendering tile fills at most (lean_block)
 
@@ -50,6 +52,11 @@ struct RayMarchArgs
 	int             back;           // ceil(sampling_factor): the step back after a probe that found an occupied cell (frag:253)
 	uint32_t        clamp_always;   // k_raymarch_lean: 1 = no clamp-free march loop (VkvTuning.clamp_always: A/B switch, same bits)
 	float           mapf[3], mapb[3];        // k_raymarch_lean, clamp-free loop: the map extent as floats, and the largest floats below them
+	// launch-uniform values the kernels used to derive in every wave, from the host (fill_render_args; helpers and their exactness: host_arith.hpp):
+	// cells_per_unit = (float) extent / block_size per axis (frag:192; zeros without empty-space skipping), free_margin = the clamp-free loop's g,
+	// and the schedule's integer divisions as multiply-and-shift (div_per_row: by img_tiles_x - tiles_x, the fill's tiles left and right of the rectangle)
+	float           cells_per_unit[3], free_margin;
+	vkv::UniformDiv div_blocks_per_tile, div_blocks_per_tile_x, div_tiles_x, div_img_tiles_x, div_per_row;
 	uint32_t        wave_pw_log2;            // k_raymarch_lean: log2 of the width in pixels of a wave's 64-pixel patch (2, 3, 4: 4x16, 8x8, 16x4)
 	const uint32_t *addr_lut;       // k_raymarch_lean: per-axis byte offsets of the packed image (packed_addr_lut, context.hpp), or null
 	uint32_t        lut_y, lut_z, lut_words;        // word offsets of the y and z tables inside addr_lut and the length of the two-level tables

@@ -91,9 +91,16 @@ __device__ __forceinline__ bool stage_tables_er(const RayMarchArgs &A, RmLds &L,
 		__syncthreads();
 	return sep;
 }
-// ray `rb` (0..255) of 16x16 block `b` of the tile schedule -> pixel and output index.  A wave's 64/W rays form a compact patch.
+// tile column and row, inside the schedule's rectangle, of schedule entry k (wave-uniform; multiply-and-shift: RayMarchArgs.div_tiles_x)
+__device__ __forceinline__ void entry_tile(const RayMarchArgs &A, uint32_t k, uint32_t &tx, uint32_t &ty)
+{
+	uniform_divmod(A.tile_first + k * A.tile_stride, A.tiles_x, A.div_tiles_x, ty, tx);
+}
+// ray `rb` (0..255) of the 16x16 block in column sbx, row sby of schedule entry k's tile (tx, ty) -> pixel and output index.  A wave's 64/W rays
+// form a compact patch.  The callers hold k, the block and the tile apart already: nothing is multiplied together to be divided apart here.
 template <int W>
-__device__ __forceinline__ bool block_pixel(const RayMarchArgs &A, uint32_t b, uint32_t rb, uint32_t &px, uint32_t &py, uint32_t &o)
+__device__ __forceinline__ bool block_pixel(const RayMarchArgs &A, uint32_t k, uint32_t sbx, uint32_t sby, uint32_t tx, uint32_t ty, uint32_t rb, uint32_t &px, uint32_t &py,
+                                            uint32_t &o)
 {
 	// A wave's 64 pixels (W = 1) are 8x8, 4 wide x 16 tall or 16 wide x 4 tall: the launcher picks the shape whose footprint in VOXELS is the most
 	// compact for this view (RayMarchArgs::wave_pw: with anisotropic voxels a pixel step in x can cover twice the voxels of a step in y; the rays of
@@ -113,10 +120,8 @@ __device__ __forceinline__ bool block_pixel(const RayMarchArgs &A, uint32_t b, u
 		constexpr uint32_t pw = G >= 32 ? 8 : (G >= 8 ? 4 : 2), ph = G / pw, ppr = 16 / pw;
 		bx = (wb % ppr) * pw + g % pw, by = (wb / ppr) * ph + g / pw;
 	}
-	const uint32_t k = b / A.blocks_per_tile, sb = b % A.blocks_per_tile;
-	const uint32_t t  = A.tile_first + k * A.tile_stride;
-	const uint32_t lx = (sb % A.blocks_per_tile_x) * 16 + bx, ly = (sb / A.blocks_per_tile_x) * 16 + by;
-	px = A.org_x + (t % A.tiles_x) * A.tile_w + lx, py = A.org_y + (t / A.tiles_x) * A.tile_h + ly;
+	const uint32_t lx = sbx * 16 + bx, ly = sby * 16 + by;
+	px = A.org_x + tx * A.tile_w + lx, py = A.org_y + ty * A.tile_h + ly;
 	o  = A.compact ? (k * A.tile_h + ly) * A.tile_w + lx : py * A.img_w + px;
 	return px < A.img_w && py < A.img_h;
 }
@@ -540,8 +545,8 @@ __device__ __forceinline__ bool lean_free_wave(const RayMarchArgs &A, const Ray 
 {
 	if (A.clamp_always)
 		return false;
-	const float kx = (float) A.W / A.block_size[0], ky = (float) A.H / A.block_size[1], kz = (float) A.D / A.block_size[2];
-	const float g  = 0.25f / (float) max(max(A.W, A.H), A.D);
+	const float kx = A.cells_per_unit[0], ky = A.cells_per_unit[1], kz = A.cells_per_unit[2];        // (divided on the host: fill_render_args)
+	const float g  = A.free_margin;
 	const float last = (float) R.n_steps - 1.0f;
 	// pos at positions 0 (= the entry) and n - 1
 	const float lx = __builtin_fmaf(last, R.sx, R.ex), ly = __builtin_fmaf(last, R.sy, R.ey), lz = __builtin_fmaf(last, R.sz, R.ez);
@@ -564,8 +569,14 @@ __device__ __forceinline__ void lean_march(const RayMarchArgs &A, Ray &R, const 
 	constexpr bool kAsync = (LF & kLeanAsync) != 0 && kTf && SKIP != VKV_SKIP_NONE;        // (not the texture path: its texel fetch is a load the compiler issues)
 	uint32_t       stamp_prev = 0, stamp_kind = 3;
 	const int      W = A.W, H = A.H, D = A.D;
-	const float    kx = SKIP != VKV_SKIP_NONE ? (float) W / A.block_size[0] : 0.0f, ky = SKIP != VKV_SKIP_NONE ? (float) H / A.block_size[1] : 0.0f,
-	            kz = SKIP != VKV_SKIP_NONE ? (float) D / A.block_size[2] : 0.0f;
+	// frag:192, divided once per launch on the host (zeros without skipping); the loops' multiplications take them as scalar operands
+	const float kx = A.cells_per_unit[0], ky = A.cells_per_unit[1], kz = A.cells_per_unit[2];
+	if (kLut && !kFull)
+	{        // the extents as packed_footprint_lut reads them, loaded and converted HERE (the divisions that used to stand here needed them; without
+		 // a use ahead of the loop the batch kernel loads and converts them again in every iteration)
+		const float fw = (float) W, fh = (float) H, fd = (float) D;
+		asm volatile("" : : "v"(fw), "v"(fh), "v"(fd));
+	}
 	const int   mw1 = A.mw - 1, mh1 = A.mh - 1, md1 = A.md - 1;
 	// (the multipliers of the cell index, pinned in scalar registers: the batch kernel's arguments sit in memory and the compiler would
 	// otherwise be free to load them again in every iteration)
@@ -909,7 +920,11 @@ __device__ __forceinline__ void lean_block(const RayMarchArgs &A, uint32_t bid, 
 	// WPB = waves per workgroup (4: a workgroup is a 16x16 block; 2 / 1: a half / a quarter of it, its parts stay on one XCD)
 	constexpr uint32_t kParts = 4 / WPB;
 	const uint32_t x = bid & 7u, idx = (bid >> 3) / kParts, part = (bid >> 3) % kParts;
-	const uint32_t rank = (idx / A.blocks_per_tile) * 8u + x, sb = idx % A.blocks_per_tile;
+	// (the deal's divisions are multiply-and-shift with constants from the host - UniformDiv, host_arith.hpp: a 32-bit division is some twenty
+	// dependent instructions that start with a reciprocal in a vector register, and a workgroup ran eight of them before its first ray)
+	uint32_t group, sb;
+	uniform_divmod(idx, A.blocks_per_tile, A.div_blocks_per_tile, group, sb);
+	const uint32_t rank = group * 8u + x;
 	if (rank >= A.tile_count)
 		return;
 	// Tiles are STARTED centre of the image first (tile_order, built by the launcher): the volume sits there, so the tiles with the
@@ -917,9 +932,18 @@ __device__ __forceinline__ void lean_block(const RayMarchArgs &A, uint32_t bid, 
 	// frame; on C3 this one shortens a single frame's launch from 0.324 to 0.306 ms and the tail of an 8-frame launch from 0.18 to
 	// 0.03 ms (bench.py).  Several single-frame launches in flight on their own streams prefer the plain order
 	// (VKV_RAYMARCH_TILE_ORDER=linear: 0.157 vs 0.167 ms per frame with three in flight) - their heavy centres then do not coincide.
-	const uint32_t k = A.tile_order ? A.tile_order[rank] : (A.order_h ? start_entry(A, rank) : rank);
+	const bool computed = !A.tile_order && A.order_h != 0u;        // start_entry knows the tile's column and row: they are not divided out of k again
+	uint32_t   k = rank, tx = 0, ty = 0;
+	if (computed)
+		k = start_entry(A, rank, tx, ty);
+	else if (A.tile_order)
+		k = A.tile_order[rank];
 	if (k >= A.tile_count)
 		return;        // never with a well-formed order; keeps a damaged one (a target shared by two streams without an event) from becoming a wild address
+	if (!computed)
+		entry_tile(A, k, tx, ty);
+	uint32_t sbx, sby;        // the block's column and row in its tile
+	uniform_divmod(sb, A.blocks_per_tile_x, A.div_blocks_per_tile_x, sby, sbx);
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	uint32_t       px, py, o;
 	const uint32_t rb = (part * WPB + wave) * 64u + lane;        // ray of the block this lane marches: the lane's own pixel of its 8x8 quadrant
@@ -937,20 +961,22 @@ __device__ __forceinline__ void lean_block(const RayMarchArgs &A, uint32_t bid, 
 			if (j >= A.fill_tiles)
 				break;
 			const uint32_t top = A.rect_ty0 * A.img_tiles_x, per_row = A.img_tiles_x - A.tiles_x, mid = A.rect_th * per_row;
-			uint32_t       tx, ty;
+			uint32_t       ftx, fty;        // the outside tile's column and row in the image
 			if (j < top)
-				ty = j / A.img_tiles_x, tx = j % A.img_tiles_x;
+				uniform_divmod(j, A.img_tiles_x, A.div_img_tiles_x, fty, ftx);
 			else if (j - top < mid)
 			{
-				const uint32_t q = j - top, c = q % per_row;
-				ty = A.rect_ty0 + q / per_row, tx = c < A.rect_tx0 ? c : c + A.tiles_x;
+				uint32_t row, c;
+				uniform_divmod(j - top, per_row, A.div_per_row, row, c);
+				fty = A.rect_ty0 + row, ftx = c < A.rect_tx0 ? c : c + A.tiles_x;
 			}
 			else
 			{
-				const uint32_t q = j - top - mid;
-				ty = A.rect_ty0 + A.rect_th + q / A.img_tiles_x, tx = q % A.img_tiles_x;
+				uint32_t row;
+				uniform_divmod(j - top - mid, A.img_tiles_x, A.div_img_tiles_x, row, ftx);
+				fty = A.rect_ty0 + A.rect_th + row;
 			}
-			const uint32_t bx0 = tx * A.tile_w + (sb % A.blocks_per_tile_x) * 16u, by0 = ty * A.tile_h + (sb / A.blocks_per_tile_x) * 16u;        // the block's first pixel
+			const uint32_t bx0 = ftx * A.tile_w + sbx * 16u, by0 = fty * A.tile_h + sby * 16u;        // the block's first pixel
 			if (A.fill_rgba8_rows != 0u && bx0 + 16u <= A.img_w)
 			{
 				// the production frame (RGBA8 only, no blend state, rows of the image 16-byte aligned: the launcher's flag): a 16-pixel row of the block
@@ -975,7 +1001,7 @@ __device__ __forceinline__ void lean_block(const RayMarchArgs &A, uint32_t bid, 
 			}
 		}
 	}
-	const bool     inside = block_pixel<1>(A, k * A.blocks_per_tile + sb, rb, px, py, o);
+	const bool     inside = block_pixel<1>(A, k, sbx, sby, tx, ty, rb, px, py, o);
 	Ray R;
 	R.o = o;
 	const unsigned long long t_start = A.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1102,13 +1128,16 @@ __global__ void __launch_bounds__(256) k_raymarch_lean(const RayMarchArgs A)
 // back in smaller pieces: three single-frame launches in flight gain 5 % in the lab (0.1181 against 0.1242 ms per frame, variants 112 / 21),
 // this kernel loses 6 % (0.1167 against 0.1099; the two-level tables alone 0.1116): twice the workgroups to set up and to stage tables for.)
 template <int SKIP, bool ERT, int GRAD, uint32_t LF>
-__global__ void __launch_bounds__(256) VKV_NO_PACKED_FP32 __attribute__((amdgpu_waves_per_eu((GRAD == 2 || SKIP == VKV_SKIP_NONE || (LF & kLeanLut) == 0) ? 1 : 8))) k_raymarch_lean_batch(const RayMarchArgs *__restrict__ frames, uint32_t n, uint32_t groups_per_frame)
+__global__ void __launch_bounds__(256) VKV_NO_PACKED_FP32 __attribute__((amdgpu_waves_per_eu((GRAD == 2 || SKIP == VKV_SKIP_NONE || (LF & kLeanLut) == 0) ? 1 : 8))) k_raymarch_lean_batch(const RayMarchArgs *__restrict__ frames, uint32_t n, uint32_t groups_per_frame, UniformDiv split)
 {
 	lean_lds_check();
 	RmLds &        L = lean_lds();
 	const uint32_t g = blockIdx.x >> 3;
 	// groups_per_frame == 0: frames interleaved in groups of eight workgroups; otherwise one frame after the other (A/B switch of the launcher)
-	const uint32_t f = groups_per_frame == 0 ? g % n : g / groups_per_frame, gi = groups_per_frame == 0 ? g / n : g % groups_per_frame;
+	// (split: the launcher's multiply-and-shift for the divisor used here - n, or groups_per_frame; the order the workgroups are dealt in is the same)
+	uint32_t q, r;
+	uniform_divmod(g, groups_per_frame == 0 ? n : groups_per_frame, split, q, r);
+	const uint32_t f = groups_per_frame == 0 ? r : q, gi = groups_per_frame == 0 ? q : r;
 	// (the anisotropic kernels that keep the per-pixel counters have no room under the 64-VGPR cap for the second march loop: they would spill)
 	constexpr uint32_t kLfBatch = (SKIP == VKV_SKIP_ANISOTROPIC_DISTANCE && (LF & kLeanNoCounts) == 0) ? (LF & ~kLeanSafe) : LF;
 	lean_block<SKIP, ERT, GRAD, true, kLfBatch, 4, true>(frames[f], (gi << 3) | (blockIdx.x & 7u), L);
@@ -1159,7 +1188,10 @@ __device__ __forceinline__ void pull_units(const RayMarchArgs *__restrict__ fram
 		if (k >= A.tile_count)
 			continue;
 		uint32_t            px, py, o;
-		const bool          inside = block_pixel<1>(A, k * A.blocks_per_tile + (w >> 2), (w & 3u) * 64u + lane, px, py, o);
+		uint32_t            tx, ty, sbx, sby;
+		entry_tile(A, k, tx, ty);
+		uniform_divmod(w >> 2, A.blocks_per_tile_x, A.div_blocks_per_tile_x, sby, sbx);
+		const bool          inside = block_pixel<1>(A, k, sbx, sby, tx, ty, (w & 3u) * 64u + lane, px, py, o);
 		Ray                 R = {};        // every field defined per unit: nothing of the previous unit's ray is carried round the loop
 		R.o = o;
 		const unsigned long long t_start = A.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;

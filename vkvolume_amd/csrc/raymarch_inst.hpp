@@ -132,6 +132,7 @@ void RayMarchLaunchers<SKIP, ERT>::load()
 template <int SKIP, bool ERT, int GRAD>
 static void launch_batch_kind(LeanChoice c, bool no_counts, const RayMarchArgs *d_frames, uint32_t n, uint32_t grid, uint32_t gpf, hipStream_t s)
 {
+	const UniformDiv split = uniform_div_of(gpf == 0 ? n : gpf);        // the kernel's frame / group split (k_raymarch_lean_batch)
 	if constexpr (GRAD != 2)
 	{
 		if constexpr (SKIP != VKV_SKIP_NONE && ERT && GRAD == 1)
@@ -139,20 +140,20 @@ static void launch_batch_kind(LeanChoice c, bool no_counts, const RayMarchArgs *
 			if (c.kind != 0 && no_counts)
 			{
 				if (c.kind == 2)
-					hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfFullNc>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf);
+					hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfFullNc>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf, split);
 				else
-					hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfLutNc>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf);
+					hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfLutNc>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf, split);
 				return;
 			}
 		}
 		if (c.kind == 2)
-			hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfFull>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf);
+			hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfFull>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf, split);
 		else if (c.kind == 1)
-			hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfLut>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf);
+			hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfLut>), dim3(grid), dim3(256), c.lds, s, d_frames, n, gpf, split);
 		if (c.kind != 0)
 			return;
 	}
-	hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfPlain>), dim3(grid), dim3(256), lean_lds_bytes(0, 0, 0, 0, 0), s, d_frames, n, gpf);
+	hipLaunchKernelGGL((k_raymarch_lean_batch<SKIP, ERT, GRAD, kLfPlain>), dim3(grid), dim3(256), lean_lds_bytes(0, 0, 0, 0, 0), s, d_frames, n, gpf, split);
 }
 
 template <int SKIP, bool ERT>

@@ -29,6 +29,51 @@ static inline uint32_t iso_threshold(float iso)
 	return thr;
 }
 
+// ---- launch-uniform arithmetic of the ray-march kernels, done once on the host (fill_render_args) ---------------------------------------
+#if defined(__HIPCC__)        // (always inlined: a kernel built with target attributes of its own cannot inline a plain function, and a call costs it a stack)
+#define VKV_HOST_DEVICE __host__ __device__ inline __attribute__((always_inline))
+#else
+#define VKV_HOST_DEVICE static inline
+#endif
+// Division of a u32 below 2^30 by a launch-uniform divisor d >= 1 without a division: q = mulhi(n << 2, mul) >> shift, with shift = ceil(log2 d)
+// and mul = ceil(2^(30 + shift) / d), in [2^30, 2^31).  Exact: mul = (2^(30 + shift) + e) / d with 0 <= e < d <= 2^shift, so n * mul / 2^(30 + shift) =
+// n / d + n e / (d 2^(30 + shift)), and the second term is below 1 / d for n < 2^30 - too small to carry n / d over the next integer.  d = 1 gives
+// mul = 2^30, shift = 0: the same path (no special case, no correction round).  Numerators: fill_render_args admits at most 0x3fffffff blocks
+// and 2^30 - 1 output indices per launch.  In a kernel both operands are wave-uniform: three scalar instructions for the quotient (shift, s_mul_hi_u32,
+// shift) and a multiply and a subtraction for the remainder.  tests/test_uniform_div_cpu.py checks it against / and %.
+struct UniformDiv
+{
+	uint32_t mul, shift;
+};
+constexpr uint32_t kUniformDivMax = 0x3fffffffu;        // the largest numerator
+static inline UniformDiv uniform_div_of(uint32_t d)
+{
+	if (d == 0u)
+		return {0u, 0u};        // a divisor nobody divides by (a launch with nothing to fill): the quotient is 0
+	uint32_t shift = 0;
+	while (shift < 31u && (1u << shift) < d)
+		++shift;
+	const uint64_t p = 1ull << (30u + shift);
+	return {(uint32_t) ((p + d - 1u) / d), shift};
+}
+VKV_HOST_DEVICE uint32_t uniform_quot(uint32_t n, const UniformDiv &v) { return (uint32_t) (((uint64_t) (n << 2) * v.mul) >> 32) >> v.shift; }
+// n = q * d + r
+VKV_HOST_DEVICE void uniform_divmod(uint32_t n, uint32_t d, const UniformDiv &v, uint32_t &q, uint32_t &r)
+{
+	q = uniform_quot(n, v);
+	r = n - q * d;
+}
+// frag:192 volume_to_distance_map_u, one axis: map cells per unit of the texture coordinate.  The kernels used to divide per wave; the host code
+// is built with -ffp-contract=off and the device divides with correct rounding, so these are the same bits.  Kept as the plain expressions:
+// tests/test_uniform_div_cpu.py holds them to that.
+static inline float cells_per_unit(int extent, float block_size) { return (float) extent / block_size; }
+// the clamp-free march loop's margin g (lean_free_wave): a quarter of a voxel of the longest axis, in texture coordinates
+static inline float clamp_free_margin(int W, int H, int D)
+{
+	const int m = W > H ? (W > D ? W : D) : (H > D ? H : D);
+	return 0.25f / (float) m;
+}
+
 // Range checks of a tuning block, shared by vkv_set_tuning (which rejects a bad block) and default_tuning (which falls back to the
 // built-in value of a field the environment set out of range).  Returns null when the block is fine, else what is wrong with it.
 const char *tuning_problem(const VkvTuning &t);
