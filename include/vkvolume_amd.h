@@ -864,6 +864,52 @@ int vkv_label_components(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exte
 int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
                           const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, void *stream);
 
+/* ---- measurements of labelled components and selection by table ----------------------------------------------------------
+ * vkv_component_stats writes one record per label: bounding box, voxel count, coordinate sums (the centroid) and, with a volume, the
+ * smallest and largest byte and the sums of bytes and squared bytes (mean and variance).  vkv_select_components_by_table keeps or fills
+ * components by a table of one byte per label, so any rule computed from the records is applied on the device: neither the labels nor the
+ * voxels leave it.
+ * Inputs.  d_labels has the box's shape, box.width x box.height x box.depth with x fastest (NULL box: the volume's shape), as written by
+ * vkv_label_components for the same box; any array of that shape whose values lie in 0 .. d_counts[0] is accepted as well, so a caller's own
+ * segmentation can be measured.  Of d_counts only d_counts[0], the number of labels, is read, and it is read on the device: no host wait.
+ * What is written.  written = min(d_counts[0], capacity_components).  The records d_stats[0 .. written) are written completely, record
+ * k - 1 for label k; not one byte beyond them is touched.  Voxels with label 0 and voxels with a label above `written` are ignored.
+ * A record.  min_* / max_*: the inclusive bounding box of the label's voxels in VOLUME coordinates (the box's origin is added), voxels: their
+ * number, sum_x, sum_y, sum_z: the sums of their volume coordinates (centroid = sum / voxels), min_value, max_value, sum_value, sum_value2:
+ * the smallest and the largest of their bytes of d_volume, the sum of the bytes and the sum of their squares (mean = sum_value / voxels,
+ * variance = sum_value2 / voxels - mean^2).  A label that no voxel carries gets voxels = 0, sums 0, mins 0xffffffff and maxes 0.  d_volume ==
+ * NULL is allowed: the four value fields of every written record are then 0 and no byte of a volume is read.  No sum can overflow: the box
+ * holds fewer than 2^32 voxels, every coordinate is below 2^32 and a squared byte is below 2^16, so every sum stays below 2^64.
+ * Kernels only (no allocation, no memset or copy node, no host wait; no scratch buffer is needed, the kernels use no scratch memory, and none
+ * waits for another lane, wave or workgroup): after one direct call on `stream` it can be captured into a hipGraph.  Integer atomics
+ * (addition, minimum, maximum) are used where the result does not depend on their order: two runs give the same bytes.  Nothing in the
+ * context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_labels
+ * or d_counts, a null d_stats with a non-zero capacity, a zero extent, an empty box or one not inside `extent`, a d_labels that is not
+ * 4-byte aligned, a d_counts or d_stats that is not 8-byte aligned, a capacity_components above 0xffffffff.  VKV_E_UNSUPPORTED: a box of more
+ * than 2^32 - 1 voxels.  capacity_components == 0 is VKV_OK and enqueues nothing.  d_volume may start at any byte; every extent is
+ * accepted, widths below 4 and axes of length 1 included; nothing outside any buffer is read or written.
+ *
+ * vkv_select_components_by_table: pointwise, one kernel launch.  For every voxel v of the box, at its volume position in d_dst, with L =
+ * d_labels[v] (the box's shape): L == 0 or L > table_entries: dst = src, what the table does not name is not removed; d_keep[L - 1] != 0:
+ * dst = src; d_keep[L - 1] == 0: dst = fill.  Bytes of d_dst outside the box are untouched.  d_keep (table_entries bytes, any alignment) may
+ * be NULL with table_entries == 0.  d_dst == d_src is allowed (in place); any other overlap of [d_src, d_src + W H D) and [d_dst, d_dst + W
+ * H D) is VKV_E_INVALID_ARGUMENT, as are a null ctx, d_src, d_dst or d_labels, a null d_keep with table_entries != 0, a zero extent, an
+ * empty box or one not inside `extent`, fill > 255 and a d_labels that is not 4-byte aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1
+ * voxels.  The result is an ordinary volume for every other entry point. */
+typedef struct VkvComponentStats {        /* 80 bytes, 8-byte aligned; offsets 0 4 8 | 12 16 20 | 24 28 | 32 | 40 48 56 | 64 72 */
+    uint32_t min_x, min_y, min_z;         /* bounding box, VOLUME coordinates, inclusive */
+    uint32_t max_x, max_y, max_z;
+    uint32_t min_value, max_value;        /* the component's smallest and largest byte of d_volume */
+    uint64_t voxels;
+    uint64_t sum_x, sum_y, sum_z;         /* sums of volume coordinates: centroid = sum / voxels */
+    uint64_t sum_value, sum_value2;       /* sum of bytes and of squared bytes: mean and variance */
+} VkvComponentStats;
+int vkv_component_stats(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
+                        const uint64_t *d_counts, VkvComponentStats *d_stats, uint64_t capacity_components, void *stream);
+int vkv_select_components_by_table(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box,
+                                   const uint32_t *d_labels, const uint8_t *d_keep, uint64_t table_entries, uint32_t fill, void *stream);
+
 /* ---- exact Euclidean distance transform and ball morphology ---------------------------------------------------------------
  * vkv_distance_transform writes the exact squared Euclidean distance of every voxel of a box to the nearest TARGET voxel of the box;
  * vkv_select_by_distance fills the voxels whose distance lies in a range: ball erosion and dilation (hence opening and closing), shells,

@@ -147,6 +147,25 @@ DISTANCE_TO_INSIDE, DISTANCE_TO_OUTSIDE = 0, 1  # VkvDistanceTarget: the target 
 DISTANCE_NONE = 0xffffffff  # VKV_DISTANCE_NONE: no limit
 
 
+class ComponentStats(C.Structure):
+    """VkvComponentStats (vkv_component_stats): one label's bounding box (volume coordinates, inclusive), smallest and largest byte, voxel
+    count, coordinate sums, sum of bytes and of squared bytes; 80 bytes"""
+    _fields_ = [("min_x", C.c_uint32), ("min_y", C.c_uint32), ("min_z", C.c_uint32), ("max_x", C.c_uint32), ("max_y", C.c_uint32),
+                ("max_z", C.c_uint32), ("min_value", C.c_uint32), ("max_value", C.c_uint32), ("voxels", C.c_uint64), ("sum_x", C.c_uint64),
+                ("sum_y", C.c_uint64), ("sum_z", C.c_uint64), ("sum_value", C.c_uint64), ("sum_value2", C.c_uint64)]
+
+
+COMPONENT_STATS_BYTES = 80  # sizeof(VkvComponentStats)
+# the same 80 bytes as a numpy structured dtype (numpy itself is imported where it is used: this module loads nothing)
+COMPONENT_STATS_FIELDS = [(name, "<u4" if ctype is C.c_uint32 else "<u8") for name, ctype in ComponentStats._fields_]
+
+
+def component_stats_dtype():
+    """numpy's structured dtype of VkvComponentStats: the fields of ComponentStats at the C offsets, itemsize 80"""
+    import numpy as np
+    return np.dtype(COMPONENT_STATS_FIELDS, align=True)
+
+
 class SlabOptions(C.Structure):
     """VkvSlabOptions (vkv_render_slab): the plane (origin, du, dv) and the slab's sample step dn in texture space, samples per pixel, mode
     (SLAB_MAX / SLAB_MIN / SLAB_MEAN), grey window, optional max map (SLAB_MAX only), optional value output, flags (0)"""

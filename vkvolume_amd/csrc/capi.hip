@@ -477,6 +477,52 @@ int vkv_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, Vk
 	                                (hipStream_t) stream);
 }
 
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_component_stats(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels, const uint64_t *d_counts,
+                        VkvComponentStats *d_stats, uint64_t capacity_components, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_labels || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "component_stats: null pointer or zero extent");
+	if (const int rc = check_box(ctx, "component_stats", extent, box))
+		return rc;
+	if (capacity_components > 0xffffffffull)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "component_stats: a capacity of %llu components is past 32-bit labels", (unsigned long long) capacity_components);
+	if (capacity_components != 0 && !d_stats)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "component_stats: a capacity of %llu components needs d_stats", (unsigned long long) capacity_components);
+	if (((uintptr_t) d_labels & 3u) != 0 || (((uintptr_t) d_counts | (uintptr_t) d_stats) & 7u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "component_stats: d_labels must be 4-byte aligned, d_counts and d_stats 8-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "component_stats: a box of more than 2^32 - 1 voxels; measure it box by box");
+	DeviceGuard guard(ctx->device);
+	return launch_component_stats(ctx, d_volume, extent, whole_or(extent, box), d_labels, d_counts, d_stats, capacity_components, (hipStream_t) stream);
+}
+
+// every argument is checked before the launch (and before the device is touched)
+int vkv_select_components_by_table(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_labels,
+                                   const uint8_t *d_keep, uint64_t table_entries, uint32_t fill, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_src || !d_dst || !d_labels || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components_by_table: null pointer or zero extent");
+	if (!d_keep && table_entries != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components_by_table: a table of %llu entries needs d_keep", (unsigned long long) table_entries);
+	if (const int rc = check_box(ctx, "select_components_by_table", extent, box))
+		return rc;
+	if (fill > 255u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components_by_table: fill %u is no byte", fill);
+	if (((uintptr_t) d_labels & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "select_components_by_table: d_labels must be 4-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "select_components_by_table: a box of more than 2^32 - 1 voxels");
+	if (const int rc = check_in_place_or_disjoint(ctx, "select_components_by_table", d_src, d_dst, extent, true))
+		return rc;
+	DeviceGuard guard(ctx->device);
+	return launch_select_components_by_table(ctx, d_src, d_dst, extent, whole_or(extent, box), d_labels, d_keep, table_entries, fill, (hipStream_t) stream);
+}
+
 size_t vkv_distance_transform_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return edt_scratch_bytes(extent, box); }
 
 // every argument is checked before the first launch (and before the device is touched); nothing in the context is written

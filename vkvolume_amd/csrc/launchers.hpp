@@ -127,6 +127,14 @@ int launch_label_components(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, c
 int launch_select_components(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels,
                              const uint32_t *d_sizes, const uint64_t *d_counts, uint64_t min_voxels, uint64_t max_voxels, uint32_t fill, hipStream_t s);
 
+// ---- component_stats.hip
+// vkv_component_stats (nothing is enqueued for a capacity of 0) and vkv_select_components_by_table after the entry points' argument checks
+// (b inside e, components_launch_ok)
+int launch_component_stats(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels, const uint64_t *d_counts,
+                           VkvComponentStats *d_stats, uint64_t capacity, hipStream_t s);
+int launch_select_components_by_table(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_labels,
+                                      const uint8_t *d_keep, uint64_t table_entries, uint32_t fill, hipStream_t s);
+
 // ---- edt.hip
 // vkv_distance_transform_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan and no box
 // axis above 32768), and vkv_distance_transform / vkv_select_by_distance after the entry points' argument checks (b inside e)

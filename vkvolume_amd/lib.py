@@ -27,6 +27,7 @@ EXPORTS = [
     "vkv_isosurface_mesh_scratch_bytes", "vkv_isosurface_mesh",
     "vkv_isosurface_mesh_indexed_scratch_bytes", "vkv_isosurface_mesh_indexed",
     "vkv_label_components_scratch_bytes", "vkv_label_components", "vkv_select_components",
+    "vkv_component_stats", "vkv_select_components_by_table",
     "vkv_distance_transform_scratch_bytes", "vkv_distance_transform", "vkv_select_by_distance",
 ]
 # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
@@ -127,6 +128,8 @@ def load():
     L.vkv_label_components_scratch_bytes.restype = C.c_size_t
     L.vkv_label_components.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, i32, vp, abi.Extent3D, vp, vp, vp, C.c_uint64, vp, vp]
     L.vkv_select_components.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), vp, vp, vp, C.c_uint64, C.c_uint64, u32, vp]
+    L.vkv_component_stats.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), vp, vp, vp, C.c_uint64, vp]
+    L.vkv_select_components_by_table.argtypes = [vp, vp, vp, abi.Extent3D, P(abi.Box), vp, vp, C.c_uint64, u32, vp]
     L.vkv_distance_transform_scratch_bytes.argtypes = [abi.Extent3D, P(abi.Box)]
     L.vkv_distance_transform_scratch_bytes.restype = C.c_size_t
     L.vkv_distance_transform.argtypes = [vp, vp, abi.Extent3D, P(abi.Box), C.c_float, i32, u32, vp, vp, vp]
@@ -411,6 +414,27 @@ class Context:
         """Like select_components() but returns the status code (error-path tests)."""
         return self._lib.vkv_select_components(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), d_labels, d_sizes, d_counts,
                                                int(min_voxels), int(max_voxels), int(fill), stream)
+
+    def component_stats(self, d_volume, extent, box, d_labels, d_counts, d_stats, capacity_components, stream=0):
+        """vkv_component_stats: d_stats (abi.ComponentStats records, 80 bytes each) = for every label 1 .. min(d_counts[0],
+        capacity_components) of d_labels (uint32, the shape of `box`; None: of the volume) its bounding box in volume coordinates, voxel
+        count and coordinate sums and, unless d_volume is None, the smallest and largest byte and the sums of bytes and squared bytes"""
+        self.check(self.component_stats_rc(d_volume, extent, box, d_labels, d_counts, d_stats, capacity_components, stream))
+
+    def component_stats_rc(self, d_volume, extent, box, d_labels, d_counts, d_stats, capacity_components, stream=0):
+        """Like component_stats() but returns the status code (error-path tests)."""
+        return self._lib.vkv_component_stats(self.handle, d_volume, extent, None if box is None else C.byref(box), d_labels, d_counts, d_stats,
+                                             int(capacity_components), stream)
+
+    def select_components_by_table(self, d_src, d_dst, extent, box, d_labels, d_keep, table_entries, fill=0, stream=0):
+        """vkv_select_components_by_table: the voxels of `box` of d_dst = d_src, but `fill` where the voxel's label L (d_labels, uint32, the
+        box's shape) has d_keep[L - 1] == 0 (one byte per label, table_entries of them; labels beyond the table are kept); d_dst may be d_src"""
+        self.check(self.select_components_by_table_rc(d_src, d_dst, extent, box, d_labels, d_keep, table_entries, fill, stream))
+
+    def select_components_by_table_rc(self, d_src, d_dst, extent, box, d_labels, d_keep, table_entries, fill=0, stream=0):
+        """Like select_components_by_table() but returns the status code (error-path tests)."""
+        return self._lib.vkv_select_components_by_table(self.handle, d_src, d_dst, extent, None if box is None else C.byref(box), d_labels, d_keep,
+                                                        int(table_entries), int(fill), stream)
 
     def distance_transform(self, d_volume, extent, box, iso, target, limit, d_scratch, d_dist2, stream=0):
         """vkv_distance_transform: d_dist2 (uint32, the shape of `box`; None: of the volume) = min(limit, the squared Euclidean distance to

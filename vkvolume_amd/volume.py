@@ -33,6 +33,66 @@ def _as_box(box):
     return abi.Box(x0, y0, z0, w, h, d)
 
 
+class ComponentStats:
+    """The records of vkv_component_stats on the device: ``raw`` is the uint8 tensor [K, 80] the call wrote (record k - 1: label k); every
+    view below is computed from it by torch on the device, without a host wait.  A label that no voxel carries has voxels 0, bbox_min
+    0xffffffff, bbox_max 0 and NaN centroid, mean and variance."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        self._u64 = raw.view(torch.int64)  # [K, 10]; 4 .. 9 are the record's uint64 fields (every sum of a real volume is below 2^63)
+
+    def _u32(self, first, last):
+        """the record's uint32 fields first .. last - 1 (of eight) as int64 [K, last - first]"""
+        return self.raw.view(torch.int32)[:, first:last].to(torch.int64) & 0xffffffff
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def bbox_min(self):
+        """int64 [K, 3]: (min_x, min_y, min_z), volume coordinates, inclusive"""
+        return self._u32(0, 3)
+
+    @property
+    def bbox_max(self):
+        """int64 [K, 3]: (max_x, max_y, max_z), volume coordinates, inclusive"""
+        return self._u32(3, 6)
+
+    @property
+    def min_value(self):
+        return self._u32(6, 7)[:, 0]
+
+    @property
+    def max_value(self):
+        return self._u32(7, 8)[:, 0]
+
+    @property
+    def voxels(self):
+        """int64 [K]"""
+        return self._u64[:, 4]
+
+    @property
+    def centroid(self):
+        """float64 [K, 3]: (sum_x, sum_y, sum_z) / voxels, volume coordinates"""
+        return self._u64[:, 5:8].to(torch.float64) / self.voxels.to(torch.float64)[:, None]
+
+    @property
+    def mean(self):
+        """float64 [K]: sum_value / voxels, in bytes"""
+        return self._u64[:, 8].to(torch.float64) / self.voxels.to(torch.float64)
+
+    @property
+    def variance(self):
+        """float64 [K]: sum_value2 / voxels - mean^2"""
+        m = self.mean
+        return self._u64[:, 9].to(torch.float64) / self.voxels.to(torch.float64) - m * m
+
+    def numpy(self):
+        """the records as a numpy structured array of abi.component_stats_dtype() (a copy to the host: it waits for the stream)"""
+        return self.raw.cpu().numpy().view(abi.component_stats_dtype()).reshape(-1)
+
+
 class Volume:
     """Owns the volume / gradient / transfer-function / distance-map device buffers
     (Volume::Image members, src/volume_component.h:87-90)."""
@@ -418,6 +478,60 @@ class Volume:
         map (if built) is rebuilt over the box on the current stream, as update_region() does; no host wait"""
         if self.max_map is not None and out.untyped_storage().data_ptr() == self.volume.untyped_storage().data_ptr():
             self.build_max_map(box)
+
+    def component_stats(self, labels, counts, box=None, values=True, capacity=None):
+        """The measurements of the labelled components on the current stream (vkv_component_stats): a ComponentStats over the device records
+        of the labels 1 .. K.  ``labels``, ``counts``: as returned by label_components() for the same ``box``; any contiguous uint32 (or
+        int32) device tensor of the box's shape [depth, height, width] with values 0 .. counts[0] does as well.  ``values=False`` measures
+        geometry only: the volume is not read and the four value fields are 0.  ``capacity``: the number of records; None reads K from
+        ``counts``, which is ONE host wait; with a number there is none, the labels above it are ignored, and records beyond
+        min(K, capacity) are not written: they hold whatever the allocation held."""
+        box = _as_box(box)
+        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
+        if labels.dtype not in (torch.uint32, torch.int32) or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != self.volume.device:
+            raise ValueError("Volume.component_stats: `labels` must be a contiguous uint32 tensor of shape %s on %s" % (shape, self.volume.device))
+        k = int(counts[0].item()) if capacity is None else int(capacity)
+        raw = torch.empty((k, abi.COMPONENT_STATS_BYTES), dtype=torch.uint8, device=self.device)
+        self.ctx.component_stats(_ptr(self.volume) if values else None, self.extent, box, _ptr(labels), _ptr(counts), _ptr(raw) if k else None, k, _stream())
+        return ComponentStats(raw)
+
+    def select_components(self, labels, keep, fill=0, out=None, box=None):
+        """The volume without the components that a table rejects, on the current stream (vkv_select_components_by_table): a uint8 tensor of
+        the volume's shape in which every voxel of the box whose label L (``labels``: as for component_stats()) has ``keep[L - 1]`` false
+        holds ``fill``; everything else is the volume's byte, labels beyond the table included.  ``keep``: a bool or uint8 device tensor,
+        one element per label, e.g. a comparison of ComponentStats views.  ``out``, ``box`` and what happens in place: as for
+        remove_islands().  No host wait."""
+        if int(fill) != fill or not 0 <= fill <= 255:
+            raise ValueError("Volume.select_components: fill must be a byte")
+        box = _as_box(box)
+        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
+        if labels.dtype not in (torch.uint32, torch.int32) or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != self.volume.device:
+            raise ValueError("Volume.select_components: `labels` must be a contiguous uint32 tensor of shape %s on %s" % (shape, self.volume.device))
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1 or not keep.is_contiguous() or keep.device != self.volume.device:
+            raise ValueError("Volume.select_components: `keep` must be a contiguous one-dimensional bool or uint8 tensor on %s" % (self.volume.device,))
+        if out is None:
+            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
+        else:
+            self._check_out("select_components", out)
+        n = keep.numel()
+        self.ctx.select_components_by_table(_ptr(self.volume), _ptr(out), self.extent, box, _ptr(labels), _ptr(keep) if n else None, n, int(fill), _stream())
+        self._written_in_place(out, box)
+        return out
+
+    def clear_border(self, iso, connectivity=6, fill=0, out=None, box=None):
+        """The volume without the components at ``iso`` that touch a face of the box (the whole volume without one): bodies that the scan
+        cuts (skimage.segmentation.clear_border of the labels).  label_components(), component_stats(values=False), the keep table by
+        torch on the device, select_components(): a component is kept when its bounding box touches no face of the box.  K is read back once
+        to size the records: ONE host wait.  ``connectivity``, ``fill``, ``out``, ``box`` and what happens in place: as for
+        remove_islands()."""
+        box = _as_box(box)
+        labels, _, counts = self.label_components(iso, connectivity=connectivity, box=box, sizes=False)
+        stats = self.component_stats(labels, counts, box=box, values=False)
+        b = abi.Box(0, 0, 0, *self.extent.as_tuple()) if box is None else box
+        lo = torch.tensor([b.x0, b.y0, b.z0], dtype=torch.int64, device=self.device)
+        hi = lo + torch.tensor([b.width - 1, b.height - 1, b.depth - 1], dtype=torch.int64, device=self.device)
+        keep = ((stats.bbox_min > lo) & (stats.bbox_max < hi)).all(dim=1)
+        return self.select_components(labels, keep, fill=fill, out=out, box=box)
 
     _DISTANCE_TARGETS = {"inside": abi.DISTANCE_TO_INSIDE, "outside": abi.DISTANCE_TO_OUTSIDE}
 
