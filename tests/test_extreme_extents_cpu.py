@@ -205,7 +205,8 @@ def test_constants_are_the_kernels():
     assert "kLdsBase + sizeof(RmLds) + (size_t) lut_words * 4" in core and "kLdsBase + (size_t) kFullLutWord * 4 + ((full_lut_bytes(W, H, D) + 15u) & ~(size_t) 15u)" in core
     tables = open(os.path.join(csrc, "addr_tables.hpp")).read()
     assert "nmx = (uint32_t) (W + 1) / 32 + 1" in tables and "ny = 96 + nmx, nz = (ny + nmy + 1) & ~1u, total = nz + 2 * nmz" in tables
-    assert "c.kind != choice.kind || c.lds != choice.lds || host[i].lut_words != host[ref].lut_words" in open(os.path.join(csrc, "raymarch.hip")).read()
+    assert ("choices[i].kind != choices[p.ref].kind || choices[i].lds != choices[p.ref].lds || a.lut_words != frames[p.ref].lut_words"
+            in open(os.path.join(csrc, "raymarch_plan.hpp")).read())                       # plan_batch: frames that disagree about the tables
     assert "kFullLutWord * 4 + full_lut_bytes(a.W, a.H, a.D)" in open(os.path.join(csrc, "raymarch.hip")).read()
 
 

@@ -1,5 +1,5 @@
 // context.hip — the context behind a vkv_ctx handle (context.hpp): its arena, the per-stream scratch blocks, the cached device tables, the
-// capture slots, the start-order feedback targets and the tuning block, with the entry points that create, trim and destroy them.
+// capture slots and the argument upload of vkv_render_batch that claims them, the start-order feedback targets and the tuning block, with the entry points that create, trim and destroy them.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +9,7 @@
 
 #include "addr_tables.hpp"
 #include "launchers.hpp"
+#include "raymarch_args.hpp"        // sizeof(RayMarchArgs): what a batch upload holds
 #include "../../include/vkvolume_amd_debug.h"
 
 namespace vkv
@@ -128,6 +129,116 @@ StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup)
 	r.p     = b->p;
 	r.block = b;
 	return r;
+}
+
+// ---- the argument upload of vkv_render_batch ----
+// The argument blocks go through the stream's scratch block: an earlier batch on the same stream has finished with it by the time the copy
+// (same stream) runs, and the block's lock keeps other threads' writes into it (same stream) out from the copy to the launch.
+static_assert(kMaxBatch * sizeof(RayMarchArgs) <= kScratchBytes - kBatchArgsOffset, "batch argument blocks must fit the stream scratch");
+static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kCaptureSlotBytes, "a captured launch's upload must fit its pinned slot");
+static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kUploadSlotBytes, "a launch's upload must fit a slot of the block's pinned ring");
+
+// The upload is assembled once, in place, in a pinned slot of the block's ring: no pageable source that the runtime has to stage, nothing
+// allocated.  A slot is free once the event behind the copy that read it has completed; with every slot still in flight (or none: a block
+// beyond the reserve, a captured launch, which gets a slot of its own in commit) the upload comes from pageable memory - never a wait.
+BatchUpload::BatchUpload(vkv_ctx *ctx, const StreamScratch &scratch, hipStream_t stream, size_t bytes)
+    : ctx_(ctx), stream_(stream), bytes_(bytes), device_(scratch.p + kBatchArgsOffset - kPullHeadsBytes)
+{
+	hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+	capturing_                     = hipStreamIsCapturing(stream, &capture) == hipSuccess && capture == hipStreamCaptureStatusActive;
+	vkv_ctx::ScratchBlock &b       = *scratch.block;
+	for (uint32_t k = 0; k < vkv_ctx::kUploadRing && !capturing_ && !ring_slot_; ++k)
+	{
+		vkv_ctx::UploadSlot &u = b.upload[(b.upload_next + k) % vkv_ctx::kUploadRing];
+		if (!u.pinned)
+			continue;
+		if (u.pending && hipEventQuery(u.done.get()) == hipSuccess)
+			u.pending = false;
+		if (!u.pending)
+		{
+			ring_slot_    = &u;
+			b.upload_next = (b.upload_next + k + 1) % vkv_ctx::kUploadRing;
+		}
+	}
+	(void) hipGetLastError();        // (a slot that is still being read answers hipErrorNotReady: not this launch's error)
+	if (!ring_slot_)
+		pageable_.resize(bytes);
+	host_ = ring_slot_ ? ring_slot_->pinned : pageable_.data();
+	std::memset(host_, 0, bytes);        // the counters, and every field fill_render_args leaves alone (an empty frame's block)
+}
+
+BatchUpload::BatchUpload(BatchUpload &&o)
+    : ctx_(o.ctx_), stream_(o.stream_), bytes_(o.bytes_), capturing_(o.capturing_), ring_slot_(o.ring_slot_), pageable_(std::move(o.pageable_)), host_(o.host_),
+      device_(o.device_), slot_(o.slot_), slot_taken_(o.slot_taken_)
+{
+	o.slot_taken_ = false;
+}
+
+BatchUpload::~BatchUpload()
+{
+	if (!slot_taken_)
+		return;
+	std::lock_guard<std::mutex> lock(ctx_->mutex);
+	if (slot_ < ctx_->capture_slots.size())
+		ctx_->capture_slots[slot_].in_use = false, ctx_->capture_slots[slot_].owner = VkvStreamKey{};
+}
+
+int BatchUpload::commit()
+{
+	const void *src = host_;
+	if (capturing_)
+	{
+		// A stream that is being captured into a hipGraph records the copy's SOURCE POINTER and reads it at every replay, so the source has to
+		// outlive the call; and the graph can be replayed on any stream, concurrently with other graphs and with live launches on the capture
+		// stream, so it must not go through that stream's scratch block (whose users are serialised by the stream, which a replay elsewhere is
+		// not).  A captured launch therefore gets a slot of its own - pinned source AND device target of the upload.  vkv_create set
+		// kCaptureSlots slots aside, so that the usual capture allocates nothing; beyond them a slot is allocated here, with this thread's
+		// capture mode relaxed for the calls (an allocation under the global / thread-local mode would invalidate the capture).  Slots return
+		// with vkv_release_captured(stream), vkv_trim and vkv_destroy - or with this object, unless the launch was recorded (keep).
+		std::lock_guard<std::mutex> lock(ctx_->mutex);
+		vkv_ctx::CaptureSlot *      slot = nullptr;
+		for (auto &c : ctx_->capture_slots)
+			if (!c.in_use)
+			{
+				slot = &c;
+				break;
+			}
+		if (!slot)
+		{
+			vkv_ctx::CaptureSlot c;
+			void *               hp = nullptr, *dp = nullptr;
+			hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+			(void) hipThreadExchangeStreamCaptureMode(&mode);
+			const hipError_t ea = hipHostMalloc(&hp, kCaptureSlotBytes, hipHostMallocDefault);
+			const hipError_t eb = ea == hipSuccess ? hipMalloc(&dp, kCaptureSlotBytes) : ea;
+			const bool failed = ea != hipSuccess || eb != hipSuccess || !hp || !dp;
+			if (failed && hp)
+				(void) hipHostFree(hp);        // still inside the relaxed window: a free under the capture's own mode could invalidate it
+			(void) hipThreadExchangeStreamCaptureMode(&mode);
+			if (failed)
+				return set_error(ctx_, VKV_E_UNSUPPORTED, "render_batch: no argument block for a captured launch: %s", hipGetErrorString(ea != hipSuccess ? ea : eb));
+			c.pinned = static_cast<uint8_t *>(hp), c.device = static_cast<uint8_t *>(dp);
+			c.own_pinned.reset(c.pinned), c.own_device.reset(c.device);        // the context's from here on
+			ctx_->capture_slots.push_back(std::move(c));
+			slot = &ctx_->capture_slots.back();
+		}
+		slot->in_use = true, slot->owner = stream_key(stream_);
+		slot_ = (size_t) (slot - ctx_->capture_slots.data()), slot_taken_ = true;
+		std::memcpy(slot->pinned, host_, bytes_);
+		src     = slot->pinned;
+		device_ = slot->device;
+	}
+	const hipError_t e = hipMemcpyAsync(device_, src, bytes_, hipMemcpyHostToDevice, stream_);
+	if (e != hipSuccess)
+		return set_error(ctx_, (int) e, "render_batch: argument upload: %s", hipGetErrorString(e));
+	if (ring_slot_)
+	{        // the slot is the copy's source until this event has completed; if it cannot be recorded, wait for the copy here
+		if (hipEventRecord(ring_slot_->done.get(), stream_) == hipSuccess)
+			ring_slot_->pending = true;
+		else
+			(void) hipStreamSynchronize(stream_);
+	}
+	return VKV_OK;
 }
 
 // Device copy of a new table: memory out of the arena, asynchronous upload from the entry's own host copy on the launch's stream, an
@@ -449,13 +560,15 @@ int vkv_register_target(vkv_ctx *ctx, const void *d_target, uint32_t image_width
 	const bool     whole   = tiles->rect.w == 0 || tiles->rect.h == 0;
 	const uint32_t org_x = whole ? 0u : tiles->rect.x0 * tiles->tile_width, org_y = whole ? 0u : tiles->rect.y0 * tiles->tile_height;
 	const uint32_t tiles_x = whole ? (image_width + tiles->tile_width - 1) / tiles->tile_width : tiles->rect.w;
-	std::unique_ptr<vkv_ctx::TileFeedback> f(e != hipSuccess ? nullptr : new (std::nothrow) vkv_ctx::TileFeedback{d_target, image_width, image_height, tiles->tile_width, tiles->tile_height,
-	    tiles->tile_first, tiles->tile_stride, tiles->tile_count, org_x, org_y, tiles_x, std::move(cost), std::move(order), false, 0u, 0u, 8u, 0u});
+	std::unique_ptr<vkv_ctx::TileFeedback> f(e != hipSuccess ? nullptr : new (std::nothrow) vkv_ctx::TileFeedback);
 	if (!f)
 		return set_error(ctx, e != hipSuccess ? (int) e : VKV_E_UNSUPPORTED, "register_target: %s", e != hipSuccess ? hipGetErrorString(e) : "out of memory");
+	f->target = d_target, f->img_w = image_width, f->img_h = image_height, f->tile_w = tiles->tile_width, f->tile_h = tiles->tile_height;
+	f->first = tiles->tile_first, f->stride = tiles->tile_stride, f->count = tiles->tile_count, f->org_x = org_x, f->org_y = org_y, f->tiles_x = tiles_x;
+	f->d_cost = std::move(cost), f->d_order = std::move(order);
 	load_feedback_code();        // the sort kernels' code object on this device now, not inside the first launch into the target
 	std::lock_guard<std::mutex> lock(ctx->mutex);
-	f->period = ctx->tuning.feedback_period;
+	f->state.period = ctx->tuning.feedback_period;
 	ctx->feedback.push_back(std::move(f));
 	return VKV_OK;
 }

@@ -151,18 +151,11 @@ struct vkv_ctx
 	// behind and the buffer its longest-first order is written to (raymarch.hip, apply_feedback); heap objects, so their addresses stay valid
 	struct TileFeedback
 	{
-		const void *target;
-		uint32_t    img_w, img_h, tile_w, tile_h, first, stride, count;
-		uint32_t    org_x, org_y, tiles_x;        // the schedule's tile rectangle as the launcher sees it (pixels of its first tile, tile columns)
+		const void *target = nullptr;
+		uint32_t    img_w = 0, img_h = 0, tile_w = 0, tile_h = 0, first = 0, stride = 0, count = 0;
+		uint32_t    org_x = 0, org_y = 0, tiles_x = 0;        // the schedule's tile rectangle as the launcher sees it (pixels of its first tile, tile columns)
 		vkv::DevicePtr<uint32_t> d_cost, d_order;
-		bool        has_cost;        // a frame has been rendered into this target with the cost buffer attached
-		uint32_t    frames;          // frames rendered into this target so far (costs are measured and sorted every few frames)
-		uint32_t    measured_at = 0; // value of `frames` at the last measured frame
-		uint32_t    period = 8;      // frames until the next measurement (doubles while no frame can use the measured order)
-		uint32_t    used = 0;        // frames since the last measurement that started in its order
-		float       view_dir[3] = {0, 0, 0}, view_pos[3] = {0, 0, 0};        // central ray and camera position (texture space) of the measured frame
-		float       prev_dir[3] = {0, 0, 0}, prev_pos[3] = {0, 0, 0};        // ... of the previous frame into the target (measured or not)
-		bool        has_prev = false;
+		vkv::FeedbackState       state;        // when to measure, when to use the order (feedback_step, ../host/host_arith.hpp)
 	};
 	std::vector<std::unique_ptr<TileFeedback>> feedback;
 };
@@ -181,6 +174,32 @@ struct StreamScratch
 	vkv_ctx::ScratchBlock *      block = nullptr;        // its pinned upload ring (used under `lock`)
 };
 StreamScratch stream_scratch(vkv_ctx *ctx, hipStream_t stream, bool setup = false);
+// The upload of a vkv_render_batch launch: `bytes` of the (zeroed) ticket counters of the pull kernel followed by the argument blocks, assembled
+// in host() and brought to the device by commit().  Created under the lock of `scratch`, which the caller keeps until its last enqueue.
+class BatchUpload
+{
+      public:
+	BatchUpload(vkv_ctx *ctx, const StreamScratch &scratch, hipStream_t stream, size_t bytes);
+	~BatchUpload();        // a capture slot whose launch was not recorded returns to the context
+	BatchUpload(BatchUpload &&o);
+	BatchUpload &operator=(BatchUpload &&) = delete;
+	uint8_t *host() const { return host_; }
+	// enqueues the copy; VKV_OK, or the error with the context's text set.  d_heads() and d_args() are valid after it.
+	int       commit();
+	uint32_t *d_heads() const { return reinterpret_cast<uint32_t *>(device_); }
+	uint8_t * d_args() const;
+	void      keep() { slot_taken_ = false; }        // the launch was recorded: the capture slot is the graph's until it is released
+      private:
+	vkv_ctx *            ctx_;
+	hipStream_t          stream_;
+	size_t               bytes_;
+	bool                 capturing_;
+	vkv_ctx::UploadSlot *ring_slot_ = nullptr;
+	std::vector<uint8_t> pageable_;
+	uint8_t *            host_, *device_;
+	size_t               slot_ = 0;        // index of the capture slot taken by commit()
+	bool                 slot_taken_ = false;
+};
 // start order of a tile schedule: entry indices sorted by the distance of the tile's centre from the image centre (device array of
 // `count` uint32, cached per schedule shape); nullptr when the table cannot be allocated (the kernel then takes the tiles in order)
 // Per-axis byte offsets of the packed sampling image: the offset of the footprint whose padded base texel is (bx, by, bz) is
@@ -214,6 +233,7 @@ constexpr size_t kBatchArgsOffset  = 32 * 1024 + kPullHeadsBytes;        // vkv_
 constexpr uint32_t kMaxBatch       = VKV_MAX_BATCH;
 static_assert(kTfRangesOffset >= kQueueHeadsOffset + 32 && kTfRangesOffset + 4 * 2048 * 8 <= kScratchBytes, "the range table must fit the scratch block");
 static_assert(8 * kPullHeadStride * sizeof(uint32_t) == kPullHeadsBytes, "the pull kernel's counters fill the bytes the upload zeroes");
+inline uint8_t *BatchUpload::d_args() const { return device_ + kPullHeadsBytes; }
 
 // Every device entry point runs on the context's device whatever the calling thread's current device is, and leaves the
 // caller's current device as it found it.

@@ -1,9 +1,7 @@
 // raymarch.hip — launchers of the ray-march integrator (device code: raymarch_core.hpp and the headers it includes).
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <mutex>
-#include <vector>
 
 #include "raymarch_inst.hpp"
 #include "launchers.hpp"
@@ -203,11 +201,8 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 		a.fill_tiles = 0, a.img_tiles_x = full_x, a.rect_tx0 = a.rect_ty0 = a.rect_th = 0;
 		if (!whole_schedule && P->tiles.fill_outside)
 		{
-			// fill_outside (the integrator's alone; checked by check_render_params: the whole rectangle, image-indexed outputs): the workgroups of a
-			// vkv_render_batch launch fill the tiles outside the rectangle themselves; vkv_render (argument block by value: lean_block) and the
-			// resident-wave schedulers (A/B switches) simply render the whole-image schedule - the same frame either way
-			if (!batch || T.scheduler == 1 || T.batch_mode == 1 || (uint64_t) full_x * full_y - (uint64_t) r.w * r.h > (uint64_t) kFillPerTile * r.w * r.h)
-			{        // (also a rectangle so small that its tiles could not fill the rest: a cheap frame anyway)
+			if (fill_outside_as_whole_image(batch, T, full_x, full_y, r.w, r.h))
+			{
 				whole_schedule = true;
 				a.tile_count = full_x * full_y, a.tiles_x = full_x, a.org_x = a.org_y = 0u;
 			}
@@ -272,16 +267,13 @@ int fill_render_args(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_
 // turns them into the longest-first order the next frame into that target starts its tiles in.  The per-target device state is created by
 // vkv_register_target (a set-up call): a target that was never registered, the first frame into a registered one, and every frame when
 // VkvTuning.feedback is 0, use the centre-of-image-first order.  Nothing is allocated, freed or waited for here.  Any order renders the
-// same frame.  Returns true when `a` now asks for a sort (order_out set).
-static bool apply_feedback(vkv_ctx *ctx, RayMarchArgs &a, hipStream_t s)
+// same frame.  When a target is measured and when its order is used: feedback_step (../host/host_arith.cpp).  Returns true when `a` now
+// asks for a sort (order_out set).
+static bool apply_feedback(vkv_ctx *ctx, RayMarchArgs &a)
 {
-	(void) s;
-	// costs are measured (and sorted behind the render) on the first frame into a target and then every `period`-th one: a camera that
-	// moves little keeps the order good for a few frames, and the sort kernel + the cost atomics are then paid once per period
 	const void *      target = a.out_rgba8 ? (const void *) a.out_rgba8 : (const void *) a.out_color;
 	vkv_ctx::TileFeedback *     f = nullptr;
 	std::lock_guard<std::mutex> lock(ctx->mutex);
-	const uint32_t              period = ctx->tuning.feedback_period < 1u ? 1u : ctx->tuning.feedback_period;
 	if (!ctx->tuning.feedback || !target || a.tile_count < 64 || ctx->d_debug_orders)
 		return false;
 	for (auto &e : ctx->feedback)
@@ -293,65 +285,26 @@ static bool apply_feedback(vkv_ctx *ctx, RayMarchArgs &a, hipStream_t s)
 		}
 	if (!f)
 		return false;        // not registered (or registered for another schedule): centre-first
-	// the view of this frame: central ray (normalised) and camera position in texture space.  Costs measured on a view that was more
-	// than ~12 degrees away (or from a camera that has moved by more than a fifth of its distance to the volume's centre) say little
-	// about this frame - an order sorted by them scatters the heavy tiles (measured: -3 % for targets that alternate between views
-	// 45 degrees apart) - so such a frame starts centre-first.
-	float dir[3], len2 = 0.0f;
-	for (int i = 0; i < 3; ++i)
-	{
-		dir[i] = a.dir00[i] + 0.5f * ((float) a.img_w * a.ddx[i] + (float) a.img_h * a.ddy[i]);
-		len2 += dir[i] * dir[i];
-	}
-	const float inv = len2 > 0.0f ? 1.0f / std::sqrt(len2) : 0.0f;
-	float       cosine = 0.0f, moved2 = 0.0f, dist2 = 0.0f;
-	for (int i = 0; i < 3; ++i)
-	{
-		dir[i] *= inv;
-		cosine += dir[i] * f->view_dir[i];
-		moved2 += (a.cam[i] - f->view_pos[i]) * (a.cam[i] - f->view_pos[i]);
-		dist2 += (f->view_pos[i] - 0.5f) * (f->view_pos[i] - 0.5f);
-	}
-	const bool     stale   = f->has_cost && !(cosine >= 0.978f && moved2 <= 0.04f * dist2);
-	const uint32_t since   = f->frames - f->measured_at;
-	// Round 6: a target is only measured again while its camera holds still or moves slowly - this frame's view within the same ~12 degrees
-	// of the PREVIOUS frame into the target.  A camera that moves fast between a target's frames (24 targets in flight and one degree per
-	// frame: 6 - 72 degrees from one frame into a target to the next) cannot use a measured order, and measuring cost it 0.3 - 2.9 % (the
-	// cost atomics of every measured frame, the sort behind it: profiles/r6_feedback_moving_camera.txt); now it pays for the first frame only.
-	float prev_cos = 0.0f, prev_moved2 = 0.0f, prev_dist2 = 0.0f;
-	for (int i = 0; i < 3; ++i)
-	{
-		prev_cos += dir[i] * f->prev_dir[i];
-		prev_moved2 += (a.cam[i] - f->prev_pos[i]) * (a.cam[i] - f->prev_pos[i]);
-		prev_dist2 += (f->prev_pos[i] - 0.5f) * (f->prev_pos[i] - 0.5f);
-	}
-	const bool steady = f->has_prev && prev_cos >= 0.978f && prev_moved2 <= 0.04f * prev_dist2;
-	for (int i = 0; i < 3; ++i)
-		f->prev_dir[i] = dir[i], f->prev_pos[i] = a.cam[i];
-	f->has_prev        = true;
-	const bool measure = !f->has_cost || (since >= f->period && steady);
-	if (measure)
-	{
-		// a measurement whose order no frame could use (the target kept jumping between far views) doubles the distance to the next
-		// one, up to 8 periods: such a target then pays next to nothing for the feedback it cannot use
-		f->period      = (f->has_cost && f->used == 0) ? std::min(2u * f->period, 8u * period) : period;
-		f->measured_at = f->frames;
-		f->used        = 0;
-	}
-	++f->frames;
-	if (f->has_cost && !stale)
-	{
+	const FeedbackStep step = feedback_step(f->state, frame_view(a.dir00, a.ddx, a.ddy, a.cam, a.img_w, a.img_h), std::max(1u, ctx->tuning.feedback_period));
+	if (step.use_order)
 		a.tile_order = f->d_order.get();        // the order the last sort behind a frame into this target left
-		++f->used;
+	if (step.measure)
+	{
+		a.tile_cost = f->d_cost.get();
+		a.order_out = f->d_order.get();        // written by the sort that FOLLOWS this frame's render on the stream
 	}
-	if (!measure)
-		return false;
-	for (int i = 0; i < 3; ++i)
-		f->view_dir[i] = dir[i], f->view_pos[i] = a.cam[i];
-	a.tile_cost = f->d_cost.get();
-	a.order_out = f->d_order.get();        // written by the sort that FOLLOWS this frame's render on the stream
-	f->has_cost = true;
-	return true;
+	return step.measure;
+}
+
+// the two options of a parameter block that select a kernel family: early ray termination, and grad = 0 unused, 1 precomputed map, 2 on the fly
+struct RenderKind
+{
+	bool ert;
+	int  grad;
+};
+static RenderKind render_kind(const VkvRenderParams &P)
+{
+	return {P.options.early_ray_termination != 0, !P.transfer_function.use_gradient ? 0 : (P.use_precomputed_gradient ? 1 : 2)};
 }
 
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s)
@@ -366,13 +319,12 @@ int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut
 	// waves (bit-identical output; measured 2.7x slower: the re-fill breaks the spatial coherence of a wave)
 	const int   sched = T.scheduler == 1 ? (int) kSchedPersistent : (int) kSchedLean;
 
-	const bool ert  = P->options.early_ray_termination != 0;
-	const int  grad = !P->transfer_function.use_gradient ? 0 : (P->use_precomputed_gradient ? 1 : 2);
+	const RenderKind kind = render_kind(*P);
 	// start-order feedback as in vkv_render_batch (with early ray termination only; the sort runs BEHIND the render on the stream): a
 	// frame that runs alone also ends earlier when its long tiles start first (C3: 0.256 -> 0.246 ms)
-	const bool sort = sched == (int) kSchedLean && ert && apply_feedback(ctx, a, s);
+	const bool sort = sched == (int) kSchedLean && kind.ert && apply_feedback(ctx, a);
 	int        rc2 = VKV_OK;
-	if (!with_launchers(P->options.skipping_type, ert, [&](auto l) { rc2 = decltype(l)::single(ctx, sched, T, grad, a, s); }))
+	if (!with_launchers(P->options.skipping_type, kind.ert, [&](auto l) { rc2 = decltype(l)::single(ctx, sched, T, kind.grad, a, s); }))
 		rc2 = set_error(ctx, VKV_E_INVALID_ARGUMENT, "render: bad skipping_type %d", P->options.skipping_type);
 	if (rc2 == VKV_OK && sort)
 	{
@@ -403,47 +355,16 @@ int prepare_render(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, hipStream
 	return VKV_OK;
 }
 
-// ---- several frames in one launch (vkv_render_batch) --------------------------------------------------------------
+// ---- several frames in one launch (vkv_render_batch; n <= kMaxBatch) -----------------------------------------------------------------
 int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, const float *alpha_luts, hipStream_t s)
 {
-	// the argument blocks go through this stream's scratch buffer: an earlier batch on the same stream has finished with it by the
-	// time the copy (same stream) runs, and the block's lock keeps other threads' writes into it (same stream) out from the copy to the
-	// launch
-	static_assert(kMaxBatch * sizeof(RayMarchArgs) <= kScratchBytes - kBatchArgsOffset, "batch argument blocks must fit the stream scratch");
-	static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kCaptureSlotBytes, "a captured launch's upload must fit its pinned slot");
-	static_assert(kPullHeadsBytes + kMaxBatch * sizeof(RayMarchArgs) <= kUploadSlotBytes, "a launch's upload must fit a slot of the block's pinned ring");
 	const VkvTuning     T = tuning_of(ctx);
-	const StreamScratch scratch = stream_scratch(ctx, s);
+	const StreamScratch scratch = stream_scratch(ctx, s);        // locked until the last enqueue below
 	if (!scratch.p)
 		return VKV_E_UNSUPPORTED;
-	hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-	const bool             capturing = hipStreamIsCapturing(s, &capture) == hipSuccess && capture == hipStreamCaptureStatusActive;
-	// The upload - the (zeroed) ticket counters of the pull kernel, then the argument blocks - is assembled once, in place, in a pinned slot of
-	// the block's ring: no pageable source that the runtime has to stage, nothing allocated.  A slot is free once the event behind the copy
-	// that read it has completed; with every slot still in flight (or none: a block beyond the reserve, a captured launch, which has a slot
-	// of its own below) the upload comes from pageable memory as before - never a wait.
-	const size_t          upload_bytes = kPullHeadsBytes + n * sizeof(RayMarchArgs);
-	vkv_ctx::UploadSlot * ring_slot = nullptr;
-	for (uint32_t k = 0; k < vkv_ctx::kUploadRing && !capturing && !ring_slot; ++k)
-	{
-		vkv_ctx::UploadSlot &u = scratch.block->upload[(scratch.block->upload_next + k) % vkv_ctx::kUploadRing];
-		if (!u.pinned)
-			continue;
-		if (u.pending && hipEventQuery(u.done.get()) == hipSuccess)
-			u.pending = false;
-		if (!u.pending)
-		{
-			ring_slot                  = &u;
-			scratch.block->upload_next = (scratch.block->upload_next + k + 1) % vkv_ctx::kUploadRing;
-		}
-	}
-	(void) hipGetLastError();        // (a slot that is still being read answers hipErrorNotReady: not this launch's error)
-	std::vector<uint8_t> pageable;
-	if (!ring_slot)
-		pageable.resize(upload_bytes);
-	uint8_t *const upload = ring_slot ? ring_slot->pinned : pageable.data();
-	std::memset(upload, 0, upload_bytes);        // the counters, and every field fill_render_args leaves alone (an empty frame's block)
-	RayMarchArgs *const host = reinterpret_cast<RayMarchArgs *>(upload + kPullHeadsBytes);
+	BatchUpload         upload(ctx, scratch, s, kPullHeadsBytes + n * sizeof(RayMarchArgs));
+	RayMarchArgs *const host = reinterpret_cast<RayMarchArgs *>(upload.host() + kPullHeadsBytes);
+	LeanChoice          choices[kMaxBatch] = {};
 	for (uint32_t i = 0; i < n; ++i)
 	{
 		const int rc = fill_render_args(ctx, &P[i], alpha_luts + (size_t) i * 256, host[i], s, T, false, true);
@@ -451,142 +372,33 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 			return rc;
 		if (!host[i].packed)
 			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: frame %u has no packed sampling image (d_packed_volume)", i);
-		// the frames of a launch share the tile SIZE; their tile counts may differ (every frame of a multi-GPU launch has its own screen
-		// rectangle): the grid is sized for the largest, a frame's surplus workgroups leave at once
 		if (host[i].blocks_per_tile != host[0].blocks_per_tile)
 			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: frame %u has a different tile size than frame 0", i);
 		if (ctx->d_debug_orders && i < ctx->debug_order_frames && ctx->debug_order_count == host[i].tile_count)
 			host[i].tile_order = ctx->d_debug_orders + (size_t) i * ctx->debug_order_count;        // diagnostic start orders
-	}
-	uint32_t max_tiles = 0, ref = 0;        // ref: the first frame with tiles (an empty frame's argument block is only filled up to its tile count)
-	bool     same_count = true;
-	for (uint32_t i = n; i-- > 0;)
-	{
-		max_tiles = std::max(max_tiles, host[i].nblocks ? host[i].tile_count : 0u);
 		if (host[i].nblocks)
-			ref = i;
+			choices[i] = choose_lean(host[i], T);
 	}
-	if (max_tiles == 0)
+	const BatchPlan plan = plan_batch(host, choices, n, T, ctx->cu_count);
+	if (plan.max_tiles == 0)
 		return VKV_OK;
-	for (uint32_t i = 0; i < n; ++i)
-		same_count = same_count && host[i].nblocks != 0 && host[i].tile_count == max_tiles;
+	const RenderKind kind = render_kind(P[0]);
 	// measured start order only with early ray termination: without it every covered tile is about equally long, nothing is gained by
 	// starting the longest first, and an order sorted by cost scatters neighbouring tiles (C3 without ERT: 0.394 against 0.373 ms per frame)
 	bool any_sort = false;
-	for (uint32_t i = 0; i < n && P[0].options.early_ray_termination != 0; ++i)
-		any_sort = apply_feedback(ctx, host[i], s) || any_sort;
-	RayMarchArgs *   d_frames = reinterpret_cast<RayMarchArgs *>(scratch.p + kBatchArgsOffset);
-	uint32_t *       d_heads  = reinterpret_cast<uint32_t *>(scratch.p + kBatchArgsOffset - kPullHeadsBytes);
-	const void *upload_src = upload;
-	// a capture slot taken below returns to the context on every error path: only a launch that was recorded keeps it
-	struct SlotGuard
-	{
-		vkv_ctx *ctx;
-		size_t   index;
-		bool     armed;
-		~SlotGuard()
-		{
-			if (!armed)
-				return;
-			std::lock_guard<std::mutex> lock(ctx->mutex);
-			if (index < ctx->capture_slots.size())
-				ctx->capture_slots[index].in_use = false, ctx->capture_slots[index].owner = VkvStreamKey{};
-		}
-	} slot_guard{ctx, 0, false};
-	{        // A stream that is being captured into a hipGraph records the copy's SOURCE POINTER and reads it at every replay: the block then has to
-		 // outlive the call - a pinned slot the context keeps until vkv_trim / vkv_destroy
-		if (capturing)
-		{
-			// A captured launch gets a slot of its own - pinned source AND device target of the upload: the graph can be replayed on any stream,
-			// concurrently with other graphs and with live launches on the capture stream, so it must not go through that stream's scratch block
-			// (whose users are serialised by the stream, which a replay elsewhere is not).  vkv_create set kCaptureSlots slots aside, so that the
-			// usual capture allocates nothing; beyond them a slot is allocated here, with this thread's capture mode relaxed for the calls (an
-			// allocation under the global / thread-local mode would invalidate the capture).  Slots return with vkv_release_captured(stream),
-			// vkv_trim and vkv_destroy.
-			std::lock_guard<std::mutex> lock(ctx->mutex);
-			vkv_ctx::CaptureSlot *      slot = nullptr;
-			for (auto &c : ctx->capture_slots)
-				if (!c.in_use)
-				{
-					slot = &c;
-					break;
-				}
-			if (!slot)
-			{
-				vkv_ctx::CaptureSlot c;
-				void *               hp = nullptr, *dp = nullptr;
-				hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-				(void) hipThreadExchangeStreamCaptureMode(&mode);
-				const hipError_t ea = hipHostMalloc(&hp, kCaptureSlotBytes, hipHostMallocDefault);
-				const hipError_t eb = ea == hipSuccess ? hipMalloc(&dp, kCaptureSlotBytes) : ea;
-				const bool failed = ea != hipSuccess || eb != hipSuccess || !hp || !dp;
-				if (failed && hp)
-					(void) hipHostFree(hp);        // still inside the relaxed window: a free under the capture's own mode could invalidate it
-				(void) hipThreadExchangeStreamCaptureMode(&mode);
-				if (failed)
-					return set_error(ctx, VKV_E_UNSUPPORTED, "render_batch: no argument block for a captured launch: %s", hipGetErrorString(ea != hipSuccess ? ea : eb));
-				c.pinned = static_cast<uint8_t *>(hp), c.device = static_cast<uint8_t *>(dp);
-				c.own_pinned.reset(c.pinned), c.own_device.reset(c.device);        // the context's from here on
-				ctx->capture_slots.push_back(std::move(c));
-				slot = &ctx->capture_slots.back();
-			}
-			slot->in_use = true, slot->owner = stream_key(s);
-			slot_guard.index = (size_t) (slot - ctx->capture_slots.data()), slot_guard.armed = true;
-			std::memcpy(slot->pinned, upload, upload_bytes);
-			upload_src = slot->pinned;
-			d_heads    = reinterpret_cast<uint32_t *>(slot->device);
-			d_frames   = reinterpret_cast<RayMarchArgs *>(slot->device + kPullHeadsBytes);
-		}
-	}
-	const hipError_t e = hipMemcpyAsync(d_heads, upload_src, upload_bytes, hipMemcpyHostToDevice, s);
-	if (e != hipSuccess)
-		return set_error(ctx, (int) e, "render_batch: argument upload: %s", hipGetErrorString(e));
-	if (ring_slot)
-	{        // the slot is the copy's source until this event has completed; if it cannot be recorded, wait for the copy here
-		if (hipEventRecord(ring_slot->done.get(), s) == hipSuccess)
-			ring_slot->pending = true;
-		else
-			(void) hipStreamSynchronize(s);
-	}
-	const uint64_t grid = (uint64_t) ((max_tiles + 7u) / 8u) * 8u * host[0].blocks_per_tile * n;
-	if (grid > 0x7fffffffull)
+	for (uint32_t i = 0; i < n && kind.ert; ++i)
+		any_sort = apply_feedback(ctx, host[i]) || any_sort;
+	const int rc = upload.commit();
+	if (rc != VKV_OK)
+		return rc;
+	if (plan.too_many)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "render_batch: too many workgroups for one launch");
-	const bool ert  = P[0].options.early_ray_termination != 0;
-	const int  grad = !P[0].transfer_function.use_gradient ? 0 : (P[0].use_precomputed_gradient ? 1 : 2);
-	// frames interleaved in groups of eight workgroups (default) or one frame after the other (VkvTuning.batch_sequential, A/B
-	// switch: measured 0.183 vs 0.169 ms per frame on C3 with 8 frames per launch)
-	const bool        sequential = T.batch_sequential != 0;
-	const uint32_t    gpf        = sequential ? (uint32_t) (grid / n / 8) : 0u;
-	LeanChoice        choice     = choose_lean(host[ref], T);
-	bool              no_counts  = true;        // no frame reads the per-pixel counters (no counter buffer, no sample-count test output): the loop without them
-	for (uint32_t i = 0; i < n; ++i)
-		no_counts = no_counts && (host[i].nblocks == 0 || !wants_counts(host[i]));
-	for (uint32_t i = 0; i < n; ++i)
-	{        // one kernel for all frames: the most general choice any of them needs
-		if (i == ref || host[i].nblocks == 0)
-			continue;
-		const LeanChoice c = choose_lean(host[i], T);
-		if (c.kind != choice.kind || c.lds != choice.lds || host[i].lut_words != host[ref].lut_words)
-			choice = {0, 0};
-	}
-	// VkvTuning.batch_mode = 1 (pull): resident workgroups whose waves pull 8x8 units from per-XCD ticket counters (k_raymarch_lean_pull), possible
-	// when every frame shares the LDS tables (same packed image and extents, TF tables, opacity table).  Bit-identical; measured on C3 with 8
-	// frames per launch: the CU stays full (7 900 of 8 192 wave slots against 5 300) and everything but the last marching tiles is done after
-	// 0.83 ms instead of 1.0, but those last tiles - the volume's silhouette, 100-250 iterations of cold probes - then run 340 us with their
-	// four 8x8 units on four different CUs (150 us as one workgroup on one CU): 0.151 ms per frame against 0.137.  Not the default.
-	bool              pull      = T.batch_mode == 1 && !sequential && same_count;        // (its tickets count one tile count for every frame)
-	const uint64_t    units     = (uint64_t) max_tiles * host[0].blocks_per_tile * 4u * n;
-	for (uint32_t i = 1; i < n && pull; ++i)
-	{
-		const RayMarchArgs &a = host[i], &b = host[0];
-		pull = a.packed == b.packed && a.tf_bits == b.tf_bits && a.tf == b.tf && a.addr_lut == b.addr_lut && a.W == b.W && a.H == b.H && a.D == b.D &&
-		       std::memcmp(a.alpha_lut, b.alpha_lut, sizeof(a.alpha_lut)) == 0;
-	}
-	if (!with_launchers(P[0].options.skipping_type, ert, [&](auto l) {
-		    if (pull)
-			    decltype(l)::pull(ctx, grad, d_frames, n, d_heads, choice, units, s);
+	const RayMarchArgs *const d_frames = reinterpret_cast<const RayMarchArgs *>(upload.d_args());
+	if (!with_launchers(P[0].options.skipping_type, kind.ert, [&](auto l) {
+		    if (plan.pull)
+			    decltype(l)::pull(kind.grad, d_frames, n, upload.d_heads(), plan.choice, plan.pull_grid, s);
 		    else
-			    decltype(l)::batch(grad, d_frames, n, (uint32_t) grid, gpf, choice, no_counts, s);
+			    decltype(l)::batch(kind.grad, d_frames, n, (uint32_t) plan.grid, plan.gpf, plan.choice, plan.no_counts, s);
 	    }))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "render_batch: bad skipping_type %d", P[0].options.skipping_type);
 	// behind the render, on the same stream: the costs it measured become the start order of the next frames into these targets (the
@@ -594,7 +406,8 @@ int launch_render_batch(vkv_ctx *ctx, const VkvRenderParams *P, uint32_t n, cons
 	if (any_sort)
 		hipLaunchKernelGGL(k_tile_orders_from_cost, dim3(n), dim3(256), 0, s, d_frames);
 	const int rc_launch = check_launch(ctx, "render_batch");
-	slot_guard.armed = slot_guard.armed && rc_launch != VKV_OK;
+	if (rc_launch == VKV_OK)
+		upload.keep();
 	return rc_launch;
 }
 

@@ -6,6 +6,7 @@
 
 #include "context.hpp"
 #include "raymarch_core.hpp"
+#include "raymarch_plan.hpp"
 
 namespace vkv
 {
@@ -27,18 +28,7 @@ constexpr uint32_t kLfFull   = kLeanLut | kLeanFull | kLeanSafe | kLeanAsync; //
 constexpr uint32_t kLfFullNc = kLfFull | kLeanNoCounts;          // the same without the per-pixel counters (what a renderer launches)
 constexpr uint32_t kLfLutNc  = kLfLut | kLeanNoCounts;
 
-struct LeanChoice
-{
-	int    kind;        // 0 plain, 1 two-level tables, 2 full tables
-	size_t lds;         // dynamic LDS bytes (lean_lds_bytes: the kernels' whole LDS layout lives in the dynamic segment)
-};
-
-LeanChoice choose_lean(const RayMarchArgs &a, const VkvTuning &T);        // raymarch.hip
-
-// A launch may run the loop without the three per-pixel counters when nothing reads them: no counter buffer and not the frag's
-// sample-count test output (frag:324-334 turns n_vol + n_dist into the colour - Test::NumTextureSamples is independent of ERT and of
-// the skipping type in the reference's GUI, src/volume_render.cpp:539)
-inline bool wants_counts(const RayMarchArgs &a) { return a.out_counts != nullptr || a.test == VKV_TEST_NUM_TEXTURE_SAMPLES; }
+LeanChoice choose_lean(const RayMarchArgs &a, const VkvTuning &T);        // raymarch.hip (LeanChoice, wants_counts: raymarch_plan.hpp)
 
 template <int SKIP, bool ERT>
 struct RayMarchLaunchers
@@ -47,8 +37,8 @@ struct RayMarchLaunchers
 	static int single(vkv_ctx *ctx, int sched, const VkvTuning &T, int grad, RayMarchArgs &a, hipStream_t s);
 	// n frames interleaved in one grid (vkv_render_batch); c = {0, 0}: the frames disagree about the tables
 	static void batch(int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t grid, uint32_t gpf, LeanChoice c, bool no_counts, hipStream_t s);
-	// the same with resident workgroups whose waves pull their units; returns the grid size
-	static uint32_t pull(vkv_ctx *ctx, int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, LeanChoice c, uint64_t units, hipStream_t s);
+	// the same with `grid` resident workgroups whose waves pull their units (BatchPlan::pull_grid)
+	static void pull(int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, LeanChoice c, uint32_t grid, hipStream_t s);
 	// set-up: the runtime loads a translation unit's code object (device memory, milliseconds) at the first use of one of its kernels - make
 	// that now, on the current device, instead of inside the first launch (vkv_prepare_render)
 	static void load();
@@ -169,37 +159,30 @@ void RayMarchLaunchers<SKIP, ERT>::batch(int grad, const RayMarchArgs *d_frames,
 }
 
 // ---- the same, with resident workgroups whose waves pull their units ------------------------------------------------
-// grid = the workgroups the device holds at once (occupancy of this instantiation x CUs), never more than there are units / 4
-template <int SKIP, bool ERT, int GRAD, uint32_t LF>
-static uint32_t launch_pull_one(vkv_ctx *ctx, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, size_t lds, uint64_t units, hipStream_t s)
-{
-	// eight workgroups of four waves fill a CU's 32 wave slots (this instantiation is held to 64 VGPRs); should fewer fit, the surplus
-	// workgroups start when others have finished and take what tickets are left
-	const uint64_t resident = (uint64_t) 8 * (uint64_t) (ctx->cu_count > 1 ? ctx->cu_count : 1);
-	const uint64_t want     = resident < (units + 3) / 4 ? resident : (units + 3) / 4;
-	const uint32_t grid     = (uint32_t) (want < 8 ? 8 : want);
-	hipLaunchKernelGGL((k_raymarch_lean_pull<SKIP, ERT, GRAD, LF>), dim3(grid), dim3(256), lds, s, d_frames, n, d_heads);
-	return grid;
-}
-
 template <int SKIP, bool ERT, int GRAD>
-static uint32_t launch_pull_kind(vkv_ctx *ctx, LeanChoice c, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, uint64_t units, hipStream_t s)
+static void launch_pull_kind(LeanChoice c, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, uint32_t grid, hipStream_t s)
 {
 	if constexpr (GRAD != 2)
 	{
 		if (c.kind == 2)
-			return launch_pull_one<SKIP, ERT, GRAD, kLfFull>(ctx, d_frames, n, d_heads, c.lds, units, s);
-		if (c.kind == 1)
-			return launch_pull_one<SKIP, ERT, GRAD, kLfLut>(ctx, d_frames, n, d_heads, c.lds, units, s);
+			hipLaunchKernelGGL((k_raymarch_lean_pull<SKIP, ERT, GRAD, kLfFull>), dim3(grid), dim3(256), c.lds, s, d_frames, n, d_heads);
+		else if (c.kind == 1)
+			hipLaunchKernelGGL((k_raymarch_lean_pull<SKIP, ERT, GRAD, kLfLut>), dim3(grid), dim3(256), c.lds, s, d_frames, n, d_heads);
+		if (c.kind != 0)
+			return;
 	}
-	return launch_pull_one<SKIP, ERT, GRAD, kLfPlain>(ctx, d_frames, n, d_heads, lean_lds_bytes(0, 0, 0, 0, 0), units, s);
+	hipLaunchKernelGGL((k_raymarch_lean_pull<SKIP, ERT, GRAD, kLfPlain>), dim3(grid), dim3(256), lean_lds_bytes(0, 0, 0, 0, 0), s, d_frames, n, d_heads);
 }
 
 template <int SKIP, bool ERT>
-uint32_t RayMarchLaunchers<SKIP, ERT>::pull(vkv_ctx *ctx, int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, LeanChoice c, uint64_t units, hipStream_t s)
+void RayMarchLaunchers<SKIP, ERT>::pull(int grad, const RayMarchArgs *d_frames, uint32_t n, uint32_t *d_heads, LeanChoice c, uint32_t grid, hipStream_t s)
 {
-	return grad == 0 ? launch_pull_kind<SKIP, ERT, 0>(ctx, c, d_frames, n, d_heads, units, s)
-	                 : (grad == 1 ? launch_pull_kind<SKIP, ERT, 1>(ctx, c, d_frames, n, d_heads, units, s) : launch_pull_kind<SKIP, ERT, 2>(ctx, c, d_frames, n, d_heads, units, s));
+	if (grad == 0)
+		launch_pull_kind<SKIP, ERT, 0>(c, d_frames, n, d_heads, grid, s);
+	else if (grad == 1)
+		launch_pull_kind<SKIP, ERT, 1>(c, d_frames, n, d_heads, grid, s);
+	else
+		launch_pull_kind<SKIP, ERT, 2>(c, d_frames, n, d_heads, grid, s);
 }
 
 #else        // declarations only (raymarch.hip): the definitions are instantiated by the eight raymarch_s*e*.hip files

@@ -74,6 +74,32 @@ static inline float clamp_free_margin(int W, int H, int D)
 	return 0.25f / (float) m;
 }
 
+// ---- start-order feedback: when a registered target is measured again and when its measured order may be used (raymarch.hip attaches the
+// buffers; vkv_ctx::TileFeedback holds a state per target).  No device, no lock: the caller holds the context's mutex.
+// the view of a frame: its central ray (normalised) and the camera position, both in texture space
+struct FrameView
+{
+	float dir[3] = {0, 0, 0}, pos[3] = {0, 0, 0};
+};
+FrameView frame_view(const float dir00[3], const float ddx[3], const float ddy[3], const float cam[3], uint32_t img_w, uint32_t img_h);
+struct FeedbackState
+{
+	bool      has_cost = false;        // a frame has been rendered into this target with the cost buffer attached
+	uint32_t  frames = 0;              // frames rendered into this target so far
+	uint32_t  measured_at = 0;         // value of `frames` at the last measured frame
+	uint32_t  period = 8;              // frames until the next measurement (doubles while no frame can use the measured order)
+	uint32_t  used = 0;                // frames since the last measurement that started in its order
+	FrameView measured, prev;          // the view of the measured frame, and of the previous frame into the target (measured or not)
+	bool      has_prev = false;
+};
+struct FeedbackStep
+{
+	bool use_order;        // start this frame's tiles in the order the last measurement left
+	bool measure;          // attach the cost buffer to this frame and sort behind it
+};
+// one frame into the target; base_period = max(1, VkvTuning.feedback_period)
+FeedbackStep feedback_step(FeedbackState &f, const FrameView &view, uint32_t base_period);
+
 // Range checks of a tuning block, shared by vkv_set_tuning (which rejects a bad block) and default_tuning (which falls back to the
 // built-in value of a field the environment set out of range).  Returns null when the block is fine, else what is wrong with it.
 const char *tuning_problem(const VkvTuning &t);
