@@ -30,7 +30,6 @@ ctx = lib.Context(0)
 LAB = C.CDLL(os.path.join(ROOT, "tools", "lab", "libvkv_lab.so"))
 LAB.vkv_lab_render.argtypes = [C.c_void_p, C.POINTER(abi.RenderParams), C.c_int, C.c_void_p]
 L = lib.load()
-L.vkv_debug_trace.argtypes = [C.c_void_p, C.c_void_p]
 
 v, tf, frame, skip = bench.build_scene(ctx, name)
 fw, fh = frame

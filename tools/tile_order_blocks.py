@@ -13,8 +13,6 @@ fw, fh = frame
 views = bench.cameras(v, fw / fh)
 sp = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=skip, clip_distance=1.0, early_ray_termination=not os.environ.get("NO_ERT")), (fw, fh))
 L = lib.load()
-L.vkv_debug_trace.argtypes = [C.c_void_p, C.c_void_p]
-L.vkv_debug_tile_orders.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
 sizes = [7, 7, 6]
 streams = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
 sets, k = [], 0

@@ -19,8 +19,6 @@ fw, fh = frame
 views = bench.cameras(v, fw / fh)
 sp = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=skip, clip_distance=1.0, early_ray_termination=True), (fw, fh))
 L = lib.load()
-L.vkv_debug_trace.argtypes = [C.c_void_p, C.c_void_p]
-L.vkv_debug_tile_orders.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
 streams = [torch.cuda.current_stream()] + [torch.cuda.Stream() for _ in range(nstreams - 1)]
 sets = []
 for s in range(nstreams):

@@ -18,7 +18,7 @@ nblocks = ((p.tiles.tile_count + 7) // 8) * 8
 trace = torch.zeros((nblocks * 4, 10), dtype=torch.int64, device="cuda")  # kTraceWords = 10 per wave
 for _ in range(3): sp.draw(p, rgba8=rgba8)
 torch.cuda.synchronize()
-L = lib.load(); L.vkv_debug_trace.argtypes = [C.c_void_p, C.c_void_p]
+L = lib.load()
 L.vkv_debug_trace(ctx.handle, trace.data_ptr())
 sp.draw(p, rgba8=rgba8); torch.cuda.synchronize()
 L.vkv_debug_trace(ctx.handle, None)

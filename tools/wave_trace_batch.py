@@ -23,7 +23,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 nblocks = ((plist[0].tiles.tile_count + 7) // 8) * 8 * n
 trace = torch.zeros((nblocks * 4, 10), dtype=torch.int64, device="cuda")
-L = lib.load(); L.vkv_debug_trace.argtypes = [C.c_void_p, C.c_void_p]
+L = lib.load()
 L.vkv_debug_trace(ctx.handle, trace.data_ptr())
 ctx.render_batch(plist, st); torch.cuda.synchronize()
 L.vkv_debug_trace(ctx.handle, None)

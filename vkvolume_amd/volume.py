@@ -172,18 +172,31 @@ class Volume:
         the occupancy map and the transform of `skipping_type` (grows the map list like ComputeDistanceMap.compute); `d_count`: a device
         int64 tensor that receives the occupied-voxel count."""
         self.set_number_of_distance_maps(8 if skipping_type == abi.SKIP_ANISOTROPIC_DISTANCE else 1)
-        grad = self.gradient if self.options.use_precomputed_gradient else None
-        self.ctx.update_transfer_function(self.options, _ptr(self.volume), _ptr(grad), self.extent, _ptr(self.transfer_function),
+        self.ctx.update_transfer_function(self.options, _ptr(self.volume), _ptr(self._gradient_or_none()), self.extent, _ptr(self.transfer_function),
                                           _ptr(self.transfer_function_bits), [_ptr(m) for m in self.distance_maps], _ptr(self.distance_map_swap),
                                           self.map_extent, skipping_type, _ptr(d_count), _stream())
 
     def _gradient_or_none(self):
         return self.gradient if self.options.use_precomputed_gradient else None
 
-    def _check_out(self, name, out):
-        """`out` of Volume.<name>: a contiguous uint8 tensor of the volume's shape on its device"""
+    def _out(self, name, out, box):
+        """the tensor that Volume.<name> writes the voxels of `box` (None: all) into: the caller's `out`, which must be a contiguous uint8
+        tensor of the volume's shape on its device, or a new one: a copy of the volume where a box leaves voxels unwritten"""
+        if out is None:
+            return self.volume.clone() if box is not None else torch.empty_like(self.volume)
         if out.dtype != torch.uint8 or out.shape != self.volume.shape or not out.is_contiguous() or out.device != self.volume.device:
             raise ValueError("Volume.%s: `out` must be a contiguous uint8 tensor of shape %s on %s" % (name, tuple(self.volume.shape), self.volume.device))
+        return out
+
+    def _box_shape(self, box):
+        """[depth, height, width] of what a call over `box` (an abi.Box; None: the whole volume) writes per voxel"""
+        return tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
+
+    def _check_labels(self, name, labels, box):
+        """`labels` of Volume.<name>: a contiguous uint32 (or int32) tensor of the shape of `box` on the volume's device"""
+        shape = self._box_shape(box)
+        if labels.dtype not in (torch.uint32, torch.int32) or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != self.volume.device:
+            raise ValueError("Volume.%s: `labels` must be a contiguous uint32 tensor of shape %s on %s" % (name, shape, self.volume.device))
 
     def _scratch(self, nbytes, rejected):
         """the scratch block of a call that needs `nbytes` (a *_scratch_bytes result; 0: ValueError(rejected)), 8-byte aligned"""
@@ -275,10 +288,9 @@ class Volume:
             if len(self.distance_maps) < n:
                 raise RuntimeError("Volume.update_region: the maps of skipping type %d have not been built" % skipping_type)
             maps = [_ptr(m) for m in self.distance_maps[:n]]
-        grad = self.gradient if self.options.use_precomputed_gradient else None
         x, y, z = origin_xyz
-        self.ctx.update_volume_region(_ptr(src), vt, big_endian, float(lo), float(hi), abi.Box(x, y, z, w, h, d), _ptr(self.volume), _ptr(grad),
-                                      _ptr(self.packed), self.extent, _ptr(self.transfer_function), self.get_transfer_function_uniform(), maps,
+        self.ctx.update_volume_region(_ptr(src), vt, big_endian, float(lo), float(hi), abi.Box(x, y, z, w, h, d), _ptr(self.volume),
+                                      _ptr(self._gradient_or_none()), _ptr(self.packed), self.extent, _ptr(self.transfer_function), self.get_transfer_function_uniform(), maps,
                                       _ptr(self.distance_map_swap), self.map_extent, skipping_type, _stream())
         src.record_stream(torch.cuda.current_stream())  # the source stays allocated until the update has read it
         if self.cell_summary is not None:  # the summary of every cell the grown box meets (the gradient changes one voxel around the box)
@@ -306,8 +318,7 @@ class Volume:
         elif out.dtype != torch.int64 or tuple(out.shape) != (256, 256) or not out.is_contiguous() or out.device != self.volume.device:
             raise ValueError("Volume.histogram: `out` must be a contiguous (256, 256) int64 tensor on %s" % (self.volume.device,))
         box = _as_box(box)
-        grad = self.gradient if self.options.use_precomputed_gradient else None
-        self.ctx.volume_histogram(_ptr(self.volume), _ptr(grad), self.extent, box, mode, _ptr(out), _stream())
+        self.ctx.volume_histogram(_ptr(self.volume), _ptr(self._gradient_or_none()), self.extent, box, mode, _ptr(out), _stream())
         return out
 
     _FILTER_KINDS = (abi.FILTER_BINOMIAL3, abi.FILTER_MEDIAN3)
@@ -323,12 +334,9 @@ class Volume:
             raise ValueError("Volume.filter: unknown kind %r" % (kind,))
         if int(passes) != passes or passes < 1:
             raise ValueError("Volume.filter: passes must be a positive integer")
-        if out is None:
-            if box is not None:
-                raise ValueError("Volume.filter: a box needs `out` (the bytes outside the box are kept)")
-            out = torch.empty_like(self.volume)
-        else:
-            self._check_out("filter", out)
+        if out is None and box is not None:
+            raise ValueError("Volume.filter: a box needs `out` (the bytes outside the box are kept)")
+        out = self._out("filter", out, box)
         if box is not None:
             if passes != 1:
                 raise ValueError("Volume.filter: a box takes one pass")
@@ -426,9 +434,8 @@ class Volume:
         max_map, map_extent = self._max_map_args("label_components", use_max_map)
         scratch = self._scratch(lib.components_scratch_bytes(self.extent, box),
                                 "Volume.label_components: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
-        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
         counts = torch.empty((3,), dtype=torch.int64, device=self.device)
-        labels = torch.empty(shape, dtype=torch.uint32, device=self.device)
+        labels = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
 
         def call(d_sizes, n):
             self.ctx.label_components(_ptr(self.volume), self.extent, box, iso, connectivity, _ptr(max_map), map_extent, _ptr(scratch), _ptr(labels),
@@ -461,10 +468,7 @@ class Volume:
         if int(fill) != fill or not 0 <= fill <= 255:
             raise ValueError("Volume.remove_islands: fill must be a byte")
         box = _as_box(box)
-        if out is None:
-            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
-        else:
-            self._check_out("remove_islands", out)
+        out = self._out("remove_islands", out, box)
         labels, sizes, counts = self.label_components(iso, connectivity=connectivity, box=box)
         if keep_largest:
             min_voxels = int(sizes.to(torch.int64).max().item()) if sizes.numel() else 0
@@ -487,9 +491,7 @@ class Volume:
         ``counts``, which is ONE host wait; with a number there is none, the labels above it are ignored, and records beyond
         min(K, capacity) are not written: they hold whatever the allocation held."""
         box = _as_box(box)
-        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
-        if labels.dtype not in (torch.uint32, torch.int32) or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != self.volume.device:
-            raise ValueError("Volume.component_stats: `labels` must be a contiguous uint32 tensor of shape %s on %s" % (shape, self.volume.device))
+        self._check_labels("component_stats", labels, box)
         k = int(counts[0].item()) if capacity is None else int(capacity)
         raw = torch.empty((k, abi.COMPONENT_STATS_BYTES), dtype=torch.uint8, device=self.device)
         self.ctx.component_stats(_ptr(self.volume) if values else None, self.extent, box, _ptr(labels), _ptr(counts), _ptr(raw) if k else None, k, _stream())
@@ -504,15 +506,10 @@ class Volume:
         if int(fill) != fill or not 0 <= fill <= 255:
             raise ValueError("Volume.select_components: fill must be a byte")
         box = _as_box(box)
-        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
-        if labels.dtype not in (torch.uint32, torch.int32) or tuple(labels.shape) != shape or not labels.is_contiguous() or labels.device != self.volume.device:
-            raise ValueError("Volume.select_components: `labels` must be a contiguous uint32 tensor of shape %s on %s" % (shape, self.volume.device))
+        self._check_labels("select_components", labels, box)
         if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1 or not keep.is_contiguous() or keep.device != self.volume.device:
             raise ValueError("Volume.select_components: `keep` must be a contiguous one-dimensional bool or uint8 tensor on %s" % (self.volume.device,))
-        if out is None:
-            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
-        else:
-            self._check_out("select_components", out)
+        out = self._out("select_components", out, box)
         n = keep.numel()
         self.ctx.select_components_by_table(_ptr(self.volume), _ptr(out), self.extent, box, _ptr(labels), _ptr(keep) if n else None, n, int(fill), _stream())
         self._written_in_place(out, box)
@@ -539,8 +536,7 @@ class Volume:
         """vkv_distance_transform of the uint8 tensor `src` (the volume's shape) on the current stream; box: an abi.Box or None"""
         scratch = self._scratch(lib.distance_transform_scratch_bytes(self.extent, box),
                                 "Volume.distance_transform: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
-        shape = tuple(self.volume.shape) if box is None else (box.depth, box.height, box.width)
-        dist2 = torch.empty(shape, dtype=torch.uint32, device=self.device)
+        dist2 = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
         self.ctx.distance_transform(_ptr(src), self.extent, box, iso, target, limit, _ptr(scratch), _ptr(dist2), _stream())
         return dist2
 
@@ -582,10 +578,7 @@ class Volume:
             if int(f) != f or not 0 <= f <= 255:
                 raise ValueError("Volume.%s: inside_fill and outside_fill must be bytes" % name)
         box = _as_box(box)
-        if out is None:
-            out = self.volume.clone() if box is not None else torch.empty_like(self.volume)
-        else:
-            self._check_out(name, out)
+        out = self._out(name, out, box)
         src = self.volume
         for step in steps:
             erode = step == "erode"
@@ -643,8 +636,7 @@ class Volume:
         n = self.ctx.packed_volume_bytes(self.extent)
         if self.packed is None or self.packed.numel() != n:
             self.packed = torch.empty(n, dtype=torch.uint8, device=self.device)
-        grad = self.gradient if self.options.use_precomputed_gradient else None
-        self.ctx.pack_volume(_ptr(self.volume), _ptr(grad), self.extent, _ptr(self.packed), _stream())
+        self.ctx.pack_volume(_ptr(self.volume), _ptr(self._gradient_or_none()), self.extent, _ptr(self.packed), _stream())
 
 
 class ComputeGradientMap:
@@ -665,8 +657,7 @@ class ComputeDistanceMap:
     def compute(self, volume, transfer_function_uniform, skipping_type):
         n = 8 if skipping_type == abi.SKIP_ANISOTROPIC_DISTANCE else 1
         volume.set_number_of_distance_maps(n)
-        grad = volume.gradient if volume.options.use_precomputed_gradient else None
-        self.ctx.compute_distance_map(_ptr(volume.volume), _ptr(grad), _ptr(volume.transfer_function), transfer_function_uniform,
+        self.ctx.compute_distance_map(_ptr(volume.volume), _ptr(volume._gradient_or_none()), _ptr(volume.transfer_function), transfer_function_uniform,
                                       volume.extent, [_ptr(m) for m in volume.distance_maps], _ptr(volume.distance_map_swap),
                                       volume.map_extent, skipping_type, _stream())
 
@@ -703,7 +694,7 @@ class VolumeRenderSubpass:
         v = self.volume
         p = abi.RenderParams.from_buffer_copy(params)
         p.d_volume = _ptr(v.volume)
-        p.d_gradient = _ptr(v.gradient) if v.options.use_precomputed_gradient else None
+        p.d_gradient = _ptr(v._gradient_or_none())
         p.d_transfer_function = _ptr(v.transfer_function)
         for i in range(8):
             p.d_distance_maps[i] = _ptr(v.distance_maps[i]) if i < len(v.distance_maps) else None
@@ -713,12 +704,25 @@ class VolumeRenderSubpass:
         p.d_transfer_function_bits = _ptr(v.transfer_function_bits) if v.use_packed else None
         return p
 
-    def draw(self, params, color=None, rgba8=None, counts=None, depth=None, in_depth=None, blend=False):
-        """``in_depth``: scene depth for options.depth_attachment; ``blend``: blend onto the contents of color / rgba8
-        (the subpass's blend state) instead of overwriting them."""
+    @staticmethod
+    def _bind_outputs(params, color, rgba8, counts, depth=None, in_depth=None, blend=False):
+        """point ``params`` at the buffers a draw call writes (None: not written) and reads (in_depth)"""
         params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
         params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
         params.d_in_depth, params.blend_over_target = _ptr(in_depth), 1 if blend else 0
+
+    def _skip_map(self, name, skip):
+        """the max map that <name>(skip=...) skips over, which must have been built; None without skip"""
+        if not skip:
+            return None
+        if self.volume.max_map is None:
+            raise RuntimeError("VolumeRenderSubpass.%s: skip=True needs the volume's max map (call Volume.build_max_map first)" % name)
+        return self.volume.max_map
+
+    def draw(self, params, color=None, rgba8=None, counts=None, depth=None, in_depth=None, blend=False):
+        """``in_depth``: scene depth for options.depth_attachment; ``blend``: blend onto the contents of color / rgba8
+        (the subpass's blend state) instead of overwriting them."""
+        self._bind_outputs(params, color, rgba8, counts, depth, in_depth, blend)
         self.ctx.render(params, _stream())
 
     def draw_mip(self, params, threshold, window_max, color=None, rgba8=None, intensity=None, depth=None, counts=None, skip=True, in_depth=None):
@@ -726,14 +730,8 @@ class VolumeRenderSubpass:
         level is (m - threshold) / (window_max - threshold) clamped to [0, 1].  ``skip``: jump over the cells of the volume's max map
         (build_max_map() first; the same bits as the dense path); False: filter every sample.  ``in_depth``: scene depth for
         options.depth_attachment."""
-        max_map = None
-        if skip:
-            if self.volume.max_map is None:
-                raise RuntimeError("VolumeRenderSubpass.draw_mip: skip=True needs the volume's max map (call Volume.build_max_map first)")
-            max_map = self.volume.max_map
-        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
-        params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
-        params.d_in_depth, params.blend_over_target = _ptr(in_depth), 0
+        max_map = self._skip_map("draw_mip", skip)
+        self._bind_outputs(params, color, rgba8, counts, depth, in_depth)
         mip = abi.MipOptions(threshold=float(threshold), window_max=float(window_max), d_max_map=_ptr(max_map), d_out_intensity=_ptr(intensity),
                              flags=0)
         self.ctx.render_mip(params, mip, _stream())
@@ -745,14 +743,8 @@ class VolumeRenderSubpass:
         integer exponent ``shininess``); ``normal``: 4 floats per pixel, the world-space unit normal facing the camera.  ``skip``: jump over the
         cells of the volume's max map (build_max_map() first; the same bits as the dense path); False: filter every sample up to the hit.
         ``in_depth``: scene depth for options.depth_attachment."""
-        max_map = None
-        if skip:
-            if self.volume.max_map is None:
-                raise RuntimeError("VolumeRenderSubpass.draw_iso: skip=True needs the volume's max map (call Volume.build_max_map first)")
-            max_map = self.volume.max_map
-        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
-        params.d_out_counts, params.d_out_depth = _ptr(counts), _ptr(depth)
-        params.d_in_depth, params.blend_over_target = _ptr(in_depth), 0
+        max_map = self._skip_map("draw_iso", skip)
+        self._bind_outputs(params, color, rgba8, counts, depth, in_depth)
         opts = abi.IsoOptions(iso=float(iso), refine_steps=int(refine_steps), base_color=(C.c_float * 3)(*[float(c) for c in base_color]),
                               ambient=float(ambient), diffuse=float(diffuse), specular=float(specular), shininess=int(shininess),
                               d_max_map=_ptr(max_map), d_out_normal=_ptr(normal), flags=0)
@@ -766,14 +758,8 @@ class VolumeRenderSubpass:
         image size, schedule and extents of ``params`` are read: no camera is needed."""
         if isinstance(plane, dict):
             plane = (plane["origin"], plane["du"], plane["dv"], plane["dn"])
-        max_map = None
-        if skip and mode == abi.SLAB_MAX:
-            if self.volume.max_map is None:
-                raise RuntimeError("VolumeRenderSubpass.draw_slab: skip=True needs the volume's max map (call Volume.build_max_map first)")
-            max_map = self.volume.max_map
-        params.d_out_color, params.d_out_rgba8 = _ptr(color), _ptr(rgba8)
-        params.d_out_counts, params.d_out_depth = _ptr(counts), None
-        params.d_in_depth, params.blend_over_target = None, 0
+        max_map = self._skip_map("draw_slab", skip and mode == abi.SLAB_MAX)
+        self._bind_outputs(params, color, rgba8, counts)
         vec = lambda a: (C.c_float * 3)(*[float(x) for x in a])  # noqa: E731
         origin, du, dv, dn = plane
         opts = abi.SlabOptions(origin=vec(origin), du=vec(du), dv=vec(dv), dn=vec(dn), samples=int(samples), mode=int(mode),
