@@ -950,6 +950,28 @@ int vkv_distance_transform(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D ex
 int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box,
                            const uint32_t *d_dist2, uint32_t lo, uint32_t hi, uint32_t fill, void *stream);
 
+/* ---- the distance transform with a weight per axis: voxel spacing ---------------------------------------------------------
+ * vkv_distance_transform_weighted is vkv_distance_transform for voxels that are not cubes: `weights` is a HOST pointer to three integers
+ * (wx, wy, wz), read during the call, and
+ *   d_dist2[v] = min(limit, min over the target voxels u of the box of (wx dx)^2 + (wy dy)^2 + (wz dz)^2),
+ * an integer again, so the result is unique and two runs give the same bytes.  A scan of 0.5 x 0.5 x 1.25 mm voxels takes (2, 2, 5): the
+ * values are squared distances in units of 0.25 mm.  Everything else is as above: the inside rule, the targets, only the box exists, the
+ * box-shaped output with every element written, `limit` everywhere where the box holds no target, VKV_DISTANCE_NONE for unlimited, limit == 0
+ * invalid.  With weights (1, 1, 1) the bytes are those of vkv_distance_transform.  The result feeds vkv_select_by_distance unchanged; lo and
+ * hi are then in weighted units (an erosion by r^2 removes what lies within sum (w_a k_a)^2 <= r^2 of the outside).
+ * d_scratch: the SAME block, vkv_distance_transform_scratch_bytes(extent, box) bytes, 8-byte aligned; one allocation serves both calls.
+ * The y and z passes build the lower envelope of each line's parabolas (one line per lane; the envelope's stack lives in the line of the
+ * output that it is about to overwrite), so the cost does not grow with the distance found, as that of vkv_distance_transform does: this
+ * call is the one for large or unlimited distances, the other one for small limits (README.md has the measured crossover).
+ * Kernels only (no allocation, no memset or copy node, no host wait, no atomics; the kernels use no scratch memory, and none waits for another
+ * lane, wave or workgroup): after one direct call on `stream` it can be captured into a hipGraph.  Nothing in the context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: everything that
+ * vkv_distance_transform rejects so, a null `weights` and a weight of 0.  VKV_E_UNSUPPORTED: everything that vkv_distance_transform rejects
+ * so, and weights whose largest possible value does not fit: the sum over the axes of (w_a (len_a - 1))^2, len the box's shape, must be at
+ * most 0xfffffffe, with every w_a (len_a - 1) at most 65535 (an axis of length 1 admits every weight but 0). */
+int vkv_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
+                                    const uint32_t weights[3], uint32_t limit, void *d_scratch, uint32_t *d_dist2, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

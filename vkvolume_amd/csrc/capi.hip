@@ -525,28 +525,55 @@ int vkv_select_components_by_table(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *
 
 size_t vkv_distance_transform_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return edt_scratch_bytes(extent, box); }
 
+// what vkv_distance_transform and vkv_distance_transform_weighted check alike (ctx is not null); 0: accepted so far
+static int check_distance_transform(vkv_ctx *ctx, const char *name, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
+                                    uint32_t limit, void *d_scratch, uint32_t *d_dist2)
+{
+	if (!d_volume || !d_scratch || !d_dist2 || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null pointer or zero extent", name);
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: iso must be finite", name);
+	if (target != VKV_DISTANCE_TO_INSIDE && target != VKV_DISTANCE_TO_OUTSIDE)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: unknown target %d", name, (int) target);
+	if (limit == 0u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: limit 0 (VKV_DISTANCE_NONE: unlimited)", name);
+	if (const int rc = check_box(ctx, name, extent, box))
+		return rc;
+	if (((uintptr_t) d_scratch & 7u) != 0 || ((uintptr_t) d_dist2 & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_scratch must be 8-byte aligned, d_dist2 4-byte aligned", name);
+	if (!edt_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: a box of more than 2^32 - 1 voxels or an axis above 32768; transform it box by box", name);
+	return VKV_OK;
+}
+
 // every argument is checked before the first launch (and before the device is touched); nothing in the context is written
 int vkv_distance_transform(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target, uint32_t limit,
                            void *d_scratch, uint32_t *d_dist2, void *stream)
 {
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
-	if (!d_volume || !d_scratch || !d_dist2 || !extent_ok(extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: null pointer or zero extent");
-	if (!std::isfinite(iso))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: iso must be finite");
-	if (target != VKV_DISTANCE_TO_INSIDE && target != VKV_DISTANCE_TO_OUTSIDE)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: unknown target %d", (int) target);
-	if (limit == 0u)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: limit 0 (VKV_DISTANCE_NONE: unlimited)");
-	if (const int rc = check_box(ctx, "distance_transform", extent, box))
+	if (const int rc = check_distance_transform(ctx, "distance_transform", d_volume, extent, box, iso, target, limit, d_scratch, d_dist2))
 		return rc;
-	if (((uintptr_t) d_scratch & 7u) != 0 || ((uintptr_t) d_dist2 & 3u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform: d_scratch must be 8-byte aligned, d_dist2 4-byte aligned");
-	if (!edt_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768; transform it box by box");
 	DeviceGuard guard(ctx->device);
 	return launch_distance_transform(ctx, d_volume, extent, whole_or(extent, box), iso, target, limit, d_scratch, d_dist2, (hipStream_t) stream);
+}
+
+// the same checks, then the weights (read here, on the host): none null or 0, and the largest value they can give fits below VKV_DISTANCE_NONE
+int vkv_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
+                                    const uint32_t weights[3], uint32_t limit, void *d_scratch, uint32_t *d_dist2, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!weights || weights[0] == 0u || weights[1] == 0u || weights[2] == 0u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "distance_transform_weighted: null weights or a weight of 0");
+	if (const int rc = check_distance_transform(ctx, "distance_transform_weighted", d_volume, extent, box, iso, target, limit, d_scratch, d_dist2))
+		return rc;
+	const VkvBox b = whole_or(extent, box);
+	if (!edt_weights_fit(weights, b.width, b.height, b.depth))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform_weighted: weights (%u, %u, %u) can give a value above 0xfffffffe in this box", weights[0],
+		                 weights[1], weights[2]);
+	DeviceGuard guard(ctx->device);
+	return launch_distance_transform_weighted(ctx, d_volume, extent, b, iso, target, weights, limit, d_scratch, d_dist2, (hipStream_t) stream);
 }
 
 // every argument is checked before the launch (and before the device is touched)

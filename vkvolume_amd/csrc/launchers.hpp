@@ -145,6 +145,12 @@ int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e,
 int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_dist2, uint32_t lo,
                               uint32_t hi, uint32_t fill, hipStream_t s);
 
+// ---- edt_envelope.hip
+// vkv_distance_transform_weighted after the entry point's argument checks (b inside e, edt_launch_ok, edt_weights_fit of host_arith.hpp); the
+// scratch block is edt_scratch_bytes()
+int launch_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, const uint32_t weights[3],
+                                       uint32_t limit, void *d_scratch, uint32_t *d_dist2, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

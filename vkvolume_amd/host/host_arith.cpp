@@ -23,6 +23,30 @@ static bool tile_mix_ok(const VkvTuning &t)
 	       t.tile_mix_spread <= 1.0f;
 }
 
+bool edt_weights_fit(const uint32_t weights[3], uint32_t bw, uint32_t bh, uint32_t bd)
+{
+	const uint32_t len[3] = {bw, bh, bd};
+	uint64_t       sum    = 0;
+	for (int a = 0; a < 3; ++a)
+	{
+		if (weights[a] == 0u || len[a] == 0u)
+			return false;
+		const uint64_t far = (uint64_t) weights[a] * (len[a] - 1u);        // below 2^64
+		if (far > 65535u)
+			return false;
+		sum += far * far;        // three terms below 2^32
+	}
+	return sum <= 0xfffffffeull;
+}
+
+uint32_t edt_weighted_reach(uint32_t limit, uint32_t w)
+{
+	uint64_t root = 0;        // the smallest root with root^2 >= limit: at most 65536
+	while (root * root < limit)
+		++root;
+	return (uint32_t) ((root + w - 1u) / w);        // (w r)^2 >= limit iff w r >= root
+}
+
 const char *tuning_problem(const VkvTuning &t)
 {
 	if (t.scheduler < 0 || t.scheduler > 1 || t.batch_mode < 0 || t.batch_mode > 1 || t.address_tables < 0 || t.address_tables > 2 || t.feedback_period == 0 ||

@@ -29,6 +29,14 @@ static inline uint32_t iso_threshold(float iso)
 	return thr;
 }
 
+// ---- vkv_distance_transform_weighted (csrc/edt_envelope.hip): what the entry point works out before it enqueues anything -----------------
+// The weights (wx, wy, wz) are accepted for a box of (bw, bh, bd) voxels iff none is 0 and the largest value that can occur,
+// sum over the axes of (w (len - 1))^2, is at most 0xfffffffe (one below VKV_DISTANCE_NONE).  No step wraps: each w (len - 1) is held to 65535 in 64 bits
+// first, so each square is below 2^32 and the sum of three is formed in 64 bits.  An axis of length 1 admits every weight but 0.
+bool edt_weights_fit(const uint32_t weights[3], uint32_t bw, uint32_t bh, uint32_t bd);
+// the x pass's reach: the smallest r with (w r)^2 >= limit, w >= 1: a target further away along the row gives the cap anyway.  At most 65536
+uint32_t edt_weighted_reach(uint32_t limit, uint32_t w);
+
 // ---- launch-uniform arithmetic of the ray-march kernels, done once on the host (fill_render_args) ---------------------------------------
 #if defined(__HIPCC__)        // (always inlined: a kernel built with target attributes of its own cannot inline a plain function, and a call costs it a stack)
 #define VKV_HOST_DEVICE __host__ __device__ inline __attribute__((always_inline))

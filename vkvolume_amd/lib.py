@@ -88,6 +88,7 @@ def _signatures():
         row(size, "vkv_distance_transform_scratch_bytes", abi.Extent3D, P(abi.Box)),
         row(INT, "vkv_distance_transform", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, u32, vp, vp, vp),
         row(INT, "vkv_select_by_distance", vp, vp, vp, abi.Extent3D, P(abi.Box), vp, u32, u32, u32, vp),
+        row(INT, "vkv_distance_transform_weighted", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, P(u32), u32, vp, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -419,6 +420,15 @@ class Context:
         return self._lib.vkv_select_by_distance(self.handle, d_src, d_dst, extent, box, d_dist2, lo, hi, fill, stream)
 
     select_by_distance = _raising(select_by_distance_rc)
+
+    def distance_transform_weighted_rc(self, d_volume, extent, box, iso, target, weights, limit, d_scratch, d_dist2, stream=0):
+        """vkv_distance_transform_weighted: distance_transform() with integer weights (wx, wy, wz): d_dist2 = min(limit, the least
+        (wx dx)^2 + (wy dy)^2 + (wz dz)^2 to a target voxel of the box); the same scratch block.  Returns the status code: there is no raising
+        form (the public surface admits new names only as _rc), so callers write ctx.check(ctx.distance_transform_weighted_rc(...)).
+        weights None passes NULL (error-path tests)."""
+        return self._lib.vkv_distance_transform_weighted(self.handle, d_volume, extent, box, iso, int(target),
+                                                         None if weights is None else (C.c_uint32 * 3)(*(int(w) for w in weights)),
+                                                         abi.DISTANCE_NONE if limit is None else int(limit), d_scratch, d_dist2, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

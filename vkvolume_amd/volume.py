@@ -532,26 +532,84 @@ class Volume:
 
     _DISTANCE_TARGETS = {"inside": abi.DISTANCE_TO_INSIDE, "outside": abi.DISTANCE_TO_OUTSIDE}
 
-    def _distance_transform(self, src, iso, target, limit, box):
-        """vkv_distance_transform of the uint8 tensor `src` (the volume's shape) on the current stream; box: an abi.Box or None"""
+    def _distance_transform(self, src, iso, target, limit, box, weights=None):
+        """vkv_distance_transform (weights None) or vkv_distance_transform_weighted (a checked triple) of the uint8 tensor `src` (the volume's
+        shape) on the current stream; box: an abi.Box or None"""
         scratch = self._scratch(lib.distance_transform_scratch_bytes(self.extent, box),
                                 "Volume.distance_transform: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
         dist2 = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
-        self.ctx.distance_transform(_ptr(src), self.extent, box, iso, target, limit, _ptr(scratch), _ptr(dist2), _stream())
+        if weights is None:
+            self.ctx.distance_transform(_ptr(src), self.extent, box, iso, target, limit, _ptr(scratch), _ptr(dist2), _stream())
+        else:
+            self.ctx.check(self.ctx.distance_transform_weighted_rc(_ptr(src), self.extent, box, iso, target, weights, limit, _ptr(scratch), _ptr(dist2),
+                                                                   _stream()))
         return dist2
 
-    def distance_transform(self, iso, to="inside", limit=None, box=None):
+    @staticmethod
+    def _as_weights(name, weights):
+        """None, or the triple (wx, wy, wz) of positive integers below 2^32 as ints"""
+        if weights is None:
+            return None
+        try:
+            w = tuple(weights)
+            ok = len(w) == 3 and all(int(a) == a and 1 <= a <= 0xffffffff for a in w)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("Volume.%s: weights must be None or three positive integers (x, y, z)" % name)
+        return tuple(int(a) for a in w)
+
+    def distance_transform(self, iso, to="inside", limit=None, box=None, weights=None):
         """The exact squared Euclidean distance transform on the current stream (vkv_distance_transform): a torch.uint32 tensor of the box's
         shape [depth, height, width] (the volume's without a box) that holds, per voxel, the squared distance in voxel units to the nearest
         voxel with value >= ``iso`` (``to="inside"``; the mesh's inside rule) or below it (``to="outside"``), 0 on such a voxel.  ``limit``:
         values are capped at it (cheaper: the work grows with the distance found); None: unlimited, and 0xffffffff everywhere where the box
-        holds no such voxel.  Only the box's voxels exist: nothing beyond it counts as inside or outside.  No host wait."""
+        holds no such voxel.  Only the box's voxels exist: nothing beyond it counts as inside or outside.  No host wait.
+        ``weights``: None, or three positive integers (x, y, z) for voxels that are not cubes (vkv_distance_transform_weighted; see
+        spacing_weights()): the values are then (wx dx)^2 + (wy dy)^2 + (wz dz)^2, and ``limit`` is in those units.  Weights whose largest
+        possible value in the box exceeds 0xfffffffe raise VkvError.  The weighted call's cost does not grow with the distance found; None
+        stays on vkv_distance_transform, which is the faster one at small limits and wherever targets are dense: measured on the 1024 x 1024
+        x 795 bench volume to the inside, the crossover lies between limits 10 (11.5 against 13.0 ms) and 101 (21.0 against 16.2 ms), and
+        unlimited it is 207 against 36 ms (profiles/distance_weighted_times.txt); pass (1, 1, 1) to get the same values from the other call."""
         if to not in self._DISTANCE_TARGETS:
             raise ValueError("Volume.distance_transform: `to` must be 'inside' or 'outside'")
         if limit is not None and (int(limit) != limit or not 1 <= limit <= abi.DISTANCE_NONE):
             raise ValueError("Volume.distance_transform: limit must be an integer in 1 .. 0xffffffff or None")
         box = _as_box(box)
-        return self._distance_transform(self.volume, iso, self._DISTANCE_TARGETS[to], limit, box)
+        return self._distance_transform(self.volume, iso, self._DISTANCE_TARGETS[to], limit, box, self._as_weights("distance_transform", weights))
+
+    @staticmethod
+    def spacing_weights(voxel_size, max_weight=64, rel_tol=1e-3):
+        """Integer weights for a voxel size (sx, sy, sz), e.g. VkvVolumeHeader.voxel_size: ``((wx, wy, wz), unit)`` with w_a * unit close to
+        s_a, so that a squared distance d2 of a weighted call is sqrt(d2) * unit in the caller's length.  With s_min the smallest size, m = 1,
+        2, ... in turn gives w_a = floor(m s_a / s_min + 0.5), until a w_a would exceed ``max_weight``; the first m whose largest relative error
+        max_a |w_a s_min / m - s_a| / s_a is at most ``rel_tol`` is taken, else the m with the smallest error (the smaller m of equals);
+        unit = s_min / m.  (0.5, 0.5, 1.25) gives ((2, 2, 5), 0.25).  Sizes that are not finite and positive, and sizes whose ratio
+        exceeds ``max_weight`` (no m fits), raise ValueError."""
+        try:
+            sizes = tuple(float(s) for s in voxel_size)
+        except (TypeError, ValueError):
+            sizes = ()
+        if len(sizes) != 3 or not all(np.isfinite(s) and s > 0 for s in sizes):
+            raise ValueError("Volume.spacing_weights: voxel_size must be three finite positive numbers")
+        if int(max_weight) != max_weight or max_weight < 1 or not rel_tol >= 0:
+            raise ValueError("Volume.spacing_weights: max_weight must be a positive integer and rel_tol non-negative")
+        s_min = min(sizes)
+        best = None
+        m = 1
+        while True:
+            w = tuple(int(np.floor(m * s / s_min + 0.5)) for s in sizes)
+            if max(w) > max_weight:
+                break
+            err = max(abs(wa * s_min / m - s) / s for wa, s in zip(w, sizes))
+            if best is None or err < best[0]:
+                best = (err, w, m)
+            if err <= rel_tol:
+                break
+            m += 1
+        if best is None:        # m = 1 already exceeds max_weight: the ratio of the sizes is above it
+            raise ValueError("Volume.spacing_weights: the sizes' ratio exceeds max_weight")
+        return best[1], s_min / best[2]
 
     @staticmethod
     def ball_radius2(radius=None, radius2=None):
@@ -571,24 +629,25 @@ class Volume:
             raise ValueError("the squared radius must lie in 1 .. 0xfffffffe")
         return r2
 
-    def _morphology(self, name, steps, iso, radius, radius2, inside_fill, outside_fill, out, box):
+    def _morphology(self, name, steps, iso, radius, radius2, inside_fill, outside_fill, out, box, weights=None):
         """steps: "erode" / "dilate" in order; the first reads the volume, each further one the result before it (in place in `out`)"""
         r2 = self.ball_radius2(radius, radius2)
         for f in (inside_fill, outside_fill):
             if int(f) != f or not 0 <= f <= 255:
                 raise ValueError("Volume.%s: inside_fill and outside_fill must be bytes" % name)
+        weights = self._as_weights(name, weights)
         box = _as_box(box)
         out = self._out(name, out, box)
         src = self.volume
         for step in steps:
             erode = step == "erode"
-            dist2 = self._distance_transform(src, iso, abi.DISTANCE_TO_OUTSIDE if erode else abi.DISTANCE_TO_INSIDE, r2 + 1, box)
+            dist2 = self._distance_transform(src, iso, abi.DISTANCE_TO_OUTSIDE if erode else abi.DISTANCE_TO_INSIDE, r2 + 1, box, weights)
             self.ctx.select_by_distance(_ptr(src), _ptr(out), self.extent, box, _ptr(dist2), 1, r2, int(outside_fill if erode else inside_fill), _stream())
             src = out
         self._written_in_place(out, box)
         return out
 
-    def erode(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+    def erode(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None, weights=None):
         """The volume eroded by a ball on the current stream (vkv_distance_transform to the outside with limit radius2 + 1, then
         vkv_select_by_distance): a uint8 tensor of the volume's shape in which every inside voxel (value >= ``iso``) within the ball of an
         outside voxel holds ``outside_fill``; everything else is the volume's byte.  Give ``radius`` (radius2 = floor(radius * radius)) or
@@ -598,21 +657,24 @@ class Volume:
         eat at the box's faces (scipy's border_value=1).  ``self.volume`` is not touched unless ``out`` is the volume.  In place, a max map
         built with build_max_map() is rebuilt over the box after the last step, on the same stream and without a host wait, so
         extract_isosurface / label_components(use_max_map=True) and draw_mip / draw_iso / draw_slab(skip=True) see the new voxels; the gradient
-        map, the packed image, the cell summary and the occupancy and distance maps are the caller's to re-derive."""
-        return self._morphology("erode", ("erode",), iso, radius, radius2, inside_fill, outside_fill, out, box)
+        map, the packed image, the cell summary and the occupancy and distance maps are the caller's to re-derive.
+        ``weights``: None, or three positive integers (x, y, z) as for distance_transform(): ``radius`` and ``radius2`` are then in weighted
+        units, a step along axis a counting w_a, and the ball holds the offsets with (wx dx)^2 + (wy dy)^2 + (wz dz)^2 <= radius2: with
+        spacing_weights() of the voxel size, a ball in the caller's length and not an ellipsoid."""
+        return self._morphology("erode", ("erode",), iso, radius, radius2, inside_fill, outside_fill, out, box, weights)
 
-    def dilate(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+    def dilate(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None, weights=None):
         """The volume dilated by a ball: every outside voxel within the ball of an inside voxel holds ``inside_fill``; see erode()."""
-        return self._morphology("dilate", ("dilate",), iso, radius, radius2, inside_fill, outside_fill, out, box)
+        return self._morphology("dilate", ("dilate",), iso, radius, radius2, inside_fill, outside_fill, out, box, weights)
 
-    def open(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+    def open(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None, weights=None):
         """The opening by a ball: erode(), then dilate() of the result.  It cuts bridges and removes parts thinner than the ball, after which
         remove_islands() can drop what they held on by; see erode()."""
-        return self._morphology("open", ("erode", "dilate"), iso, radius, radius2, inside_fill, outside_fill, out, box)
+        return self._morphology("open", ("erode", "dilate"), iso, radius, radius2, inside_fill, outside_fill, out, box, weights)
 
-    def close(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None):
+    def close(self, iso, radius=None, radius2=None, inside_fill=255, outside_fill=0, out=None, box=None, weights=None):
         """The closing by a ball: dilate(), then erode() of the result.  It fills pores and cracks thinner than the ball; see erode()."""
-        return self._morphology("close", ("dilate", "erode"), iso, radius, radius2, inside_fill, outside_fill, out, box)
+        return self._morphology("close", ("dilate", "erode"), iso, radius, radius2, inside_fill, outside_fill, out, box, weights)
 
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
