@@ -972,6 +972,39 @@ int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, V
 int vkv_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
                                     const uint32_t weights[3], uint32_t limit, void *d_scratch, uint32_t *d_dist2, void *stream);
 
+/* ---- the nearest-target (feature) transform and label propagation --------------------------------------------------------
+ * vkv_nearest_target says not how far the nearest target is but WHICH it is.  The inside rule, the targets, "only the box exists", `weights`
+ * (a HOST pointer, read during the call) and `limit` are exactly those of vkv_distance_transform_weighted.  With D(v) the least
+ * (wx dx)^2 + (wy dy)^2 + (wz dz)^2 over the box's targets, d_nearest (uint32, the box's shape, every element written) is
+ *   d_nearest[v] = the SMALLEST BOX-LINEAR INDEX ((z' - z0) height + (y' - y0)) width + (x' - x0) among the targets at distance D(v)
+ *                  if the box holds a target and D(v) < limit,
+ *                  VKV_NEAREST_NONE otherwise.
+ * A box holds at most 2^32 - 1 voxels, so no index equals VKV_NEAREST_NONE; a target voxel's nearest target is itself.  The tie rule makes
+ * the answer unique: two runs, and any two correct implementations, give the same bytes.  d_dist2 may be NULL; otherwise it receives
+ * min(limit, D(v)), byte for byte what vkv_distance_transform_weighted writes.
+ * d_scratch: the SAME block, vkv_distance_transform_scratch_bytes(extent, box) bytes, 8-byte aligned: the passes carry features, not
+ * distances, between d_nearest and the block's uint32 buffer.  Kernels only (no allocation, no memset or copy node, no host wait, no
+ * atomics, no scratch memory, no lane waits for another): after one direct call on `stream` it can be captured into a hipGraph.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  The codes are those of
+ * vkv_distance_transform_weighted; also VKV_E_INVALID_ARGUMENT: a null d_nearest, a d_nearest or a non-NULL d_dist2 that is not 4-byte
+ * aligned, and a d_dist2 that overlaps d_nearest.
+ *
+ * vkv_propagate_labels is the gather that every use of d_nearest comes to.  All three arrays have the box's shape (uint32, 4-byte aligned):
+ *   d_out[v] = 0                          if d_nearest[v] == VKV_NEAREST_NONE, or is any other value >= the box's voxels (nothing is read),
+ *            = 0                          if d_mask_volume is given and voxel v of it is outside (the inside rule, with mask_iso),
+ *            = d_labels[d_nearest[v]]     otherwise.
+ * d_mask_volume == NULL: no mask, and no byte of a volume is read.  d_out may overlap neither d_labels nor d_nearest (the call is a gather):
+ * VKV_E_INVALID_ARGUMENT, as are a null array, a bad box, a misaligned array and (with a mask) a mask_iso that is not finite;
+ * VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels.  One launch.  With d_labels of vkv_label_components the result is a label array
+ * with values in 0 .. K, which vkv_component_stats and vkv_select_components_by_table take unchanged.  Erode, label, vkv_nearest_target of
+ * the eroded volume, propagate with the original volume as the mask: touching bodies split at full size ("nearest" is Euclidean, not
+ * geodesic). */
+#define VKV_NEAREST_NONE 0xffffffffu
+int vkv_nearest_target(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
+                       const uint32_t weights[3], uint32_t limit, void *d_scratch, uint32_t *d_nearest, uint32_t *d_dist2, void *stream);
+int vkv_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t *d_labels, uint32_t *d_out, VkvExtent3D extent,
+                         const VkvBox *box, const uint8_t *d_mask_volume, float mask_iso, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

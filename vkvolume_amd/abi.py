@@ -145,6 +145,7 @@ FILTER_BINOMIAL3, FILTER_MEDIAN3 = 0, 1  # VkvFilterKind
 CONNECT_6, CONNECT_14, CONNECT_26 = 6, 14, 26  # VKV_CONNECT_*: the neighbourhoods of vkv_label_components
 DISTANCE_TO_INSIDE, DISTANCE_TO_OUTSIDE = 0, 1  # VkvDistanceTarget: the target voxels of vkv_distance_transform
 DISTANCE_NONE = 0xffffffff  # VKV_DISTANCE_NONE: no limit
+NEAREST_NONE = 0xffffffff  # VKV_NEAREST_NONE: vkv_nearest_target found no target (within the limit)
 
 
 class ComponentStats(C.Structure):

@@ -525,11 +525,12 @@ int vkv_select_components_by_table(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *
 
 size_t vkv_distance_transform_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return edt_scratch_bytes(extent, box); }
 
-// what vkv_distance_transform and vkv_distance_transform_weighted check alike (ctx is not null); 0: accepted so far
+// what vkv_distance_transform, vkv_distance_transform_weighted and vkv_nearest_target check alike (ctx is not null); 0: accepted so far.
+// dist2_optional: vkv_nearest_target's d_dist2 may be null
 static int check_distance_transform(vkv_ctx *ctx, const char *name, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target,
-                                    uint32_t limit, void *d_scratch, uint32_t *d_dist2)
+                                    uint32_t limit, void *d_scratch, uint32_t *d_dist2, bool dist2_optional = false)
 {
-	if (!d_volume || !d_scratch || !d_dist2 || !extent_ok(extent))
+	if (!d_volume || !d_scratch || (!d_dist2 && !dist2_optional) || !extent_ok(extent))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null pointer or zero extent", name);
 	if (!std::isfinite(iso))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: iso must be finite", name);
@@ -574,6 +575,60 @@ int vkv_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_volume, VkvEx
 		                 weights[1], weights[2]);
 	DeviceGuard guard(ctx->device);
 	return launch_distance_transform_weighted(ctx, d_volume, extent, b, iso, target, weights, limit, d_scratch, d_dist2, (hipStream_t) stream);
+}
+
+// vkv_distance_transform_weighted's checks (the shared function, the weights), then the feature buffer: not null, 4-byte aligned, and apart
+// from d_dist2 where that is given.  Both hold 4 bytes per voxel of the box
+int vkv_nearest_target(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, int32_t target, const uint32_t weights[3],
+                       uint32_t limit, void *d_scratch, uint32_t *d_nearest, uint32_t *d_dist2, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!weights || weights[0] == 0u || weights[1] == 0u || weights[2] == 0u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "nearest_target: null weights or a weight of 0");
+	if (!d_nearest || ((uintptr_t) d_nearest & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "nearest_target: d_nearest must be given and 4-byte aligned");
+	if (const int rc = check_distance_transform(ctx, "nearest_target", d_volume, extent, box, iso, target, limit, d_scratch, d_dist2, true))
+		return rc;
+	const VkvBox b = whole_or(extent, box);
+	if (!edt_weights_fit(weights, b.width, b.height, b.depth))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "nearest_target: weights (%u, %u, %u) can give a value above 0xfffffffe in this box", weights[0], weights[1],
+		                 weights[2]);
+	if (d_dist2)
+	{        // edt_launch_ok: at most 2^32 - 1 voxels
+		const uint64_t  bytes = 4ull * b.width * b.height * b.depth;
+		const uintptr_t p = (uintptr_t) d_nearest, q = (uintptr_t) d_dist2;
+		if ((p < q ? q - p : p - q) < bytes)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "nearest_target: d_nearest and d_dist2 overlap");
+	}
+	DeviceGuard guard(ctx->device);
+	return launch_nearest_target(ctx, d_volume, extent, b, iso, target, weights, limit, d_scratch, d_nearest, d_dist2, (hipStream_t) stream);
+}
+
+// every argument is checked before the launch (and before the device is touched).  The call is a gather: d_out apart from both inputs
+int vkv_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t *d_labels, uint32_t *d_out, VkvExtent3D extent, const VkvBox *box,
+                         const uint8_t *d_mask_volume, float mask_iso, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_nearest || !d_labels || !d_out || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "propagate_labels: null pointer or zero extent");
+	if (d_mask_volume && !std::isfinite(mask_iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "propagate_labels: mask_iso must be finite");
+	if (const int rc = check_box(ctx, "propagate_labels", extent, box))
+		return rc;
+	if ((((uintptr_t) d_nearest | (uintptr_t) d_labels | (uintptr_t) d_out) & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "propagate_labels: d_nearest, d_labels and d_out must be 4-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "propagate_labels: a box of more than 2^32 - 1 voxels");
+	const VkvBox    b     = whole_or(extent, box);
+	const uint64_t  bytes = 4ull * b.width * b.height * b.depth;
+	const uintptr_t o     = (uintptr_t) d_out;
+	for (const uintptr_t in : {(uintptr_t) d_nearest, (uintptr_t) d_labels})
+		if ((o < in ? in - o : o - in) < bytes)
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "propagate_labels: d_out overlaps d_nearest or d_labels (a gather does not run in place)");
+	DeviceGuard guard(ctx->device);
+	return launch_propagate_labels(ctx, d_nearest, d_labels, d_out, extent, b, d_mask_volume, mask_iso, (hipStream_t) stream);
 }
 
 // every argument is checked before the launch (and before the device is touched)

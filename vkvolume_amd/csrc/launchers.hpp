@@ -151,6 +151,14 @@ int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst
 int launch_distance_transform_weighted(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, const uint32_t weights[3],
                                        uint32_t limit, void *d_scratch, uint32_t *d_dist2, hipStream_t s);
 
+// ---- nearest.hip
+// vkv_nearest_target after the entry point's argument checks (those of vkv_distance_transform_weighted; d_dist2 may be null), with the same
+// scratch block, and vkv_propagate_labels after its checks (b inside e, components_launch_ok; d_mask_vol null: no mask)
+int launch_nearest_target(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, const uint32_t weights[3], uint32_t limit,
+                          void *d_scratch, uint32_t *d_nearest, uint32_t *d_dist2, hipStream_t s);
+int launch_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t *d_labels, uint32_t *d_out, VkvExtent3D e, const VkvBox &b,
+                            const uint8_t *d_mask_vol, float mask_iso, hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

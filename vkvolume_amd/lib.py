@@ -89,6 +89,8 @@ def _signatures():
         row(INT, "vkv_distance_transform", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, u32, vp, vp, vp),
         row(INT, "vkv_select_by_distance", vp, vp, vp, abi.Extent3D, P(abi.Box), vp, u32, u32, u32, vp),
         row(INT, "vkv_distance_transform_weighted", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, P(u32), u32, vp, vp, vp),
+        row(INT, "vkv_nearest_target", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, P(u32), u32, vp, vp, vp, vp),
+        row(INT, "vkv_propagate_labels", vp, vp, vp, vp, abi.Extent3D, P(abi.Box), vp, f32, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -429,6 +431,22 @@ class Context:
         return self._lib.vkv_distance_transform_weighted(self.handle, d_volume, extent, box, iso, int(target),
                                                          None if weights is None else (C.c_uint32 * 3)(*(int(w) for w in weights)),
                                                          abi.DISTANCE_NONE if limit is None else int(limit), d_scratch, d_dist2, stream)
+
+    def nearest_target_rc(self, d_volume, extent, box, iso, target, weights, limit, d_scratch, d_nearest, d_dist2=None, stream=0):
+        """vkv_nearest_target: d_nearest (uint32, the shape of `box`) = the smallest box-linear index among the targets at the least
+        (wx dx)^2 + (wy dy)^2 + (wz dz)^2 from each voxel, abi.NEAREST_NONE where the box holds no target or that distance is >= limit;
+        d_dist2 (None: not wanted) = distance_transform_weighted_rc()'s bytes.  Targets, weights, limit and the scratch block
+        (distance_transform_scratch_bytes) are that call's.  Returns the status code: there is no raising form (the public surface admits
+        new names only as _rc), so callers write ctx.check(ctx.nearest_target_rc(...)).  weights None passes NULL (error-path tests)."""
+        return self._lib.vkv_nearest_target(self.handle, d_volume, extent, box, iso, int(target),
+                                            None if weights is None else (C.c_uint32 * 3)(*(int(w) for w in weights)),
+                                            abi.DISTANCE_NONE if limit is None else int(limit), d_scratch, d_nearest, d_dist2, stream)
+
+    def propagate_labels_rc(self, d_nearest, d_labels, d_out, extent, box, d_mask_volume=None, mask_iso=0.0, stream=0):
+        """vkv_propagate_labels: d_out = d_labels[d_nearest] per voxel of `box` (three uint32 arrays of its shape), 0 where d_nearest is
+        abi.NEAREST_NONE (or any value >= the box's voxels) or where voxel v of d_mask_volume (None: no mask) is below mask_iso; d_out
+        overlaps neither input.  Returns the status code, as nearest_target_rc()."""
+        return self._lib.vkv_propagate_labels(self.handle, d_nearest, d_labels, d_out, extent, box, d_mask_volume, mask_iso, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

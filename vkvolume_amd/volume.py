@@ -676,6 +676,74 @@ class Volume:
         """The closing by a ball: dilate(), then erode() of the result.  It fills pores and cracks thinner than the ball; see erode()."""
         return self._morphology("close", ("dilate", "erode"), iso, radius, radius2, inside_fill, outside_fill, out, box, weights)
 
+    def _nearest_target(self, src, iso, target, limit, box, weights, distance=False):
+        """vkv_nearest_target of the uint8 tensor `src` (the volume's shape) on the current stream: (nearest, dist2 or None); box: an abi.Box or
+        None, weights: a checked triple"""
+        scratch = self._scratch(lib.distance_transform_scratch_bytes(self.extent, box),
+                                "Volume.nearest_target: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels or an axis above 32768")
+        nearest = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
+        dist2 = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device) if distance else None
+        self.ctx.check(self.ctx.nearest_target_rc(_ptr(src), self.extent, box, iso, target, weights, limit, _ptr(scratch), _ptr(nearest), _ptr(dist2), _stream()))
+        return nearest, dist2
+
+    def _propagate_labels(self, nearest, labels, box, mask, mask_iso):
+        """vkv_propagate_labels on the current stream: a new uint32 tensor of the box's shape; mask: a uint8 tensor of the volume's shape or None"""
+        out = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
+        self.ctx.check(self.ctx.propagate_labels_rc(_ptr(nearest), _ptr(labels), _ptr(out), self.extent, box, _ptr(mask), float(mask_iso), _stream()))
+        return out
+
+    def nearest_target(self, iso, to="inside", limit=None, box=None, weights=None, distance=False):
+        """The nearest-target (feature) transform on the current stream (vkv_nearest_target): a torch.uint32 tensor of the box's shape [depth,
+        height, width] (the volume's without a box) that holds, per voxel, the index of the nearest voxel with value >= ``iso``
+        (``to="inside"``) or below it (``to="outside"``): the box-linear index (z' * height + y') * width + x' in box coordinates, which is the
+        index into any flattened array of the box's shape, so ``values.flatten()[nearest.long()]`` gathers.  Among several nearest targets the
+        smallest index is taken, so the result is unique; a target voxel's nearest target is itself.  abi.NEAREST_NONE (0xffffffff) where the
+        box holds no target or the squared distance is >= ``limit`` (None: unlimited).  ``weights``: None means (1, 1, 1); else as for
+        distance_transform(), and ``limit`` is in weighted units.  ``distance=True`` returns ``(nearest, dist2)``, dist2 being what
+        distance_transform(iso, to, limit, box, weights) gives.  scipy.ndimage.distance_transform_edt(return_indices=True) with unique ties.
+        No host wait."""
+        if to not in self._DISTANCE_TARGETS:
+            raise ValueError("Volume.nearest_target: `to` must be 'inside' or 'outside'")
+        if limit is not None and (int(limit) != limit or not 1 <= limit <= abi.DISTANCE_NONE):
+            raise ValueError("Volume.nearest_target: limit must be an integer in 1 .. 0xffffffff or None")
+        weights = self._as_weights("nearest_target", weights) or (1, 1, 1)
+        nearest, dist2 = self._nearest_target(self.volume, iso, self._DISTANCE_TARGETS[to], limit, _as_box(box), weights, distance)
+        return (nearest, dist2) if distance else nearest
+
+    def expand_labels(self, labels, iso, radius=None, radius2=None, box=None, weights=None, mask=None, mask_iso=None):
+        """Labels grown into their surroundings on the current stream (vkv_nearest_target, then vkv_propagate_labels): a new torch.uint32
+        tensor of the box's shape in which every voxel within the ball of an inside voxel (value >= ``iso``) holds the label of the NEAREST
+        inside voxel (the smallest index of equals), and 0 elsewhere: skimage.segmentation.expand_labels with unique ties.  ``labels``: the
+        labels of this volume's inside voxels at ``iso``, as label_components() returns them for the same ``box``.  ``radius`` / ``radius2``:
+        as for erode() (the call's limit is radius2 + 1); neither: unlimited, the Voronoi regions of the components.  ``weights``: as for
+        nearest_target().  ``mask``: an optional Volume of the same extent that confines the growth: voxels of it below ``mask_iso``
+        (None: ``iso``) get 0.  No host wait."""
+        box = _as_box(box)
+        self._check_labels("expand_labels", labels, box)
+        limit = None if radius is None and radius2 is None else self.ball_radius2(radius, radius2) + 1
+        weights = self._as_weights("expand_labels", weights) or (1, 1, 1)
+        if mask is not None and (mask.extent.as_tuple() != self.extent.as_tuple() or mask.volume.device != self.volume.device):
+            raise ValueError("Volume.expand_labels: `mask` must be a Volume of the same extent on the same device")
+        nearest, _ = self._nearest_target(self.volume, iso, abi.DISTANCE_TO_INSIDE, limit, box, weights)
+        return self._propagate_labels(nearest, labels, box, None if mask is None else mask.volume, iso if mask_iso is None else mask_iso)
+
+    def split_bodies(self, iso, radius=None, radius2=None, connectivity=6, box=None, weights=None):
+        """Touching bodies split at full size, on the current stream: ``(labels, counts)``.  erode() by the ball (``radius`` / ``radius2`` /
+        ``weights`` as there), label_components() of the eroded volume (``connectivity``), nearest_target() of the eroded volume, unlimited,
+        and vkv_propagate_labels with this volume as the mask at ``iso``: every inside voxel of THIS volume gets the label of the nearest
+        surviving core, 0 only where nothing survived anywhere in the box, and outside voxels get 0.  ``labels`` (torch.uint32, the box's
+        shape, values 0 .. K) and ``counts`` (label_components()'s, K first) go to component_stats() and select_components() unchanged, which
+        then measure and select the full-size bodies.  "Nearest" is EUCLIDEAN, not geodesic: a thin fragment that vanished whole takes the
+        label of a core across a gap, and a bridge is divided by the perpendicular bisector of the cores' surfaces, not by its waist.  The
+        volume is not touched.  No host wait: label_components() runs with sizes=False."""
+        box = _as_box(box)
+        weights = self._as_weights("split_bodies", weights)
+        eroded = Volume(self.ctx, self.name + ".eroded", device=self.device)
+        eroded.volume, eroded.extent = self.erode(iso, radius=radius, radius2=radius2, box=box, weights=weights), self.extent
+        core, _, counts = eroded.label_components(iso, connectivity=connectivity, box=box, sizes=False)
+        nearest, _ = eroded._nearest_target(eroded.volume, iso, abi.DISTANCE_TO_INSIDE, None, box, weights or (1, 1, 1))
+        return self._propagate_labels(nearest, core, box, self.volume, iso), counts
+
     def occupied_count_from_histogram(self, hist, d_count):
         """The occupied-voxel count of the current options' analytic transfer function read off ``hist`` (a histogram() result) into
         ``d_count`` (a one-element int64 CUDA tensor), on the current stream; equals vkv_occupied_voxel_count when the histogram was built
