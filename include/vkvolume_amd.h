@@ -1005,6 +1005,52 @@ int vkv_nearest_target(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent
 int vkv_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t *d_labels, uint32_t *d_out, VkvExtent3D extent,
                          const VkvBox *box, const uint8_t *d_mask_volume, float mask_iso, void *stream);
 
+/* ---- geodesic distance and label propagation inside the mask ---------------------------------------------------------------
+ * vkv_geodesic_propagate answers "how far is this voxel from a seed THROUGH the inside voxels, and from which seed": the geodesic distance map
+ * with chamfer step costs, and the labels that travel with it.  Every other distance of this header crosses walls; this one does not.
+ * The inside rule, "only the voxels of `box` exist" and the box-shaped arrays (x fastest) are those of vkv_label_components.
+ * Moves.  From an inside voxel to an inside voxel of the box at an offset (dx, dy, dz) in {-1, 0, 1}^3 other than 0.  The offset's class is
+ * m = |dx| + 2 |dy| + 4 |dz|, 1 .. 7, and the move costs steps[m - 1]; `steps` is a HOST pointer to seven integers, read during the call.  A
+ * cost of 0 means that this class of move does not exist.  Both ends inside is all a move needs: a diagonal move may pass between two outside
+ * voxels, so with every class present the mask's connectivity is VKV_CONNECT_26.  (1, 1, 0, 1, 0, 0, 0) counts 6-connected steps;
+ * (3, 3, 4, 3, 4, 4, 5) is the 3-4-5 chamfer (distances in thirds of a voxel); a table made from the voxel spacing gives a length.
+ * Seeds.  d_seeds (uint32, the box's shape): a non-zero value on an inside voxel makes it a seed with that value as its label; non-zero
+ * values on outside voxels are ignored.
+ * The result.  key(v) = the lexicographic minimum of (cost, seed label) over all paths of moves from a seed to v, the cost of a path being the
+ * sum of its moves': of all seeds at the least cost the SMALLEST LABEL wins, so the answer is unique.  v is REACHED iff that least cost is
+ * below `limit`; VKV_GEODESIC_NONE (0xffffffff) means unlimited, so a stored cost is at most 0xfffffffe; limit == 0 is invalid.  Costs are
+ * summed in 64 bits.  Either output may be NULL, not both; every element of a given output is written:
+ *   d_dist[v]   = the least cost, VKV_GEODESIC_NONE where v is not reached or outside,
+ *   d_labels[v] = that label, 0 where v is not reached or outside.
+ * Rounds.  The work is done in rounds, each one kernel over tiles of 8 x 8 x 8 voxels: a tile whose surroundings changed in the round before
+ * relaxes its voxels until nothing in it changes.  A body is settled after about as many rounds as the longest shortest path crosses tiles.
+ * resume == 0: the state is set up from d_seeds, then `rounds` rounds (1 .. VKV_GEODESIC_MAX_ROUNDS) run, then the outputs are written.
+ * resume == 1: d_seeds is not read and may be NULL; d_scratch holds the state an earlier call left for the same volume, box, iso, steps and
+ * limit (the caller's promise); the call runs `rounds` more rounds and writes the outputs again.
+ * d_counts (2 x uint64): d_counts[0] = 1 iff the last round that did any work left no tile to be relaxed again, i.e. the state is the fixed
+ * point, else 0; d_counts[1] = the reached voxels.  While d_counts[0] is 0 the outputs are upper bounds whose bytes are not specified; once it
+ * is 1 they are the definition's, further rounds cost an empty launch each and change nothing, and two runs give the same bytes.
+ * d_scratch: vkv_geodesic_scratch_bytes(extent, box) bytes, 8-byte aligned: 8 bytes per voxel of the box (cost and label, kept as ONE 64-bit
+ * value) + 32 + 8 per tile, the tiles being ceil(width / 8) ceil(height / 8) ceil(depth / 8) of the box; 0 for an extent or box this call
+ * rejects.  Between a call and the call that resumes it the block is the state and must be left alone.
+ * d_labels == d_seeds is allowed (labels grow in place); any other overlap among d_seeds, d_dist, d_labels (4 bytes per voxel of the box each)
+ * and the scratch block is VKV_E_INVALID_ARGUMENT.
+ * Kernels only (no allocation, no memset or copy node, no host wait; the host never reads a flag; the kernels use no scratch memory, and no
+ * lane waits for another wave or workgroup): after one direct call on `stream` it can be captured into a hipGraph.  Keys are exchanged
+ * between workgroups by relaxed 64-bit atomic loads and stores, the count is an integer atomic sum.  Nothing in the context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_volume,
+ * d_scratch, d_counts or steps, a null d_seeds with resume == 0, both outputs null, a zero extent, an empty box or one not inside `extent`, a
+ * non-finite iso, limit == 0, rounds == 0 or above VKV_GEODESIC_MAX_ROUNDS, a resume other than 0 and 1, seven steps of 0, a step above
+ * 65535, a d_seeds, d_dist or d_labels that is not 4-byte aligned, a d_counts or d_scratch that is not 8-byte aligned, the overlaps above.
+ * VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels.  d_volume may start at any byte; every extent is accepted, axes of length 1
+ * included; nothing outside any buffer is read or written. */
+#define VKV_GEODESIC_NONE 0xffffffffu
+#define VKV_GEODESIC_MAX_ROUNDS 1024
+size_t vkv_geodesic_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_geodesic_propagate(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint32_t *d_seeds,
+                           const uint32_t steps[7], uint32_t limit, uint32_t rounds, int32_t resume, void *d_scratch, uint32_t *d_dist,
+                           uint32_t *d_labels, uint64_t *d_counts, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

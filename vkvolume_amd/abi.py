@@ -146,6 +146,8 @@ CONNECT_6, CONNECT_14, CONNECT_26 = 6, 14, 26  # VKV_CONNECT_*: the neighbourhoo
 DISTANCE_TO_INSIDE, DISTANCE_TO_OUTSIDE = 0, 1  # VkvDistanceTarget: the target voxels of vkv_distance_transform
 DISTANCE_NONE = 0xffffffff  # VKV_DISTANCE_NONE: no limit
 NEAREST_NONE = 0xffffffff  # VKV_NEAREST_NONE: vkv_nearest_target found no target (within the limit)
+GEODESIC_NONE = 0xffffffff  # VKV_GEODESIC_NONE: vkv_geodesic_propagate did not reach the voxel; as a limit: unlimited
+GEODESIC_MAX_ROUNDS = 1024  # VKV_GEODESIC_MAX_ROUNDS: the rounds of one vkv_geodesic_propagate call
 
 
 class ComponentStats(C.Structure):

@@ -631,6 +631,63 @@ int vkv_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t
 	return launch_propagate_labels(ctx, d_nearest, d_labels, d_out, extent, b, d_mask_volume, mask_iso, (hipStream_t) stream);
 }
 
+size_t vkv_geodesic_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return geodesic_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written.  `steps` is read
+// here, on the host
+int vkv_geodesic_propagate(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint32_t *d_seeds,
+                           const uint32_t steps[7], uint32_t limit, uint32_t rounds, int32_t resume, void *d_scratch, uint32_t *d_dist, uint32_t *d_labels,
+                           uint64_t *d_counts, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (resume != 0 && resume != 1)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: resume %d is neither 0 nor 1", (int) resume);
+	if (resume)
+		d_seeds = nullptr;        // not read
+	if (!d_volume || !d_scratch || !d_counts || !steps || (!d_seeds && !resume) || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: null pointer or zero extent");
+	if (!d_dist && !d_labels)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: neither d_dist nor d_labels is given");
+	if (!std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: iso must be finite");
+	if (limit == 0u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: limit 0 (VKV_GEODESIC_NONE: unlimited)");
+	if (rounds == 0u || rounds > VKV_GEODESIC_MAX_ROUNDS)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: %u rounds (1 .. %d)", rounds, VKV_GEODESIC_MAX_ROUNDS);
+	uint32_t largest = 0;
+	for (int m = 0; m < 7; ++m)
+		largest = steps[m] > largest ? steps[m] : largest;
+	if (largest == 0u || largest > 65535u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: every step is 0, or a step is above 65535");
+	if (const int rc = check_box(ctx, "geodesic_propagate", extent, box))
+		return rc;
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || (((uintptr_t) d_seeds | (uintptr_t) d_dist | (uintptr_t) d_labels) & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: d_scratch and d_counts must be 8-byte aligned, d_seeds, d_dist and d_labels 4-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "geodesic_propagate: a box of more than 2^32 - 1 voxels");
+	const VkvBox b = whole_or(extent, box);
+	{        // the three arrays hold 4 bytes per voxel of the box; only d_labels == d_seeds may meet
+		const uint64_t array = 4ull * b.width * b.height * b.depth, block = geodesic_scratch_bytes(extent, box);
+		struct Range
+		{
+			uintptr_t p;
+			uint64_t  bytes;
+		} ranges[4] = {{(uintptr_t) d_seeds, array}, {(uintptr_t) d_dist, array}, {(uintptr_t) d_labels, array}, {(uintptr_t) d_scratch, block}};
+		for (int i = 0; i < 4; ++i)
+			for (int j = i + 1; j < 4; ++j)
+			{
+				const Range &lo = ranges[i].p <= ranges[j].p ? ranges[i] : ranges[j], &hi = ranges[i].p <= ranges[j].p ? ranges[j] : ranges[i];
+				if (!lo.p || !hi.p || hi.p - lo.p >= lo.bytes || (i == 0 && j == 2 && lo.p == hi.p))
+					continue;
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "geodesic_propagate: d_seeds, d_dist, d_labels and d_scratch overlap (only d_labels == d_seeds may)");
+			}
+	}
+	DeviceGuard guard(ctx->device);
+	return launch_geodesic_propagate(ctx, d_volume, extent, b, iso, d_seeds, steps, limit, rounds, resume != 0, d_scratch, d_dist, d_labels, d_counts,
+	                                 (hipStream_t) stream);
+}
+
 // every argument is checked before the launch (and before the device is touched)
 int vkv_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_dist2, uint32_t lo,
                            uint32_t hi, uint32_t fill, void *stream)

@@ -159,6 +159,14 @@ int launch_nearest_target(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, con
 int launch_propagate_labels(vkv_ctx *ctx, const uint32_t *d_nearest, const uint32_t *d_labels, uint32_t *d_out, VkvExtent3D e, const VkvBox &b,
                             const uint8_t *d_mask_vol, float mask_iso, hipStream_t s);
 
+// ---- geodesic.hip
+// vkv_geodesic_scratch_bytes (0 for an extent or box that is not accepted) and vkv_geodesic_propagate after the entry point's argument checks
+// (b inside e, components_launch_ok, steps and limit valid, rounds 1 .. VKV_GEODESIC_MAX_ROUNDS; d_seeds is not read on a resumed call)
+size_t geodesic_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+int launch_geodesic_propagate(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, const uint32_t *d_seeds, const uint32_t steps[7],
+                              uint32_t limit, uint32_t rounds, bool resume, void *d_scratch, uint32_t *d_dist, uint32_t *d_labels, uint64_t *d_counts,
+                              hipStream_t s);
+
 // ---- raymarch.hip
 // vkv_render /vkv_render_batch (n frames in one launch) after the entry point's argument checks
 int launch_render(vkv_ctx *ctx, const VkvRenderParams *P, const float *alpha_lut, hipStream_t s);

@@ -91,6 +91,8 @@ def _signatures():
         row(INT, "vkv_distance_transform_weighted", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, P(u32), u32, vp, vp, vp),
         row(INT, "vkv_nearest_target", vp, vp, abi.Extent3D, P(abi.Box), f32, i32, P(u32), u32, vp, vp, vp, vp),
         row(INT, "vkv_propagate_labels", vp, vp, vp, vp, abi.Extent3D, P(abi.Box), vp, f32, vp),
+        row(size, "vkv_geodesic_scratch_bytes", abi.Extent3D, P(abi.Box)),
+        row(INT, "vkv_geodesic_propagate", vp, vp, abi.Extent3D, P(abi.Box), f32, vp, P(u32), u32, u32, i32, vp, vp, vp, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -447,6 +449,20 @@ class Context:
         abi.NEAREST_NONE (or any value >= the box's voxels) or where voxel v of d_mask_volume (None: no mask) is below mask_iso; d_out
         overlaps neither input.  Returns the status code, as nearest_target_rc()."""
         return self._lib.vkv_propagate_labels(self.handle, d_nearest, d_labels, d_out, extent, box, d_mask_volume, mask_iso, stream)
+
+    def geodesic_propagate_rc(self, d_volume, extent, box, iso, d_seeds, steps, limit, rounds, resume, d_scratch, d_dist, d_labels, d_counts, stream=0):
+        """vkv_geodesic_propagate: the geodesic distance map of `box` through the inside voxels (>= iso) from the seeds (d_seeds, uint32, the
+        box's shape: non-zero = a seed with that label) with the move costs `steps` (seven integers, class |dx| + 2 |dy| + 4 |dz| - 1; 0: no
+        such move): d_dist = the least cost below `limit` (None or abi.GEODESIC_NONE: unlimited), abi.GEODESIC_NONE where not reached;
+        d_labels = the smallest label at that cost, 0 where not reached; either may be None.  `rounds` rounds (1 .. abi.GEODESIC_MAX_ROUNDS)
+        from the seeds (resume False) or from the state that an earlier call left in d_scratch (resume True; d_seeds may be None).  d_counts
+        (2 x uint64) = 1 once the state is the fixed point, the reached voxels.  d_scratch: geodesic.scratch_bytes(extent, box) bytes.
+        Returns the status code: there is no raising form (the public surface admits new names only as _rc), so callers write
+        ctx.check(ctx.geodesic_propagate_rc(...)).  steps None passes NULL and resume may be any integer (error-path tests)."""
+        return self._lib.vkv_geodesic_propagate(self.handle, d_volume, extent, box, iso, d_seeds,
+                                                None if steps is None else (C.c_uint32 * 7)(*(int(c) for c in steps)),
+                                                abi.GEODESIC_NONE if limit is None else int(limit), int(rounds), int(resume), d_scratch, d_dist, d_labels,
+                                                d_counts, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import abi, camera, lib
+from . import abi, camera, geodesic, lib
 
 
 def _ptr(t):
@@ -727,7 +727,66 @@ class Volume:
         nearest, _ = self._nearest_target(self.volume, iso, abi.DISTANCE_TO_INSIDE, limit, box, weights)
         return self._propagate_labels(nearest, labels, box, None if mask is None else mask.volume, iso if mask_iso is None else mask_iso)
 
-    def split_bodies(self, iso, radius=None, radius2=None, connectivity=6, box=None, weights=None):
+    def _geodesic_call(self, d_seeds, iso, steps, limit, box, rounds, resume, scratch, dist, labels, counts):
+        self.ctx.check(self.ctx.geodesic_propagate_rc(_ptr(self.volume), self.extent, box, iso, d_seeds, steps, limit, rounds, resume, _ptr(scratch), _ptr(dist),
+                                                      _ptr(labels), _ptr(counts), _stream()))
+
+    def geodesic_propagate(self, seeds, iso, steps=None, limit=None, box=None, rounds=None, distance=True):
+        """Geodesic distance and label propagation INSIDE the mask on the current stream (vkv_geodesic_propagate): ``(labels, dist, counts)``.
+        ``seeds``: a contiguous uint32 (or int32) tensor of the box's shape [depth, height, width]; a non-zero value on an inside voxel
+        (value >= ``iso``) makes it a seed with that label.  Paths run through inside voxels of the box only, a move to one of the 26
+        neighbours costing ``steps[|dx| + 2 |dy| + 4 |dz| - 1]`` (0: no such move; None: the 3-4-5 chamfer, distances in thirds of a voxel;
+        see geodesic.chamfer_steps()).  ``dist`` (torch.uint32, None with ``distance=False``): the least cost from a seed, abi.GEODESIC_NONE
+        where no seed is reached at a cost below ``limit`` (None: unlimited) and on outside voxels; ``labels`` (torch.uint32): the label of
+        the seed at that cost, the smallest of equals, 0 where not reached.  ``counts``: the call's int64 device tensor: 1 once the result is
+        final, and the reached voxels.  ``seeds`` is not written.
+        ``rounds``: an integer 1 .. abi.GEODESIC_MAX_ROUNDS makes exactly ONE call of that many rounds, without a host wait; the caller
+        reads ``counts[0]``, and while it is 0 the outputs are upper bounds only (a path needs about one round per 8 voxels of its length).
+        None: a call of 64 rounds, then resumed calls of 128, 256, ... rounds (at most abi.GEODESIC_MAX_ROUNDS each) until ``counts[0]``
+        is 1, which is read on the host between the calls: this is THE ONE HOST WAIT of the segmentation chain."""
+        box = _as_box(box)
+        self._check_labels("geodesic_propagate", seeds, box)
+        steps = geodesic.CHAMFER_345 if steps is None else tuple(int(c) for c in steps)
+        if len(steps) != 7:
+            raise ValueError("Volume.geodesic_propagate: steps must be seven integers")
+        if limit is not None and (int(limit) != limit or not 1 <= limit <= abi.GEODESIC_NONE):
+            raise ValueError("Volume.geodesic_propagate: limit must be an integer in 1 .. 0xffffffff or None")
+        if rounds is not None and (int(rounds) != rounds or not 1 <= rounds <= abi.GEODESIC_MAX_ROUNDS):
+            raise ValueError("Volume.geodesic_propagate: rounds must be an integer in 1 .. %d or None" % abi.GEODESIC_MAX_ROUNDS)
+        scratch = self._scratch(geodesic.scratch_bytes(self.extent, box),
+                                "Volume.geodesic_propagate: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
+        labels = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device)
+        dist = torch.empty(self._box_shape(box), dtype=torch.uint32, device=self.device) if distance else None
+        counts = torch.empty((2,), dtype=torch.int64, device=self.device)
+        n = 64 if rounds is None else int(rounds)
+        self._geodesic_call(_ptr(seeds), iso, steps, limit, box, n, False, scratch, dist, labels, counts)
+        while rounds is None and int(counts[0].item()) == 0:        # the host wait
+            n = min(2 * n, abi.GEODESIC_MAX_ROUNDS)
+            self._geodesic_call(None, iso, steps, limit, box, n, True, scratch, dist, labels, counts)
+        return labels, dist, counts
+
+    def grow_from_points(self, points, iso, steps=None, limit=None, box=None, rounds=None, distance=True):
+        """Seeded region growing with a reach limit (click to select): geodesic_propagate() from the voxels ``points``, a sequence of
+        (x, y, z) in volume coordinates, point i carrying the label i + 1 (of equal points the first).  A point on an outside voxel seeds
+        nothing; a point outside the box (or the volume) raises ValueError.  ``labels != 0`` is the part of the clicked bodies within
+        ``limit`` (in units of ``steps``; None: the whole bodies) of a point, each voxel with the label of the point it is reached from
+        most cheaply.  Everything else, the host wait of ``rounds=None`` included, as for geodesic_propagate()."""
+        box = _as_box(box)
+        d, h, w = self._box_shape(box)
+        x0, y0, z0 = (box.x0, box.y0, box.z0) if box is not None else (0, 0, 0)
+        first = {}
+        for k, point in enumerate(points):
+            x, y, z = (int(c) for c in point)
+            if not (x0 <= x < x0 + w and y0 <= y < y0 + h and z0 <= z < z0 + d):
+                raise ValueError("Volume.grow_from_points: point %d, %r, lies outside the box" % (k, (x, y, z)))
+            first.setdefault(((z - z0) * h + (y - y0)) * w + (x - x0), k + 1)
+        seeds = torch.zeros((d, h, w), dtype=torch.int32, device=self.device)
+        if first:
+            index = torch.tensor(sorted(first), dtype=torch.int64, device=self.device)
+            seeds.view(-1)[index] = torch.tensor([first[i] for i in sorted(first)], dtype=torch.int32, device=self.device)
+        return self.geodesic_propagate(seeds, iso, steps=steps, limit=limit, box=box, rounds=rounds, distance=distance)
+
+    def split_bodies(self, iso, radius=None, radius2=None, connectivity=6, box=None, weights=None, metric="euclidean"):
         """Touching bodies split at full size, on the current stream: ``(labels, counts)``.  erode() by the ball (``radius`` / ``radius2`` /
         ``weights`` as there), label_components() of the eroded volume (``connectivity``), nearest_target() of the eroded volume, unlimited,
         and vkv_propagate_labels with this volume as the mask at ``iso``: every inside voxel of THIS volume gets the label of the nearest
@@ -735,12 +794,21 @@ class Volume:
         shape, values 0 .. K) and ``counts`` (label_components()'s, K first) go to component_stats() and select_components() unchanged, which
         then measure and select the full-size bodies.  "Nearest" is EUCLIDEAN, not geodesic: a thin fragment that vanished whole takes the
         label of a core across a gap, and a bridge is divided by the perpendicular bisector of the cores' surfaces, not by its waist.  The
-        volume is not touched.  No host wait: label_components() runs with sizes=False."""
+        volume is not touched.  No host wait: label_components() runs with sizes=False.
+        ``metric="geodesic"`` closes that gap: the erosion and the cores as above, then geodesic_propagate() of the cores' labels through
+        THIS volume's inside voxels, unlimited, with the 3-4-5 chamfer (with ``weights``: geodesic.chamfer_steps(weights)): every inside
+        voxel gets the label of the core it reaches most cheaply through inside voxels (26-connected), the smallest label of equals, and
+        a voxel that reaches no core, such as a fragment across a gap, gets 0.  That call waits on the host for its rounds to settle."""
+        if metric not in ("euclidean", "geodesic"):
+            raise ValueError("Volume.split_bodies: metric must be 'euclidean' or 'geodesic'")
         box = _as_box(box)
         weights = self._as_weights("split_bodies", weights)
         eroded = Volume(self.ctx, self.name + ".eroded", device=self.device)
         eroded.volume, eroded.extent = self.erode(iso, radius=radius, radius2=radius2, box=box, weights=weights), self.extent
         core, _, counts = eroded.label_components(iso, connectivity=connectivity, box=box, sizes=False)
+        if metric == "geodesic":
+            steps = geodesic.chamfer_steps(weights)[0]
+            return self.geodesic_propagate(core, iso, steps=steps, box=box, distance=False)[0], counts
         nearest, _ = eroded._nearest_target(eroded.volume, iso, abi.DISTANCE_TO_INSIDE, None, box, weights or (1, 1, 1))
         return self._propagate_labels(nearest, core, box, self.volume, iso), counts
 
