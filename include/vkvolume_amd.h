@@ -1051,6 +1051,65 @@ int vkv_geodesic_propagate(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D ex
                            const uint32_t steps[7], uint32_t limit, uint32_t rounds, int32_t resume, void *d_scratch, uint32_t *d_dist,
                            uint32_t *d_labels, uint64_t *d_counts, void *stream);
 
+/* ---- label volumes as pictures: per-label colours, pick buffer, exact skipping ---------------------------------------------
+ * What vkv_label_components, vkv_propagate_labels, vkv_geodesic_propagate and the calls built on them produce is a uint32 label array of the
+ * shape of a box (x fastest; box == NULL: of the volume; at most 2^32 - 1 voxels).  These two calls show it: every body in its own colour,
+ * bodies switched off by a table entry, and the label under each pixel.
+ * Visible.  d_colors holds table_entries words of uint32; entry L - 1 belongs to label L (the convention of vkv_select_components_by_table);
+ * R is bits 0-7, G bits 8-15, B bits 16-23, A bits 24-31.  visible(L) iff 1 <= L <= table_entries and the A byte of d_colors[L - 1] is not 0.
+ * Alpha only switches a label on or off: a visible label is opaque.  Label 0 and every label the table does not name are never visible.
+ * Voxel of a texture-space point q, per axis: c = fma(q, (float) extent, -0.5f) (the samplers' own coordinate), v = clamp((int) floorf(c +
+ * 0.5f), 0, extent - 1).  label(q) = 0 if that voxel lies outside `box`, else d_labels[((z - z0) bh + (y - y0)) bw + (x - x0)].
+ *
+ * vkv_label_visibility_map: one byte per cell of map_extent, the geometry of vkv_max_map.  A cell holds 255 if any voxel of the cell's voxel
+ * box, grown by one voxel per side and clipped to the volume, lies in `box` and carries a visible label; otherwise, and past the volume, 0.
+ * Every cell is written.  The map depends on the labels and on the table: rebuild it after either changes.  Kernels only (one launch: no
+ * memset, no allocation, no host wait, no scratch block; the kernel uses no scratch memory), so after one direct call on `stream` it can be
+ * captured into a hipGraph.  Every argument is checked before anything is enqueued, and a rejected call writes nothing.
+ * VKV_E_INVALID_ARGUMENT: a null ctx, d_labels or d_map, a null d_colors with table_entries != 0, a d_labels or d_colors that is not 4-byte
+ * aligned, a zero extent, a map_extent that is not valid for it, an empty box or one not inside `extent`.  VKV_E_UNSUPPORTED: a box of more
+ * than 2^32 - 1 voxels, a map too large for one launch. */
+int vkv_label_visibility_map(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors,
+                             uint64_t table_entries, VkvExtent3D map_extent, uint8_t *d_map, void *stream);
+
+typedef struct VkvLabelRenderOptions
+{
+	const uint32_t *d_labels;         /* the labels of `box`, uint32, 4-byte aligned                                                              */
+	const VkvBox *  box;              /* HOST pointer, read during the call; NULL: the whole volume                                               */
+	const uint32_t *d_colors;         /* table_entries colour words, 4-byte aligned; may be NULL with table_entries == 0 (nothing is visible)     */
+	uint64_t        table_entries;
+	uint32_t        refine_steps;     /* 0 .. 16 bisection steps between samples k - 1 and k                                                      */
+	uint32_t        shade;            /* 0: the table's colour as it is (d_volume is not read and may be NULL); 1: lit by the isosurface's headlight */
+	float           ambient, diffuse, specular; /* finite, >= 0 (checked with shade == 0 too)                                                    */
+	uint32_t        shininess;        /* 1 .. 1024                                                                                                */
+	const uint8_t * d_visibility_map; /* vkv_label_visibility_map of d_labels, box and d_colors with params->map_extent, or NULL (dense)         */
+	uint32_t *      d_out_label;      /* the label under each pixel, indexed like the other outputs; 0 without a hit; or NULL: the pick buffer    */
+	float *         d_out_normal;     /* as VkvIsoOptions.d_out_normal; zeros with shade == 0; or NULL                                            */
+	uint32_t        flags;            /* must be 0 */
+} VkvLabelRenderOptions;
+
+/* The first visible label along each ray.  Rays, samples q_i = fma(i, s, e), clipping plane, options.depth_attachment with d_in_depth,
+ * sampling_factor, the tile schedules (whole image, rect, compact strided shares that assemble through vkv_scatter_tiles) and what is
+ * unsupported are vkv_render_isosurface's.  k = the first i with visible(label(q_i)).  t = 0 for k == 0, else the isosurface's bisection
+ * between k - 1 and k on the predicate visible(label(fma(mid, s, e))): hi = mid where it holds, else lo = mid; t = hi.  p = fma(t, s, e),
+ * L = label(p), visible by construction.  A pixel with a hit gets d_out_label = L, d_out_depth the first-hit depth of p, and base_c =
+ * (float) byte_c * kInv255 of d_colors[L - 1].  shade == 0: RGBA32F (base, 1), normal zeros; RGBA8 is then exactly the table's bytes with
+ * A = 255.  shade == 1: the normal n from the isosurface's tetrahedron gradient of d_volume (linear or packed: the same bits) at p, its
+ * headlight term L_light in its order of operations, RGBA32F (clamp(base L_light, 0, 1), 1), d_out_normal (n, 1).  RGBA8 is the
+ * round-to-nearest of the colour.  Every other pixel gets what the isosurface gives a pixel without a hit, and label 0.  d_out_counts (3 x
+ * u32 per pixel): samples looked up on the march, map bytes read, samples skipped; [0] + [2] is k + 1 on a hit and the ray's sample count
+ * without one (refinement and gradient taps are not counted).
+ * With d_visibility_map a ray jumps over the samples of a cell whose byte is 0: the results equal the dense path's bit for bit (a sample in
+ * the grown cell has its voxel in the grown box the byte covers: DESIGN.md §5.21).  A map built for other labels or another table breaks that.
+ * VKV_E_INVALID_ARGUMENT: null params or options, null d_labels, null d_colors with table_entries != 0, misaligned d_labels or d_colors, an
+ * empty box or one not inside volume_extent, shade > 1, shade == 1 without d_volume, flags != 0, refine_steps > 16, a negative or non-finite
+ * coefficient, shininess outside 1 .. 1024, a map without a valid map_extent, no output at all, and what vkv_render_isosurface rejects of the
+ * fields read.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels, blend_over_target, tiles.fill_outside, options.test != VKV_TEST_NONE.
+ * Every argument is checked before anything is enqueued: a rejected call writes nothing.  One kernel launch and nothing else (no scratch
+ * block, no table, no allocation, no host wait; the kernels use no scratch memory), so after one direct call on `stream` it can be captured
+ * into a hipGraph. */
+int vkv_render_labels(vkv_ctx *ctx, const VkvRenderParams *params, const VkvLabelRenderOptions *labels, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

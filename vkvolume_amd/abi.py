@@ -140,6 +140,17 @@ class IsoOptions(C.Structure):
                 ("specular", C.c_float), ("shininess", C.c_uint32), ("d_max_map", C.c_void_p), ("d_out_normal", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class LabelRenderOptions(C.Structure):
+    """VkvLabelRenderOptions (vkv_render_labels): the labels (uint32, the shape of ``box``; a NULL box: of the volume), the colour table
+    (entry L - 1: R | G << 8 | B << 16 | A << 24, alpha 0 hides the label), bisection steps, shade (0: the table's colour; 1: the
+    isosurface's headlight with ambient, diffuse, specular, shininess), optional visibility map (vkv_label_visibility_map), optional label
+    and normal outputs, flags (0).  ``box`` is a host pointer: assign ctypes.pointer(an abi.Box), which the structure keeps alive."""
+    _fields_ = [("d_labels", C.c_void_p), ("box", C.POINTER(Box)), ("d_colors", C.c_void_p), ("table_entries", C.c_uint64),
+                ("refine_steps", C.c_uint32), ("shade", C.c_uint32), ("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float),
+                ("shininess", C.c_uint32), ("d_visibility_map", C.c_void_p), ("d_out_label", C.c_void_p), ("d_out_normal", C.c_void_p),
+                ("flags", C.c_uint32)]
+
+
 SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2  # VkvSlabMode
 FILTER_BINOMIAL3, FILTER_MEDIAN3 = 0, 1  # VkvFilterKind
 CONNECT_6, CONNECT_14, CONNECT_26 = 6, 14, 26  # VKV_CONNECT_*: the neighbourhoods of vkv_label_components

@@ -1,7 +1,8 @@
-// direct_render.hpp — what the direct renderers share: the maximum-intensity projection (k_mip), the isosurface (k_iso, §5.10) and
-// the slab (k_slab, §5.11).  Device side: the deal of a launch's workgroups and lanes to pixels, the filtered intensity of one sample or of a
+// direct_render.hpp — what the direct renderers share: the maximum-intensity projection (k_mip), the isosurface (k_iso, §5.10),
+// the slab (k_slab, §5.11) and the label render (k_labels, §5.21).  Device side: the deal of a launch's workgroups and lanes to pixels, the
+// filtered intensity of one sample or of a
 // group of samples, the max map's geometry, the grown-cell test and the exact skip step over the per-cell max map (vkv_max_map), the first-hit
-// depth and the stores every kernel ends with.  Host side: the checks and the arguments of the three entry points.  k_mip keeps its own inline
+// depth and the stores every kernel ends with.  Host side: the checks and the arguments of their four entry points.  k_mip keeps its own inline
 // copy of the skip step: calling max_map_skip cost its skipping variant 1-2 % (§5.10).
 #pragma once
 
@@ -181,8 +182,9 @@ __device__ __forceinline__ int max_map_skip(const RayMarchArgs &A, const MaxMapG
 // the checks of the fields of P a MIP / isosurface call reads (`what`: the entry point's name in the messages), with the max map d_max_map
 // (or null) and `has_output`: an output of the call's own options is set; VKV_OK or the code (nothing is enqueued before they pass).
 // rays = false (vkv_render_slab): the call casts no rays, so it has no depth (options.depth_attachment and d_out_depth are unsupported) and
-// reads no sampling_factor
-int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, const uint8_t *d_max_map, bool has_output, bool rays = true)
+// reads no sampling_factor.  needs_volume = false (vkv_render_labels with shade == 0): the call reads no voxel, so d_volume may be null
+int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams *P, const uint8_t *d_max_map, bool has_output, bool rays = true,
+                           bool needs_volume = true)
 {
 	if (P->blend_over_target)
 		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: blend_over_target is not supported", what);
@@ -196,7 +198,7 @@ int check_first_hit_params(vkv_ctx *ctx, const char *what, const VkvRenderParams
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: options.depth_attachment needs d_in_depth", what);
 	if (!extent_ok(P->volume_extent) || P->image_width == 0 || P->image_height == 0)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: zero extent", what);
-	if (!P->d_volume)
+	if (needs_volume && !P->d_volume)
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null volume", what);
 	if (rays && !(P->transfer_function.sampling_factor > 0.0f))
 		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: sampling_factor must be positive", what);

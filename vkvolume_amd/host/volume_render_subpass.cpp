@@ -136,6 +136,17 @@ void VolumeRenderSubpass::draw_iso(const RenderTarget &target, const VkvIsoOptio
 		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_iso: ") + vkv_last_error(dc.ctx));
 }
 
+void VolumeRenderSubpass::draw_labels(const RenderTarget &target, const VkvLabelRenderOptions &labels, const VkvTileSchedule *tiles)
+{
+	Volume *volume = volumes.front();
+	if (labels.shade && !volume->get_packed_volume())
+		volume->pack(dc);
+	VkvRenderParams p = make_params(*volume, target, tiles, false);
+	p.options.test    = VKV_TEST_NONE;        // the test modes are the integrator's outputs (benchmark mode sets one)
+	if (vkv_render_labels(dc.ctx, &p, &labels, dc.stream) != VKV_OK)
+		throw std::runtime_error(std::string("VolumeRenderSubpass::draw_labels: ") + vkv_last_error(dc.ctx));
+}
+
 void VolumeRenderSubpass::draw_slab(const RenderTarget &target, const VkvSlabOptions &slab, bool skip, const VkvTileSchedule *tiles)
 {
 	Volume *volume = volumes.front();

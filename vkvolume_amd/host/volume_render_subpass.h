@@ -90,6 +90,12 @@ class VolumeRenderSubpass
 	// comes from the volume when skip is set: Volume::build_max_map first; the same bits as the dense path).
 	void draw_iso(const RenderTarget &target, const VkvIsoOptions &iso, bool skip = true, const VkvTileSchedule *tiles = nullptr);
 
+	// A label array of the first volume as a picture into `target` (vkv_render_labels): the first sample whose nearest voxel
+	// carries a label that the colour table shows, in that label's colour.  `labels` fills every field of VkvLabelRenderOptions as the call
+	// takes it: the labels, their box, the table, the shading, the label and normal outputs, and d_visibility_map (vkv_label_visibility_map of
+	// the same labels, box and table with the volume's map extent; null: dense, the same bits).  With shade == 0 the volume is not read.
+	void draw_labels(const RenderTarget &target, const VkvLabelRenderOptions &labels, const VkvTileSchedule *tiles = nullptr);
+
 	// Oblique slice or thick slab of the first volume into `target` (vkv_render_slab): no camera, `slab` gives the plane, the
 	// sample step, the mode and the grey window (every field of VkvSlabOptions but d_max_map, which comes from the volume when skip is set
 	// and the mode is VKV_SLAB_MAX: Volume::build_max_map first; the same bits as the dense path).  target.depth is not written.

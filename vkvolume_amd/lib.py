@@ -93,6 +93,8 @@ def _signatures():
         row(INT, "vkv_propagate_labels", vp, vp, vp, vp, abi.Extent3D, P(abi.Box), vp, f32, vp),
         row(size, "vkv_geodesic_scratch_bytes", abi.Extent3D, P(abi.Box)),
         row(INT, "vkv_geodesic_propagate", vp, vp, abi.Extent3D, P(abi.Box), f32, vp, P(u32), u32, u32, i32, vp, vp, vp, vp, vp),
+        row(INT, "vkv_label_visibility_map", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, abi.Extent3D, vp, vp),
+        row(INT, "vkv_render_labels", vp, P(abi.RenderParams), P(abi.LabelRenderOptions), vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -463,6 +465,18 @@ class Context:
                                                 None if steps is None else (C.c_uint32 * 7)(*(int(c) for c in steps)),
                                                 abi.GEODESIC_NONE if limit is None else int(limit), int(rounds), int(resume), d_scratch, d_dist, d_labels,
                                                 d_counts, stream)
+
+    def label_visibility_map_rc(self, d_labels, extent, box, d_colors, table_entries, map_extent, d_map, stream=0):
+        """vkv_label_visibility_map: per cell of map_extent 255 where a voxel of the cell grown by one voxel per side carries a visible label
+        (d_labels: uint32, the shape of `box`; None: of the volume; d_colors: table_entries colour words, entry L - 1 for label L, alpha 0
+        hides), else 0.  Returns the status code: there is no raising form (the public surface admits new names only as _rc), so callers
+        write ctx.check(ctx.label_visibility_map_rc(...))."""
+        return self._lib.vkv_label_visibility_map(self.handle, d_labels, extent, box, d_colors, int(table_entries), map_extent, d_map, stream)
+
+    def render_labels_rc(self, params, labels, stream=0):
+        """vkv_render_labels: the first visible label along each ray of params, coloured by its table entry, with the
+        abi.LabelRenderOptions `labels`.  Returns the status code, as label_visibility_map_rc()."""
+        return self._lib.vkv_render_labels(self.handle, params, labels, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

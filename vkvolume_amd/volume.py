@@ -112,6 +112,7 @@ class Volume:
         self.extent = self.map_extent = None
         self.cell_summary = None  # vkv_cell_summary of the current volume (build_cell_summary), kept current by update_region
         self.max_map = None  # vkv_max_map of the current volume (build_max_map), kept current by update_region
+        self.label_visibility_map = None  # vkv_label_visibility_map of the labels and table last given to build_label_visibility_map
 
     # -- load_from_file's device half (src/volume_component.cpp:55-153): take voxels, allocate images --
     def load_from_array(self, voxels_dhw, distance_map_block_size=4, image_transform=None):
@@ -135,7 +136,7 @@ class Volume:
         self.gradient_valid = False  # set by ComputeGradientMap.compute; the packed image must not be built from an empty map
         self.transfer_function = torch.zeros((256, 256, 4), dtype=torch.uint8, device=self.device)
         self.transfer_function_bits = torch.zeros(abi.TF_BITS_WORDS, dtype=torch.int32, device=self.device)
-        self.packed = self.cell_summary = self.max_map = None
+        self.packed = self.cell_summary = self.max_map = self.label_visibility_map = None
         self.distance_map_swap = torch.empty((self.map_extent.depth, self.map_extent.height, self.map_extent.width),
                                              dtype=torch.uint8, device=self.device)
         self.distance_maps = []
@@ -239,6 +240,29 @@ class Volume:
             self.max_map = torch.empty((me.depth, me.height, me.width), dtype=torch.uint8, device=self.device)
         self.ctx.max_map(_ptr(self.volume), self.extent, self.map_extent, box, _ptr(self.max_map), _stream())
         return self.max_map
+
+    def _check_colors(self, name, colors):
+        """`colors` of <name>: a contiguous one-dimensional uint32 (or int32) tensor on the volume's device, one word per label"""
+        if colors.dtype not in (torch.uint32, torch.int32) or colors.dim() != 1 or not colors.is_contiguous() or colors.device != self.volume.device:
+            raise ValueError("%s: `colors` must be a contiguous one-dimensional uint32 tensor on %s" % (name, self.volume.device))
+
+    def build_label_visibility_map(self, labels, colors, box=None):
+        """The skipping map of VolumeRenderSubpass.draw_labels (vkv_label_visibility_map) on the current stream: per occupancy cell 255
+        where a voxel of the cell grown by one voxel per side carries a label that ``colors`` shows, else 0.  ``labels``: as returned by
+        label_components() for the same ``box`` (any contiguous uint32 device tensor of the box's shape does); ``colors``: a uint32 device
+        tensor, entry L - 1 the R | G << 8 | B << 16 | A << 24 word of label L, alpha 0 hides the label (labels.color_table makes one).
+        The (map depth, height, width) uint8 buffer is allocated at the first call and kept in ``label_visibility_map``; it belongs to these
+        labels and this table, so call again after either changes.  No host wait."""
+        box = _as_box(box)
+        self._check_labels("build_label_visibility_map", labels, box)
+        self._check_colors("Volume.build_label_visibility_map", colors)
+        if self.label_visibility_map is None:
+            me = self.map_extent
+            self.label_visibility_map = torch.empty((me.depth, me.height, me.width), dtype=torch.uint8, device=self.device)
+        n = colors.numel()
+        self.ctx.check(self.ctx.label_visibility_map_rc(_ptr(labels), self.extent, box, _ptr(colors) if n else None, n, self.map_extent,
+                                                        _ptr(self.label_visibility_map), _stream()))
+        return self.label_visibility_map
 
     def update_transfer_function_from_summary(self, skipping_type, d_count=None, histogram=None, d_unresolved=None):
         """update_transfer_function() with the occupancy map decided from the cell summaries (vkv_update_transfer_function_from_summary):
@@ -947,6 +971,50 @@ class VolumeRenderSubpass:
                               ambient=float(ambient), diffuse=float(diffuse), specular=float(specular), shininess=int(shininess),
                               d_max_map=_ptr(max_map), d_out_normal=_ptr(normal), flags=0)
         self.ctx.render_isosurface(params, opts, _stream())
+
+    def draw_labels(self, params, labels, colors, box=None, refine_steps=4, shade=True, ambient=0.1, diffuse=0.8, specular=0.3, shininess=32,
+                    color=None, rgba8=None, label=None, depth=None, normal=None, counts=None, skip=True, in_depth=None):
+        """A label volume as a picture (vkv_render_labels) of ``params``' rays into the given buffers: the first sample whose nearest voxel
+        carries a label that ``colors`` shows, refined by ``refine_steps`` bisection steps, in that label's colour.  ``labels``, ``colors``,
+        ``box``: as for Volume.build_label_visibility_map().  ``shade``: light the colour by draw_iso's headlight on the volume's gradient
+        at the hit (``normal`` then receives the normal); False: the table's colour as it is, and the volume is not read.  ``label``: a
+        uint32 (or int32) tensor, one element per pixel: the label under the pixel, 0 where nothing is hit (the pick buffer).  ``skip``:
+        jump over the cells of the volume's label visibility map (build_label_visibility_map() with the same labels, box and colors first;
+        the same bits as the dense path); False: look every sample up.  ``in_depth``: scene depth for options.depth_attachment."""
+        box = _as_box(box)
+        self.volume._check_labels("draw_labels", labels, box)
+        self.volume._check_colors("VolumeRenderSubpass.draw_labels", colors)
+        vis = None
+        if skip:
+            vis = self.volume.label_visibility_map
+            if vis is None:
+                raise RuntimeError("VolumeRenderSubpass.draw_labels: skip=True needs the label visibility map "
+                                   "(call Volume.build_label_visibility_map first)")
+        self._bind_outputs(params, color, rgba8, counts, depth, in_depth)
+        n = colors.numel()
+        opts = abi.LabelRenderOptions(d_labels=_ptr(labels), box=None if box is None else C.pointer(box), d_colors=_ptr(colors) if n else None,
+                                      table_entries=n, refine_steps=int(refine_steps), shade=1 if shade else 0, ambient=float(ambient),
+                                      diffuse=float(diffuse), specular=float(specular), shininess=int(shininess), d_visibility_map=_ptr(vis),
+                                      d_out_label=_ptr(label), d_out_normal=_ptr(normal), flags=0)
+        self.ctx.check(self.ctx.render_labels_rc(params, opts, _stream()))
+
+    def pick(self, params, labels, colors, x, y, box=None):
+        """The label under pixel (x, y) of ``params``' frame and its depth: ``(label, depth)``, (0, 0.0) where the ray hits nothing visible.
+        Renders the one 16x16 tile that holds the pixel through a rect schedule, dense and unshaded, with draw_labels' default refinement
+        and without the scene depth (options.depth_attachment is ignored), and reads the pixel back: ONE host wait."""
+        w, h = params.image_width, params.image_height
+        if not (0 <= x < w and 0 <= y < h):
+            raise ValueError("VolumeRenderSubpass.pick: pixel (%d, %d) outside the %dx%d frame" % (x, y, w, h))
+        p = abi.RenderParams.from_buffer_copy(params)
+        p.options.depth_attachment = 0
+        p.tiles = abi.full_frame_tiles(w, h, compact=True, rect=abi.TileRect(x // 16, y // 16, 1, 1))
+        dev = self.volume.device
+        label = torch.empty((256,), dtype=torch.uint32, device=dev)
+        depth = torch.empty((256,), dtype=torch.float32, device=dev)
+        self.draw_labels(p, labels, colors, box=box, shade=False, label=label, depth=depth, skip=False)
+        at = (y % 16) * 16 + x % 16
+        both = torch.stack([label.view(torch.int32)[at].to(torch.float64), depth[at].to(torch.float64)]).cpu()
+        return int(both[0].item()) & 0xffffffff, float(both[1].item())
 
     def draw_slab(self, params, plane, samples=1, mode=abi.SLAB_MAX, window=(0.0, 1.0), skip=True, color=None, rgba8=None, value=None, counts=None):
         """Oblique slice or thick slab (vkv_render_slab) into the given buffers.  ``plane``: (origin, du, dv, dn) in texture coordinates, or
