@@ -1110,6 +1110,50 @@ typedef struct VkvLabelRenderOptions
  * into a hipGraph. */
 int vkv_render_labels(vkv_ctx *ctx, const VkvRenderParams *params, const VkvLabelRenderOptions *labels, void *stream);
 
+/* ---- label volumes as meshes: one closed surface per visible body -----------------------------------------------------------
+ * vkv_label_mesh: the surfaces of the visible bodies of a label array as a triangle list in a defined order, with one uint32 label per
+ * triangle.  Everything not restated here is vkv_isosurface_mesh's: the cubes whose eight voxels lie in `box`, the corner numbering, the six
+ * tetrahedra in their order and their local vertices, the triangles of a mask m and the winding swap (odd tetrahedron XOR m in {2, 5, 8, 10,
+ * 11, 14}), the coordinates, the order by cube (x fastest, then y, then z) and then tetrahedron, 9 floats per triangle.
+ * Labels.  d_labels has the shape of `box` (x fastest; box == NULL: of the volume), 4-byte aligned.  visible(L) is vkv_render_labels' rule:
+ * 1 <= L <= table_entries and the A byte of d_colors[L - 1] is not 0.  For this call only, d_colors == NULL with table_entries == 0 means
+ * "every non-zero label is visible" (a table that shows nothing would give an empty mesh).
+ * Per tetrahedron.  Walk its local vertices 0 .. 3.  Each visible label L that has not appeared at a lower local vertex of this tetrahedron
+ * starts a group, so the groups are ordered by the first local vertex that carries L.  For each group, bit i of m is set if local vertex i
+ * carries exactly L; the triangles of case m are emitted with the isosurface's winding ("inside" = "carries L"), each tagged L in
+ * d_triangle_labels.  Hidden and zero labels start no group and are outside for every group.  A tetrahedron gives at most 4 triangles (label
+ * patterns 1+1+1+1, 2+1+1 and 2+2 give 4; 3+1 gives 2), a cube at most 24.
+ * Vertex on an edge (i, j) of local vertices: a = the voxel of the lower local index, b = the other; it depends on the edge alone, never on
+ * L.  If d_volume is not NULL and (f_a >= iso) != (f_b >= iso), t = (iso - f_a) / (f_b - f_a), exactly the isosurface's operations (f =
+ * (float) byte * kInv255); otherwise t = 0.5f.  Component c is (float) a_c + t where b differs from a, else (float) a_c.  iso is ignored
+ * when d_volume is NULL.
+ * Consequences.  Two bodies that touch share bit-equal vertices on their interface, and the triangles of each label are watertight under
+ * exact comparison wherever the body does not touch a face of the box.  If label != 0 exactly where a voxel is inside, the outer surface has
+ * the isosurface's own vertices.  For the labels of vkv_label_components(.., VKV_CONNECT_14) at `iso`, with d_volume and the same iso, the
+ * triangle list equals vkv_isosurface_mesh's bit for bit, in the same order, with the same total (every tetrahedron edge is a 14-neighbour
+ * pair, so the inside corners of a tetrahedron share one label): d_triangle_labels is then the split of that mesh by body.
+ * d_counts[0] = the exact total, d_counts[1] = min(total, capacity_triangles).  Exactly the first d_counts[1] triangles and their labels are
+ * written, and not one element beyond.  capacity_triangles == 0 is the counting call: d_triangles and d_triangle_labels may be NULL and no
+ * emit is enqueued.  d_scratch: vkv_label_mesh_scratch_bytes(extent, box) bytes (at least 16, a multiple of 8; 0 for an extent or box the
+ * call rejects), 8-byte aligned, contents undefined afterwards.
+ * d_visibility_map (NULL: dense) is vkv_label_visibility_map of the same labels, box and table, with map_extent: a tile of cubes whose
+ * cells all hold 0 is counted empty without reading a label, and gives the same bits (a cube whose origin lies in a cell has its eight
+ * voxels in that cell grown by one).  With d_colors == NULL a map is rejected: no table it could have been built from means "all visible".
+ * Kernels only (count, two scans, emit: no allocation, memset or copy node, no host wait, no atomics; the kernels use no scratch memory), so
+ * after one direct call on `stream` it can be captured into a hipGraph; two runs give the same bytes; nothing in the context is written.
+ * Every argument is checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_labels,
+ * d_scratch or d_counts, a zero extent, an empty box or one not inside `extent`, a non-finite iso with a d_volume, a null d_colors with
+ * table_entries != 0, a non-zero capacity with a null d_triangles or d_triangle_labels, a map with a null d_colors or without a valid
+ * map_extent, a d_labels, d_colors, d_triangles or d_triangle_labels that is not 4-byte aligned, a d_scratch or d_counts that is not 8-byte
+ * aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels, or one too large for the launches.  Every extent is accepted, widths
+ * below 4 and axes of length 1 included; d_volume may start at any byte; nothing outside any buffer is read or written.
+ * Not here: the faces of the box stay open, as the isosurface mesh's do, so a body that touches a face is open there (clear the border
+ * first, or pass labels with a box one voxel larger); there is no indexed variant and there are no normals. */
+size_t vkv_label_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors, uint64_t table_entries,
+                   const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
+                   float *d_triangles, uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
+
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`
  * (kind = 1 | shells << 8 | thickness << 16 | noise << 28): only the first `shells` (1 .. 39; 0 = all 40) of the seed's shells, their

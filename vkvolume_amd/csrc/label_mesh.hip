@@ -1,0 +1,446 @@
+// label_mesh.hip — the surfaces of the visible bodies of a uint32 label array as a triangle list with one label per triangle (vkv_label_mesh,
+// DESIGN.md §5.22): marching tetrahedra on the Kuhn decomposition of every cube, each tetrahedron cut once per visible label it touches, in a
+// defined order, with an exact total and a prefix under a capacity.  Dword streaming; no MFMA.
+//
+// The steps are mesh.hip's, and so are the tile geometry, the plan and the entry layout (mesh_common.hpp, read here and not changed):
+//   k_lmesh_count  a lane owns four x-adjacent cubes of one row and marches along z; a wave is 256 cubes of one row, a workgroup four rows and
+//                  kMeshSegment slices.  Per slice a lane loads its four labels of its two rows as one 16-byte load each, takes label x + 4
+//                  from the lane above and keeps the previous slice's two rows in registers.  Twenty equal labels end the lane's slice; a cube
+//                  of eight equal labels gives nothing; otherwise the table is looked up once per distinct label of the cube (a hidden label
+//                  becomes 0: it starts no group and is outside for every group), a cube with ONE visible label takes the isosurface's corner
+//                  mask and its 256 triangle counts, and only the rest walks its six tetrahedra.  The wave's sum goes to the entry of its 256
+//                  cubes.  With a visibility map a workgroup whose cells all hold 0 writes zeros without reading a label.
+//   k_lmesh_scan_* fixed_scan.hpp's two scans; the second writes d_counts.
+//   k_lmesh_emit   a wave whose entries are all zero, or all start at or past the capacity, leaves at once; for every other entry it loads the
+//                  two slices again, prefixes its lanes' counts and walks cube, tetrahedron, group (only the local vertices that start one:
+//                  trying all four cost 2.2 x the whole call) and triangle, storing the triangles and
+//                  labels whose index is below the capacity.  The byte volume is read here only, by the waves and in the slices that emit:
+//                  a dword per lane and row, asked for together with the labels.
+// No kernel uses scratch memory or atomics (tests/test_label_mesh_cpu.py reads the listing).
+#include <algorithm>
+
+#include "launchers.hpp"
+#include "mesh_common.hpp"
+#include "mtet_table.hpp"
+#include "row_loads.hpp"
+
+using namespace vkv;
+
+__constant__ MtetTable d_lmtet = kMtetTable;
+
+namespace
+{
+
+struct LabelGeom
+{
+	MeshGeom        G;             // the box's cubes, the tiles and the visibility map (thr = 1: a byte of 255 passes, 0 does not); vol may be null
+	const uint32_t *labels;        // the box's shape, x fastest
+	const uint32_t *colors;        // entry L - 1: A in bits 24 .. 31; null: every non-zero label is visible
+	uint32_t        entries;       // min(table_entries, 2^32 - 1)
+	int             bw, bh;        // the labels' row and slice: the box's width and height
+};
+
+// What a lane holds of one row of labels: x .. x + 3 (zero past the row's end) and x + 4, the first label of the lane above (wave_shl:1;
+// every lane of the wave takes part), in the wave's last lane a dword load.  WIDE (bw >= 4): one 16-byte load at min(x, bw - 4), at any
+// 4-byte alignment, shifted down where it was moved; narrower rows gather.  Nothing outside the row is read; what is not a label of the row
+// only reaches cubes that are not counted.
+struct Lab5
+{
+	uint32_t v[5];
+};
+
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+template <bool WIDE>
+__device__ __forceinline__ Lab5 lab5(const uint32_t *row, int x, int bw, uint32_t lane)
+{
+	Lab5 r;
+	if (WIDE)
+	{
+		const u32x4_a4 q = *reinterpret_cast<const u32x4_a4 *>(row + min(x, bw - 4));
+		r.v[0] = q.x, r.v[1] = q.y, r.v[2] = q.z, r.v[3] = q.w;
+		const int over = x + 4 - bw;
+#pragma unroll
+		for (int s = 1; s <= 4; ++s)
+			if (over >= s)
+				r.v[0] = r.v[1], r.v[1] = r.v[2], r.v[2] = r.v[3], r.v[3] = 0u;
+	}
+	else
+	{
+#pragma unroll
+		for (int i = 0; i < 4; ++i)
+			r.v[i] = x + i < bw ? row[x + i] : 0u;
+	}
+	r.v[4] = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) r.v[0], 0x130, 0xf, 0xf, false);        // wave_shl:1
+	if (lane == 63)
+		r.v[4] = row[min(x + 4, bw - 1)];
+	return r;
+}
+
+// the rows of a cube's corners: slice * 2 + row, so that corner j of the lane's cube i is label i + (j & 1) of row j >> 1
+struct CubeRows
+{
+	Lab5 r[4];
+};
+
+// the eight labels with the hidden ones replaced by 0.  The table is read once per distinct label, at the label's first corner, and every
+// read is issued before the first word is looked at
+__device__ __forceinline__ void shown8(const LabelGeom &A, const uint32_t c[8], uint32_t E[8])
+{
+	if (!A.colors)
+	{
+#pragma unroll
+		for (int j = 0; j < 8; ++j)
+			E[j] = c[j];
+		return;
+	}
+	uint32_t word[8];
+#pragma unroll
+	for (int j = 0; j < 8; ++j)
+	{
+		bool first = c[j] - 1u < A.entries;        // label 0 gives 2^32 - 1, which no table names
+#pragma unroll
+		for (int k = 0; k < j; ++k)
+			first = first && c[k] != c[j];
+		word[j] = 0u;
+		if (first)
+			word[j] = A.colors[c[j] - 1u];
+	}
+#pragma unroll
+	for (int j = 0; j < 8; ++j)
+	{
+		uint32_t w = word[j];        // the word of the label's first corner: the others hold 0
+#pragma unroll
+		for (int k = 0; k < j; ++k)
+			w |= c[k] == c[j] ? word[k] : 0u;
+		E[j] = (w >> 24) != 0u ? c[j] : 0u;
+	}
+}
+
+// the triangles of a group of pc local vertices
+__device__ __forceinline__ uint32_t group_triangles(uint32_t pc) { return pc == 2u ? 2u : pc == 4u ? 0u : 1u; }
+
+// the triangles of a tetrahedron with the (shown) labels l0 .. l3 at its local vertices
+__device__ __forceinline__ uint32_t tet_count(uint32_t l0, uint32_t l1, uint32_t l2, uint32_t l3)
+{
+	uint32_t n = 0;
+	if (l0 != 0u)
+		n += group_triangles(1u + (l1 == l0) + (l2 == l0) + (l3 == l0));
+	if (l1 != 0u && l1 != l0)
+		n += group_triangles(1u + (l2 == l1) + (l3 == l1));
+	if (l2 != 0u && l2 != l0 && l2 != l1)
+		n += group_triangles(1u + (l3 == l2));
+	if (l3 != 0u && l3 != l0 && l3 != l1 && l3 != l2)
+		n += 1u;
+	return n;
+}
+
+// the triangles of the cube with the labels c; lut: mtet_table.hpp's count by corner mask
+__device__ __forceinline__ uint32_t cube_count(const LabelGeom &A, const uint8_t *lut, const uint32_t c[8])
+{
+	uint32_t dif = 0;
+#pragma unroll
+	for (int j = 1; j < 8; ++j)
+		dif |= c[j] ^ c[0];
+	if (dif == 0u)
+		return 0u;
+	uint32_t E[8];
+	shown8(A, c, E);
+	uint32_t top = 0;
+#pragma unroll
+	for (int j = 0; j < 8; ++j)
+		top = max(top, E[j]);
+	if (top == 0u)
+		return 0u;
+	uint32_t cm  = 0;
+	bool     one = true;
+#pragma unroll
+	for (int j = 0; j < 8; ++j)
+	{
+		cm |= (E[j] != 0u ? 1u : 0u) << j;
+		one = one && (E[j] == 0u || E[j] == top);
+	}
+	if (one)        // one visible label: the isosurface's cube
+		return lut[cm];
+	uint32_t n = 0;
+#pragma unroll
+	for (int t = 0; t < 6; ++t)
+		n += tet_count(E[0], E[kMtetCorners[t][1]], E[kMtetCorners[t][2]], E[7]);
+	return n;
+}
+
+// the triangles of the lane's first nvalid cubes
+__device__ __forceinline__ uint32_t lane_count(const LabelGeom &A, const uint8_t *lut, const CubeRows &R, int nvalid)
+{
+	uint32_t dif = 0;
+#pragma unroll
+	for (int j = 0; j < 4; ++j)
+#pragma unroll
+		for (int i = 0; i < 5; ++i)
+			dif |= R.r[j].v[i] ^ R.r[0].v[0];
+	if (dif == 0u)
+		return 0u;
+	uint32_t n = 0;
+#pragma unroll
+	for (int i = 0; i < 4; ++i)
+		if (i < nvalid)
+		{
+			uint32_t c[8];
+#pragma unroll
+			for (int j = 0; j < 8; ++j)
+				c[j] = R.r[j >> 1].v[i + (j & 1)];
+			n += cube_count(A, lut, c);
+		}
+	return n;
+}
+
+__device__ __forceinline__ uint32_t sel4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, int i) { return i == 0 ? a : i == 1 ? b : i == 2 ? c : d; }
+
+// the five voxels x .. x + 4 of a row of the volume as one 64-bit value (zero past the row's end): a dword at any alignment and, as in lab5(),
+// the first byte of the lane above (every lane of the wave takes part), in the wave's last lane a byte load.  Nothing outside the row is read
+__device__ __forceinline__ uint64_t bytes5(const uint8_t *row, int x, int W, uint32_t lane)
+{
+	const uint32_t d = x < W ? load4_clipped(row, x, W) : 0u;
+	uint32_t       e = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) d, 0x130, 0xf, 0xf, false) & 0xffu;        // wave_shl:1
+	if (lane == 63)
+		e = row[min(x + 4, W - 1)];
+	return (uint64_t) d | (uint64_t) e << 32;
+}
+
+// the vertex on the edge `code` = a | b << 3 of the cube with origin (cx, cy, cz) in the volume: from a towards b, halfway unless the volume
+// (cb: the cube's eight bytes, corner j in byte j; read with a volume only) crosses iso between them
+__device__ __forceinline__ void label_edge_vertex(bool with_volume, uint64_t cb, uint32_t code, int cx, int cy, int cz, float iso, float *out)
+{
+	const uint32_t a = code & 7u, b = code >> 3, dif = a ^ b;
+	float          t = 0.5f;
+	if (with_volume)
+	{
+		const float fa = (float) ((uint32_t) (cb >> (8u * a)) & 0xffu) * kInv255, fb = (float) ((uint32_t) (cb >> (8u * b)) & 0xffu) * kInv255;
+		if ((fa >= iso) != (fb >= iso))
+			t = (iso - fa) / (fb - fa);
+	}
+	const float ax = (float) (cx + (int) (a & 1u)), ay = (float) (cy + (int) ((a >> 1) & 1u)), az = (float) (cz + (int) (a >> 2));
+	out[0] = (dif & 1u) ? ax + t : ax;
+	out[1] = (dif & 2u) ? ay + t : ay;
+	out[2] = (dif & 4u) ? az + t : az;
+}
+
+}        // namespace
+
+template <bool WIDE>
+__global__ void __launch_bounds__(256) k_lmesh_count(LabelGeom A, uint32_t *__restrict__ counts)
+{
+	__shared__ uint8_t lut[256];
+	const MeshGeom &   G    = A.G;
+	const MeshTile     T    = mesh_tile(G, G.ny, G.nz);
+	const uint32_t     lane = threadIdx.x & 63u;
+	if (G.mm.map && tile_is_empty(G, T, G.nx, G.ny))
+	{
+		if (threadIdx.x < 4 * kMeshSegment)
+		{
+			const int yc = T.yc - (int) (threadIdx.x >> 6) + (int) (threadIdx.x & 3u), zc = T.zc0 + (int) (threadIdx.x >> 2);
+			if (yc < G.ny && zc < T.zc1)
+				counts[((uint32_t) zc * (uint32_t) G.ny + (uint32_t) yc) * G.segs_x + T.xs] = 0u;
+		}
+		return;
+	}
+	lut[threadIdx.x] = d_lmtet.count[threadIdx.x];
+	__syncthreads();
+	if (T.yc >= G.ny)        // whole waves only: the lanes exchange labels below
+		return;
+	const int    nvalid = min(max(G.nx - T.xc, 0), 4);
+	const size_t plane = (size_t) A.bh * (size_t) A.bw, row = (size_t) T.yc * (size_t) A.bw;
+	auto         load  = [&](int zc, Lab5 &a, Lab5 &b) {
+        const uint32_t *base = A.labels + (size_t) zc * plane + row;
+        a = lab5<WIDE>(base, T.xc, A.bw, lane), b = lab5<WIDE>(base + A.bw, T.xc, A.bw, lane);
+	};
+	CubeRows R;
+	Lab5     na, nb;
+	load(T.zc0, R.r[0], R.r[1]);
+	load(T.zc0 + 1, na, nb);
+	uint32_t e = T.e0;
+	for (int zc = T.zc0; zc < T.zc1; ++zc, e += T.e_step)
+	{
+		R.r[2] = na, R.r[3] = nb;
+		if (zc + 1 < T.zc1)        // wave-uniform; slice zc + 2 <= nz is a slice of the box
+			load(zc + 2, na, nb);
+		const uint32_t n = wave_sum(lane_count(A, lut, R, nvalid));
+		if (lane == 0)
+			counts[e] = n;
+		R.r[0] = R.r[2], R.r[1] = R.r[3];
+	}
+}
+
+__global__ void __launch_bounds__(256) k_lmesh_scan_chunks(const uint32_t *__restrict__ counts, uint32_t *__restrict__ local, uint64_t *__restrict__ sums,
+                                                           uint32_t n_entries)
+{
+	scan_chunk(counts, local, sums, n_entries);
+}
+
+__global__ void __launch_bounds__(256) k_lmesh_scan_total(uint64_t *__restrict__ sums, uint32_t n_chunks, uint64_t capacity, uint64_t *__restrict__ d_counts)
+{
+	scan_total(sums, n_chunks, capacity, d_counts);
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ local,
+                                                    const uint64_t *__restrict__ chunk_before, float iso, float *__restrict__ triangles,
+                                                    uint32_t *__restrict__ triangle_labels, uint64_t capacity)
+{
+	__shared__ MtetTable tab;
+	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
+	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&d_lmtet)[threadIdx.x];
+	__syncthreads();
+	const MeshGeom &G    = A.G;
+	const MeshTile  T    = mesh_tile(G, G.ny, G.nz);
+	const uint32_t  lane = threadIdx.x & 63u;
+	if (T.yc >= G.ny)        // whole waves only; there is no barrier below
+		return;
+	// the wave's entries, one per lane: those with triangles that start below the capacity
+	uint64_t start = 0;
+	bool     work  = false;
+	if (T.zc0 + (int) lane < T.zc1)
+	{
+		const uint32_t e = T.e0 + lane * T.e_step;
+		start            = chunk_before[e / kScanChunk] + local[e];
+		work             = counts[e] != 0u && start < capacity;
+	}
+	uint64_t todo = __ballot(work);
+	if (todo == 0)
+		return;
+	const int    nvalid = min(max(G.nx - T.xc, 0), 4);
+	const size_t plane = (size_t) A.bh * (size_t) A.bw, row = (size_t) T.yc * (size_t) A.bw;
+	while (todo)        // wave-uniform
+	{
+		const int k = __ffsll((long long) todo) - 1;
+		todo &= todo - 1;
+		const int       zc = T.zc0 + k;
+		const uint32_t  lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint32_t *base = A.labels + (size_t) zc * plane + row;
+		CubeRows        R;
+		R.r[0] = lab5<WIDE>(base, T.xc, A.bw, lane), R.r[1] = lab5<WIDE>(base + A.bw, T.xc, A.bw, lane);
+		R.r[2] = lab5<WIDE>(base + plane, T.xc, A.bw, lane), R.r[3] = lab5<WIDE>(base + plane + A.bw, T.xc, A.bw, lane);
+		// the bytes around the lane's cubes, asked for together with the labels: a second round trip after the counts costs more than the bytes
+		CubeBytes B{};
+		if (G.vol)        // wave-uniform
+		{
+			const size_t   vplane = (size_t) G.H * (size_t) G.W;
+			const uint8_t *vrow   = G.vol + (size_t) (G.z0 + zc) * vplane + (size_t) (G.y0 + T.yc) * (size_t) G.W;
+			const int      vx     = G.x0 + T.xc;
+			B.v[0] = bytes5(vrow, vx, G.W, lane), B.v[1] = bytes5(vrow + G.W, vx, G.W, lane);
+			B.v[2] = bytes5(vrow + vplane, vx, G.W, lane), B.v[3] = bytes5(vrow + vplane + G.W, vx, G.W, lane);
+		}
+		const uint32_t mine = lane_count(A, tab.count, R, nvalid);
+		uint64_t       idx  = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
+		if (mine == 0)
+			continue;
+#pragma unroll 1
+		for (int i = 0; i < nvalid; ++i)
+		{
+			uint32_t c[8], dif = 0;
+#pragma unroll
+			for (int j = 0; j < 8; ++j)
+			{
+				const Lab5 &r = R.r[j >> 1];
+				c[j]          = (j & 1) ? sel4(r.v[1], r.v[2], r.v[3], r.v[4], i) : sel4(r.v[0], r.v[1], r.v[2], r.v[3], i);
+				dif |= c[j] ^ c[0];
+			}
+			if (dif == 0u)
+				continue;
+			uint32_t E[8];
+			shown8(A, c, E);
+			const int cx = G.x0 + T.xc + i, cy = G.y0 + T.yc, cz = G.z0 + zc;
+			uint64_t  cb = 0;        // the cube's bytes, corner j in byte j: bytes i and i + 1 of row j >> 1
+#pragma unroll
+			for (int r = 0; r < 4; ++r)
+				cb |= ((B.v[r] >> (8 * i)) & 0xffffull) << (16 * r);
+#pragma unroll 1
+			for (int t = 0; t < 6; ++t)
+			{
+				const uint32_t p = (kMtetMid1 >> (4 * t)) & 7u, q = (kMtetMid2 >> (4 * t)) & 7u;
+				const uint32_t l0 = E[0], l1 = p == 1u ? E[1] : p == 2u ? E[2] : E[4], l2 = q == 3u ? E[3] : q == 5u ? E[5] : E[6], l3 = E[7];
+				// the local vertices that start a group: a visible label that no lower vertex carries
+				uint32_t starts = (l0 != 0u ? 1u : 0u) | (l1 != 0u && l1 != l0 ? 2u : 0u) | (l2 != 0u && l2 != l0 && l2 != l1 ? 4u : 0u) |
+				                  (l3 != 0u && l3 != l0 && l3 != l1 && l3 != l2 ? 8u : 0u);
+				while (starts)
+				{
+					const int g = __ffs((int) starts) - 1;
+					starts &= starts - 1u;
+					const uint32_t L  = sel4(l0, l1, l2, l3, g);
+					const uint32_t m  = (l0 == L ? 1u : 0u) | (l1 == L ? 2u : 0u) | (l2 == L ? 4u : 0u) | (l3 == L ? 8u : 0u);
+					const uint64_t cs = *reinterpret_cast<const uint64_t *>(&tab.c[t][m]);        // n, swap, e[0 .. 5]
+					const int      n  = (int) (cs & 0xffu);
+					for (int tri = 0; tri < n; ++tri, ++idx)
+					{
+						if (idx >= capacity)
+							continue;
+						float v[9];
+#pragma unroll
+						for (int j = 0; j < 3; ++j)
+							label_edge_vertex(G.vol != nullptr, cb, (uint32_t) (cs >> (16 + 24 * tri + 8 * j)) & 0x3fu, cx, cy, cz, iso, v + 3 * j);
+						float *out = triangles + 9 * idx;        // 36 bytes at a 4-byte alignment: two 16-byte stores and a dword
+						*reinterpret_cast<f32x4_a4 *>(out)     = f32x4_a4{v[0], v[1], v[2], v[3]};
+						*reinterpret_cast<f32x4_a4 *>(out + 4) = f32x4_a4{v[4], v[5], v[6], v[7]};
+						out[8]                                 = v[8];
+						triangle_labels[idx]                   = L;
+					}
+				}
+			}
+		}
+	}
+}
+
+namespace vkv
+{
+
+// the box's cubes dealt as mesh.hip deals them; false: not accepted, more than 2^32 - 1 voxels, or too large for the launches
+static bool label_mesh_plan(VkvExtent3D e, const VkvBox *box, MeshPlan &p)
+{
+	return extent_and_box_ok(e, box) && components_launch_ok(e, box) && mesh_plan(e, whole_or(e, box), p);
+}
+
+// [chunk sums, then sums before: u64 x chunks][counts: u32 x entries][local prefix: u32 x entries]; 0: the extent and box are not accepted
+size_t label_mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box)
+{
+	MeshPlan p;
+	if (!label_mesh_plan(e, box, p))
+		return 0;
+	return std::max<size_t>(16, 8 * (size_t) p.chunks + 8 * (size_t) p.entries);
+}
+
+bool label_mesh_launch_ok(VkvExtent3D e, const VkvBox *box)
+{
+	MeshPlan p;
+	return label_mesh_plan(e, box, p);
+}
+
+int launch_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e, const VkvBox &b, const uint32_t *d_colors, uint64_t table_entries,
+                      const uint8_t *d_vol, float iso, const uint8_t *d_visibility_map, VkvExtent3D me, void *d_scratch, float *d_triangles,
+                      uint32_t *d_triangle_labels, uint64_t capacity, uint64_t *d_counts, hipStream_t s)
+{
+	MeshPlan p;
+	if (!mesh_plan(e, b, p))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh: volume too large for the launches");
+	uint64_t *sums   = static_cast<uint64_t *>(d_scratch);
+	uint32_t *counts = reinterpret_cast<uint32_t *>(sums + p.chunks), *local = counts + p.entries;
+	LabelGeom A{};
+	A.G     = mesh_geom(d_vol, e, b, 0.0f, d_visibility_map, me, p);
+	A.G.thr = 1u;        // of the visibility map's bytes, 255 passes and 0 does not
+	A.labels = d_labels, A.colors = d_colors, A.entries = table_entries > 0xffffffffull ? 0xffffffffu : (uint32_t) table_entries;
+	A.bw = (int) b.width, A.bh = (int) b.height;
+	const bool wide = b.width >= 4;        // the kernels' 16-byte row loads
+	if (p.entries)
+	{
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_lmesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts); });
+		hipLaunchKernelGGL(k_lmesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, counts, local, sums, p.entries);
+	}
+	hipLaunchKernelGGL(k_lmesh_scan_total, dim3(1), dim3(256), 0, s, sums, p.chunks, capacity, d_counts);
+	if (p.entries && capacity)
+		dispatch_wide(wide, [&](auto w) {
+			hipLaunchKernelGGL(k_lmesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts, local, sums, iso, d_triangles, d_triangle_labels,
+			                   capacity);
+		});
+	return check_launch(ctx, "label_mesh");
+}
+
+}        // namespace vkv

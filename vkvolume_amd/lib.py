@@ -95,6 +95,8 @@ def _signatures():
         row(INT, "vkv_geodesic_propagate", vp, vp, abi.Extent3D, P(abi.Box), f32, vp, P(u32), u32, u32, i32, vp, vp, vp, vp, vp),
         row(INT, "vkv_label_visibility_map", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, abi.Extent3D, vp, vp),
         row(INT, "vkv_render_labels", vp, P(abi.RenderParams), P(abi.LabelRenderOptions), vp),
+        row(size, "vkv_label_mesh_scratch_bytes", abi.Extent3D, P(abi.Box)),
+        row(INT, "vkv_label_mesh", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, vp, f32, vp, abi.Extent3D, vp, vp, vp, u64, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -477,6 +479,18 @@ class Context:
         """vkv_render_labels: the first visible label along each ray of params, coloured by its table entry, with the
         abi.LabelRenderOptions `labels`.  Returns the status code, as label_visibility_map_rc()."""
         return self._lib.vkv_render_labels(self.handle, params, labels, stream)
+
+    def label_mesh_rc(self, d_labels, extent, box, d_colors, table_entries, d_volume, iso, d_visibility_map, map_extent, d_scratch, d_triangles,
+                      d_triangle_labels, capacity, d_counts, stream=0):
+        """vkv_label_mesh: the surfaces of the visible bodies of d_labels (uint32, the shape of `box`; None: of the volume) as
+        marching-tetrahedra triangles in their defined order, each tetrahedron cut once per visible label it touches; d_triangle_labels one
+        uint32 label per triangle; d_counts (2 x uint64) = the total and min(total, capacity).  d_colors None with table_entries 0: every
+        non-zero label is visible.  d_volume None: vertices at edge midpoints (iso is ignored); else interpolated where the volume crosses
+        iso.  d_visibility_map / map_extent None: dense.  d_scratch: labels.mesh_scratch_bytes(extent, box) bytes.  Returns the status
+        code, as label_visibility_map_rc()."""
+        return self._lib.vkv_label_mesh(self.handle, d_labels, extent, box, d_colors, int(table_entries), d_volume, iso, d_visibility_map,
+                                        abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_triangles, d_triangle_labels,
+                                        capacity, d_counts, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

@@ -4,7 +4,9 @@
 ``.cpu().numpy()``).  Triangles wind so that (v1 - v0) x (v2 - v0) points from the inside (f >= iso) to the outside.  The indexed form of
 Volume.extract_isosurface_indexed / vkv_isosurface_mesh_indexed is ``vertices`` [v, 3] float32 and ``faces`` [n, 3] of vertex numbers (any
 integer type; a torch.uint32 tensor's ``.cpu().numpy()``): unindex() turns it into ``tri``, write_ply() stores it, and the coordinate maps take
-a vertex array as well.
+a vertex array as well.  Volume.extract_label_mesh / vkv_label_mesh adds ``tri_labels``, one uint32 label per triangle: split_by_label()
+groups the triangles by body, body_measures() gives each body's area and volume, and write_ply(face_colors=label_face_colors(...)) stores all
+bodies in one coloured file.
 """
 import struct
 
@@ -94,8 +96,49 @@ def write_stl(path, tri, header=b"vkvolume_amd isosurface"):
         f.write(rec.tobytes())
 
 
-def write_ply(path, vertices, faces, normals=None):
-    """binary little-endian PLY: per vertex x y z (and nx ny nz with ``normals`` [v, 3]) as float32, per face a uchar 3 and three uint32"""
+def split_by_label(tri, tri_labels):
+    """The triangles of Volume.extract_label_mesh / vkv_label_mesh grouped by body: ``(labels, starts, tri_sorted)``.  ``labels``: the
+    distinct triangle labels in ascending order; ``tri_sorted``: the triangles sorted by label, stably, so that each body keeps the
+    extraction's order; the body ``labels[k]`` is ``tri_sorted[starts[k]:starts[k + 1]]`` (``starts`` has one entry more than ``labels``)."""
+    tri = _tri(tri)
+    tri_labels = np.asarray(tri_labels).reshape(-1)
+    if len(tri_labels) != len(tri):
+        raise ValueError("%d labels for %d triangles" % (len(tri_labels), len(tri)))
+    order = np.argsort(tri_labels, kind="stable")
+    labels, first = np.unique(tri_labels[order], return_index=True)
+    return labels, np.append(first, len(tri)).astype(np.int64), np.ascontiguousarray(tri[order])
+
+
+def body_measures(tri, tri_labels, n_labels):
+    """``(area, volume)`` of the bodies 1 .. n_labels, two float64 arrays of n_labels entries (entry L - 1: label L): the sum of the
+    triangle areas, and the enclosed volume by the divergence theorem, sum of v0 . (v1 x v2) / 6, which is exact for a closed surface and
+    positive for the extraction's winding.  Triangles with label 0 or above n_labels are ignored.  Voxel units: scale by the spacing for
+    physical ones."""
+    t = _tri(tri).astype(np.float64)
+    tri_labels = np.asarray(tri_labels).reshape(-1).astype(np.int64)
+    if len(tri_labels) != len(t):
+        raise ValueError("%d labels for %d triangles" % (len(tri_labels), len(t)))
+    keep = (tri_labels >= 1) & (tri_labels <= int(n_labels))
+    t, at = t[keep], tri_labels[keep] - 1
+    cross = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    area = np.bincount(at, weights=0.5 * np.linalg.norm(cross, axis=1), minlength=int(n_labels))
+    volume = np.bincount(at, weights=np.einsum("ij,ij->i", t[:, 0], np.cross(t[:, 1], t[:, 2])) / 6.0, minlength=int(n_labels))
+    return area, volume
+
+
+def label_face_colors(tri_labels, table):
+    """[n, 3] uint8 RGB per triangle from a colour table of vkvolume_amd.labels (entry L - 1 for label L); black for a label the table
+    does not name"""
+    tri_labels = np.asarray(tri_labels).reshape(-1).astype(np.int64)
+    table = np.asarray(table, np.uint32).reshape(-1)
+    named = (tri_labels >= 1) & (tri_labels <= len(table))
+    words = np.where(named, table[np.where(named, tri_labels - 1, 0)] if len(table) else 0, 0).astype(np.uint32)
+    return np.stack([words & 255, (words >> 8) & 255, (words >> 16) & 255], axis=1).astype(np.uint8)
+
+
+def write_ply(path, vertices, faces, normals=None, face_colors=None):
+    """binary little-endian PLY: per vertex x y z (and nx ny nz with ``normals`` [v, 3]) as float32, per face a uchar 3 and three uint32
+    (and red green blue as uchar with ``face_colors`` [n, 3] uint8, e.g. label_face_colors() of a labels.color_table palette)"""
     vertices = np.ascontiguousarray(vertices, np.float32)
     faces = np.asarray(faces)
     if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
@@ -110,9 +153,19 @@ def write_ply(path, vertices, faces, normals=None):
         columns.append(normals)
     header = ["ply", "format binary_little_endian 1.0", "comment vkvolume_amd isosurface", "element vertex %d" % len(vertices)]
     header += ["property float %s" % n for n in names]
-    header += ["element face %d" % len(faces), "property list uchar uint vertex_indices", "end_header"]
-    rec = np.zeros(len(faces), np.dtype([("n", "u1"), ("v", "<u4", 3)]))
+    header += ["element face %d" % len(faces), "property list uchar uint vertex_indices"]
+    fields = [("n", "u1"), ("v", "<u4", 3)]
+    if face_colors is not None:
+        face_colors = np.asarray(face_colors)
+        if face_colors.shape != (len(faces), 3) or face_colors.dtype != np.uint8:
+            raise ValueError("face_colors must be a uint8 array of shape (%d, 3), not %s %s" % (len(faces), face_colors.dtype, face_colors.shape))
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+        fields.append(("c", "u1", 3))
+    header.append("end_header")
+    rec = np.zeros(len(faces), np.dtype(fields))
     rec["n"], rec["v"] = 3, faces
+    if face_colors is not None:
+        rec["c"] = face_colors
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(np.concatenate(columns, axis=1).astype("<f4").tobytes())

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import abi, camera, geodesic, lib
+from . import labels as label_tables
 
 
 def _ptr(t):
@@ -403,6 +404,58 @@ class Volume:
         if total:
             call(tri, total)
         return tri, total
+
+    def extract_label_mesh(self, labels, colors=None, iso=None, box=None, use_visibility_map=False, capacity=None):
+        """The surfaces of the visible bodies of ``labels`` on the current stream (vkv_label_mesh: marching tetrahedra in
+        extract_isosurface()'s order, every tetrahedron cut once per visible label it touches): returns ``(triangles, triangle_labels,
+        total)``, an [n, 3, 3] float32 device tensor, the [n] torch.uint32 label of each triangle and the triangle count.  Two bodies that
+        touch share bit-equal vertices, and each label's triangles are closed wherever the body does not touch a face of the box.
+        ``labels``: as returned by label_components() or split_bodies() for the same ``box``.  ``colors``: a colour table as for
+        build_label_visibility_map() (alpha 0 hides a label, and so does a label past the table); None: every non-zero label is visible.
+        ``iso`` None: vertices at edge midpoints, and the volume is not read; else a vertex is interpolated where the volume crosses ``iso``
+        between its two voxels, so that the labels of label_components(iso, 14) give extract_isosurface(iso)'s triangles bit for bit.
+        ``use_visibility_map``: skip tiles through the volume's label visibility map (build_label_visibility_map() with the same labels,
+        box and colors first; the same bits).  ``capacity`` None: a counting call, ONE host read of the total, then the emit into tensors of
+        exactly that size; total is an int.  With a capacity it is one call and no host read: n = capacity, the rows past min(total,
+        capacity) are not written, and total is the call's two-element int64 device tensor.  vkvolume_amd.mesh splits the result by label
+        (split_by_label), measures the bodies (body_measures) and writes one coloured PLY (write_ply with face_colors)."""
+        box = _as_box(box)
+        self._check_labels("extract_label_mesh", labels, box)
+        n_colors = 0
+        if colors is not None:
+            self._check_colors("Volume.extract_label_mesh", colors)
+            n_colors = colors.numel()
+            if n_colors == 0:  # (the C call reads a NULL table of 0 entries as "every label is visible", the opposite of an empty table)
+                raise ValueError("Volume.extract_label_mesh: an empty colour table shows nothing; pass colors=None to show every label")
+        vis = map_extent = None
+        if use_visibility_map:
+            if colors is None or self.label_visibility_map is None:
+                raise RuntimeError("Volume.extract_label_mesh: use_visibility_map=True needs `colors` and the volume's label visibility map "
+                                   "(call Volume.build_label_visibility_map first)")
+            vis, map_extent = self.label_visibility_map, self.map_extent
+        if capacity is not None and (int(capacity) != capacity or capacity < 0):
+            raise ValueError("Volume.extract_label_mesh: capacity must be a non-negative integer or None")
+        scratch = self._scratch(label_tables.mesh_scratch_bytes(self.extent, box),
+                                "Volume.extract_label_mesh: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
+        counts = torch.empty((2,), dtype=torch.int64, device=self.device)
+
+        def call(tri, tri_labels, n):
+            self.ctx.check(self.ctx.label_mesh_rc(_ptr(labels), self.extent, box, _ptr(colors), n_colors, None if iso is None else _ptr(self.volume), 0.0 if iso is None else iso, _ptr(vis), map_extent,
+                                                  _ptr(scratch), _ptr(tri), _ptr(tri_labels), n, _ptr(counts), _stream()))
+
+        def outputs(n):
+            return (torch.empty((n, 3, 3), dtype=torch.float32, device=self.device), torch.empty((n,), dtype=torch.uint32, device=self.device))
+
+        if capacity is not None:
+            tri, tri_labels = outputs(int(capacity))
+            call(tri if capacity else None, tri_labels if capacity else None, int(capacity))
+            return tri, tri_labels, counts
+        call(None, None, 0)
+        total = int(counts[0].item())
+        tri, tri_labels = outputs(total)
+        if total:
+            call(tri, tri_labels, total)
+        return tri, tri_labels, total
 
     def extract_isosurface_indexed(self, iso, box=None, use_max_map=False, normals=False, capacity=None):
         """The isosurface of extract_isosurface() as an indexed mesh on the current stream (vkv_isosurface_mesh_indexed): returns ``(vertices,
