@@ -14,7 +14,7 @@ import torch
 from tests import helpers as T
 from tests.test_components_cpu import components_np
 from tests.test_gpu_mip import make_volume
-from tests.test_label_mesh_cpu import (SKIP_COLORS, SKIP_SHAPE, bordered, distinct_labels, label_mesh_np, random_labels, skip_labels)
+from tests.test_label_mesh_cpu import (SKIP_COLORS, SKIP_SHAPE, bordered, distinct_labels, label_mesh_np, random_labels, rounds_labels, skip_labels)
 from tests.test_mesh_cpu import mesh_contents, mesh_np, same_bits
 from vkvolume_amd import abi, labels as LB, lib
 
@@ -140,6 +140,16 @@ def test_every_extent_and_content(ctx, extent):
     same_bits(want[0], mesh_np(vol, iso), "14-components %s" % (extent,))
     _, tri, _ = check(ctx, labels, want, vol=vol, iso=iso, what="14-components %s" % (extent,))
     same_bits(tri[:len(want[0])], isosurface(ctx, vol, iso, len(want[0])), "against vkv_isosurface_mesh %s" % (extent,))
+
+
+def test_more_chunk_sums_than_one_round_of_the_scan(ctx):
+    """2 x 1026 x 1026 with five labelled rows far apart: 1025 x 1025 entries = 257 chunks of 4096, so the single workgroup that scans the
+    chunk sums carries a total into a second round"""
+    labels = rounds_labels()
+    want = label_mesh_np(labels)
+    assert len(want[0]) > 0 and sorted(set(want[1].tolist())) == [1, 2, 3]
+    check(ctx, labels, want, what="257 chunks")
+    check(ctx, labels, want, capacity=len(want[0]) - 1, what="257 chunks, capacity total - 1")
 
 
 # ---- alignment --------------------------------------------------------------------------------------------------------------------------

@@ -34,12 +34,13 @@ def shown_np(labels, colors):
     return np.where(visible_np(colors, labels.astype(np.int64)), labels, 0).astype(np.int64)
 
 
-def label_mesh_np(labels_dhw, colors=None, vol_dhw=None, iso=None, box=None):
+def label_mesh_np(labels_dhw, colors=None, vol_dhw=None, iso=None, box=None, origin=(0, 0, 0)):
     """vectorised statement: (triangles [n, 3, 3] float32, labels [n] uint32), all cubes at once, then sorted into the defined order.
-    labels_dhw has the box's shape; vol_dhw (None: midpoints) the volume's; box = (x0, y0, z0, w, h, d)"""
+    labels_dhw has the box's shape; vol_dhw (None: midpoints) the volume's; box = (x0, y0, z0, w, h, d); origin: where voxel (0, 0, 0) of
+    vol_dhw lies in the volume whose coordinates the vertices carry (vol_dhw is a window cut from it)"""
     E = shown_np(labels_dhw, colors)
     d, h, w = E.shape
-    origin = (0, 0, 0) if box is None else tuple(box[:3])
+    origin = tuple(int(a) + int(b) for a, b in zip((0, 0, 0) if box is None else box[:3], origin))
     f = None
     if vol_dhw is not None:
         vol, _ = _crop(vol_dhw, box)
@@ -173,6 +174,33 @@ def skip_labels():
     labels[2:18, 1:8, 3:90] = np.random.default_rng(31).integers(0, 7, size=(16, 7, 87), dtype=np.uint32)        # 6: past the table
     labels[:, :, 200:300][np.random.default_rng(32).random((20, 9, 100)) < 0.05] = 2        # hidden salt in the second segment
     return labels
+
+
+ROUNDS_ROWS = ((0, 0), (3, 1000), (512, 513), (1023, 0), (1025, 1025))        # (z, y), rising in the output's order
+
+
+def rounds_labels():
+    """2 x 1026 x 1026, the case of tests/test_gpu_label_mesh.py whose 1025 x 1025 entries are 257 scan chunks: five labelled rows far
+    apart, three labels"""
+    w, h, d = 2, 1026, 1026
+    labels = np.zeros((d, h, w), np.uint32)
+    for k, (z, y) in enumerate(ROUNDS_ROWS):
+        labels[z, y, :] = 1 + k % 3
+    return labels
+
+
+def test_the_statement_on_the_sparse_rounds_case_is_the_rows_own_meshes_in_order():
+    """label_mesh_np takes a few seconds on the million cubes of rounds_labels(); its list is, row by row, the mesh of the 3 x 3 rows around
+    each labelled row as a box of its own"""
+    labels = rounds_labels()
+    tri, lab = label_mesh_np(labels)
+    parts = []
+    for z, y in ROUNDS_ROWS:
+        z0, y0 = max(z - 1, 0), max(y - 1, 0)
+        z1, y1 = min(z + 2, labels.shape[0]), min(y + 2, labels.shape[1])
+        parts.append(label_mesh_np(labels[z0:z1, y0:y1, :], box=(0, y0, z0, 2, y1 - y0, z1 - z0)))
+        assert len(parts[-1][0]) > 0
+    same_mesh((tri, lab), (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])), "rounds case")
 
 
 def empty_tiles(vis_map, shape_dhw, box, map_extent):

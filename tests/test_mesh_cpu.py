@@ -60,9 +60,11 @@ def _crop(vol, box):
     return vol[z0:z0 + d, y0:y0 + h, x0:x0 + w], (x0, y0, z0)
 
 
-def mesh_np(vol_dhw, iso, box=None):
-    """vectorised statement: [n, 3, 3] float32, all cubes at once, then sorted into the defined order.  box = (x0, y0, z0, w, h, d)"""
-    vol, origin = _crop(vol_dhw, box)
+def mesh_np(vol_dhw, iso, box=None, origin=(0, 0, 0)):
+    """vectorised statement: [n, 3, 3] float32, all cubes at once, then sorted into the defined order.  box = (x0, y0, z0, w, h, d);
+    origin: where voxel (0, 0, 0) of vol_dhw lies in the volume whose coordinates the vertices carry (vol_dhw is a window cut from it)"""
+    vol, first = _crop(vol_dhw, box)
+    origin = tuple(int(a) + int(b) for a, b in zip(first, origin))
     iso = np.float32(iso)
     f = vol.astype(np.float32) * KINV255
     inside = f >= iso

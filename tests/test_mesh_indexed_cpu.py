@@ -20,8 +20,9 @@ from vkvolume_amd import abi, lib, mesh as M, volume as V
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def indexed_np(vol_dhw, iso, box=None):
-    """(vertices [v, 3] float32, normals [v, 3] float32, faces [n, 3] int64) of the header's sentences.  box = (x0, y0, z0, w, h, d)"""
+def indexed_np(vol_dhw, iso, box=None, origin=(0, 0, 0)):
+    """(vertices [v, 3] float32, normals [v, 3] float32, faces [n, 3] int64) of the header's sentences.  box = (x0, y0, z0, w, h, d);
+    origin: where voxel (0, 0, 0) of vol_dhw lies in the volume whose coordinates the vertices carry (vol_dhw is a window cut from it)"""
     whole = np.ascontiguousarray(vol_dhw, np.uint8)
     x0, y0, z0, w, h, d = (0, 0, 0) + whole.shape[::-1] if box is None else box
     vol = whole[z0:z0 + d, y0:y0 + h, x0:x0 + w]
@@ -45,7 +46,7 @@ def indexed_np(vol_dhw, iso, box=None):
     t = (iso - fa) / (fb - fa)
     assert t.dtype == np.float32
     vertices = np.empty((len(z), 3), np.float32)
-    for c, (p, o, has) in enumerate(((x, x0, dx), (y, y0, dy), (z, z0, dz))):
+    for c, (p, o, has) in enumerate(((x, x0 + int(origin[0]), dx), (y, y0 + int(origin[1]), dy), (z, z0 + int(origin[2]), dz))):
         ac = (p + o).astype(np.float32)
         vertices[:, c] = np.where(has == 1, ac + t, ac)
     # normals: central differences of the WHOLE volume's bytes, neighbours clamped to the volume
