@@ -1148,11 +1148,63 @@ int vkv_render_labels(vkv_ctx *ctx, const VkvRenderParams *params, const VkvLabe
  * aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels, or one too large for the launches.  Every extent is accepted, widths
  * below 4 and axes of length 1 included; d_volume may start at any byte; nothing outside any buffer is read or written.
  * Not here: the faces of the box stay open, as the isosurface mesh's do, so a body that touches a face is open there (clear the border
- * first, or pass labels with a box one voxel larger); there is no indexed variant and there are no normals. */
+ * first, or pass labels with a box one voxel larger).  The indexed variant, with normals, is vkv_label_mesh_indexed below. */
 size_t vkv_label_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
 int vkv_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors, uint64_t table_entries,
                    const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
                    float *d_triangles, uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
+
+/* ---- label volumes as indexed meshes: shared vertices, normals, and what lies across ------------------------------------------
+ * vkv_label_mesh_indexed: the surfaces of vkv_label_mesh as a vertex list and three vertex numbers per triangle.  Everything not restated
+ * here is vkv_label_mesh's: the labels' shape (that of `box`) and the visible(L) rule, with d_colors == NULL && table_entries == 0 meaning
+ * "every non-zero label is visible"; cubes, tetrahedra, groups per tetrahedron, case masks, winding and triangle order; the vertex rule (t from
+ * the volume where it crosses iso between the edge's voxels, else 0.5f); that every argument is checked before anything is enqueued and a
+ * rejected call writes nothing.  Write shown(L) = L if visible(L), else 0.
+ * Vertex list.  An EDGE is a pair (voxel v, direction d = dx + 2 dy + 4 dz, 1 <= d <= 7; v + d means v + (dx, dy, dz)) with both v and v + d
+ * inside the box, and every axis of the box at least 2 voxels long: vkv_isosurface_mesh_indexed's definition.  An edge is CROSSING iff
+ * shown(label(v)) != shown(label(v + d)): two different hidden labels do not cross, and neither does a hidden label against 0.  The vertex
+ * list is the crossing edges ordered by v (x fastest, then y, then z), then by d rising: one vertex per crossing edge.  Position: the vertex
+ * rule with a = v, b = v + d, so positions are bit-equal to the triangle list's; 3 floats per vertex.  Every triangle vertex of
+ * vkv_label_mesh lies on a crossing edge, and every crossing edge carries a vertex of at least one triangle (DESIGN.md §5.23 proves both),
+ * so the list has no orphans.  Two bodies that meet on an edge share that one vertex.
+ * Normals (d_normals may be NULL: none are computed; with d_normals, d_volume is required).  Exactly vkv_isosurface_mesh_indexed's: G_c(p)
+ * = (int) vol[p + e_c] - (int) vol[p - e_c] from the VOLUME's bytes, both neighbours clamped to the volume; n_c = -((float) G_c(a) + t *
+ * (float) (G_c(b) - G_c(a))) with the vertex's own t (0.5f where the volume does not cross): one multiplication, one addition, no FMA.  3
+ * floats per vertex, not normalised.  What they are worth: on a body's outer surface, where the labels follow the volume, they are the
+ * isosurface's smooth normal.  On an interface inside the material they follow the volume and not the bodies, and their sign there suits
+ * neither body by construction: orient them per triangle (vkvolume_amd.mesh.oriented_corner_normals).
+ * Vertex labels (d_vertex_labels may be NULL: none).  Two uint32 per vertex: shown(label(v)), then shown(label(v + d)).  They differ by
+ * definition and at most one is 0.  A triangle tagged L has L in the pair of each of its three vertices; the other member is what lies
+ * across the surface there, 0 meaning free surface.
+ * Indices.  The triangles of vkv_label_mesh in its order, 3 x uint32 each (v0 v1 v2): the edge (a, b) of the cube with origin o is the edge
+ * (o + a, a ^ b), and its index is that edge's position in the FULL vertex list, reduced mod 2^32; it depends on neither capacity.
+ * d_triangle_labels is as in vkv_label_mesh, one uint32 per triangle.
+ * d_counts holds four values: [0] = the total number of triangles, [1] = min([0], capacity_triangles), [2] = the total number of vertices,
+ * [3] = min([2], capacity_vertices).  Exactly the first [1] triangles' indices and labels and the first [3] vertices (and their normals and
+ * label pairs, if asked for) are written, and not one element beyond them.  A capacity of zero for either list (its pointers NULL or not)
+ * enqueues no emit for that list; both zero is the counting call.  capacity_vertices may not exceed 0xffffffff, so a call with [2] == [3]
+ * has exact indices; a larger surface is extracted box by box.  d_scratch: vkv_label_mesh_indexed_scratch_bytes(extent, box) bytes (at least
+ * 16, a multiple of 8; 0 for an extent or box this call rejects; 16 bytes per 256 x-adjacent voxels of a row of the box and one byte per
+ * voxel, rows rounded up to 4 voxels), 8-byte aligned; its contents mean nothing between calls.
+ * d_visibility_map (NULL: dense) is vkv_label_visibility_map of the same labels, box and table, with map_extent: a tile of VOXELS whose
+ * cells all hold 0 owns no vertex and starts no triangle, and gives the same bits (v + d lies in v's cell grown by one).  With d_colors ==
+ * NULL a map is rejected.
+ * Kernels only (no allocation, no memset or copy node, no host wait, no atomics; the kernels use no scratch memory): two runs give the same
+ * bytes, and after one direct call on `stream` it can be captured into a hipGraph.  Nothing in the context is written.
+ * VKV_E_INVALID_ARGUMENT: everything vkv_label_mesh rejects (a null ctx, d_labels, d_scratch or d_counts, a zero extent, an empty box or
+ * one not inside `extent`, a non-finite iso with a d_volume, a null d_colors with table_entries != 0, a map with a null d_colors or without
+ * a valid map_extent), capacity_vertices > 0xffffffff, a non-zero capacity_vertices with a NULL d_vertices, a non-zero capacity_triangles
+ * with a NULL d_indices or d_triangle_labels, d_normals or d_vertex_labels with capacity_vertices == 0, d_normals without d_volume, a
+ * d_labels, d_colors, d_vertices, d_normals, d_vertex_labels, d_indices or d_triangle_labels that is not 4-byte aligned, a d_scratch or
+ * d_counts that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels, or one too large for the launches.  Every
+ * extent is accepted, widths below 4 and axes of length 1 included; d_volume may start at any byte; nothing outside any buffer is read or
+ * written.
+ * Not here: the box's faces stay open, the normals come from the volume and not from the labels, and nothing is smoothed or decimated. */
+size_t vkv_label_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
+int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors, uint64_t table_entries,
+                           const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
+                           float *d_vertices, float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices,
+                           uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
 
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`

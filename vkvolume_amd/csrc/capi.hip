@@ -456,6 +456,56 @@ int vkv_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, c
 	                         d_scratch, d_triangles, d_triangle_labels, capacity_triangles, d_counts, (hipStream_t) stream);
 }
 
+size_t vkv_label_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return label_mesh_indexed_scratch_bytes(extent, box); }
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors, uint64_t table_entries,
+                           const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
+                           float *d_vertices, float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices,
+                           uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_labels || !d_scratch || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: null pointer or zero extent");
+	if (d_volume && !std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: iso must be finite when d_volume is given");
+	if (const int rc = check_box(ctx, "label_mesh_indexed", extent, box))
+		return rc;
+	if (!d_colors && table_entries != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a table of %llu entries needs d_colors", (unsigned long long) table_entries);
+	if (d_visibility_map && !d_colors)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a visibility map needs the d_colors it was built from");
+	if (d_visibility_map && !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: the visibility map needs a valid map_extent");
+	if (capacity_vertices > 0xffffffffull)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu vertices is past 32-bit indices; split the surface by boxes",
+		                 (unsigned long long) capacity_vertices);
+	if (capacity_vertices != 0 && !d_vertices)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu vertices needs d_vertices", (unsigned long long) capacity_vertices);
+	if (capacity_vertices == 0 && (d_normals || d_vertex_labels))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: d_normals and d_vertex_labels need a capacity of vertices");
+	if (d_normals && !d_volume)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: d_normals needs the d_volume they are taken from");
+	if (capacity_triangles != 0 && (!d_indices || !d_triangle_labels))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu triangles needs d_indices and d_triangle_labels",
+		                 (unsigned long long) capacity_triangles);
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 ||
+	    (((uintptr_t) d_labels | (uintptr_t) d_colors | (uintptr_t) d_vertices | (uintptr_t) d_normals | (uintptr_t) d_vertex_labels | (uintptr_t) d_indices |
+	      (uintptr_t) d_triangle_labels) & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
+		                 "label_mesh_indexed: d_scratch and d_counts must be 8-byte aligned, d_labels, d_colors, d_vertices, d_normals, d_vertex_labels, "
+		                 "d_indices and d_triangle_labels 4-byte aligned");
+	if (!components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh_indexed: a box of more than 2^32 - 1 voxels");
+	if (!label_mesh_indexed_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh_indexed: volume too large for the launches");
+	DeviceGuard guard(ctx->device);
+	return launch_label_mesh_indexed(ctx, d_labels, extent, whole_or(extent, box), d_colors, table_entries, d_volume, iso, d_visibility_map, map_extent,
+	                                 d_scratch, d_vertices, d_normals, d_vertex_labels, capacity_vertices, d_indices, d_triangle_labels, capacity_triangles,
+	                                 d_counts, (hipStream_t) stream);
+}
+
 size_t vkv_label_components_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return components_scratch_bytes(extent, box); }
 
 // every argument is checked before the first launch (and before the device is touched); nothing in the context is written

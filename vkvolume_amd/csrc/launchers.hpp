@@ -127,6 +127,16 @@ int launch_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e, con
                       const uint8_t *d_vol, float iso, const uint8_t *d_visibility_map, VkvExtent3D me, void *d_scratch, float *d_triangles,
                       uint32_t *d_triangle_labels, uint64_t capacity, uint64_t *d_counts, hipStream_t s);
 
+// ---- label_mesh_indexed.hip
+// vkv_label_mesh_indexed_scratch_bytes (0 as for label_mesh_scratch_bytes), what the launches can take, and vkv_label_mesh_indexed after the
+// entry point's argument checks (as launch_label_mesh; d_normals and d_vertex_labels may be null; a capacity of 0 enqueues no emit of its list)
+size_t label_mesh_indexed_scratch_bytes(VkvExtent3D e, const VkvBox *box);
+bool   label_mesh_indexed_launch_ok(VkvExtent3D e, const VkvBox *box);
+int launch_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e, const VkvBox &b, const uint32_t *d_colors, uint64_t table_entries,
+                              const uint8_t *d_vol, float iso, const uint8_t *d_visibility_map, VkvExtent3D me, void *d_scratch, float *d_vertices,
+                              float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices, uint32_t *d_triangle_labels,
+                              uint64_t capacity_triangles, uint64_t *d_counts, hipStream_t s);
+
 // ---- components.hip
 // vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan: at most
 // 2^32 - 1 voxels in the box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)

@@ -1,7 +1,7 @@
 """Host helpers of vkv_render_labels and vkv_label_visibility_map (include/vkvolume_amd.h): the colour table.  A table is a
 numpy uint32 array with one word per label, entry L - 1 for label L: R in bits 0-7, G in bits 8-15, B in bits 16-23, A in bits 24-31.  Alpha
 only switches a label on (not 0) or off (0).  Upload it with torch.from_numpy(table).to(device).  The table functions need no device and no
-library; mesh_scratch_bytes() asks the library (vkv_label_mesh)."""
+library; mesh_scratch_bytes() and mesh_indexed_scratch_bytes() ask the library (vkv_label_mesh, vkv_label_mesh_indexed)."""
 import numpy as np
 
 ALPHA = np.uint32(0xff000000)
@@ -54,3 +54,10 @@ def mesh_scratch_bytes(extent, box=None):
     least 16, a multiple of 8; 0 for an extent or box the call rejects (a box of more than 2^32 - 1 voxels included)"""
     from . import lib
     return lib.load().vkv_label_mesh_scratch_bytes(extent, box)
+
+
+def mesh_indexed_scratch_bytes(extent, box=None):
+    """vkv_label_mesh_indexed_scratch_bytes: the scratch vkv_label_mesh_indexed needs for `box` (None: the whole volume) of `extent` (an
+    abi.Extent3D): at least 16, a multiple of 8; 0 for an extent or box the call rejects (a box of more than 2^32 - 1 voxels included)"""
+    from . import lib
+    return lib.load().vkv_label_mesh_indexed_scratch_bytes(extent, box)

@@ -97,6 +97,8 @@ def _signatures():
         row(INT, "vkv_render_labels", vp, P(abi.RenderParams), P(abi.LabelRenderOptions), vp),
         row(size, "vkv_label_mesh_scratch_bytes", abi.Extent3D, P(abi.Box)),
         row(INT, "vkv_label_mesh", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, vp, f32, vp, abi.Extent3D, vp, vp, vp, u64, vp, vp),
+        row(size, "vkv_label_mesh_indexed_scratch_bytes", abi.Extent3D, P(abi.Box)),
+        row(INT, "vkv_label_mesh_indexed", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, vp, f32, vp, abi.Extent3D, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -491,6 +493,16 @@ class Context:
         return self._lib.vkv_label_mesh(self.handle, d_labels, extent, box, d_colors, int(table_entries), d_volume, iso, d_visibility_map,
                                         abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_triangles, d_triangle_labels,
                                         capacity, d_counts, stream)
+
+    def label_mesh_indexed_rc(self, d_labels, extent, box, d_colors, table_entries, d_volume, iso, d_visibility_map, map_extent, d_scratch, d_vertices,
+                              d_normals, d_vertex_labels, capacity_vertices, d_indices, d_triangle_labels, capacity_triangles, d_counts, stream=0):
+        """vkv_label_mesh_indexed: the surfaces of label_mesh_rc() as a vertex list (one vertex per crossing edge, 3 floats; d_normals None or
+        as many gradient normals of d_volume; d_vertex_labels None or two uint32 per vertex, the shown labels on either side) and 3 x uint32
+        vertex numbers plus one uint32 label per triangle; d_counts (4 x uint64) = the triangles, those written, the vertices, those written.
+        d_scratch: labels.mesh_indexed_scratch_bytes(extent, box) bytes.  Returns the status code, as label_visibility_map_rc()."""
+        return self._lib.vkv_label_mesh_indexed(self.handle, d_labels, extent, box, d_colors, int(table_entries), d_volume, iso, d_visibility_map,
+                                                abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_vertices, d_normals,
+                                                d_vertex_labels, capacity_vertices, d_indices, d_triangle_labels, capacity_triangles, d_counts, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

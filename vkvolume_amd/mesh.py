@@ -6,7 +6,9 @@ Volume.extract_isosurface_indexed / vkv_isosurface_mesh_indexed is ``vertices`` 
 integer type; a torch.uint32 tensor's ``.cpu().numpy()``): unindex() turns it into ``tri``, write_ply() stores it, and the coordinate maps take
 a vertex array as well.  Volume.extract_label_mesh / vkv_label_mesh adds ``tri_labels``, one uint32 label per triangle: split_by_label()
 groups the triangles by body, body_measures() gives each body's area and volume, and write_ply(face_colors=label_face_colors(...)) stores all
-bodies in one coloured file.
+bodies in one coloured file.  Volume.extract_label_mesh_indexed / vkv_label_mesh_indexed gives the bodies as ONE indexed mesh with
+``face_labels``, volume normals and ``vertex_labels`` (the two shown labels a vertex separates): body_submesh() cuts one body out,
+oriented_corner_normals() turns the normals to each face's side, contact_areas() sums what touches what.
 """
 import struct
 
@@ -124,6 +126,76 @@ def body_measures(tri, tri_labels, n_labels):
     area = np.bincount(at, weights=0.5 * np.linalg.norm(cross, axis=1), minlength=int(n_labels))
     volume = np.bincount(at, weights=np.einsum("ij,ij->i", t[:, 0], np.cross(t[:, 1], t[:, 2])) / 6.0, minlength=int(n_labels))
     return area, volume
+
+
+def _indexed(vertices, faces):
+    vertices = np.ascontiguousarray(vertices, np.float32)
+    faces = np.asarray(faces)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices must have the shape [v, 3] and faces [n, 3], not %s and %s" % (vertices.shape, faces.shape))
+    return vertices, faces.astype(np.int64)
+
+
+def body_submesh(vertices, faces, face_labels, label, normals=None):
+    """One body of Volume.extract_label_mesh_indexed / vkv_label_mesh_indexed as a mesh of its own: ``(vertices, faces, normals)`` with the
+    faces tagged ``label`` in their order, the vertices they use compacted in the list's order, the faces renumbered (int64), and the
+    normals of those vertices (None without ``normals``).  Interface vertices are copied into every body that uses them."""
+    vertices, faces = _indexed(vertices, faces)
+    face_labels = np.asarray(face_labels).reshape(-1)
+    if len(face_labels) != len(faces):
+        raise ValueError("%d labels for %d faces" % (len(face_labels), len(faces)))
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, np.float32)
+        if normals.shape != vertices.shape:
+            raise ValueError("normals must have the vertices' shape %s, not %s" % (vertices.shape, normals.shape))
+    own = faces[face_labels == label]
+    used = np.zeros(len(vertices), bool)
+    used[own.reshape(-1)] = True
+    number = np.cumsum(used, dtype=np.int64) - 1
+    return vertices[used], number[own], None if normals is None else normals[used]
+
+
+def oriented_corner_normals(vertices, faces, normals):
+    """[n, 3, 3] float32, one normal per face corner: the vertex normal, negated where its dot product with the face's (v1 - v0) x (v2 - v0)
+    is negative.  The normals of vkv_label_mesh_indexed follow the volume; on an interface between two bodies their sign suits neither, and
+    the faces of the two bodies wind against each other: this gives each face the normals on its own side."""
+    vertices, faces = _indexed(vertices, faces)
+    normals = np.ascontiguousarray(normals, np.float32)
+    if normals.shape != vertices.shape:
+        raise ValueError("normals must have the vertices' shape %s, not %s" % (vertices.shape, normals.shape))
+    tri = vertices[faces].astype(np.float64)
+    face = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    corner = normals[faces]
+    against = np.einsum("nkc,nc->nk", corner.astype(np.float64), face) < 0
+    return np.where(against[:, :, None], -corner, corner).astype(np.float32)
+
+
+MIXED = 0xffffffff        # contact_areas(): the three vertices of a face do not agree on what lies across
+
+
+def contact_areas(vertices, faces, face_labels, vertex_labels):
+    """What each body touches, from the label pairs of vkv_label_mesh_indexed: ``(across, areas)``.  ``across`` [n] uint32: per face the
+    label on its other side, the common other member of its three vertices' pairs (0: nothing, the free surface), or MIXED where they
+    differ (a face next to a junction of three bodies).  ``areas``: {(label, across): the summed area of those faces} in voxel units,
+    float.  An interface appears twice, as (L, K) from body L's faces and as (K, L) from body K's, with equal areas."""
+    vertices, faces = _indexed(vertices, faces)
+    face_labels = np.asarray(face_labels).reshape(-1).astype(np.int64)
+    pairs = np.asarray(vertex_labels).astype(np.int64)
+    if len(face_labels) != len(faces):
+        raise ValueError("%d labels for %d faces" % (len(face_labels), len(faces)))
+    if pairs.shape != (len(vertices), 2):
+        raise ValueError("vertex_labels must have the shape (%d, 2), not %s" % (len(vertices), pairs.shape))
+    p = pairs[faces]        # [n, 3, 2]
+    own = face_labels[:, None]
+    if not ((p[:, :, 0] == own) | (p[:, :, 1] == own)).all():
+        raise ValueError("a face's label is missing from a pair of one of its vertices")
+    other = np.where(p[:, :, 0] == own, p[:, :, 1], p[:, :, 0])
+    across = np.where((other[:, 0] == other[:, 1]) & (other[:, 1] == other[:, 2]), other[:, 0], MIXED)
+    tri = vertices[faces].astype(np.float64)
+    area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
+    keys, inverse = np.unique(np.stack([face_labels, across], axis=1), axis=0, return_inverse=True)
+    sums = np.bincount(inverse.reshape(-1), weights=area, minlength=len(keys))
+    return across.astype(np.uint32), {(int(k[0]), int(k[1])): float(s) for k, s in zip(keys, sums)}
 
 
 def label_face_colors(tri_labels, table):

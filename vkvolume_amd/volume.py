@@ -457,6 +457,62 @@ class Volume:
             call(tri, tri_labels, total)
         return tri, tri_labels, total
 
+    def extract_label_mesh_indexed(self, labels, colors=None, iso=None, box=None, use_visibility_map=False, normals=False, vertex_labels=False,
+                                   capacity=None):
+        """The surfaces of extract_label_mesh() as an indexed mesh on the current stream (vkv_label_mesh_indexed): returns ``(vertices, faces,
+        face_labels, normals, vertex_labels)``: [nv, 3] float32, [nt, 3] torch.uint32, [nt] torch.uint32 and, where asked for, [nv, 3] float32
+        gradient normals of the volume (not normalised; they need ``iso``) and [nv, 2] torch.uint32 pairs of the shown labels on either side
+        of each vertex (0: nothing, the free surface), else None.  One vertex per crossing edge: ``vertices[faces]`` is extract_label_mesh()'s
+        triangle list bit for bit, and two bodies that touch name the same vertices on their interface.  ``labels``, ``colors``, ``iso``,
+        ``box`` and ``use_visibility_map`` as for extract_label_mesh().  ``capacity`` None: a counting call, ONE host read of the four counts,
+        then the emit into tensors of exactly those sizes.  ``capacity=(vertices, triangles)``: one call and no host read; the tensors have
+        those sizes, the rows past the written counts are not written, and a sixth result is the call's int64 device tensor (triangles,
+        triangles written, vertices, vertices written).  vkvolume_amd.mesh cuts one body out (body_submesh), orients the normals per
+        triangle (oriented_corner_normals), measures what touches what (contact_areas) and writes PLY."""
+        box = _as_box(box)
+        self._check_labels("extract_label_mesh_indexed", labels, box)
+        n_colors = 0
+        if colors is not None:
+            self._check_colors("Volume.extract_label_mesh_indexed", colors)
+            n_colors = colors.numel()
+            if n_colors == 0:  # (the C call reads a NULL table of 0 entries as "every label is visible", the opposite of an empty table)
+                raise ValueError("Volume.extract_label_mesh_indexed: an empty colour table shows nothing; pass colors=None to show every label")
+        vis = map_extent = None
+        if use_visibility_map:
+            if colors is None or self.label_visibility_map is None:
+                raise RuntimeError("Volume.extract_label_mesh_indexed: use_visibility_map=True needs `colors` and the volume's label visibility map "
+                                   "(call Volume.build_label_visibility_map first)")
+            vis, map_extent = self.label_visibility_map, self.map_extent
+        if normals and iso is None:
+            raise ValueError("Volume.extract_label_mesh_indexed: normals are the volume's gradient and need `iso`")
+        if capacity is not None:
+            cap_v, cap_t = capacity
+            if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
+                raise ValueError("Volume.extract_label_mesh_indexed: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32")
+        scratch = self._scratch(label_tables.mesh_indexed_scratch_bytes(self.extent, box),
+                                "Volume.extract_label_mesh_indexed: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
+        counts = torch.empty((4,), dtype=torch.int64, device=self.device)
+
+        def call(nv, nt):
+            vertices = torch.empty((nv, 3), dtype=torch.float32, device=self.device)
+            faces = torch.empty((nt, 3), dtype=torch.uint32, device=self.device)
+            face_labels = torch.empty((nt,), dtype=torch.uint32, device=self.device)
+            nrm = torch.empty((nv, 3), dtype=torch.float32, device=self.device) if normals else None
+            pairs = torch.empty((nv, 2), dtype=torch.uint32, device=self.device) if vertex_labels else None
+            self.ctx.check(self.ctx.label_mesh_indexed_rc(
+                _ptr(labels), self.extent, box, _ptr(colors), n_colors, None if iso is None else _ptr(self.volume), 0.0 if iso is None else iso, _ptr(vis),
+                map_extent, _ptr(scratch), _ptr(vertices) if nv else None, _ptr(nrm) if nv else None, _ptr(pairs) if nv else None, nv,
+                _ptr(faces) if nt else None, _ptr(face_labels) if nt else None, nt, _ptr(counts), _stream()))
+            return vertices, faces, face_labels, nrm, pairs
+
+        if capacity is not None:
+            return call(int(cap_v), int(cap_t)) + (counts,)
+        call(0, 0)
+        total = counts.cpu().tolist()
+        if total[2] > 0xffffffff:
+            raise ValueError("Volume.extract_label_mesh_indexed: %d vertices are past 32-bit indices; extract the surface box by box" % total[2])
+        return call(total[2], total[0])
+
     def extract_isosurface_indexed(self, iso, box=None, use_max_map=False, normals=False, capacity=None):
         """The isosurface of extract_isosurface() as an indexed mesh on the current stream (vkv_isosurface_mesh_indexed): returns ``(vertices,
         faces, normals)``: [nv, 3] float32, [nt, 3] torch.uint32 and, with ``normals``, [nv, 3] float32 gradient normals (not normalised,
