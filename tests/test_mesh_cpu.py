@@ -366,6 +366,22 @@ def test_header_table_equals_numpy_entry_for_entry(tmp_path):
     assert '#include "mtet_table.hpp"' in text and "d_mtet = kMtetTable" in text
 
 
+def test_scratch_layout_matches_the_promised_sizes_under_asan_and_ubsan(tmp_path):
+    """MeshScratch, which the four extractors' *_scratch_bytes() and launchers share: its size against the formulas of include/vkvolume_amd.h and
+    its pointers against the size, for plans without a cube, with one entry and with 4096 and 4097 (tests/mesh_scratch_driver.cpp, the header's
+    host pass: no GPU, no kernel)"""
+    hipcc = T.HIPCC if os.path.exists(T.HIPCC) else shutil.which("hipcc")
+    if hipcc is None:
+        pytest.skip("no hipcc")
+    exe = tmp_path / "mesh_scratch_driver"
+    cmd = [hipcc, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "--cuda-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+           "-fno-sanitize-recover=undefined", "-I", T.CSRC, os.path.join(ROOT, "tests", "mesh_scratch_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:]
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "mesh scratch layout ok", r.stdout[-2000:]
+
+
 def test_kernels_use_no_scratch_memory(tmp_path):
     kernels = T.kernel_listing("mesh.hip", tmp_path / "mesh.s")
     assert len([k for k in kernels if "k_mesh_count" in k]) == 2 and len([k for k in kernels if "k_mesh_emit" in k]) == 2, sorted(kernels)  # WIDE, narrow

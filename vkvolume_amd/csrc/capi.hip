@@ -93,6 +93,67 @@ static int check_in_place_or_disjoint(vkv_ctx *ctx, const char *what, const void
 // the transfer-function texture and its tables are read and written as dwords
 static bool tf_pointers_aligned(const void *d_tf, const void *d_tables) { return (((uintptr_t) d_tf | (uintptr_t) d_tables) & 3u) == 0; }
 
+// ---- what the four mesh extractors check alike (vkv_isosurface_mesh, _indexed, vkv_label_mesh, _indexed); each calls them in this order ----
+// the pointers every call needs, iso, the box
+// d_input: the volume or the labels; iso_when: null where iso is not read, else what follows "iso must be finite"
+static int check_mesh_inputs(vkv_ctx *ctx, const char *what, const void *d_input, const void *d_scratch, const void *d_counts, VkvExtent3D extent, float iso,
+                             const char *iso_when, const VkvBox *box)
+{
+	if (!d_input || !d_scratch || !d_counts || !extent_ok(extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null pointer or zero extent", what);
+	if (iso_when && !std::isfinite(iso))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: iso must be finite%s", what, iso_when);
+	return check_box(ctx, what, extent, box);
+}
+// the max map or the visibility map (`map_name`), where one is given
+static int check_skip_map(vkv_ctx *ctx, const char *what, const char *map_name, const uint8_t *d_map, VkvExtent3D extent, VkvExtent3D map_extent)
+{
+	if (d_map && !map_extent_ok(extent, map_extent))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: the %s needs a valid map_extent", what, map_name);
+	return VKV_OK;
+}
+// the colour table of the label meshes, the visibility map's need of it, and the map
+static int check_label_table(vkv_ctx *ctx, const char *what, const uint32_t *d_colors, uint64_t table_entries, const uint8_t *d_visibility_map, VkvExtent3D extent,
+                             VkvExtent3D map_extent)
+{
+	if (!d_colors && table_entries != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: a table of %llu entries needs d_colors", what, (unsigned long long) table_entries);
+	if (d_visibility_map && !d_colors)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: a visibility map needs the d_colors it was built from", what);
+	return check_skip_map(ctx, what, "visibility map", d_visibility_map, extent, map_extent);
+}
+// a capacity of `things` needs its outputs (`names`)
+static int check_capacity(vkv_ctx *ctx, const char *what, uint64_t capacity, const char *things, bool have_outputs, const char *names)
+{
+	if (capacity != 0 && !have_outputs)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: a capacity of %llu %s needs %s", what, (unsigned long long) capacity, things, names);
+	return VKV_OK;
+}
+// the indexed meshes' vertices: numbered in 32 bits, and written to d_vertices
+static int check_vertex_capacity(vkv_ctx *ctx, const char *what, uint64_t capacity_vertices, const float *d_vertices)
+{
+	if (capacity_vertices > 0xffffffffull)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: a capacity of %llu vertices is past 32-bit indices; split the surface by boxes", what,
+		                 (unsigned long long) capacity_vertices);
+	return check_capacity(ctx, what, capacity_vertices, "vertices", d_vertices != nullptr, "d_vertices");
+}
+// any_dword: the bitwise or of the pointers that are read or written as dwords, `names`
+static int check_mesh_alignment(vkv_ctx *ctx, const char *what, const void *d_scratch, const void *d_counts, uintptr_t any_dword, const char *names)
+{
+	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || (any_dword & 3u) != 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_scratch and d_counts must be 8-byte aligned, %s 4-byte aligned", what, names);
+	return VKV_OK;
+}
+// labels: a label array's 2^32 - 1 voxels first; launch_ok: the unit's *_launch_ok
+static int check_mesh_limits(vkv_ctx *ctx, const char *what, VkvExtent3D extent, const VkvBox *box, bool labels, bool (*launch_ok)(VkvExtent3D, const VkvBox *))
+{
+	if (labels && !components_launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: a box of more than 2^32 - 1 voxels", what);
+	if (!launch_ok(extent, box))
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: volume too large for the launches", what);
+	return VKV_OK;
+}
+
 }        // namespace vkv
 
 using namespace vkv;
@@ -362,22 +423,19 @@ size_t vkv_isosurface_mesh_scratch_bytes(VkvExtent3D extent, const VkvBox *box) 
 int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
                         VkvExtent3D map_extent, void *d_scratch, float *d_triangles, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
 {
+	const char *what = "isosurface_mesh";
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
-	if (!d_volume || !d_scratch || !d_counts || !extent_ok(extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: null pointer or zero extent");
-	if (!std::isfinite(iso))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: iso must be finite");
-	if (const int rc = check_box(ctx, "isosurface_mesh", extent, box))
+	if (const int rc = check_mesh_inputs(ctx, what, d_volume, d_scratch, d_counts, extent, iso, "", box))
 		return rc;
-	if (d_max_map && !map_extent_ok(extent, map_extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: the max map needs a valid map_extent");
-	if (capacity_triangles != 0 && !d_triangles)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: a capacity of %llu triangles needs d_triangles", (unsigned long long) capacity_triangles);
-	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || ((uintptr_t) d_triangles & 3u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh: d_scratch and d_counts must be 8-byte aligned, d_triangles 4-byte aligned");
-	if (!mesh_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh: volume too large for the launches");
+	if (const int rc = check_skip_map(ctx, what, "max map", d_max_map, extent, map_extent))
+		return rc;
+	if (const int rc = check_capacity(ctx, what, capacity_triangles, "triangles", d_triangles != nullptr, "d_triangles"))
+		return rc;
+	if (const int rc = check_mesh_alignment(ctx, what, d_scratch, d_counts, (uintptr_t) d_triangles, "d_triangles"))
+		return rc;
+	if (const int rc = check_mesh_limits(ctx, what, extent, box, false, mesh_launch_ok))
+		return rc;
 	DeviceGuard guard(ctx->device);
 	return launch_isosurface_mesh(ctx, d_volume, extent, whole_or(extent, box), iso, d_max_map, map_extent,
 	                              d_scratch, d_triangles, capacity_triangles, d_counts, (hipStream_t) stream);
@@ -390,30 +448,24 @@ int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent
                                 VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
                                 uint32_t *d_indices, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
 {
+	const char *what = "isosurface_mesh_indexed";
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
-	if (!d_volume || !d_scratch || !d_counts || !extent_ok(extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: null pointer or zero extent");
-	if (!std::isfinite(iso))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: iso must be finite");
-	if (const int rc = check_box(ctx, "isosurface_mesh_indexed", extent, box))
+	if (const int rc = check_mesh_inputs(ctx, what, d_volume, d_scratch, d_counts, extent, iso, "", box))
 		return rc;
-	if (d_max_map && !map_extent_ok(extent, map_extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: the max map needs a valid map_extent");
-	if (capacity_vertices > 0xffffffffull)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu vertices is past 32-bit indices; split the surface by boxes",
-		                 (unsigned long long) capacity_vertices);
-	if (capacity_vertices != 0 && !d_vertices)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu vertices needs d_vertices", (unsigned long long) capacity_vertices);
+	if (const int rc = check_skip_map(ctx, what, "max map", d_max_map, extent, map_extent))
+		return rc;
+	if (const int rc = check_vertex_capacity(ctx, what, capacity_vertices, d_vertices))
+		return rc;
 	if (capacity_vertices == 0 && d_normals)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: d_normals needs a capacity of vertices");
-	if (capacity_triangles != 0 && !d_indices)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "isosurface_mesh_indexed: a capacity of %llu triangles needs d_indices", (unsigned long long) capacity_triangles);
-	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 || (((uintptr_t) d_vertices | (uintptr_t) d_normals | (uintptr_t) d_indices) & 3u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
-		                 "isosurface_mesh_indexed: d_scratch and d_counts must be 8-byte aligned, d_vertices, d_normals and d_indices 4-byte aligned");
-	if (!mesh_indexed_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh_indexed: volume too large for the launches");
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_normals needs a capacity of vertices", what);
+	if (const int rc = check_capacity(ctx, what, capacity_triangles, "triangles", d_indices != nullptr, "d_indices"))
+		return rc;
+	if (const int rc = check_mesh_alignment(ctx, what, d_scratch, d_counts, (uintptr_t) d_vertices | (uintptr_t) d_normals | (uintptr_t) d_indices,
+	                                        "d_vertices, d_normals and d_indices"))
+		return rc;
+	if (const int rc = check_mesh_limits(ctx, what, extent, box, false, mesh_indexed_launch_ok))
+		return rc;
 	DeviceGuard guard(ctx->device);
 	return launch_isosurface_mesh_indexed(ctx, d_volume, extent, whole_or(extent, box), iso, d_max_map, map_extent, d_scratch, d_vertices, d_normals,
 	                                      capacity_vertices, d_indices, capacity_triangles, d_counts, (hipStream_t) stream);
@@ -426,31 +478,21 @@ int vkv_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, c
                    const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
                    float *d_triangles, uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
 {
+	const char *what = "label_mesh";
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
-	if (!d_labels || !d_scratch || !d_counts || !extent_ok(extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: null pointer or zero extent");
-	if (d_volume && !std::isfinite(iso))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: iso must be finite when d_volume is given");
-	if (const int rc = check_box(ctx, "label_mesh", extent, box))
+	if (const int rc = check_mesh_inputs(ctx, what, d_labels, d_scratch, d_counts, extent, iso, d_volume ? " when d_volume is given" : nullptr, box))
 		return rc;
-	if (!d_colors && table_entries != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: a table of %llu entries needs d_colors", (unsigned long long) table_entries);
-	if (d_visibility_map && !d_colors)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: a visibility map needs the d_colors it was built from");
-	if (d_visibility_map && !map_extent_ok(extent, map_extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: the visibility map needs a valid map_extent");
-	if (capacity_triangles != 0 && (!d_triangles || !d_triangle_labels))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh: a capacity of %llu triangles needs d_triangles and d_triangle_labels",
-		                 (unsigned long long) capacity_triangles);
-	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 ||
-	    (((uintptr_t) d_labels | (uintptr_t) d_colors | (uintptr_t) d_triangles | (uintptr_t) d_triangle_labels) & 3u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
-		                 "label_mesh: d_scratch and d_counts must be 8-byte aligned, d_labels, d_colors, d_triangles and d_triangle_labels 4-byte aligned");
-	if (!components_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh: a box of more than 2^32 - 1 voxels");
-	if (!label_mesh_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh: volume too large for the launches");
+	if (const int rc = check_label_table(ctx, what, d_colors, table_entries, d_visibility_map, extent, map_extent))
+		return rc;
+	if (const int rc = check_capacity(ctx, what, capacity_triangles, "triangles", d_triangles && d_triangle_labels, "d_triangles and d_triangle_labels"))
+		return rc;
+	if (const int rc = check_mesh_alignment(ctx, what, d_scratch, d_counts,
+	                                        (uintptr_t) d_labels | (uintptr_t) d_colors | (uintptr_t) d_triangles | (uintptr_t) d_triangle_labels,
+	                                        "d_labels, d_colors, d_triangles and d_triangle_labels"))
+		return rc;
+	if (const int rc = check_mesh_limits(ctx, what, extent, box, true, label_mesh_launch_ok))
+		return rc;
 	DeviceGuard guard(ctx->device);
 	return launch_label_mesh(ctx, d_labels, extent, whole_or(extent, box), d_colors, table_entries, d_volume, iso, d_visibility_map, map_extent,
 	                         d_scratch, d_triangles, d_triangle_labels, capacity_triangles, d_counts, (hipStream_t) stream);
@@ -464,42 +506,28 @@ int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e
                            float *d_vertices, float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices,
                            uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream)
 {
+	const char *what = "label_mesh_indexed";
 	if (!ctx)
 		return VKV_E_INVALID_ARGUMENT;
-	if (!d_labels || !d_scratch || !d_counts || !extent_ok(extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: null pointer or zero extent");
-	if (d_volume && !std::isfinite(iso))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: iso must be finite when d_volume is given");
-	if (const int rc = check_box(ctx, "label_mesh_indexed", extent, box))
+	if (const int rc = check_mesh_inputs(ctx, what, d_labels, d_scratch, d_counts, extent, iso, d_volume ? " when d_volume is given" : nullptr, box))
 		return rc;
-	if (!d_colors && table_entries != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a table of %llu entries needs d_colors", (unsigned long long) table_entries);
-	if (d_visibility_map && !d_colors)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a visibility map needs the d_colors it was built from");
-	if (d_visibility_map && !map_extent_ok(extent, map_extent))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: the visibility map needs a valid map_extent");
-	if (capacity_vertices > 0xffffffffull)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu vertices is past 32-bit indices; split the surface by boxes",
-		                 (unsigned long long) capacity_vertices);
-	if (capacity_vertices != 0 && !d_vertices)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu vertices needs d_vertices", (unsigned long long) capacity_vertices);
+	if (const int rc = check_label_table(ctx, what, d_colors, table_entries, d_visibility_map, extent, map_extent))
+		return rc;
+	if (const int rc = check_vertex_capacity(ctx, what, capacity_vertices, d_vertices))
+		return rc;
 	if (capacity_vertices == 0 && (d_normals || d_vertex_labels))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: d_normals and d_vertex_labels need a capacity of vertices");
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_normals and d_vertex_labels need a capacity of vertices", what);
 	if (d_normals && !d_volume)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: d_normals needs the d_volume they are taken from");
-	if (capacity_triangles != 0 && (!d_indices || !d_triangle_labels))
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "label_mesh_indexed: a capacity of %llu triangles needs d_indices and d_triangle_labels",
-		                 (unsigned long long) capacity_triangles);
-	if ((((uintptr_t) d_scratch | (uintptr_t) d_counts) & 7u) != 0 ||
-	    (((uintptr_t) d_labels | (uintptr_t) d_colors | (uintptr_t) d_vertices | (uintptr_t) d_normals | (uintptr_t) d_vertex_labels | (uintptr_t) d_indices |
-	      (uintptr_t) d_triangle_labels) & 3u) != 0)
-		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
-		                 "label_mesh_indexed: d_scratch and d_counts must be 8-byte aligned, d_labels, d_colors, d_vertices, d_normals, d_vertex_labels, "
-		                 "d_indices and d_triangle_labels 4-byte aligned");
-	if (!components_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh_indexed: a box of more than 2^32 - 1 voxels");
-	if (!label_mesh_indexed_launch_ok(extent, box))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh_indexed: volume too large for the launches");
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_normals needs the d_volume they are taken from", what);
+	if (const int rc = check_capacity(ctx, what, capacity_triangles, "triangles", d_indices && d_triangle_labels, "d_indices and d_triangle_labels"))
+		return rc;
+	if (const int rc = check_mesh_alignment(ctx, what, d_scratch, d_counts,
+	                                        (uintptr_t) d_labels | (uintptr_t) d_colors | (uintptr_t) d_vertices | (uintptr_t) d_normals |
+	                                            (uintptr_t) d_vertex_labels | (uintptr_t) d_indices | (uintptr_t) d_triangle_labels,
+	                                        "d_labels, d_colors, d_vertices, d_normals, d_vertex_labels, d_indices and d_triangle_labels"))
+		return rc;
+	if (const int rc = check_mesh_limits(ctx, what, extent, box, true, label_mesh_indexed_launch_ok))
+		return rc;
 	DeviceGuard guard(ctx->device);
 	return launch_label_mesh_indexed(ctx, d_labels, extent, whole_or(extent, box), d_colors, table_entries, d_volume, iso, d_visibility_map, map_extent,
 	                                 d_scratch, d_vertices, d_normals, d_vertex_labels, capacity_vertices, d_indices, d_triangle_labels, capacity_triangles,

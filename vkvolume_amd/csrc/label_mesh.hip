@@ -2,8 +2,9 @@
 // DESIGN.md §5.22): marching tetrahedra on the Kuhn decomposition of every cube, each tetrahedron cut once per visible label it touches, in a
 // defined order, with an exact total and a prefix under a capacity.  Dword streaming; no MFMA.
 //
-// The steps are mesh.hip's, and so are the tile geometry, the plan and the entry layout (mesh_common.hpp, read here and not changed); what
-// label_mesh_indexed.hip shares with this file is label_mesh_common.hpp's:
+// The steps are mesh.hip's: the tile geometry, the plan, the scratch layout, the empty tile's zero fill, the case table's staging, the wave's
+// entries and the triangle store are mesh_common.hpp's, stated there once for the four extractors; what label_mesh_indexed.hip shares with
+// this file alone is label_mesh_common.hpp's:
 //   k_lmesh_count  a lane owns four x-adjacent cubes of one row and marches along z; a wave is 256 cubes of one row, a workgroup four rows and
 //                  kMeshSegment slices.  Per slice a lane loads its four labels of its two rows as one 16-byte load each, takes label x + 4
 //                  from the lane above and keeps the previous slice's two rows in registers.  Twenty equal labels end the lane's slice; a cube
@@ -18,8 +19,6 @@
 //                  labels whose index is below the capacity.  The byte volume is read here only, by the waves and in the slices that emit:
 //                  a dword per lane and row, asked for together with the labels.
 // No kernel uses scratch memory or atomics (tests/test_label_mesh_cpu.py reads the listing).
-#include <algorithm>
-
 #include "label_mesh_common.hpp"
 #include "launchers.hpp"
 
@@ -36,12 +35,7 @@ __global__ void __launch_bounds__(256) k_lmesh_count(LabelGeom A, uint32_t *__re
 	const uint32_t     lane = threadIdx.x & 63u;
 	if (G.mm.map && tile_is_empty(G, T, G.nx, G.ny))
 	{
-		if (threadIdx.x < 4 * kMeshSegment)
-		{
-			const int yc = T.yc - (int) (threadIdx.x >> 6) + (int) (threadIdx.x & 3u), zc = T.zc0 + (int) (threadIdx.x >> 2);
-			if (yc < G.ny && zc < T.zc1)
-				counts[((uint32_t) zc * (uint32_t) G.ny + (uint32_t) yc) * G.segs_x + T.xs] = 0u;
-		}
+		zero_tile_counts(G, T, counts);
 		return;
 	}
 	lut[threadIdx.x] = d_lmtet.count[threadIdx.x];
@@ -88,24 +82,15 @@ __global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t 
                                                     uint32_t *__restrict__ triangle_labels, uint64_t capacity)
 {
 	__shared__ MtetTable tab;
-	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
-	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&d_lmtet)[threadIdx.x];
-	__syncthreads();
+	stage_mtet(tab, d_lmtet);
 	const MeshGeom &G    = A.G;
 	const MeshTile  T    = mesh_tile(G, G.ny, G.nz);
 	const uint32_t  lane = threadIdx.x & 63u;
 	if (T.yc >= G.ny)        // whole waves only; there is no barrier below
 		return;
 	// the wave's entries, one per lane: those with triangles that start below the capacity
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < T.zc1)
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kScanChunk] + local[e];
-		work             = counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, T.zc1, counts, local, chunk_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    nvalid = min(max(G.nx - T.xc, 0), 4);
@@ -115,7 +100,7 @@ __global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t 
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int       zc = T.zc0 + k;
-		const uint32_t  lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t  at = entry_start(start, k);
 		const uint32_t *base = A.labels + (size_t) zc * plane + row;
 		CubeRows        R;
 		R.r[0] = lab5<WIDE>(base, T.xc, A.bw, lane), R.r[1] = lab5<WIDE>(base + A.bw, T.xc, A.bw, lane);
@@ -131,13 +116,13 @@ __global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t 
 			B.v[2] = bytes5(vrow + vplane, vx, G.W, lane), B.v[3] = bytes5(vrow + vplane + G.W, vx, G.W, lane);
 		}
 		const uint32_t mine = lane_count(A, tab.count, R, nvalid);
-		uint64_t       idx  = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
+		uint64_t       idx  = at + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
 		if (mine == 0)
 			continue;
 #pragma unroll 1
 		for (int i = 0; i < nvalid; ++i)
 		{
-			uint32_t c[8], dif = 0;
+			uint32_t c[8], dif = 0;        // cube_labels() and, below, cube_bytes() spelt out: through the calls "label full" measured 0.1 - 0.2 % slower
 #pragma unroll
 			for (int j = 0; j < 8; ++j)
 			{
@@ -159,7 +144,8 @@ __global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t 
 			{
 				const uint32_t p = (kMtetMid1 >> (4 * t)) & 7u, q = (kMtetMid2 >> (4 * t)) & 7u;
 				const uint32_t l0 = E[0], l1 = p == 1u ? E[1] : p == 2u ? E[2] : E[4], l2 = q == 3u ? E[3] : q == 5u ? E[5] : E[6], l3 = E[7];
-				// the local vertices that start a group: a visible label that no lower vertex carries
+				// the local vertices that start a group: a visible label that no lower vertex carries.  (label_mesh_indexed.hip walks the groups
+				// by the same lines.  As one function template that takes the triangle's work it cost this kernel 4 VGPRs and 8 bytes of code)
 				uint32_t starts = (l0 != 0u ? 1u : 0u) | (l1 != 0u && l1 != l0 ? 2u : 0u) | (l2 != 0u && l2 != l0 && l2 != l1 ? 4u : 0u) |
 				                  (l3 != 0u && l3 != l0 && l3 != l1 && l3 != l2 ? 8u : 0u);
 				while (starts)
@@ -178,10 +164,7 @@ __global__ void __launch_bounds__(256) k_lmesh_emit(LabelGeom A, const uint32_t 
 #pragma unroll
 						for (int j = 0; j < 3; ++j)
 							label_edge_vertex(G.vol != nullptr, cb, (uint32_t) (cs >> (16 + 24 * tri + 8 * j)) & 0x3fu, cx, cy, cz, iso, v + 3 * j);
-						float *out = triangles + 9 * idx;        // 36 bytes at a 4-byte alignment: two 16-byte stores and a dword
-						*reinterpret_cast<f32x4_a4 *>(out)     = f32x4_a4{v[0], v[1], v[2], v[3]};
-						*reinterpret_cast<f32x4_a4 *>(out + 4) = f32x4_a4{v[4], v[5], v[6], v[7]};
-						out[8]                                 = v[8];
+						store_triangle(triangles + 9 * idx, v);
 						triangle_labels[idx]                   = L;
 					}
 				}
@@ -199,13 +182,13 @@ static bool label_mesh_plan(VkvExtent3D e, const VkvBox *box, MeshPlan &p)
 	return extent_and_box_ok(e, box) && components_launch_ok(e, box) && mesh_plan(e, whole_or(e, box), p);
 }
 
-// [chunk sums, then sums before: u64 x chunks][counts: u32 x entries][local prefix: u32 x entries]; 0: the extent and box are not accepted
+// MeshScratch with one list; 0: the extent and box are not accepted
 size_t label_mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
 	if (!label_mesh_plan(e, box, p))
 		return 0;
-	return std::max<size_t>(16, 8 * (size_t) p.chunks + 8 * (size_t) p.entries);
+	return MeshScratch{p, 1, 0, nullptr}.bytes();
 }
 
 bool label_mesh_launch_ok(VkvExtent3D e, const VkvBox *box)
@@ -221,24 +204,19 @@ int launch_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e, con
 	MeshPlan p;
 	if (!mesh_plan(e, b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh: volume too large for the launches");
-	uint64_t *sums   = static_cast<uint64_t *>(d_scratch);
-	uint32_t *counts = reinterpret_cast<uint32_t *>(sums + p.chunks), *local = counts + p.entries;
-	LabelGeom A{};
-	A.G     = mesh_geom(d_vol, e, b, 0.0f, d_visibility_map, me, p);
-	A.G.thr = 1u;        // of the visibility map's bytes, 255 passes and 0 does not
-	A.labels = d_labels, A.colors = d_colors, A.entries = table_entries > 0xffffffffull ? 0xffffffffu : (uint32_t) table_entries;
-	A.bw = (int) b.width, A.bh = (int) b.height;
+	const MeshScratch S{p, 1, 0, d_scratch};
+	const LabelGeom   A = label_geom(d_labels, e, b, d_colors, table_entries, d_vol, d_visibility_map, me, p);
 	const bool wide = b.width >= 4;        // the kernels' 16-byte row loads
 	if (p.entries)
 	{
-		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_lmesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts); });
-		hipLaunchKernelGGL(k_lmesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, counts, local, sums, p.entries);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_lmesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, S.counts(0)); });
+		hipLaunchKernelGGL(k_lmesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, S.counts(0), S.local(0), S.sums(0), p.entries);
 	}
-	hipLaunchKernelGGL(k_lmesh_scan_total, dim3(1), dim3(256), 0, s, sums, p.chunks, capacity, d_counts);
+	hipLaunchKernelGGL(k_lmesh_scan_total, dim3(1), dim3(256), 0, s, S.sums(0), p.chunks, capacity, d_counts);
 	if (p.entries && capacity)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_lmesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts, local, sums, iso, d_triangles, d_triangle_labels,
-			                   capacity);
+			hipLaunchKernelGGL(k_lmesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, S.counts(0), S.local(0), S.sums(0), iso, d_triangles,
+			                   d_triangle_labels, capacity);
 		});
 	return check_launch(ctx, "label_mesh");
 }

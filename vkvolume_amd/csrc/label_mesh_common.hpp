@@ -1,6 +1,7 @@
 // label_mesh_common.hpp — what only the kernels of label_mesh.hip (vkv_label_mesh) and label_mesh_indexed.hip (vkv_label_mesh_indexed) share:
 // the argument block, the row loads of labels and bytes, the table lookup that turns labels into shown labels, the triangle counts of a
-// tetrahedron, a cube and a lane, and the vertex rule; DESIGN.md §5.22, §5.23.  The tiles, the plan and the scans are mesh_common.hpp's.
+// tetrahedron, a cube and a lane, the vertex rule and the argument block's builder (label_geom); DESIGN.md §5.22, §5.23.  The tiles, the
+// plan, the scratch layout and every step of the pipeline that the isosurface meshes take as well are mesh_common.hpp's.
 #pragma once
 
 #include "mesh_common.hpp"
@@ -241,6 +242,19 @@ __device__ __forceinline__ void label_edge_vertex(float t, uint32_t code, int cx
 __device__ __forceinline__ void label_edge_vertex(bool with_volume, uint64_t cb, uint32_t code, int cx, int cy, int cz, float iso, float *out)
 {
 	label_edge_vertex(label_edge_t(with_volume, cb, code & 7u, code >> 3, iso), code, cx, cy, cz, out);
+}
+
+// ---- host side
+// the kernels' argument block of a call over box b with the plan p; d_vol null: the volume is not read
+inline LabelGeom label_geom(const uint32_t *d_labels, VkvExtent3D e, const VkvBox &b, const uint32_t *d_colors, uint64_t table_entries, const uint8_t *d_vol,
+                            const uint8_t *d_visibility_map, VkvExtent3D me, const MeshPlan &p)
+{
+	LabelGeom A{};
+	A.G     = mesh_geom(d_vol, e, b, 0.0f, d_visibility_map, me, p);
+	A.G.thr = 1u;        // of the visibility map's bytes, 255 passes and 0 does not
+	A.labels = d_labels, A.colors = d_colors, A.entries = table_entries > 0xffffffffull ? 0xffffffffu : (uint32_t) table_entries;
+	A.bw = (int) b.width, A.bh = (int) b.height;
+	return A;
 }
 
 }        // namespace vkv

@@ -19,9 +19,8 @@
 //   k_lmeshi_emit_indices   per entry with triangles below the capacity: the masks of the four owner rows (y, y + 1) x (z, z + 1), each
 //                           prefixed over the lanes, and label_mesh.hip's walk.  The owner at x + 4 is the lane above's first voxel; for the
 //                           last lane it opens the NEXT entry of the row, whose vertices begin where this entry's end.
-// No kernel uses scratch memory or atomics (tests/test_label_mesh_indexed_cpu.py reads the listing).
-#include <algorithm>
-
+// No kernel uses scratch memory or atomics (tests/test_label_mesh_indexed_cpu.py reads the listing).  box_dirs(), central_differences(),
+// store_normal() and the emit kernels' opening are mesh_common.hpp's; the argument block's builder is label_mesh_common.hpp's.
 #include "label_mesh_common.hpp"
 #include "launchers.hpp"
 
@@ -40,17 +39,6 @@ struct MaskRows
 	int      rows;        // per slice: the box's height
 	__device__ __forceinline__ uint8_t *row(int yv, int zv) const { return at + ((size_t) zv * (size_t) rows + (size_t) yv) * (size_t) stride; }
 };
-
-// the directions (bit d - 1) that stay in the box from its voxel (xv, yv, zv), relative to the box; none from a voxel past it along x
-// (mesh_indexed.hip's)
-__device__ __forceinline__ uint32_t box_dirs(const MeshGeom &G, int xv, int yv, int zv)
-{
-	uint32_t m = xv > G.nx ? 0u : 0x7fu;
-	m &= xv >= G.nx ? ~0x55u : ~0u;        // d with dx: 1, 3, 5, 7
-	m &= yv >= G.ny ? ~0x66u : ~0u;        // d with dy: 2, 3, 6, 7
-	m &= zv >= G.nz ? ~0x78u : ~0u;        // d with dz: 4 .. 7
-	return m;
-}
 
 // bit d - 1 = the shown labels at corners 0 and d of a cube differ
 __device__ __forceinline__ uint32_t crossing_mask(const uint32_t E[8])
@@ -101,16 +89,6 @@ __device__ __forceinline__ uint32_t shown1(const LabelGeom &A, uint32_t L)
 	if (!A.colors)
 		return L;
 	return L - 1u < A.entries && (A.colors[L - 1u] >> 24) != 0u ? L : 0u;        // label 0 gives 2^32 - 1, which no table names
-}
-
-// G_c of the volume's voxel (X, Y, Z): the byte after minus the byte before along each axis, both clamped to the volume (mesh_indexed.hip's)
-__device__ __forceinline__ void central_differences(const MeshGeom &G, int X, int Y, int Z, int g[3])
-{
-	const size_t   W = (size_t) G.W, plane = (size_t) G.H * W;
-	const uint8_t *p = G.vol + (size_t) Z * plane + (size_t) Y * W;
-	g[0]             = (int) p[min(X + 1, G.W - 1)] - (int) p[max(X - 1, 0)];
-	g[1]             = (int) G.vol[(size_t) Z * plane + (size_t) min(Y + 1, G.H - 1) * W + (size_t) X] - (int) G.vol[(size_t) Z * plane + (size_t) max(Y - 1, 0) * W + (size_t) X];
-	g[2]             = (int) G.vol[(size_t) min(Z + 1, G.D - 1) * plane + (size_t) Y * W + (size_t) X] - (int) G.vol[(size_t) max(Z - 1, 0) * plane + (size_t) Y * W + (size_t) X];
 }
 
 }        // namespace
@@ -201,15 +179,8 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_vertices(LabelGeom A, const
 	if (T.yc >= vy)        // whole waves only; there is no barrier
 		return;
 	// the wave's entries, one per lane: those with vertices that start below the capacity
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < T.zc1)
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kScanChunk] + local[e];
-		work             = counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, T.zc1, counts, local, chunk_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    x = G.x0 + T.xc, y = G.y0 + T.yc;
@@ -220,7 +191,7 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_vertices(LabelGeom A, const
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int      zv = T.zc0 + k, z = G.z0 + zv;
-		const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t at    = entry_start(start, k);
 		const uint32_t masks = T.xc < A.bw ? *reinterpret_cast<const uint32_t *>(M.row(T.yc, zv) + T.xc) : 0u;
 		// the far faces' rows stand in for the rows past them: what they hold only feeds directions that the masks do not have
 		CubeBytes B{};
@@ -232,7 +203,7 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_vertices(LabelGeom A, const
 			B.v[2] = bytes5(vrow + vback, x, G.W, lane), B.v[3] = bytes5(vrow + vback + vup, x, G.W, lane);
 		}
 		const uint32_t mine = __builtin_popcount(masks);
-		uint64_t       idx  = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);
+		uint64_t       idx  = at + wave_exclusive(mine, lane);
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -259,10 +230,7 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_vertices(LabelGeom A, const
 					int ga[3], gb[3];
 					central_differences(G, X, y, z, ga);
 					central_differences(G, X + (int) (d & 1u), y + (int) ((d >> 1) & 1u), z + (int) (d >> 2), gb);
-					float *n = normals + 3 * idx;
-#pragma unroll
-					for (int c = 0; c < 3; ++c)
-						n[c] = -((float) ga[c] + t * (float) (gb[c] - ga[c]));
+					store_normal(normals + 3 * idx, ga, gb, t);
 				}
 				if (vertex_labels)        // two gathers per crossing edge: rows of labels held for this alone cost more registers than the kernel has
 				{
@@ -281,24 +249,15 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_indices(LabelGeom A, const 
                                                              uint32_t *__restrict__ triangle_labels, uint64_t capacity)
 {
 	__shared__ MtetTable tab;
-	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
-	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&d_lmtet_indexed)[threadIdx.x];
-	__syncthreads();
+	stage_mtet(tab, d_lmtet_indexed);
 	const MeshGeom &G  = A.G;
 	const int       vy = G.ny + 1, vz = G.nz + 1;
 	const MeshTile  T    = mesh_tile(G, vy, vz);
 	const uint32_t  lane = threadIdx.x & 63u;
 	if (T.yc >= G.ny)        // whole waves only; there is no barrier below.  The far face's rows start no cube
 		return;
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < min(T.zc1, G.nz))
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = tri_before[e / kScanChunk] + tri_local[e];
-		work             = tri_counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, min(T.zc1, G.nz), tri_counts, tri_local, tri_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    nvalid = min(max(G.nx - T.xc, 0), 4);
@@ -308,14 +267,15 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_indices(LabelGeom A, const 
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int       zc = T.zc0 + k;
-		const uint32_t  lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t  at = entry_start(start, k);
 		const uint32_t  e  = T.e0 + (uint32_t) k * T.e_step;
 		const uint32_t *base = A.labels + (size_t) zc * plane + row;
 		CubeRows        R;
 		R.r[0] = lab5<WIDE>(base, T.xc, A.bw, lane), R.r[1] = lab5<WIDE>(base + A.bw, T.xc, A.bw, lane);
 		R.r[2] = lab5<WIDE>(base + plane, T.xc, A.bw, lane), R.r[3] = lab5<WIDE>(base + plane + A.bw, T.xc, A.bw, lane);
 		// the four owner rows r = oy + 2 oz: the masks of the lane's voxels and of voxel x + 4 (bits 32 ..), the number of the lane's first
-		// vertex, and of voxel x + 4's
+		// vertex, and of voxel x + 4's.  (mesh_indexed.hip's lines, kept as a copy for the reason given there: as a shared function the
+		// corner's rule put these arrays into 16 KiB of LDS here too)
 		uint64_t m64[4];
 		uint32_t first[4], above[4];
 #pragma unroll
@@ -336,7 +296,7 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_indices(LabelGeom A, const 
 			m64[r] = (uint64_t) m | (uint64_t) m4 << 32;
 		}
 		const uint32_t mine = lane_count(A, tab.count, R, nvalid);
-		uint64_t       idx  = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
+		uint64_t       idx  = at + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -356,7 +316,7 @@ __global__ void __launch_bounds__(256) k_lmeshi_emit_indices(LabelGeom A, const 
 			{
 				const uint32_t p = (kMtetMid1 >> (4 * t)) & 7u, q = (kMtetMid2 >> (4 * t)) & 7u;
 				const uint32_t l0 = E[0], l1 = p == 1u ? E[1] : p == 2u ? E[2] : E[4], l2 = q == 3u ? E[3] : q == 5u ? E[5] : E[6], l3 = E[7];
-				// the local vertices that start a group: a visible label that no lower vertex carries
+				// the local vertices that start a group: a visible label that no lower vertex carries (label_mesh.hip's walk, a copy: see there)
 				uint32_t starts = (l0 != 0u ? 1u : 0u) | (l1 != 0u && l1 != l0 ? 2u : 0u) | (l2 != 0u && l2 != l0 && l2 != l1 ? 4u : 0u) |
 				                  (l3 != 0u && l3 != l0 && l3 != l1 && l3 != l2 ? 8u : 0u);
 				while (starts)
@@ -406,17 +366,17 @@ static bool label_mesh_indexed_plan(VkvExtent3D e, const VkvBox *box, MeshPlan &
 // the masks' row: the box's width rounded up to a dword, so that every lane's four voxels are one aligned dword
 static uint32_t mask_stride(const VkvBox &b) { return (b.width + 3u) & ~3u; }
 
-// mesh_indexed.hip's block, 16 bytes per entry of 256 voxels: [chunk sums, then sums before: u64 x chunks] x 2, then [counts: u32 x
-// entries][local prefix: u32 x entries] x 2; behind it one crossing-mask byte per voxel in rows of mask_stride(), none for a box without
-// cubes.  0: the extent and box are not accepted
+// one crossing-mask byte per voxel in rows of mask_stride(); none for a box without cubes
+static size_t mask_bytes(const MeshPlan &p, const VkvBox &b) { return p.entries ? (size_t) mask_stride(b) * (size_t) b.height * (size_t) b.depth : 0; }
+
+// MeshScratch with two lists as in mesh_indexed.hip, 16 bytes per entry of 256 voxels, and behind them the masks; 0: the extent and box are
+// not accepted
 size_t label_mesh_indexed_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
 	if (!label_mesh_indexed_plan(e, box, p))
 		return 0;
-	const VkvBox b     = whole_or(e, box);
-	const size_t masks = p.entries ? (size_t) mask_stride(b) * (size_t) b.height * (size_t) b.depth : 0;
-	return std::max<size_t>(16, (16 * (size_t) p.chunks + 16 * (size_t) p.entries + masks + 7) & ~(size_t) 7);
+	return MeshScratch{p, 2, mask_bytes(p, whole_or(e, box)), nullptr}.bytes();
 }
 
 bool label_mesh_indexed_launch_ok(VkvExtent3D e, const VkvBox *box)
@@ -433,30 +393,24 @@ int launch_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3
 	MeshPlan p;
 	if (!mesh_plan(e, b, p, true))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "label_mesh_indexed: volume too large for the launches");
-	uint64_t    *sums   = static_cast<uint64_t *>(d_scratch);
-	uint32_t    *counts = reinterpret_cast<uint32_t *>(sums + 2 * (size_t) p.chunks), *local = counts + p.entries;
-	const size_t verts  = 2 * (size_t) p.entries;        // the vertices' counts and local prefixes lie this far behind the triangles'
-	MaskRows     M{reinterpret_cast<uint8_t *>(counts + 4 * (size_t) p.entries), mask_stride(b), (int) b.height};
-	LabelGeom    A{};
-	A.G     = mesh_geom(d_vol, e, b, 0.0f, d_visibility_map, me, p);
-	A.G.thr = 1u;        // of the visibility map's bytes, 255 passes and 0 does not
-	A.labels = d_labels, A.colors = d_colors, A.entries = table_entries > 0xffffffffull ? 0xffffffffu : (uint32_t) table_entries;
-	A.bw = (int) b.width, A.bh = (int) b.height;
+	const MeshScratch S{p, 2, mask_bytes(p, b), d_scratch};        // list 0: the triangles, list 1: the vertices; behind them the masks
+	const MaskRows    M{S.behind(), mask_stride(b), (int) b.height};
+	const LabelGeom   A = label_geom(d_labels, e, b, d_colors, table_entries, d_vol, d_visibility_map, me, p);
 	const bool wide = b.width >= 4;        // the kernels' 16-byte row loads
 	if (p.entries)
 	{
-		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_lmeshi_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts, counts + verts, M); });
-		hipLaunchKernelGGL(k_lmeshi_scan_chunks, dim3(p.chunks, 2), dim3(256), 0, s, counts, local, sums, p.entries, p.chunks);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_lmeshi_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, S.counts(0), S.counts(1), M); });
+		hipLaunchKernelGGL(k_lmeshi_scan_chunks, dim3(p.chunks, 2), dim3(256), 0, s, S.counts(0), S.local(0), S.sums(0), p.entries, p.chunks);
 	}
-	hipLaunchKernelGGL(k_lmeshi_scan_total, dim3(2), dim3(256), 0, s, sums, p.chunks, capacity_triangles, capacity_vertices, d_counts);
+	hipLaunchKernelGGL(k_lmeshi_scan_total, dim3(2), dim3(256), 0, s, S.sums(0), p.chunks, capacity_triangles, capacity_vertices, d_counts);
 	if (p.entries && capacity_vertices)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_lmeshi_emit_vertices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts + verts, local + verts, sums + p.chunks, M, iso,
+			hipLaunchKernelGGL(k_lmeshi_emit_vertices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, S.counts(1), S.local(1), S.sums(1), M, iso,
 			                   d_vertices, d_normals, d_vertex_labels, capacity_vertices);
 		});
 	if (p.entries && capacity_triangles)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_lmeshi_emit_indices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, counts, local, sums, local + verts, sums + p.chunks, M,
+			hipLaunchKernelGGL(k_lmeshi_emit_indices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, A, S.counts(0), S.local(0), S.sums(0), S.local(1), S.sums(1), M,
 			                   d_indices, d_triangle_labels, capacity_triangles);
 		});
 	return check_launch(ctx, "label_mesh_indexed");

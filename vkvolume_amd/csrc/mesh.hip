@@ -13,9 +13,9 @@
 //   k_mesh_emit    a wave whose entries are all zero, or all start at or past the capacity, leaves at once; for every other entry it loads
 //                  the two slices again, prefixes its lanes' counts and stores the triangles whose index is below the capacity (the case table in LDS).
 // No kernel uses scratch memory (tests/test_mesh_cpu.py reads the listing).  The row loads, inside bits, corner mask, tile geometry, the
-// vertex rule and the plan live in mesh_common.hpp, which mesh_indexed.hip shares; the scans' bodies in fixed_scan.hpp.
-#include <algorithm>
-
+// vertex rule, the plan and the scratch layout live in mesh_common.hpp, and so does every step that the other three mesh extractors take as
+// well: the empty tile's zero fill, the case table's staging, the wave's entries and their starts, the triangle store.  The scans' bodies are
+// fixed_scan.hpp's.
 #include "launchers.hpp"
 #include "mesh_common.hpp"
 #include "mtet_table.hpp"
@@ -32,12 +32,7 @@ __global__ void __launch_bounds__(256) k_mesh_count(MeshGeom G, uint32_t *__rest
 	const uint32_t     lane = threadIdx.x & 63u;
 	if (G.mm.map && tile_is_empty(G, T, G.nx, G.ny))
 	{
-		if (threadIdx.x < 4 * kMeshSegment)
-		{
-			const int yc = T.yc - (int) (threadIdx.x >> 6) + (int) (threadIdx.x & 3u), zc = T.zc0 + (int) (threadIdx.x >> 2);
-			if (yc < G.ny && zc < T.zc1)
-				counts[((uint32_t) zc * (uint32_t) G.ny + (uint32_t) yc) * G.segs_x + T.xs] = 0u;
-		}
+		zero_tile_counts(G, T, counts);
 		return;
 	}
 	lut[threadIdx.x] = d_mtet.count[threadIdx.x];
@@ -88,25 +83,15 @@ template <bool WIDE>
 __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ local,
                                                    const uint64_t *__restrict__ chunk_before, float iso, float *__restrict__ triangles, uint64_t capacity)
 {
-	// the case table in LDS: a cube's walk below reads it once per tetrahedron, one after the other
 	__shared__ MtetTable tab;
-	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
-	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&d_mtet)[threadIdx.x];
-	__syncthreads();
+	stage_mtet(tab, d_mtet);
 	const MeshTile T    = mesh_tile(G, G.ny, G.nz);
 	const uint32_t lane = threadIdx.x & 63u;
 	if (T.yc >= G.ny)        // whole waves only; there is no barrier below
 		return;
 	// the wave's entries, one per lane: those with triangles that start below the capacity
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < T.zc1)
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kScanChunk] + local[e];
-		work             = counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, T.zc1, counts, local, chunk_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    x = G.x0 + T.xc, y = G.y0 + T.yc, nvalid = min(max(G.nx - T.xc, 0), 4);
@@ -116,7 +101,7 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int      zc = T.zc0 + k;
-		const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t at = entry_start(start, k);
 		const uint8_t *base = G.vol + (size_t) (G.z0 + zc) * plane + row;
 		const Row5     r[4] = {row5<WIDE>(base, x, G.W, lane), row5<WIDE>(base + G.W, x, G.W, lane), row5<WIDE>(base + plane, x, G.W, lane),
 		                       row5<WIDE>(base + plane + G.W, x, G.W, lane)};
@@ -129,7 +114,7 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 #pragma unroll
 		for (int i = 0; i < 4; ++i)
 			mine += i < nvalid ? (uint32_t) tab.count[corner_mask(q0, q1, i)] : 0u;
-		uint64_t idx = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
+		uint64_t idx = at + wave_exclusive(mine, lane);        // the cubes of a row lie in lane order
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -153,10 +138,7 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 #pragma unroll
 					for (int j = 0; j < 3; ++j)
 						edge_vertex(B, i, (uint32_t) (c >> (16 + 24 * tri + 8 * j)) & 0x3fu, x + i, y, G.z0 + zc, iso, v + 3 * j);
-					float *out = triangles + 9 * idx;        // 36 bytes at a 4-byte alignment: two 16-byte stores and a dword
-					*reinterpret_cast<f32x4_a4 *>(out)     = f32x4_a4{v[0], v[1], v[2], v[3]};
-					*reinterpret_cast<f32x4_a4 *>(out + 4) = f32x4_a4{v[4], v[5], v[6], v[7]};
-					out[8]                                 = v[8];
+					store_triangle(triangles + 9 * idx, v);
 				}
 			}
 		}
@@ -166,13 +148,13 @@ __global__ void __launch_bounds__(256) k_mesh_emit(MeshGeom G, const uint32_t *_
 namespace vkv
 {
 
-// [chunk sums, then sums before: u64 x chunks][counts: u32 x entries][local prefix: u32 x entries]; 0: the extent and box are not accepted
+// MeshScratch with one list; 0: the extent and box are not accepted
 size_t mesh_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
 	if (!extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p))
 		return 0;
-	return std::max<size_t>(16, 8 * (size_t) p.chunks + 8 * (size_t) p.entries);
+	return MeshScratch{p, 1, 0, nullptr}.bytes();
 }
 
 bool mesh_launch_ok(VkvExtent3D e, const VkvBox *box)
@@ -187,19 +169,18 @@ int launch_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, co
 	MeshPlan p;
 	if (!mesh_plan(e, b, p))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh: volume too large for the launches");
-	uint64_t *sums   = static_cast<uint64_t *>(d_scratch);
-	uint32_t *counts = reinterpret_cast<uint32_t *>(sums + p.chunks), *local = counts + p.entries;
-	MeshGeom  G = mesh_geom(d_vol, e, b, iso, d_max_map, me, p);
+	const MeshScratch S{p, 1, 0, d_scratch};
+	const MeshGeom    G = mesh_geom(d_vol, e, b, iso, d_max_map, me, p);
 	const bool wide = e.width >= 4;        // the kernels' dword row loads
 	if (p.entries)
 	{
-		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_mesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts); });
-		hipLaunchKernelGGL(k_mesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, counts, local, sums, p.entries);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_mesh_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, S.counts(0)); });
+		hipLaunchKernelGGL(k_mesh_scan_chunks, dim3(p.chunks), dim3(256), 0, s, S.counts(0), S.local(0), S.sums(0), p.entries);
 	}
-	hipLaunchKernelGGL(k_mesh_scan_total, dim3(1), dim3(256), 0, s, sums, p.chunks, capacity, d_counts);
+	hipLaunchKernelGGL(k_mesh_scan_total, dim3(1), dim3(256), 0, s, S.sums(0), p.chunks, capacity, d_counts);
 	if (p.entries && capacity)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_mesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, iso, d_triangles, capacity);
+			hipLaunchKernelGGL(k_mesh_emit<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, S.counts(0), S.local(0), S.sums(0), iso, d_triangles, capacity);
 		});
 	return check_launch(ctx, "isosurface_mesh");
 }

@@ -1,6 +1,15 @@
-// mesh_common.hpp — what only the kernels of mesh.hip (vkv_isosurface_mesh) and mesh_indexed.hip (vkv_isosurface_mesh_indexed) share: the tile
-// geometry, the row loads and inside bits, the corner mask, the vertex rule and the plan; DESIGN.md §5.13, §5.14.  The scans are
-// fixed_scan.hpp's; the box, the max map and the WIDE dispatch are box_domain.hpp's.
+// mesh_common.hpp — what the kernels of the four mesh extractors share: mesh.hip (vkv_isosurface_mesh), mesh_indexed.hip
+// (vkv_isosurface_mesh_indexed) and, through label_mesh_common.hpp, label_mesh.hip and label_mesh_indexed.hip; DESIGN.md §5.13, §5.14, §5.22,
+// §5.23.  Each step of the count / scan / emit pipeline is stated here once:
+//   geometry   the tile (mesh_tile), the empty-tile test and the zero fill of its entries (tile_is_empty, zero_tile_counts), the row loads and
+//              inside bits (row5, inside5), the corner mask (corner_mask)
+//   emit       the table's staging (stage_mtet), the wave's entries and their starts (wave_entries, entry_start), edge_vertex, store_triangle
+//   owners     of the indexed meshes: the directions that stay in the box (box_dirs), central_differences and store_normal
+//   host       the plan (mesh_plan), the kernels' geometry block (mesh_geom), the scratch layout's size and pointers (MeshScratch)
+// Four steps are NOT here and remain as copies in the kernels (the last three with a note at the copy), because as shared functions they changed a
+// kernel's code size, registers or LDS (profiles/mesh_family_refactor.txt has the figures): the sum of a lane's four counts, the owner rows'
+// numbering and a corner's vertex number in the two *_emit_indices kernels, and the label emits' walk over a tetrahedron's groups.
+// The scans are fixed_scan.hpp's; the box, the max map and the WIDE dispatch are box_domain.hpp's.
 #pragma once
 
 #include "box_domain.hpp"
@@ -128,6 +137,50 @@ __device__ __forceinline__ bool tile_is_empty(const MeshGeom &G, const MeshTile 
 	return !__syncthreads_or(any);
 }
 
+// an empty tile's entries, where the tiles are dealt over the box's cubes and an entry holds one count: its 4 rows x kMeshSegment slices, one
+// entry per thread
+__device__ __forceinline__ void zero_tile_counts(const MeshGeom &G, const MeshTile &T, uint32_t *__restrict__ counts)
+{
+	if (threadIdx.x < 4 * kMeshSegment)
+	{
+		const int yc = T.yc - (int) (threadIdx.x >> 6) + (int) (threadIdx.x & 3u), zc = T.zc0 + (int) (threadIdx.x >> 2);
+		if (yc < G.ny && zc < T.zc1)
+			counts[((uint32_t) zc * (uint32_t) G.ny + (uint32_t) yc) * G.segs_x + T.xs] = 0u;
+	}
+}
+
+// the case table into LDS, by all 256 threads, a barrier behind it: a cube's walk reads it once per tetrahedron, one after the other
+__device__ __forceinline__ void stage_mtet(MtetTable &tab, const MtetTable &src)
+{
+	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
+	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&src)[threadIdx.x];
+	__syncthreads();
+}
+
+// The wave's entries, one per lane (those of the slices [T.zc0, zend)): the ballot of those that hold something and start below the capacity,
+// and in `start` the lane's entry's first output index
+__device__ __forceinline__ uint64_t wave_entries(const MeshTile &T, uint32_t lane, int zend, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ local,
+                                                 const uint64_t *__restrict__ chunk_before, uint64_t capacity, uint64_t &start)
+{
+	start     = 0;
+	bool work = false;
+	if (T.zc0 + (int) lane < zend)
+	{
+		const uint32_t e = T.e0 + lane * T.e_step;
+		start            = chunk_before[e / kScanChunk] + local[e];
+		work             = counts[e] != 0u && start < capacity;
+	}
+	return __ballot(work);
+}
+
+// entry k's start, from lane k (k is wave-uniform).  Fetch it first in the entry's loop, ahead of the row loads: behind them the same two
+// readlanes reordered the loop's code in two kernels
+__device__ __forceinline__ uint64_t entry_start(uint64_t start, int k)
+{
+	const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+	return (uint64_t) hi << 32 | lo;
+}
+
 // the five voxels of row (j >> 1) & 3 = slice * 2 + row as one 64-bit value each; corner j of cube i is byte i + (j & 1) of it
 struct CubeBytes
 {
@@ -154,6 +207,43 @@ __device__ __forceinline__ void edge_vertex(const CubeBytes &B, int i, uint32_t 
 }
 
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// a triangle's nine floats, 36 bytes at a 4-byte alignment: two 16-byte stores and a dword
+__device__ __forceinline__ void store_triangle(float *out, const float v[9])
+{
+	*reinterpret_cast<f32x4_a4 *>(out)     = f32x4_a4{v[0], v[1], v[2], v[3]};
+	*reinterpret_cast<f32x4_a4 *>(out + 4) = f32x4_a4{v[4], v[5], v[6], v[7]};
+	out[8]                                 = v[8];
+}
+
+// ---- the indexed meshes: an edge's vertex belongs to the voxel at its lower corner a and the direction d = a ^ b
+// the directions (bit d - 1) that stay in the box from its voxel (xv, yv, zv), relative to the box; none from a voxel past it along x
+__device__ __forceinline__ uint32_t box_dirs(const MeshGeom &G, int xv, int yv, int zv)
+{
+	uint32_t m = xv > G.nx ? 0u : 0x7fu;
+	m &= xv >= G.nx ? ~0x55u : ~0u;        // d with dx: 1, 3, 5, 7
+	m &= yv >= G.ny ? ~0x66u : ~0u;        // d with dy: 2, 3, 6, 7
+	m &= zv >= G.nz ? ~0x78u : ~0u;        // d with dz: 4 .. 7
+	return m;
+}
+
+// G_c of the volume's voxel (X, Y, Z): the byte after minus the byte before along each axis, both clamped to the volume
+__device__ __forceinline__ void central_differences(const MeshGeom &G, int X, int Y, int Z, int g[3])
+{
+	const size_t   W = (size_t) G.W, plane = (size_t) G.H * W;
+	const uint8_t *p = G.vol + (size_t) Z * plane + (size_t) Y * W;
+	g[0]             = (int) p[min(X + 1, G.W - 1)] - (int) p[max(X - 1, 0)];
+	g[1]             = (int) G.vol[(size_t) Z * plane + (size_t) min(Y + 1, G.H - 1) * W + (size_t) X] - (int) G.vol[(size_t) Z * plane + (size_t) max(Y - 1, 0) * W + (size_t) X];
+	g[2]             = (int) G.vol[(size_t) min(Z + 1, G.D - 1) * plane + (size_t) Y * W + (size_t) X] - (int) G.vol[(size_t) max(Z - 1, 0) * plane + (size_t) Y * W + (size_t) X];
+}
+
+// the normal of a vertex t of the way from a voxel with gradient ga to one with gb: minus the interpolated gradient
+__device__ __forceinline__ void store_normal(float *out, const int ga[3], const int gb[3], float t)
+{
+#pragma unroll
+	for (int c = 0; c < 3; ++c)
+		out[c] = -((float) ga[c] + t * (float) (gb[c] - ga[c]));
+}
 
 // ---- host side: what a call is dealt into
 struct MeshPlan
@@ -190,5 +280,25 @@ inline MeshGeom mesh_geom(const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, 
 	G.thr = iso_threshold(iso), G.mm = MaxMap(d_max_map, e, me);
 	return G;
 }
+
+// A call's scratch block, its size and its pointers from one place: [chunk sums, then sums before: u64 x chunks] x lists, then [counts: u32 x
+// entries][local prefix: u32 x entries] x lists (8 bytes per entry and list), then `extra` bytes of the unit's own; rounded up to 8, at least 16
+struct MeshScratch
+{
+	MeshPlan p;
+	uint32_t lists;
+	size_t   extra;
+	void    *base;        // null where only the size is asked for
+
+	size_t bytes() const
+	{
+		const size_t n = ((size_t) lists * (8 * (size_t) p.chunks + 8 * (size_t) p.entries) + extra + 7) & ~(size_t) 7;
+		return n < 16 ? 16 : n;
+	}
+	uint64_t *sums(uint32_t list) const { return static_cast<uint64_t *>(base) + (size_t) list * p.chunks; }
+	uint32_t *counts(uint32_t list) const { return reinterpret_cast<uint32_t *>(sums(lists)) + 2 * (size_t) list * p.entries; }
+	uint32_t *local(uint32_t list) const { return counts(list) + p.entries; }
+	uint8_t  *behind() const { return reinterpret_cast<uint8_t *>(counts(lists)); }
+};
 
 }        // namespace vkv

@@ -19,9 +19,8 @@
 //                          16 bytes per entry.  The owner at x + 4 is the lane above's first voxel (its mask and number come by wave_shl);
 //                          for the last lane it is the first voxel of the NEXT entry of the row, whose vertices begin where this entry's
 //                          end: the last lane's own number plus its own count; that voxel's mask takes one more byte per row.
-// No kernel uses scratch memory (tests/test_mesh_indexed_cpu.py reads the listing).
-#include <algorithm>
-
+// No kernel uses scratch memory (tests/test_mesh_indexed_cpu.py reads the listing).  mesh_common.hpp holds what label_mesh_indexed.hip takes
+// as well: box_dirs(), central_differences(), store_normal(), and the emit kernels' opening (stage_mtet, wave_entries, entry_start).
 #include "launchers.hpp"
 #include "mesh_common.hpp"
 #include "mtet_table.hpp"
@@ -32,16 +31,6 @@ __constant__ MtetTable d_mtet_indexed = kMtetTable;
 
 // bit d - 1 = the edge from a voxel in direction d crosses: corner d of its cube is inside and the voxel is not, or the reverse
 __device__ __forceinline__ uint32_t crossing_mask(uint32_t cm) { return (cm >> 1) ^ ((cm & 1u) ? 0x7fu : 0u); }
-
-// the directions (bit d - 1) that stay in the box from its voxel (xv, yv, zv), relative to the box; none from a voxel past it along x
-__device__ __forceinline__ uint32_t box_dirs(const MeshGeom &G, int xv, int yv, int zv)
-{
-	uint32_t m = xv > G.nx ? 0u : 0x7fu;
-	m &= xv >= G.nx ? ~0x55u : ~0u;        // d with dx: 1, 3, 5, 7
-	m &= yv >= G.ny ? ~0x66u : ~0u;        // d with dy: 2, 3, 6, 7
-	m &= zv >= G.nz ? ~0x78u : ~0u;        // d with dz: 4 .. 7
-	return m;
-}
 
 // the crossing masks of the lane's four voxels xv .. xv + 3 of row (yv, zv), one per byte, from the inside bits of corner_mask()
 __device__ __forceinline__ uint32_t owner_masks(const MeshGeom &G, uint32_t q0, uint32_t q1, int xv, int yv, int zv)
@@ -127,16 +116,6 @@ __global__ void __launch_bounds__(256) k_meshi_scan_total(uint64_t *__restrict__
 	scan_total(sums + list * n_chunks, n_chunks, list ? capacity_vertices : capacity_triangles, d_counts + 2 * list);
 }
 
-// G_c of the volume's voxel (X, Y, Z): the byte after minus the byte before along each axis, both clamped to the volume
-__device__ __forceinline__ void central_differences(const MeshGeom &G, int X, int Y, int Z, int g[3])
-{
-	const size_t   W = (size_t) G.W, plane = (size_t) G.H * W;
-	const uint8_t *p = G.vol + (size_t) Z * plane + (size_t) Y * W;
-	g[0]             = (int) p[min(X + 1, G.W - 1)] - (int) p[max(X - 1, 0)];
-	g[1]             = (int) G.vol[(size_t) Z * plane + (size_t) min(Y + 1, G.H - 1) * W + (size_t) X] - (int) G.vol[(size_t) Z * plane + (size_t) max(Y - 1, 0) * W + (size_t) X];
-	g[2]             = (int) G.vol[(size_t) min(Z + 1, G.D - 1) * plane + (size_t) Y * W + (size_t) X] - (int) G.vol[(size_t) max(Z - 1, 0) * plane + (size_t) Y * W + (size_t) X];
-}
-
 template <bool WIDE>
 __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ local,
                                                              const uint64_t *__restrict__ chunk_before, float iso, float *__restrict__ vertices,
@@ -148,15 +127,8 @@ __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const u
 	if (T.yc >= vy)        // whole waves only; there is no barrier
 		return;
 	// the wave's entries, one per lane: those with vertices that start below the capacity
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < T.zc1)
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = chunk_before[e / kScanChunk] + local[e];
-		work             = counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, T.zc1, counts, local, chunk_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    x = G.x0 + T.xc, y = G.y0 + T.yc;
@@ -167,7 +139,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const u
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int      zv = T.zc0 + k, z = G.z0 + zv;
-		const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t at = entry_start(start, k);
 		const uint8_t *base = G.vol + (size_t) z * plane + row;
 		const size_t   back = zv < G.nz ? plane : 0;
 		const Row5     r[4] = {row5<WIDE>(base, x, G.W, lane), row5<WIDE>(base + up, x, G.W, lane), row5<WIDE>(base + back, x, G.W, lane),
@@ -178,7 +150,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const u
 		for (int j = 0; j < 4; ++j)
 			B.v[j] = (uint64_t) r[j].d | (uint64_t) r[j].e << 32;
 		const uint32_t masks = owner_masks(G, q0, q1, T.xc, T.yc, zv), mine = __builtin_popcount(masks);
-		uint64_t       idx   = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);
+		uint64_t       idx   = at + wave_exclusive(mine, lane);
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -202,10 +174,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_vertices(MeshGeom G, const u
 					int ga[3], gb[3];
 					central_differences(G, X, y, z, ga);
 					central_differences(G, X + bx, y + by, z + bz, gb);
-					float *n = normals + 3 * idx;
-#pragma unroll
-					for (int c = 0; c < 3; ++c)
-						n[c] = -((float) ga[c] + t * (float) (gb[c] - ga[c]));
+					store_normal(normals + 3 * idx, ga, gb, t);
 				}
 			}
 		}
@@ -228,23 +197,14 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
                                                             const uint64_t *__restrict__ vert_before, uint32_t *__restrict__ indices, uint64_t capacity)
 {
 	__shared__ MtetTable tab;
-	static_assert(sizeof(MtetTable) == 4 * 256 && alignof(MtetTable) >= 8, "one dword per thread; a case is read as one 64-bit word");
-	reinterpret_cast<uint32_t *>(&tab)[threadIdx.x] = reinterpret_cast<const uint32_t *>(&d_mtet_indexed)[threadIdx.x];
-	__syncthreads();
+	stage_mtet(tab, d_mtet_indexed);
 	const int      vy = G.ny + 1, vz = G.nz + 1;
 	const MeshTile T    = mesh_tile(G, vy, vz);
 	const uint32_t lane = threadIdx.x & 63u;
 	if (T.yc >= G.ny)        // whole waves only; there is no barrier below.  The far face's rows start no cube
 		return;
-	uint64_t start = 0;
-	bool     work  = false;
-	if (T.zc0 + (int) lane < min(T.zc1, G.nz))
-	{
-		const uint32_t e = T.e0 + lane * T.e_step;
-		start            = tri_before[e / kScanChunk] + tri_local[e];
-		work             = tri_counts[e] != 0u && start < capacity;
-	}
-	uint64_t todo = __ballot(work);
+	uint64_t start;
+	uint64_t todo = wave_entries(T, lane, min(T.zc1, G.nz), tri_counts, tri_local, tri_before, capacity, start);
 	if (todo == 0)
 		return;
 	const int    x = G.x0 + T.xc, nvalid = min(max(G.nx - T.xc, 0), 4);
@@ -254,7 +214,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 		const int k = __ffsll((long long) todo) - 1;
 		todo &= todo - 1;
 		const int      zc = T.zc0 + k;
-		const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) start, k), hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (start >> 32), k);
+		const uint64_t at = entry_start(start, k);
 		const uint32_t e  = T.e0 + (uint32_t) k * T.e_step;
 		// inside bits of the rows (y .. y + 2) x (z .. z + 2), clamped to the box: what is clamped only feeds directions that box_dirs() cuts
 		uint32_t Q[3][3];
@@ -264,7 +224,8 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 			for (int yy = 0; yy < 3; ++yy)
 				Q[zz][yy] = inside6<WIDE>(G.vol + (size_t) (G.z0 + min(zc + zz, G.nz)) * plane + (size_t) (G.y0 + min(T.yc + yy, G.ny)) * W, x, G.W, lane, G.thr);
 		// the four owner rows r = oy + 2 oz: the masks of the lane's voxels and of voxel x + 4 (bits 32 ..), the number of the lane's first
-		// vertex, and of voxel x + 4's
+		// vertex, and of voxel x + 4's.  (label_mesh_indexed.hip numbers owners by the same lines.  As shared functions over these arrays they
+		// cost this kernel 16 to 24 bytes of code and two SGPRs for the row, and 16 KiB of LDS for the corner: the arrays left the registers)
 		uint64_t m64[4];
 		uint32_t first[4], above[4];
 #pragma unroll
@@ -288,7 +249,7 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 #pragma unroll
 		for (int i = 0; i < 4; ++i)
 			mine += i < nvalid ? (uint32_t) tab.count[corner_mask(Q[0][0] | Q[0][1] << 8, Q[1][0] | Q[1][1] << 8, i)] : 0u;
-		uint64_t idx = ((uint64_t) hi << 32 | lo) + wave_exclusive(mine, lane);
+		uint64_t idx = at + wave_exclusive(mine, lane);
 		if (mine == 0)
 			continue;
 #pragma unroll 1
@@ -332,14 +293,13 @@ __global__ void __launch_bounds__(256) k_meshi_emit_indices(MeshGeom G, const ui
 namespace vkv
 {
 
-// [chunk sums, then sums before: u64 x chunks] x 2, then [counts: u32 x entries][local prefix: u32 x entries] x 2, the triangles' before the
-// vertices': 16 bytes per entry of 256 voxels; 0: the extent and box are not accepted
+// MeshScratch with two lists, the triangles' before the vertices': 16 bytes per entry of 256 voxels; 0: the extent and box are not accepted
 size_t mesh_indexed_scratch_bytes(VkvExtent3D e, const VkvBox *box)
 {
 	MeshPlan p;
 	if (!extent_and_box_ok(e, box) || !mesh_plan(e, whole_or(e, box), p, true))
 		return 0;
-	return std::max<size_t>(16, 16 * (size_t) p.chunks + 16 * (size_t) p.entries);
+	return MeshScratch{p, 2, 0, nullptr}.bytes();
 }
 
 bool mesh_indexed_launch_ok(VkvExtent3D e, const VkvBox *box)
@@ -355,25 +315,23 @@ int launch_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent
 	MeshPlan p;
 	if (!mesh_plan(e, b, p, true))
 		return set_error(ctx, VKV_E_UNSUPPORTED, "isosurface_mesh_indexed: volume too large for the launches");
-	uint64_t      *sums   = static_cast<uint64_t *>(d_scratch);
-	uint32_t      *counts = reinterpret_cast<uint32_t *>(sums + 2 * (size_t) p.chunks), *local = counts + p.entries;
-	const size_t   verts  = 2 * (size_t) p.entries;        // the vertices' counts and local prefixes lie this far behind the triangles'
-	const MeshGeom G      = mesh_geom(d_vol, e, b, iso, d_max_map, me, p);
+	const MeshScratch S{p, 2, 0, d_scratch};        // list 0: the triangles, list 1: the vertices
+	const MeshGeom    G    = mesh_geom(d_vol, e, b, iso, d_max_map, me, p);
 	const bool     wide   = e.width >= 4;        // the kernels' dword row loads
 	if (p.entries)
 	{
-		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_meshi_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, counts + verts); });
-		hipLaunchKernelGGL(k_meshi_scan_chunks, dim3(p.chunks, 2), dim3(256), 0, s, counts, local, sums, p.entries, p.chunks);
+		dispatch_wide(wide, [&](auto w) { hipLaunchKernelGGL(k_meshi_count<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, S.counts(0), S.counts(1)); });
+		hipLaunchKernelGGL(k_meshi_scan_chunks, dim3(p.chunks, 2), dim3(256), 0, s, S.counts(0), S.local(0), S.sums(0), p.entries, p.chunks);
 	}
-	hipLaunchKernelGGL(k_meshi_scan_total, dim3(2), dim3(256), 0, s, sums, p.chunks, capacity_triangles, capacity_vertices, d_counts);
+	hipLaunchKernelGGL(k_meshi_scan_total, dim3(2), dim3(256), 0, s, S.sums(0), p.chunks, capacity_triangles, capacity_vertices, d_counts);
 	if (p.entries && capacity_vertices)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_meshi_emit_vertices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts + verts, local + verts, sums + p.chunks, iso,
+			hipLaunchKernelGGL(k_meshi_emit_vertices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, S.counts(1), S.local(1), S.sums(1), iso,
 			                   d_vertices, d_normals, capacity_vertices);
 		});
 	if (p.entries && capacity_triangles)
 		dispatch_wide(wide, [&](auto w) {
-			hipLaunchKernelGGL(k_meshi_emit_indices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, counts, local, sums, local + verts, sums + p.chunks,
+			hipLaunchKernelGGL(k_meshi_emit_indices<decltype(w)::value>, dim3(p.wgs), dim3(256), 0, s, G, S.counts(0), S.local(0), S.sums(0), S.local(1), S.sums(1),
 			                   d_indices, capacity_triangles);
 		});
 	return check_launch(ctx, "isosurface_mesh_indexed");

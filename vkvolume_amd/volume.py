@@ -374,6 +374,38 @@ class Volume:
             src = dst
         return out
 
+    def _label_table_args(self, name, colors, use_visibility_map):
+        """(n_colors, visibility map, map_extent) of Volume.<name>(colors=..., use_visibility_map=...): the checked table's length (0: none)
+        and the volume's label visibility map, which must have been built from a table, or (None, None)"""
+        n_colors = 0
+        if colors is not None:
+            self._check_colors("Volume.%s" % name, colors)
+            n_colors = colors.numel()
+            if n_colors == 0:  # (the C call reads a NULL table of 0 entries as "every label is visible", the opposite of an empty table)
+                raise ValueError("Volume.%s: an empty colour table shows nothing; pass colors=None to show every label" % name)
+        if not use_visibility_map:
+            return n_colors, None, None
+        if colors is None or self.label_visibility_map is None:
+            raise RuntimeError("Volume.%s: use_visibility_map=True needs `colors` and the volume's label visibility map "
+                               "(call Volume.build_label_visibility_map first)" % name)
+        return n_colors, self.label_visibility_map, self.map_extent
+
+    @staticmethod
+    def _capacity_pair(name, capacity):
+        """(vertices, triangles) of Volume.<name>(capacity=...) as ints, or None"""
+        if capacity is None:
+            return None
+        cap_v, cap_t = capacity
+        if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
+            raise ValueError("Volume.%s: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32" % name)
+        return int(cap_v), int(cap_t)
+
+    @staticmethod
+    def _check_vertex_total(name, vertices):
+        """the vertex count that a counting call of Volume.<name> read back must fit the 32-bit indices"""
+        if vertices > 0xffffffff:
+            raise ValueError("Volume.%s: %d vertices are past 32-bit indices; extract the surface box by box" % (name, vertices))
+
     def extract_isosurface(self, iso, box=None, use_max_map=False, capacity=None):
         """The isosurface of the volume at ``iso`` as triangles on the current stream (vkv_isosurface_mesh: marching tetrahedra in a defined
         order, voxel-index coordinates): returns ``(triangles, total)``, an [n, 3, 3] float32 device tensor and the surface's triangle count.
@@ -421,18 +453,7 @@ class Volume:
         (split_by_label), measures the bodies (body_measures) and writes one coloured PLY (write_ply with face_colors)."""
         box = _as_box(box)
         self._check_labels("extract_label_mesh", labels, box)
-        n_colors = 0
-        if colors is not None:
-            self._check_colors("Volume.extract_label_mesh", colors)
-            n_colors = colors.numel()
-            if n_colors == 0:  # (the C call reads a NULL table of 0 entries as "every label is visible", the opposite of an empty table)
-                raise ValueError("Volume.extract_label_mesh: an empty colour table shows nothing; pass colors=None to show every label")
-        vis = map_extent = None
-        if use_visibility_map:
-            if colors is None or self.label_visibility_map is None:
-                raise RuntimeError("Volume.extract_label_mesh: use_visibility_map=True needs `colors` and the volume's label visibility map "
-                                   "(call Volume.build_label_visibility_map first)")
-            vis, map_extent = self.label_visibility_map, self.map_extent
+        n_colors, vis, map_extent = self._label_table_args("extract_label_mesh", colors, use_visibility_map)
         if capacity is not None and (int(capacity) != capacity or capacity < 0):
             raise ValueError("Volume.extract_label_mesh: capacity must be a non-negative integer or None")
         scratch = self._scratch(label_tables.mesh_scratch_bytes(self.extent, box),
@@ -471,24 +492,10 @@ class Volume:
         triangle (oriented_corner_normals), measures what touches what (contact_areas) and writes PLY."""
         box = _as_box(box)
         self._check_labels("extract_label_mesh_indexed", labels, box)
-        n_colors = 0
-        if colors is not None:
-            self._check_colors("Volume.extract_label_mesh_indexed", colors)
-            n_colors = colors.numel()
-            if n_colors == 0:  # (the C call reads a NULL table of 0 entries as "every label is visible", the opposite of an empty table)
-                raise ValueError("Volume.extract_label_mesh_indexed: an empty colour table shows nothing; pass colors=None to show every label")
-        vis = map_extent = None
-        if use_visibility_map:
-            if colors is None or self.label_visibility_map is None:
-                raise RuntimeError("Volume.extract_label_mesh_indexed: use_visibility_map=True needs `colors` and the volume's label visibility map "
-                                   "(call Volume.build_label_visibility_map first)")
-            vis, map_extent = self.label_visibility_map, self.map_extent
+        n_colors, vis, map_extent = self._label_table_args("extract_label_mesh_indexed", colors, use_visibility_map)
         if normals and iso is None:
             raise ValueError("Volume.extract_label_mesh_indexed: normals are the volume's gradient and need `iso`")
-        if capacity is not None:
-            cap_v, cap_t = capacity
-            if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
-                raise ValueError("Volume.extract_label_mesh_indexed: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32")
+        capacity = self._capacity_pair("extract_label_mesh_indexed", capacity)
         scratch = self._scratch(label_tables.mesh_indexed_scratch_bytes(self.extent, box),
                                 "Volume.extract_label_mesh_indexed: the box is empty or outside the volume, or it holds more than 2^32 - 1 voxels")
         counts = torch.empty((4,), dtype=torch.int64, device=self.device)
@@ -506,11 +513,10 @@ class Volume:
             return vertices, faces, face_labels, nrm, pairs
 
         if capacity is not None:
-            return call(int(cap_v), int(cap_t)) + (counts,)
+            return call(*capacity) + (counts,)
         call(0, 0)
         total = counts.cpu().tolist()
-        if total[2] > 0xffffffff:
-            raise ValueError("Volume.extract_label_mesh_indexed: %d vertices are past 32-bit indices; extract the surface box by box" % total[2])
+        self._check_vertex_total("extract_label_mesh_indexed", total[2])
         return call(total[2], total[0])
 
     def extract_isosurface_indexed(self, iso, box=None, use_max_map=False, normals=False, capacity=None):
@@ -523,10 +529,7 @@ class Volume:
         and ``use_max_map`` as for extract_isosurface().  vkvolume_amd.mesh unindexes the result and writes PLY."""
         box = _as_box(box)
         max_map, map_extent = self._max_map_args("extract_isosurface_indexed", use_max_map)
-        if capacity is not None:
-            cap_v, cap_t = capacity
-            if int(cap_v) != cap_v or int(cap_t) != cap_t or cap_v < 0 or cap_t < 0 or cap_v > 0xffffffff:
-                raise ValueError("Volume.extract_isosurface_indexed: capacity must be (vertices, triangles), non-negative integers, vertices below 2^32")
+        capacity = self._capacity_pair("extract_isosurface_indexed", capacity)
         scratch = self._scratch(lib.mesh_indexed_scratch_bytes(self.extent, box),
                                 "Volume.extract_isosurface_indexed: the box is empty or outside the volume, or the volume is too large")
         counts = torch.empty((4,), dtype=torch.int64, device=self.device)
@@ -541,11 +544,10 @@ class Volume:
             return vertices, faces, nrm
 
         if capacity is not None:
-            return call(int(cap_v), int(cap_t)) + (counts,)
+            return call(*capacity) + (counts,)
         call(0, 0)
         total = counts.cpu().tolist()
-        if total[2] > 0xffffffff:
-            raise ValueError("Volume.extract_isosurface_indexed: %d vertices are past 32-bit indices; extract the surface box by box" % total[2])
+        self._check_vertex_total("extract_isosurface_indexed", total[2])
         if total[0] == 0 and total[2] == 0:
             return (torch.empty((0, 3), dtype=torch.float32, device=self.device), torch.empty((0, 3), dtype=torch.uint32, device=self.device),
                     torch.empty((0, 3), dtype=torch.float32, device=self.device) if normals else None)
