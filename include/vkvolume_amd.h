@@ -808,7 +808,9 @@ int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exten
  * extent, a non-finite iso, an empty box or one not inside `extent`, a max map without a valid map_extent), capacity_vertices > 0xffffffff,
  * a non-zero capacity_vertices with a NULL d_vertices or capacity_triangles with a NULL d_indices, d_normals with capacity_vertices == 0, a
  * d_vertices, d_normals or d_indices that is not 4-byte aligned, a d_counts or d_scratch that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a
- * volume too large for the launches. */
+ * volume too large for the launches.
+ * Not here: nothing is decimated.  Smoothing, and normals from the faces instead of the volume, are vkv_mesh_smooth and
+ * vkv_mesh_vertex_normals: they take this call's buffers and d_counts as they are. */
 size_t vkv_isosurface_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
 int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
                                 VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
@@ -1199,12 +1201,65 @@ int vkv_label_mesh(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, c
  * d_counts that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a box of more than 2^32 - 1 voxels, or one too large for the launches.  Every
  * extent is accepted, widths below 4 and axes of length 1 included; d_volume may start at any byte; nothing outside any buffer is read or
  * written.
- * Not here: the box's faces stay open, the normals come from the volume and not from the labels, and nothing is smoothed or decimated. */
+ * Not here: the box's faces stay open, the normals come from the volume and not from the labels, and nothing is decimated.  Smoothing, and
+ * normals from the faces of one body, are vkv_mesh_smooth and vkv_mesh_vertex_normals below: they take this call's buffers and d_counts as
+ * they are. */
 size_t vkv_label_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
 int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D extent, const VkvBox *box, const uint32_t *d_colors, uint64_t table_entries,
                            const uint8_t *d_volume, float iso, const uint8_t *d_visibility_map, VkvExtent3D map_extent, void *d_scratch,
                            float *d_vertices, float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices,
                            uint32_t *d_triangle_labels, uint64_t capacity_triangles, uint64_t *d_counts, void *stream);
+
+/* ---- indexed meshes after their extraction: adjacency, Taubin smoothing, normals from the faces --------------------------------
+ * A MESH is d_vertices (3 floats per vertex), d_indices (3 uint32 per triangle) and the four-value d_counts that vkv_isosurface_mesh_indexed
+ * and vkv_label_mesh_indexed write.  d_counts is read ON THE DEVICE: no call here waits for the host.  nt = min(d_counts[1],
+ * capacity_triangles), nv = min(d_counts[3], capacity_vertices).  USED FACES: the first nt triangles whose three indices are all below nv; a
+ * truncated extraction names vertices past its capacity, and those faces contribute nothing and are never dereferenced.
+ * NEIGHBOUR SET.  N(v) = { u != v : some used face holds both u and v }.  A set: a neighbour reached through several faces counts once, the
+ * interface faces that a label mesh emits twice with opposite winding included.  k(v) = |N(v)|.
+ * Fixed point.  q(x) = (int64) rint((double) x * 2^24), rounding half to even.  Every sum below is a sum of such integers in int64, so the
+ * order of summation cannot matter and the results are pinned to the bit; no floating-point atomic is used.
+ * vkv_mesh_adjacency builds, once per mesh, what the other two calls gather through: per vertex its neighbour set and its used faces, both
+ * rising.  It lives in d_adjacency, vkv_mesh_adjacency_scratch_bytes(capacity_vertices, capacity_triangles) bytes of caller memory, 8-byte
+ * aligned: 32 + 8 * ceil(capacity_vertices / 4096) + 3 * roundup8(4 * capacity_vertices) + 24 * capacity_triangles + roundup8(12 *
+ * capacity_triangles); 0 for a capacity above 0xffffffff.  Its layout is the library's (mesh_smooth.hip states it); it stays valid while
+ * d_indices and d_counts stay as they were, for any positions.  Steps: count per vertex (integer atomics), the fixed-tree scan, fill (an integer
+ * atomic cursor per vertex), then each vertex's segment sorted and made a set in place by one lane: the cost is quadratic in a vertex's number
+ * of faces, which is at most 14 away from junctions in the extractors' meshes and is not bounded for a mesh from elsewhere.
+ * vkv_mesh_smooth runs n_passes Jacobi passes of the uniform umbrella operator, pass i with the factor factors[i] (a HOST array, read during the
+ * call; Taubin smoothing is lambda, mu, lambda, mu, ...).  Every vertex reads the previous pass's positions.  One pass with factor f, for each
+ * component c of vertex v at p: S = the sum over u in N(v) of q(p_u,c) in int64; m = (float) ((double) S / (double) k * 2^-24); p' = p + f *
+ * (m - p) as three separately rounded fp32 operations (subtract, multiply, add; no FMA).  A vertex with k = 0, or with d_pinned[v] != 0
+ * (d_pinned: one byte per vertex, NULL: none), keeps its bits.  After the call the result is in d_vertices for every pass count, zero
+ * included; d_swap (capacity_vertices x 3 floats, not d_vertices) holds nothing of meaning.  Rows past nv are written in neither buffer.
+ * Bodies of a label mesh that share an interface vertex see it move once, so they stay closed against each other under exact comparison.
+ * Positions with |x| > 2^20 or non-finite give unspecified values, but never an access outside a buffer.
+ * vkv_mesh_vertex_normals: area-weighted vertex normals from the faces.  For a used face (i0, i1, i2) with positions p0, p1, p2: e1 = p1 - p0,
+ * e2 = p2 - p0 in fp32, n = e1 x e2 with n_x = e1_y * e2_z - e1_z * e2_y, n_y = e1_z * e2_x - e1_x * e2_z, n_z = e1_x * e2_y - e1_y * e2_x,
+ * each the two products in that order, each rounded, then one subtraction (no FMA).  N(v)_c = (float) ((double) (the sum of q(n_c)) * 2^-24)
+ * over the used faces that hold v, or with d_triangle_labels (one uint32 per triangle; NULL: no filter, `label` is ignored) over those with
+ * d_triangle_labels[face] == label.  A face that holds v more than once has n = 0 exactly, so how often it is counted cannot matter.
+ * Not normalised; zero where nothing contributes.  Over all faces an interior interface vertex of a label mesh sums to exactly zero, since its
+ * faces come in opposite pairs; per label it gets that body's outward normal, and the two bodies' normals there are exact negatives.  Rows
+ * past nv are not written.  The sums are defined while they stay below 2^63: face normals up to 2^20 in every component at the least.
+ * All three calls: kernels only (no allocation, no memset or copy node, no host wait; the kernels use no scratch memory), so after one direct
+ * call on `stream` they can be captured into a hipGraph (the factors are then the capture's); two runs give the same bytes in every output and
+ * in d_adjacency; nothing in the context is written.  Every kernel is launched for the capacities and takes its bounds from d_counts.  The
+ * capacities, d_indices and d_counts given to vkv_mesh_smooth and vkv_mesh_vertex_normals are those of the vkv_mesh_adjacency call; other
+ * values give unspecified results, but every index read from memory is compared with its bound before it is used.  Every argument is
+ * checked before anything is enqueued, and a rejected call writes nothing.  VKV_E_INVALID_ARGUMENT: a null ctx, d_indices, d_counts,
+ * d_adjacency, d_vertices, d_swap or d_normals where the call takes one; a d_vertices, d_swap, d_indices, d_triangle_labels or d_normals that
+ * is not 4-byte aligned, a d_counts or d_adjacency that is not 8-byte aligned; d_swap or d_normals equal to d_vertices; n_passes != 0 with
+ * NULL factors; a non-finite factor.  VKV_E_UNSUPPORTED: a capacity above 0xffffffff.
+ * Not here: decimation, cotangent or feature-preserving weights, smoothing during extraction. */
+size_t vkv_mesh_adjacency_scratch_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles);
+int vkv_mesh_adjacency(vkv_ctx *ctx, const uint32_t *d_indices, uint64_t capacity_triangles, uint64_t capacity_vertices, const uint64_t *d_counts,
+                       void *d_adjacency, void *stream);
+int vkv_mesh_smooth(vkv_ctx *ctx, float *d_vertices, float *d_swap, uint64_t capacity_vertices, const uint64_t *d_counts, const void *d_adjacency,
+                    const uint8_t *d_pinned, const float *factors, uint32_t n_passes, void *stream);
+int vkv_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint32_t label,
+                            uint64_t capacity_vertices, uint64_t capacity_triangles, const uint64_t *d_counts, const void *d_adjacency,
+                            float *d_normals, void *stream);
 
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`

@@ -534,6 +534,77 @@ int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e
 	                                 d_counts, (hipStream_t) stream);
 }
 
+size_t vkv_mesh_adjacency_scratch_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles)
+{
+	return mesh_adjacency_bytes(capacity_vertices, capacity_triangles);
+}
+
+// what the three calls on an indexed mesh share: the 4-byte data pointers in `data`, the 8-byte d_counts and d_adjacency, the 32-bit capacities
+static int check_mesh_post(vkv_ctx *ctx, const char *what, bool required, uintptr_t data, const char *data_names, const void *d_counts,
+                           const void *d_adjacency, uint64_t capacity_vertices, uint64_t capacity_triangles)
+{
+	if (!required || !d_counts || !d_adjacency)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null pointer", what);
+	if (data & 3u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", what, data_names);
+	if (((uintptr_t) d_counts | (uintptr_t) d_adjacency) & 7u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_counts and d_adjacency must be 8-byte aligned", what);
+	if (capacity_vertices > 0xffffffffull || capacity_triangles > 0xffffffffull)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: a capacity above 2^32 - 1 (indices are 32-bit)", what);
+	return VKV_OK;
+}
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_mesh_adjacency(vkv_ctx *ctx, const uint32_t *d_indices, uint64_t capacity_triangles, uint64_t capacity_vertices, const uint64_t *d_counts,
+                       void *d_adjacency, void *stream)
+{
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (const int rc = check_mesh_post(ctx, "mesh_adjacency", d_indices != nullptr, (uintptr_t) d_indices, "d_indices", d_counts, d_adjacency,
+	                                   capacity_vertices, capacity_triangles))
+		return rc;
+	DeviceGuard guard(ctx->device);
+	return launch_mesh_adjacency(ctx, d_indices, capacity_triangles, capacity_vertices, d_counts, d_adjacency, (hipStream_t) stream);
+}
+
+int vkv_mesh_smooth(vkv_ctx *ctx, float *d_vertices, float *d_swap, uint64_t capacity_vertices, const uint64_t *d_counts, const void *d_adjacency,
+                    const uint8_t *d_pinned, const float *factors, uint32_t n_passes, void *stream)
+{
+	const char *what = "mesh_smooth";
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (const int rc = check_mesh_post(ctx, what, d_vertices && d_swap, (uintptr_t) d_vertices | (uintptr_t) d_swap, "d_vertices and d_swap", d_counts,
+	                                   d_adjacency, capacity_vertices, 0))
+		return rc;
+	if (d_vertices == d_swap)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_swap must be a buffer of its own", what);
+	if (n_passes && !factors)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: %u passes without factors", what, n_passes);
+	for (uint32_t i = 0; i < n_passes; ++i)
+		if (!std::isfinite(factors[i]))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: factor %u is not finite", what, i);
+	DeviceGuard guard(ctx->device);
+	return launch_mesh_smooth(ctx, d_vertices, d_swap, capacity_vertices, d_counts, d_adjacency, d_pinned, factors, n_passes, (hipStream_t) stream);
+}
+
+int vkv_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint32_t label,
+                            uint64_t capacity_vertices, uint64_t capacity_triangles, const uint64_t *d_counts, const void *d_adjacency, float *d_normals,
+                            void *stream)
+{
+	const char *what = "mesh_vertex_normals";
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (const int rc = check_mesh_post(ctx, what, d_vertices && d_indices && d_normals,
+	                                   (uintptr_t) d_vertices | (uintptr_t) d_indices | (uintptr_t) d_triangle_labels | (uintptr_t) d_normals,
+	                                   "d_vertices, d_indices, d_triangle_labels and d_normals", d_counts, d_adjacency, capacity_vertices, capacity_triangles))
+		return rc;
+	if (d_vertices == d_normals)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_normals must be a buffer of its own", what);
+	DeviceGuard guard(ctx->device);
+	return launch_mesh_vertex_normals(ctx, d_vertices, d_indices, d_triangle_labels, label, capacity_vertices, capacity_triangles, d_counts, d_adjacency,
+	                                  d_normals, (hipStream_t) stream);
+}
+
 size_t vkv_label_components_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return components_scratch_bytes(extent, box); }
 
 // every argument is checked before the first launch (and before the device is touched); nothing in the context is written

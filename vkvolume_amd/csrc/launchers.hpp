@@ -137,6 +137,18 @@ int launch_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3
                               float *d_normals, uint32_t *d_vertex_labels, uint64_t capacity_vertices, uint32_t *d_indices, uint32_t *d_triangle_labels,
                               uint64_t capacity_triangles, uint64_t *d_counts, hipStream_t s);
 
+// ---- mesh_smooth.hip
+// vkv_mesh_adjacency_scratch_bytes (0 for a capacity above 2^32 - 1), and vkv_mesh_adjacency, vkv_mesh_smooth (factors: n_passes host floats,
+// read now; d_pinned may be null) and vkv_mesh_vertex_normals (d_triangle_labels null: every used face) after the entry points' argument checks
+size_t mesh_adjacency_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles);
+int launch_mesh_adjacency(vkv_ctx *ctx, const uint32_t *d_indices, uint64_t capacity_triangles, uint64_t capacity_vertices, const uint64_t *d_counts,
+                          void *d_adjacency, hipStream_t s);
+int launch_mesh_smooth(vkv_ctx *ctx, float *d_vertices, float *d_swap, uint64_t capacity_vertices, const uint64_t *d_counts, const void *d_adjacency,
+                       const uint8_t *d_pinned, const float *factors, uint32_t n_passes, hipStream_t s);
+int launch_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint32_t label,
+                               uint64_t capacity_vertices, uint64_t capacity_triangles, const uint64_t *d_counts, const void *d_adjacency, float *d_normals,
+                               hipStream_t s);
+
 // ---- components.hip
 // vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan: at most
 // 2^32 - 1 voxels in the box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)

@@ -99,6 +99,10 @@ def _signatures():
         row(INT, "vkv_label_mesh", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, vp, f32, vp, abi.Extent3D, vp, vp, vp, u64, vp, vp),
         row(size, "vkv_label_mesh_indexed_scratch_bytes", abi.Extent3D, P(abi.Box)),
         row(INT, "vkv_label_mesh_indexed", vp, vp, abi.Extent3D, P(abi.Box), vp, u64, vp, f32, vp, abi.Extent3D, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp),
+        row(size, "vkv_mesh_adjacency_scratch_bytes", u64, u64),
+        row(INT, "vkv_mesh_adjacency", vp, vp, u64, u64, vp, vp, vp),
+        row(INT, "vkv_mesh_smooth", vp, vp, vp, u64, vp, vp, vp, P(f32), u32, vp),
+        row(INT, "vkv_mesh_vertex_normals", vp, vp, vp, vp, u32, u64, u64, vp, vp, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -503,6 +507,33 @@ class Context:
         return self._lib.vkv_label_mesh_indexed(self.handle, d_labels, extent, box, d_colors, int(table_entries), d_volume, iso, d_visibility_map,
                                                 abi.Extent3D(0, 0, 0) if map_extent is None else map_extent, d_scratch, d_vertices, d_normals,
                                                 d_vertex_labels, capacity_vertices, d_indices, d_triangle_labels, capacity_triangles, d_counts, stream)
+
+    def mesh_adjacency_rc(self, d_indices, capacity_triangles, capacity_vertices, d_counts, d_adjacency, stream=0):
+        """vkv_mesh_adjacency: per vertex of an indexed mesh (d_indices: 3 x uint32 per triangle; d_counts: the 4 x uint64 of the indexed
+        extractors, read on the device) its neighbour set and its used faces, into d_adjacency (mesh.adjacency_scratch_bytes(capacity_vertices,
+        capacity_triangles) bytes); built once per mesh for mesh_smooth_rc() and mesh_vertex_normals_rc().  Returns the status code, as
+        label_visibility_map_rc()."""
+        return self._lib.vkv_mesh_adjacency(self.handle, d_indices, int(capacity_triangles), int(capacity_vertices), d_counts, d_adjacency, stream)
+
+    def mesh_smooth_rc(self, d_vertices, d_swap, capacity_vertices, d_counts, d_adjacency, d_pinned, factors, stream=0):
+        """vkv_mesh_smooth: one uniform-umbrella pass per entry of `factors` (host floats; Taubin: lambda, mu, lambda, mu, ...; None passes NULL
+        with zero passes) over the first min(d_counts[3], capacity_vertices) rows of d_vertices, in place; d_swap: as many floats; d_pinned None
+        or one byte per vertex, non-zero: the vertex stays.  `factors` may be a (pointer, count) pair (error-path tests).  Returns the status
+        code, as label_visibility_map_rc()."""
+        if isinstance(factors, tuple):
+            array, n = factors
+        else:
+            n = 0 if factors is None else len(factors)
+            array = (C.c_float * n)(*(float(f) for f in factors)) if n else None
+        return self._lib.vkv_mesh_smooth(self.handle, d_vertices, d_swap, int(capacity_vertices), d_counts, d_adjacency, d_pinned, array, n, stream)
+
+    def mesh_vertex_normals_rc(self, d_vertices, d_indices, d_triangle_labels, label, capacity_vertices, capacity_triangles, d_counts, d_adjacency,
+                               d_normals, stream=0):
+        """vkv_mesh_vertex_normals: d_normals (3 floats per vertex) = the area-weighted sum of (p1 - p0) x (p2 - p0) over each vertex's used
+        faces, or with d_triangle_labels (not None) over those tagged `label`; not normalised.  d_adjacency: of mesh_adjacency_rc() for the
+        same mesh.  Returns the status code, as label_visibility_map_rc()."""
+        return self._lib.vkv_mesh_vertex_normals(self.handle, d_vertices, d_indices, d_triangle_labels, int(label), int(capacity_vertices),
+                                                 int(capacity_triangles), d_counts, d_adjacency, d_normals, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

@@ -9,6 +9,10 @@ groups the triangles by body, body_measures() gives each body's area and volume,
 bodies in one coloured file.  Volume.extract_label_mesh_indexed / vkv_label_mesh_indexed gives the bodies as ONE indexed mesh with
 ``face_labels``, volume normals and ``vertex_labels`` (the two shown labels a vertex separates): body_submesh() cuts one body out,
 oriented_corner_normals() turns the normals to each face's side, contact_areas() sums what touches what.
+
+Three functions work ON THE DEVICE and ARE pinned to the bit (vkv_mesh_adjacency, vkv_mesh_smooth, vkv_mesh_vertex_normals):
+build_adjacency(), smooth() and vertex_normals() take an indexed mesh as torch device tensors, with the extraction's ``counts`` tensor if its
+capacities were given, and never wait for the host.  boundary_vertices() is the host helper that finds what callers will want pinned.
 """
 import struct
 
@@ -242,3 +246,123 @@ def write_ply(path, vertices, faces, normals=None, face_colors=None):
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(np.concatenate(columns, axis=1).astype("<f4").tobytes())
         f.write(rec.tobytes())
+
+
+# ---- on the device: adjacency, smoothing, normals from the faces -----------------------------------------------------------
+
+def adjacency_scratch_bytes(capacity_vertices, capacity_triangles):
+    """vkv_mesh_adjacency_scratch_bytes, and the header's formula: 32 + 8 per 4096 vertices + 3 x (4 per vertex, rounded up to 8) + 24 per
+    triangle + (12 per triangle, rounded up to 8); 0 for a capacity above 2^32 - 1"""
+    cv, ct = int(capacity_vertices), int(capacity_triangles)
+    if cv > 0xffffffff or ct > 0xffffffff:
+        return 0
+    up8 = lambda n: (n + 7) & ~7  # noqa: E731
+    return 32 + 8 * ((cv + 4095) // 4096) + 3 * up8(4 * cv) + 24 * ct + up8(12 * ct)
+
+
+def _device_mesh(name, vertices, faces, counts):
+    """the checks the three device calls share; (capacity_vertices, capacity_triangles, counts as a device tensor, the stream)"""
+    import torch
+    if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3
+            and vertices.is_contiguous()):
+        raise ValueError("mesh.%s: vertices must be a contiguous [v, 3] float32 device tensor" % name)
+    if not (isinstance(faces, torch.Tensor) and faces.device == vertices.device and faces.dtype in (torch.uint32, torch.int32) and faces.dim() == 2
+            and faces.shape[1] == 3 and faces.is_contiguous()):
+        raise ValueError("mesh.%s: faces must be a contiguous [n, 3] uint32 (or int32) tensor on the vertices' device" % name)
+    cv, ct = int(vertices.shape[0]), int(faces.shape[0])
+    if counts is None:
+        counts = torch.tensor([ct, ct, cv, cv], dtype=torch.int64).to(vertices.device)
+    elif not (isinstance(counts, torch.Tensor) and counts.device == vertices.device and counts.dtype in (torch.int64, torch.uint64) and counts.numel() == 4
+              and counts.is_contiguous()):
+        raise ValueError("mesh.%s: counts must be the extraction's four 64-bit counts on the vertices' device" % name)
+    return cv, ct, counts, torch.cuda.current_stream(vertices.device).cuda_stream
+
+
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+class Adjacency:
+    """build_adjacency()'s result: the device block and the mesh it belongs to (its faces, counts and capacities)"""
+
+    def __init__(self, block, faces, counts, capacity_vertices, capacity_triangles):
+        self.block, self.faces, self.counts = block, faces, counts
+        self.capacity_vertices, self.capacity_triangles = capacity_vertices, capacity_triangles
+
+
+def build_adjacency(ctx, vertices, faces, counts=None):
+    """vkv_mesh_adjacency on the current stream: per vertex its neighbour set and its faces, built once per mesh for smooth() and
+    vertex_normals() (``adjacency=``).  ``vertices`` [v, 3] float32 and ``faces`` [n, 3] torch.uint32 are device tensors as
+    Volume.extract_label_mesh_indexed / extract_isosurface_indexed return them; ``counts``: their int64 counts tensor when they were extracted
+    with ``capacity=`` (it is read on the device), None when every row is meant.  Only the vertices' number is used here."""
+    import torch
+    cv, ct, counts, stream = _device_mesh("build_adjacency", vertices, faces, counts)
+    block = torch.empty((adjacency_scratch_bytes(cv, ct) // 8,), dtype=torch.int64, device=vertices.device)
+    # an empty face list still gets a pointer: the call reads nothing through it
+    ctx.check(ctx.mesh_adjacency_rc(_ptr(faces) if ct else block.data_ptr(), ct, cv, counts.data_ptr(), block.data_ptr(), stream))
+    return Adjacency(block, faces, counts, cv, ct)
+
+
+def _adjacency_for(name, ctx, vertices, faces, counts, adjacency):
+    if adjacency is None:
+        return build_adjacency(ctx, vertices, faces, counts)
+    if adjacency.capacity_vertices != vertices.shape[0] or adjacency.capacity_triangles != faces.shape[0]:
+        raise ValueError("mesh.%s: the adjacency was built for another mesh" % name)
+    return adjacency
+
+
+def smooth(ctx, vertices, faces, counts=None, lam=0.5, mu=-0.53, iterations=10, pinned=None, adjacency=None):
+    """vkv_mesh_smooth on the current stream: ``iterations`` Taubin iterations (a pass with factor ``lam``, then one with ``mu``; ``mu`` None:
+    ``iterations`` passes of ``lam`` alone, plain Laplacian smoothing, which shrinks) of the uniform umbrella operator over the mesh's used
+    faces.  Returns the smoothed vertices as a new [v, 3] float32 device tensor (rows past the counts' vertices are copies); pinned to the bit,
+    no host wait.  A vertex shared by two bodies of a label mesh moves once, for both.  ``pinned``: None or a [v] bool / uint8 tensor (or
+    array: boundary_vertices()), non-zero rows stay.  ``adjacency``: build_adjacency() of the same mesh, to build it once for several calls."""
+    import torch
+    cv, ct, counts, stream = _device_mesh("smooth", vertices, faces, counts)
+    adjacency = _adjacency_for("smooth", ctx, vertices, faces, counts, adjacency)
+    if pinned is not None:
+        pinned = torch.as_tensor(np.ascontiguousarray(pinned).astype(np.uint8) if isinstance(pinned, np.ndarray) else pinned)
+        pinned = pinned.to(device=vertices.device, dtype=torch.uint8).contiguous()
+        if pinned.shape != (cv,):
+            raise ValueError("mesh.smooth: pinned must have one entry per vertex row (%d), not %s" % (cv, tuple(pinned.shape)))
+    factors = [float(lam)] * int(iterations) if mu is None else [float(lam), float(mu)] * int(iterations)
+    out, swap = vertices.clone(), torch.empty_like(vertices)
+    if cv:
+        ctx.check(ctx.mesh_smooth_rc(out.data_ptr(), swap.data_ptr(), cv, adjacency.counts.data_ptr(), adjacency.block.data_ptr(), _ptr(pinned), factors,
+                                     stream))
+    return out
+
+
+def vertex_normals(ctx, vertices, faces, counts=None, face_labels=None, label=0, adjacency=None):
+    """vkv_mesh_vertex_normals on the current stream: a new [v, 3] float32 device tensor, per vertex the sum of (v1 - v0) x (v2 - v0) over its
+    used faces (area-weighted, NOT normalised, zero where nothing contributes; rows past the counts' vertices are zero); pinned to the bit,
+    no host wait.  ``face_labels`` ([n] torch.uint32) with ``label``: only the faces of that body, which gives an interface vertex of a label
+    mesh that body's outward normal; over all faces such a vertex sums to exactly zero.  Valid for the positions given: call it after
+    smooth().  ``adjacency``: build_adjacency() of the same mesh."""
+    import torch
+    cv, ct, counts, stream = _device_mesh("vertex_normals", vertices, faces, counts)
+    adjacency = _adjacency_for("vertex_normals", ctx, vertices, faces, counts, adjacency)
+    if face_labels is not None and not (isinstance(face_labels, torch.Tensor) and face_labels.device == vertices.device and face_labels.shape == (ct,)
+                                        and face_labels.dtype in (torch.uint32, torch.int32) and face_labels.is_contiguous()):
+        raise ValueError("mesh.vertex_normals: face_labels must be a contiguous [n] uint32 tensor on the vertices' device")
+    normals = torch.zeros_like(vertices)
+    if cv:
+        ctx.check(ctx.mesh_vertex_normals_rc(vertices.data_ptr(), _ptr(faces) if ct else adjacency.block.data_ptr(), _ptr(face_labels) if ct else None,
+                                             label, cv, ct, adjacency.counts.data_ptr(), adjacency.block.data_ptr(), normals.data_ptr(), stream))
+    return normals
+
+
+def boundary_vertices(faces, n_vertices):
+    """[n_vertices] bool, on the host: the vertices on an edge that exactly one face holds, i.e. the rim of an open surface: where a body
+    leaves the box (the extractors leave the box's faces open) and the seams of a box-by-box extraction.  Pin them in smooth(), or the rim
+    shrinks and the seams part.  ``faces`` [n, 3]: any integer array (a tensor's ``.cpu().numpy()``); faces that name a vertex at or past
+    n_vertices (a truncated extraction) are not used, as on the device."""
+    f = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    f = f[(f < int(n_vertices)).all(axis=1)]
+    e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+    e = e[e[:, 0] != e[:, 1]]
+    mask = np.zeros(int(n_vertices), bool)
+    if len(e):
+        edges, n = np.unique(e, axis=0, return_counts=True)
+        mask[edges[n == 1].reshape(-1)] = True
+    return mask
