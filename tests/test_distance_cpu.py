@@ -9,6 +9,7 @@ memory.  tests/test_gpu_distance.py holds the kernels to edt2_np() and select_by
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -262,3 +263,21 @@ def test_kernels_use_no_scratch_memory(tmp_path):
     assert len(kernels) == 4
     for k, v in kernels.items():
         assert v.get("ScratchSize") == 0, (k, v)
+    # the row walk is edt_passes.hpp's: no more registers than the copy it replaced had
+    assert [v["NumVgprs"] for k, v in kernels.items() if "k_edt_x" in k][0] <= 18, kernels
+
+
+def test_the_pass_schedule_tiles_the_scratch_block_and_ends_in_the_callers_buffer_under_asan_and_ubsan(tmp_path):
+    """EdtSchedule, which vkv_distance_transform_scratch_bytes and the launchers of the three exact transforms share: its size against
+    8 entries + 4 n, its pointers against the size, the passes' buffers in all four combinations of (y runs, z runs), and the boxes it rejects
+    (tests/edt_schedule_driver.cpp, the header's host pass: no GPU, no kernel)"""
+    hipcc = T.HIPCC if os.path.exists(T.HIPCC) else shutil.which("hipcc")
+    if hipcc is None:
+        pytest.skip("no hipcc")
+    exe = tmp_path / "edt_schedule_driver"
+    cmd = [hipcc, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "--cuda-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+           "-fno-sanitize-recover=undefined", "-I", T.CSRC, os.path.join(ROOT, "tests", "edt_schedule_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:]
+    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "edt schedule ok", r.stdout[-2000:]

@@ -2,8 +2,8 @@
 edt2_weighted_brute_np() (brute force over the target voxels) and edt2_weighted_np() (a min-plus pass per axis with (w d)^2, the reference of
 tests/test_gpu_distance_weighted.py), both scipy.ndimage.distance_transform_edt(sampling=weights) squared (read exactly, through
 return_indices) and, with weights (1, 1, 1), tests/test_distance_cpu.py's edt2_np; the kernel's envelope pass restated in Python
-(envelope_line_py: the stack packed into the output line, the top entry held aside, every intermediate held to its stated range) against
-the min-plus line; the bound predicate and the x pass's reach of host_arith.cpp in a stand-alone program under AddressSanitizer and
+(tests/edt_envelope_ref.py with the distance carry: the stack packed into the output line, the top entry held aside, every intermediate held
+to its stated range) against the min-plus line; the bound predicate and the x pass's reach of host_arith.cpp in a stand-alone program under AddressSanitizer and
 UndefinedBehaviorSanitizer (tests/edt_weights_driver.cpp); the entry point declared, exported and bound; Volume.spacing_weights; the
 listing of edt_envelope.hip; and weights=None staying on vkv_distance_transform.  No device is touched."""
 import ctypes as C
@@ -18,6 +18,7 @@ import torch
 
 from tests import helpers as T
 from tests.test_binding_cpu import HANDLE, context
+from tests.edt_envelope_ref import DistanceCarry, envelope_line_py
 from tests.test_distance_cpu import NONE, TO_INSIDE, TO_OUTSIDE, edt2_np, random_mask_volume, targets_np
 from vkvolume_amd import abi, lib, volume as V
 
@@ -111,59 +112,6 @@ def test_unit_weights_are_the_unweighted_statement_and_no_target_gives_the_limit
 
 
 # ---- the envelope pass of edt_envelope.hip ------------------------------------------------------------------------------------------------
-def envelope_line_py(g, w, limit):
-    """k_env_axis on one line, statement by statement: `g` the line of the source buffer (values <= limit), the returned list the line of the
-    destination buffer, which holds the stack (entry k = s | t << 15 at position k) until the backward sweep overwrites it.  Every
-    intermediate is held to the range the kernel's types give it."""
-    n = len(g)
-    dst = [0xA5A5A5A5] * n
-
-    def f(p, i, gi):
-        wd = w * abs(p - i)
-        assert wd <= 65535 and gi < 2 ** 32
-        return gi + wd * wd        # < 2^33: 64 bits in the kernel
-
-    k = s = t = gs = 0
-    for u in range(n):
-        gu = g[u]
-        if gu >= limit:
-            continue
-        while k > 0 and f(t, s, gs) > f(t, u, gu):
-            k -= 1
-            if k > 0:
-                e = dst[k - 1]
-                s, t = e & 0x7fff, e >> 15
-                gs = g[s]
-        if k == 0:
-            t = 0
-        else:
-            num, den = gu + w * w * (u * u - s * s) - gs, 2 * w * w * (u - s)
-            assert 0 <= num < 2 ** 34 and 0 < den < 2 ** 33 and u * u < 2 ** 32 and num // den >= t, (num, den, t)
-            q = num // den
-            if q >= n - 1:
-                continue
-            t = q + 1
-        s, gs = u, gu
-        assert k <= u and t >= k and t < 2 ** 16 and s <= 32767 and t <= 32767, (k, u, t)        # entry k lies at or below u and starts at or above k
-        dst[k] = s | t << 15
-        k += 1
-    for u in range(n - 1, -1, -1):
-        out = limit
-        if k > 0:
-            assert t <= u and k - 1 <= t, (k, t, u)        # the top covers u, and the store at u hits no entry below the top
-            out = min(limit, f(u, s, gs))
-            if u == t:
-                k -= 1
-                if k > 0:
-                    assert k - 1 < u
-                    e = dst[k - 1]
-                    s, t = e & 0x7fff, e >> 15
-                    gs = g[s]
-        dst[u] = out
-    assert k == 0
-    return dst
-
-
 def min_plus_line(g, w, limit):
     n = len(g)
     return [min([limit] + [g[i] + (w * (p - i)) ** 2 for i in range(n) if g[i] < limit]) for p in range(n)]
@@ -185,7 +133,7 @@ def test_the_envelope_pass_in_python_is_the_min_plus_line():
             if kind != "no cap":
                 share = 0.5 if kind == "mixed" else 0.9
                 g = [limit if rng.random() < share else v for v in g]
-        assert envelope_line_py(g, w, limit) == min_plus_line(g, w, limit), (g, w, limit)
+        assert envelope_line_py(g, w, DistanceCarry(limit)) == min_plus_line(g, w, limit), (g, w, limit)
 
 
 def test_the_envelope_pass_at_the_longest_line_and_the_largest_values():
@@ -195,7 +143,7 @@ def test_the_envelope_pass_at_the_longest_line_and_the_largest_values():
         line = [limit] * n
         for i, v in g.items():
             line[i] = v
-        got = np.array(envelope_line_py(line, w, limit), np.int64)
+        got = np.array(envelope_line_py(line, w, DistanceCarry(limit)), np.int64)
         p = np.arange(n, dtype=np.int64)
         want = np.full(n, limit, np.int64)
         for i, v in g.items():
@@ -203,7 +151,7 @@ def test_the_envelope_pass_at_the_longest_line_and_the_largest_values():
         assert np.array_equal(got, want), (w, limit, g)
     # every position on the stack: a line of zeros, and a parabola-shaped line whose every entry survives
     for line in ([0] * 3000, [(i - 1500) ** 2 // 7 for i in range(3000)]):
-        assert envelope_line_py(line, 1, NONE) == min_plus_line(line, 1, NONE)
+        assert envelope_line_py(line, 1, DistanceCarry(NONE)) == min_plus_line(line, 1, NONE)
 
 
 # ---- the bound predicate and the reach --------------------------------------------------------------------------------------------------
@@ -279,6 +227,9 @@ def test_the_envelope_kernels_use_no_scratch_memory(tmp_path):
     assert len(kernels) == 2        # k_edt_bits is edt.hip's: declared here, defined there
     for k, v in kernels.items():
         assert v.get("ScratchSize") == 0, (k, v)
+    # the walk and the envelope pass are edt_passes.hpp's: no more registers than the copies they replaced had
+    for name, vgprs in (("k_env_x", 18), ("k_env_axis", 22)):
+        assert [v["NumVgprs"] for k, v in kernels.items() if name in k][0] <= vgprs, (name, kernels)
 
 
 # ---- weights=None keeps the old path ------------------------------------------------------------------------------------------------------

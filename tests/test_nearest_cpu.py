@@ -2,7 +2,7 @@
 nearest_brute_np() is the definition (an int64 distance matrix from the voxels to the targets, the targets in box-linear order, argmin's
 first occurrence = the smallest box-linear index); nearest_separable_np() restates the kernels pass by pass (min-plus per line with a
 first-occurrence argmin per axis, the intermediate formats x' and y' << 15 | x', the reference of tests/test_gpu_nearest.py); near_line_py()
-restates k_near_axis statement by statement with the stack-in-line inequalities as assertions.  The two restatements are held to the
+is tests/edt_envelope_ref.py with the feature carry: k_near_axis statement by statement with the stack-in-line inequalities as assertions.  The two restatements are held to the
 definition on seeded small boxes, among them contents BUILT FOR TIES, which are asserted to tie: the separable tie argument is proved here,
 not assumed.  Then scipy's distance_transform_edt(return_indices=True), the numpy statements of propagate / expand_labels / split_bodies
 with scipy.ndimage, one fixed bridge scene, the entry points declared, exported and bound, and the listing of nearest.hip.  No device is
@@ -18,6 +18,7 @@ import torch
 
 from tests import helpers as T
 from tests.test_binding_cpu import HANDLE, context
+from tests.edt_envelope_ref import feature_line_py as near_line_py
 from tests.test_distance_cpu import NONE, TO_INSIDE, TO_OUTSIDE, ball_structure, inside_np, random_mask_volume, targets_np
 from tests.test_distance_weighted_cpu import edt2_weighted_np
 from vkvolume_amd import abi, lib, volume as V
@@ -93,67 +94,7 @@ def nearest_separable_np(vol_dhw, iso, weights, target=TO_INSIDE, limit=None, bo
     return feat.astype(np.uint32), np.minimum(val, limit).astype(np.uint32)
 
 
-# ---- k_near_axis on one line ------------------------------------------------------------------------------------------------------------
-def near_line_py(src, w, limit, g_of, encode):
-    """k_near_axis on one line, statement by statement: `src` the line of the source feature buffer, g_of(feature) the lane's near_g,
-    encode(s, feature) what the backward sweep writes; returns (the line of the destination buffer, the line of d_dist2).  The destination
-    holds the stack (entry k = s | t << 15 at position k) until the backward sweep overwrites it"""
-    n = len(src)
-    dst, dist = [0xA5A5A5A5] * n, [0xA5A5A5A5] * n
-
-    def f(p, i, gi):
-        wd = w * abs(p - i)
-        assert wd <= 65535 and gi < 2 ** 32
-        return gi + wd * wd        # < 2^33: 64 bits in the kernel
-
-    k = s = t = gs = fs = 0
-    for u in range(n):
-        fu = src[u]
-        if fu == NONE:
-            continue
-        g = g_of(fu)
-        assert g < limit        # the pass before stored no feature otherwise
-        while k > 0 and f(t, s, gs) > f(t, u, g):
-            k -= 1
-            if k > 0:
-                e = dst[k - 1]
-                s, t = e & 0x7fff, e >> 15
-                fs = src[s]
-                gs = g_of(fs)
-        if k == 0:
-            t = 0
-        else:
-            num, den = g + w * w * (u * u - s * s) - gs, 2 * w * w * (u - s)
-            assert 0 <= num < 2 ** 34 and 0 < den < 2 ** 33 and u * u < 2 ** 32 and num // den >= t, (num, den, t)
-            q = num // den
-            if q >= n - 1:
-                continue
-            t = q + 1
-        s, gs, fs = u, g, fu
-        assert k <= u and t >= k and s <= 32767 and t <= 32767, (k, u, t)        # entry k lies at or below u and starts at or above k
-        dst[k] = s | t << 15
-        k += 1
-    for u in range(n - 1, -1, -1):
-        out, d2 = NONE, limit
-        if k > 0:
-            assert t <= u and k - 1 <= t, (k, t, u)        # the top covers u, and the store at u hits no entry below the top
-            v = f(u, s, gs)
-            if v < limit:
-                d2, out = v, encode(s, fs)
-                assert out < NONE
-            if u == t:
-                k -= 1
-                if k > 0:
-                    assert k - 1 < u
-                    e = dst[k - 1]
-                    s, t = e & 0x7fff, e >> 15
-                    fs = src[s]
-                    gs = g_of(fs)
-        dst[u], dist[u] = out, d2
-    assert k == 0
-    return dst, dist
-
-
+# ---- k_near_axis on whole boxes -----------------------------------------------------------------------------------------------------------
 def nearest_kernels_py(vol_dhw, iso, weights, target=TO_INSIDE, limit=None, box=None):
     """the launcher of nearest.hip with near_line_py for the y and z passes (the x pass, a bit walk, is nearest_separable_np's)"""
     limit = NONE if limit is None else int(limit)
@@ -553,3 +494,6 @@ def test_the_nearest_kernels_use_no_scratch_memory(tmp_path):
     assert len(kernels) == 4        # k_edt_bits is edt.hip's: declared here, defined there
     for k, v in kernels.items():
         assert v.get("ScratchSize") == 0, (k, v)
+    # the envelope pass is edt_passes.hpp's: no more registers than the copy it replaced had (k_near_x keeps its own walk)
+    for name, vgprs in (("k_near_x", 19), ("k_near_axisILi1E", 26), ("k_near_axisILi2E", 28)):
+        assert [v["NumVgprs"] for k, v in kernels.items() if name in k][0] <= vgprs, (name, kernels)

@@ -9,25 +9,21 @@
 // CAPPED at `limit` (0xffffffff = VKV_DISTANCE_NONE when unlimited): min(limit, min_u (a_u + b)) = min(limit, min_u (min(limit, a_u) + b))
 // for b >= 0, so capping after every pass gives the capped result, and the cap doubles as "no target in this row / column".
 //   k_edt_bits   target bits by wave ballot, one 64-bit word per entry (scratch).  Reads the volume, 1 B per voxel.
-//   k_edt_x      g(i) = min(limit, dx^2), dx = the distance along the voxel's own row to the nearest target bit: clz / ctz in the lane's own
-//                word, then whole words outward.  Reads the bits, writes buffer P0.
+//   k_edt_x      g(i) = min(limit, dx^2), dx = the distance along the voxel's own row to the nearest target bit: row_walk of edt_passes.hpp,
+//                which edt_envelope.hip's x kernel calls too.  Reads the bits, writes the schedule's first buffer.
 //   k_edt_axis   out(p) = min over p' of the line of (g(p') + (p - p')^2), for y (stride bw) and then for z (stride bw bh): from best = g(p)
 //                it looks at p - d and p + d for d = 1, 2, ... while d^2 < best, four offsets at a time.  Reads one buffer, writes the OTHER (a line's outputs need
 //                its inputs: not in place).  A pass over an axis of length 1 is not launched.
-// BUFFERS.  The two 4-byte buffers are d_dist2 and the scratch block's; the x pass writes the one that makes the last pass land in d_dist2:
-// passes = 1 + (bh > 1) + (bd > 1), P0 = d_dist2 when that is odd.  Every pass writes every element of its output, so nothing depends on what
-// the buffers held before, and two runs give the same bytes.
-// LOOP BOUNDS.  k_edt_x walks words from the lane's own to the word of the window's end, the window being the row cut to +-reach, reach =
-// ceil(sqrt(limit)) (65536 when unlimited): at most min(bw, reach) / 64 + 2 words per side.  k_edt_axis ends at the latest when neither p - d
+// BUFFERS.  The two 4-byte buffers are d_dist2 and the scratch block's, dealt out by EdtSchedule (edt_passes.hpp), which the three exact
+// transforms share: the x pass writes the one that makes the last pass land in d_dist2.
+// LOOP BOUNDS.  k_edt_x: row_walk's, with reach = ceil(sqrt(limit)) (65536 when unlimited).  k_edt_axis ends at the latest when neither p - d
 // nor p + d lies in the line: d < len <= 32768 rounds.  No lane waits for another lane, wave or workgroup; no atomics.
 // NO OVERFLOW.  Offsets along an axis are at most 32767, their squares at most 2^30 - 2^16 + 1; a true distance is at most 3 x 32767^2 =
 // 3221028867 < 2^32 - 1.  No sum is formed before it is known to fit: a candidate g + d^2 replaces best only after g < best - d^2 was seen,
 // with d^2 < best, so the difference does not wrap, a "none" g (the cap) never passes, and g + d^2 < best <= 2^32 - 1.  Box-linear
 // indices: i - d stride and i + d stride lie in the line, hence in [0, n), n <= 2^32 - 1.
 // No kernel uses scratch memory (tests/test_distance_cpu.py reads the listing).
-#include <utility>
-
-#include "box_domain.hpp"
+#include "edt_passes.hpp"
 
 using namespace vkv;
 
@@ -42,53 +38,13 @@ __global__ void __launch_bounds__(256) k_edt_bits(BoxLinear G, uint32_t outside,
 		bits[v.i >> 6] = m;
 }
 
-// the squared distance along the row, capped: the row's bits are [i - x, i - x + bw), of which [i - min(x, reach), i + min(bw - 1 - x, reach)]
-// is searched; a target further than reach = ceil(sqrt(limit)) away gives the cap anyway
+// the squared distance along the row, capped: a target further than reach = ceil(sqrt(limit)) away gives the cap anyway
 __global__ void __launch_bounds__(256) k_edt_x(BoxLinear G, const uint64_t *__restrict__ bits, uint32_t *__restrict__ out, uint32_t limit, uint32_t reach)
 {
 	const BoxVoxel v = box_voxel(G);
 	if (!v.valid)        // no wave-wide operation below
 		return;
-	const uint32_t lo = v.i - min(v.x, reach), hi = v.i + min(G.bw - 1u - v.x, reach);        // lo <= i <= hi < n
-	uint32_t       dx = 0xffffffffu;
-	{        // the highest target bit in [lo, i]
-		uint32_t w = v.i >> 6;
-		uint64_t m = bits[w] & (~0ull >> (63u - (v.i & 63u)));
-		for (;;)        // w falls to lo >> 6 at the latest
-		{
-			const bool last = w == lo >> 6;
-			if (last)
-				m &= ~0ull << (lo & 63u);
-			if (m)
-			{
-				dx = v.i - (w * 64u + 63u - (uint32_t) __clzll((long long) m));
-				break;
-			}
-			if (last)
-				break;
-			m = bits[--w];
-		}
-	}
-	if (dx != 0u)
-	{        // the lowest target bit in [i, end]: nothing further than dx - 1 can win.  end <= hi < n: no wrap
-		const uint32_t end = v.i + min(hi - v.i, dx - 1u);
-		uint32_t       w   = v.i >> 6;
-		uint64_t       m   = bits[w] & (~0ull << (v.i & 63u));
-		for (;;)        // w rises to end >> 6 at the latest
-		{
-			const bool last = w == end >> 6;
-			if (last)
-				m &= ~0ull >> (63u - (end & 63u));
-			if (m)
-			{
-				dx = w * 64u + (uint32_t) __builtin_ctzll(m) - v.i;
-				break;
-			}
-			if (last)
-				break;
-			m = bits[++w];
-		}
-	}
+	const uint32_t dx = row_walk(G, v, bits, reach);
 	// dx <= 32767 where a target was found: dx^2 < 2^30
 	out[v.i] = dx == 0xffffffffu ? limit : min(dx * dx, limit);
 }
@@ -139,71 +95,46 @@ __global__ void __launch_bounds__(256) k_edt_select(const uint8_t *src, uint8_t 
 	});
 }
 
-// the shared plan and the transform's own limit: no box axis above 32768 (NO OVERFLOW above)
-static bool edt_plan(VkvExtent3D e, const VkvBox *box, BoxLinearPlan &p)
-{
-	if (!box_linear_plan(e, box, p))
-		return false;
-	const VkvBox b = whole_or(e, box);
-	return b.width <= 32768u && b.height <= 32768u && b.depth <= 32768u;
-}
-
 namespace vkv
 {
 
-// [target bits: u64 x entries][the second distance buffer: u32 x voxels], an entry = 64 voxels: 4 bytes and one bit per voxel, the bits
-// rounded up to 8 bytes; 0: the extent and box are not accepted
-size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box)
+size_t edt_scratch_bytes(VkvExtent3D e, const VkvBox *box)        // 0: the extent and box are not accepted
 {
-	BoxLinearPlan p;
-	if (!edt_plan(e, box, p))
-		return 0;
-	return 8 * (size_t) p.entries + 4 * (size_t) p.n;
+	EdtSchedule S;
+	return S.lay(e, box, nullptr, nullptr) ? S.bytes() : 0;
 }
 
 bool edt_launch_ok(VkvExtent3D e, const VkvBox *box)
 {
-	BoxLinearPlan p;
-	return edt_plan(e, box, p);
+	EdtSchedule S;
+	return S.lay(e, box, nullptr, nullptr);
 }
 
 int launch_distance_transform(vkv_ctx *ctx, const uint8_t *d_vol, VkvExtent3D e, const VkvBox &b, float iso, int target, uint32_t limit, void *d_scratch,
                               uint32_t *d_dist2, hipStream_t s)
 {
-	BoxLinearPlan p;
-	if (!edt_plan(e, &b, p))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "distance_transform: a box of more than 2^32 - 1 voxels or an axis above 32768");
-	uint64_t     *bits  = static_cast<uint64_t *>(d_scratch);
-	uint32_t     *other = reinterpret_cast<uint32_t *>(bits + p.entries);
-	const BoxLinear G   = box_linear(d_vol, e, b, p, iso);
+	EdtSchedule S;
+	if (const int rc = edt_schedule(ctx, "distance_transform", e, b, d_scratch, d_dist2, S))
+		return rc;
+	const BoxLinear G   = box_linear(d_vol, e, b, S.p, iso);
 	uint32_t      reach = 0;        // the smallest r with r^2 >= limit: at most 65536
 	while ((uint64_t) reach * reach < limit)
 		++reach;
-	const bool y = b.height > 1u, z = b.depth > 1u;
-	uint32_t  *cur = (y != z) ? other : d_dist2, *nxt = (y != z) ? d_dist2 : other;        // one further pass: it starts in the scratch block
-	hipLaunchKernelGGL(k_edt_bits, dim3(p.wgs), dim3(256), 0, s, G, target == VKV_DISTANCE_TO_OUTSIDE ? 1u : 0u, bits);
-	hipLaunchKernelGGL(k_edt_x, dim3(p.wgs), dim3(256), 0, s, G, bits, cur, limit, reach);
-	if (y)
-	{
-		hipLaunchKernelGGL(k_edt_axis, dim3(p.wgs), dim3(256), 0, s, p.n, b.width, b.height, cur, nxt);
-		std::swap(cur, nxt);
-	}
-	if (z)
-	{
-		hipLaunchKernelGGL(k_edt_axis, dim3(p.wgs), dim3(256), 0, s, p.n, b.width * b.height, b.depth, cur, nxt);
-		std::swap(cur, nxt);
-	}
-	return check_launch(ctx, "distance_transform");        // cur == d_dist2
+	hipLaunchKernelGGL(k_edt_bits, dim3(S.p.wgs), dim3(256), 0, s, G, target == VKV_DISTANCE_TO_OUTSIDE ? 1u : 0u, S.bits);
+	hipLaunchKernelGGL(k_edt_x, dim3(S.p.wgs), dim3(256), 0, s, G, S.bits, S.cur, limit, reach);
+	S.axes([&](const uint32_t *src, uint32_t *dst) { hipLaunchKernelGGL(k_edt_axis, dim3(S.p.wgs), dim3(256), 0, s, S.p.n, b.width, b.height, src, dst); },
+	       [&](const uint32_t *src, uint32_t *dst) { hipLaunchKernelGGL(k_edt_axis, dim3(S.p.wgs), dim3(256), 0, s, S.p.n, b.width * b.height, b.depth, src, dst); });
+	return check_launch(ctx, "distance_transform");
 }
 
 int launch_select_by_distance(vkv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, VkvExtent3D e, const VkvBox &b, const uint32_t *d_dist2, uint32_t lo,
                               uint32_t hi, uint32_t fill, hipStream_t s)
 {
-	BoxLinearPlan p;
-	if (!edt_plan(e, &b, p))
-		return set_error(ctx, VKV_E_UNSUPPORTED, "select_by_distance: a box of more than 2^32 - 1 voxels or an axis above 32768");
-	const BoxLinear G = box_linear(d_src, e, b, p, 0.0f);        // thr is not read
-	hipLaunchKernelGGL(k_edt_select, dim3(p.wgs), dim3(256), 0, s, d_src, d_dst, G, d_dist2, lo, hi, fill);
+	EdtSchedule S;        // for its plan and its limits: no pass is scheduled
+	if (const int rc = edt_schedule(ctx, "select_by_distance", e, b, nullptr, nullptr, S))
+		return rc;
+	const BoxLinear G = box_linear(d_src, e, b, S.p, 0.0f);        // thr is not read
+	hipLaunchKernelGGL(k_edt_select, dim3(S.p.wgs), dim3(256), 0, s, d_src, d_dst, G, d_dist2, lo, hi, fill);
 	return check_launch(ctx, "select_by_distance");
 }
 
