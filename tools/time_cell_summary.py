@@ -18,11 +18,11 @@ import argparse
 import os
 import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools.measure import fmt as fmt_ms, run, stream as st, wall_ms  # noqa: E402
 from vkvolume_amd import abi, lib, volume as V  # noqa: E402
 
 SCENES = {
@@ -32,26 +32,8 @@ SCENES = {
 }
 
 
-def st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def timed(fn, moves, repeats, warmup=2):
-    for _ in range(warmup):
-        fn()
-    runs = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(moves):
-            fn()
-        torch.cuda.synchronize()
-        runs.append((time.perf_counter() - t0) * 1e3 / moves)
-    return runs
-
-
 def fmt(runs):
-    return "%7.3f [%7.3f .. %7.3f]" % (statistics.median(runs), min(runs), max(runs))
+    return fmt_ms(runs, 7, 3)
 
 
 def measure(ctx, name, block, imins, moves, repeats):
@@ -62,7 +44,7 @@ def measure(ctx, name, block, imins, moves, repeats):
     V.ComputeGradientMap(ctx).compute(v, v.get_transfer_function_uniform())
     v.update_transfer_function(skip)
     v.build_cell_summary()
-    build = timed(lambda: v.build_cell_summary(), max(1, moves // 2), repeats, warmup=1)
+    build = wall_ms(lambda: v.build_cell_summary(), max(1, moves // 2), repeats, warmup=1)
     me = v.map_extent
     n_cells = me.width * me.height * me.depth
     occ = torch.empty(n_cells, dtype=torch.uint8, device="cuda")
@@ -80,11 +62,11 @@ def measure(ctx, name, block, imins, moves, repeats):
             ctx.occupancy_map_from_summary(v.cell_summary.data_ptr(), v.volume.data_ptr(), v.gradient.data_ptr(), v.transfer_function.data_ptr(), tf,
                                            v.extent, occ.data_ptr(), me, unres.data_ptr(), st())
 
-        t_ov, t_os = timed(occ_voxels, moves, repeats), timed(occ_summary, moves, repeats)
+        t_ov, t_os = wall_ms(occ_voxels, moves, repeats, warmup=2), wall_ms(occ_summary, moves, repeats, warmup=2)
         torch.cuda.synchronize()
         share = int(unres.item()) / n_cells
-        t_uv = timed(lambda: v.update_transfer_function(skip), moves, repeats)
-        t_us = timed(lambda: v.update_transfer_function_from_summary(skip), moves, repeats)
+        t_uv = wall_ms(lambda: v.update_transfer_function(skip), moves, repeats, warmup=2)
+        t_us = wall_ms(lambda: v.update_transfer_function_from_summary(skip), moves, repeats, warmup=2)
         rows.append("    imin %.2f  occ voxels %s  summary %s (x%.2f)  update voxels %s  summary %s  unresolved %.4f%%" % (
             imin, fmt(t_ov), fmt(t_os), statistics.median(t_os) / statistics.median(t_ov), fmt(t_uv), fmt(t_us), 100.0 * share))
         print(rows[-1], flush=True)
@@ -102,25 +84,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# ms per call: median [min .. max] of %d blocks of %d calls (wall clock, device synchronised around each block)" % (a.repeats, a.moves),
-             "# %s, %s" % (torch.cuda.get_device_name(0), lib.load().vkv_version().decode())]
-    imins = [float(x) for x in a.imins.split(",")]
-    for name in a.scenes.split(","):
-        for block in (int(b) for b in a.blocks.split(",")):
-            try:
-                lines += measure(ctx, name, block, imins, a.moves, a.repeats)
-            except torch.cuda.OutOfMemoryError as e:
-                lines.append("%-9s block %d skipped: %s" % (name, block, str(e).splitlines()[0]))
-                torch.cuda.empty_cache()
-            print(lines[-1], flush=True)
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
-    ctx.close()
+
+    def plain(ctx):
+        lines = ["# ms per call: median [min .. max] of %d blocks of %d calls (wall clock, device synchronised around each block)" % (a.repeats, a.moves),
+                 "# %s, %s" % (torch.cuda.get_device_name(0), lib.load().vkv_version().decode())]
+        imins = [float(x) for x in a.imins.split(",")]
+        for name in a.scenes.split(","):
+            for block in (int(b) for b in a.blocks.split(",")):
+                try:
+                    lines += measure(ctx, name, block, imins, a.moves, a.repeats)
+                except torch.cuda.OutOfMemoryError as e:
+                    lines.append("%-9s block %d skipped: %s" % (name, block, str(e).splitlines()[0]))
+                    torch.cuda.empty_cache()
+                print(lines[-1], flush=True)
+        return lines
+
+    run(a, plain)
+    print()  # the report has always ended on an empty line
 
 
 if __name__ == "__main__":

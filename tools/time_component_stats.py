@@ -27,8 +27,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
+from tools.measure import alternate, fmt, run, stream as st  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
 from vkvolume_amd import abi, lib, volume as V  # noqa: E402
 
 
@@ -106,16 +106,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "component_stats_times.txt")
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# tools/time_component_stats.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
-        args.isos, args.calls, args.repeats)]
-    measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
-    ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+
+    def plain(ctx):
+        lines = ["# tools/time_component_stats.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
+            args.isos, args.calls, args.repeats)]
+        measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
+        return lines
+
+    run(args, plain, times_name="component_stats_times.txt")
 
 
 if __name__ == "__main__":

@@ -19,13 +19,9 @@ call of every variant; median [min .. max]).
                                                                  so that no mean mixes scenes or kinds
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import torch
@@ -33,9 +29,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.benchmark_sweep import PRESETS, preset_seed  # noqa: E402
-from tools.time_filter import SALT, alternate, fmt, st  # noqa: E402
-from vkvolume_amd import abi, lib, volume as V  # noqa: E402
+from tools.measure import alternate, fmt, kernel_name, kernel_stats, run, stream as st  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
+from vkvolume_amd import lib, volume as V  # noqa: E402
 
 
 def time_volume(ctx, v, tf, isos, calls, repeats, out, yardsticks):
@@ -113,19 +109,6 @@ def measure(ctx, isos, calls, repeats, out, cpu):
                 out.append("  iso %.2f, connectivity %d: %8.1f ms  (%d components)" % (iso, conn, 1e3 * (time.perf_counter() - t), k))
 
 
-def scene_volume(ctx, scene):
-    """(Volume, iso of the salt scene or None)"""
-    if scene == "c3":
-        return bench.build_scene(ctx, "c3")[0], None
-    preset = PRESETS[0]
-    extent = preset[1]
-    shells, tq, noise, imin = SALT
-    s = V.Volume(ctx)
-    s.options = abi.VolumeOptions(intensity_min=imin, intensity_max=preset[3], gradient_min=preset[4], gradient_max=preset[5])
-    s.load_synthetic(extent, kind=1 | (shells << 8) | (tq << 16) | noise, seed=preset_seed(extent), distance_map_block_size=4)
-    return s, imin
-
-
 def one_case(ctx, scene, iso, conn, kind, calls):
     """the child of --rocprof: ONE scene, iso, connectivity and kind of call (dense), and nothing else that launches a k_cc_ kernel.  The full
     call takes a capacity of one size per voxel, so that no counting call is needed to size it."""
@@ -162,18 +145,10 @@ def rocprof(args):
              "# count = vkv_label_components without sizes; full = with sizes, followed by vkv_select_components (k_cc_select, not part of the sum)."]
     for scene, iso, conn, kind in cases:
         only = "%s:%s:%d:%s" % (scene, "salt" if iso is None else repr(iso), conn, kind)
-        with tempfile.TemporaryDirectory() as d:
-            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--only", only, "--calls", str(args.calls)]
-            subprocess.run(cmd, check=True, timeout=300, stdout=subprocess.DEVNULL)
-            rows = []
-            for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-                rows += list(csv.DictReader(open(f)))
         keep = {}
-        for r in rows:
+        for r in kernel_stats(__file__, ["--only", only, "--calls", str(args.calls)], 300, quiet=True):
             if "k_cc_" in r["Name"]:
-                name = (r["Name"][5:] if r["Name"].startswith("void ") else r["Name"]).split("(")[0]
-                keep[name] = (int(r["Calls"]), float(r["AverageNs"]) / 1e6)
+                keep[kernel_name(r["Name"])] = (int(r["Calls"]), float(r["AverageNs"]) / 1e6)
         lines.append("%s, iso %s, connectivity %d, %s" % (scene, "0.071" if iso is None else "%.2f" % iso, conn, kind))
         total = 0.0
         for base in LABEL_KERNELS + ("k_cc_select",):
@@ -195,26 +170,18 @@ def main():
     ap.add_argument("--only", default=None, help="scene:iso:connectivity:kind - one case alone, untimed (what --rocprof runs under the profiler)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "components_rocprof.txt" if args.rocprof else "components_times.txt")
-    if args.only:
+
+    def only(ctx):
         scene, iso, conn, kind = args.only.split(":")
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
         one_case(ctx, scene, None if iso == "salt" else float(iso), int(conn), kind, args.calls)
-        ctx.close()
-        return
-    if args.rocprof:
-        lines = rocprof(args)
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_components.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
             args.isos, args.calls, args.repeats)]
         measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines, not args.no_cpu)
-        ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), only, times_name="components_times.txt", rocprof_name="components_rocprof.txt")
 
 
 if __name__ == "__main__":

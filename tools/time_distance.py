@@ -19,13 +19,9 @@ call of every variant; median [min .. max]).
                                         limit, so that no mean mixes cases; with each kernel's algorithmic bytes and the GB/s they make
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import torch
@@ -33,15 +29,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, event_ms, fmt, st  # noqa: E402
+from tools.measure import alternate, event_ms, fmt, kernel_name, kernel_stats, run, stream as st  # noqa: E402
+from tools.scenes import TARGETS, limit_name, scene_volume  # noqa: E402
 from vkvolume_amd import abi, lib, volume as V  # noqa: E402
-
-TARGETS = (("inside", abi.DISTANCE_TO_INSIDE), ("outside", abi.DISTANCE_TO_OUTSIDE))
-
-
-def limit_name(limit):
-    return "none" if limit is None else str(limit)
 
 
 def time_volume(ctx, v, tf, isos, limits, calls, repeats, slow_ms, out, yardsticks):
@@ -154,18 +144,10 @@ def rocprof(args):
     for scene, iso, target, limit in cases:
         only = "%s:%s:%s:%s" % (scene, "salt" if iso is None else repr(iso), target, limit_name(limit))
         print("profiling " + only, file=sys.stderr, flush=True)
-        with tempfile.TemporaryDirectory() as d:
-            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--only", only, "--calls", str(args.calls)]
-            subprocess.run(cmd, check=True, timeout=300, stdout=subprocess.DEVNULL)
-            rows = []
-            for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-                rows += list(csv.DictReader(open(f)))
         keep = {}
-        for r in rows:
+        for r in kernel_stats(__file__, ["--only", only, "--calls", str(args.calls)], 300, quiet=True):
             if "k_edt_" in r["Name"]:
-                name = (r["Name"][5:] if r["Name"].startswith("void ") else r["Name"]).split("(")[0]
-                keep[name] = (int(r["Calls"]), float(r["AverageNs"]) / 1e6)
+                keep[kernel_name(r["Name"])] = (int(r["Calls"]), float(r["AverageNs"]) / 1e6)
         lines.append("%s, iso %s, to the %s, limit %s" % (scene, "0.071" if iso is None else "%.2f" % iso, target, limit_name(limit)))
         total = 0.0
         for base, per_voxel in KERNEL_BYTES:
@@ -192,27 +174,19 @@ def main():
     args = ap.parse_args()
     if args.limits is None:
         args.limits = "10,none" if args.rocprof else "2,10,101,none"
-    out_path = args.out or os.path.join(ROOT, "profiles", "distance_rocprof.txt" if args.rocprof else "distance_times.txt")
-    if args.only:
+
+    def only(ctx):
         scene, iso, target, limit = args.only.split(":")
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
         one_case(ctx, scene, None if iso == "salt" else float(iso), target, None if limit == "none" else int(limit), args.calls)
-        ctx.close()
-        return
-    if args.rocprof:
-        lines = rocprof(args)
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_distance.py --isos %s --limits %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
             args.isos, args.limits, args.calls, args.repeats)]
         measure(ctx, [float(t) for t in args.isos.split(",")], [None if t == "none" else int(t) for t in args.limits.split(",")], args.calls, args.repeats,
                 args.slow_ms, lines, not args.no_cpu)
-        ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), only, times_name="distance_times.txt", rocprof_name="distance_rocprof.txt")
 
 
 if __name__ == "__main__":

@@ -11,25 +11,19 @@ every variant; median [min .. max]); GB/s counts the 21 algorithmic bytes per vo
                                         target, limit and call, so that no mean mixes cases
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_distance import TARGETS, limit_name  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
+from tools.measure import alternate, fmt, kernel_name, kernel_stats, run, stream as st  # noqa: E402
+from tools.scenes import CASES, TARGETS, limit_name, scene_volume  # noqa: E402
 from vkvolume_amd import lib, volume as V  # noqa: E402
 
-CASES = (("inside", 2), ("inside", 10), ("inside", 101), ("inside", None), ("outside", None))
 CALLS = (("vkv_distance_transform", None), ("weighted (1, 1, 1)", (1, 1, 1)), ("weighted (2, 2, 5)", (2, 2, 5)))
 
 
@@ -95,18 +89,12 @@ def rocprof(args):
             for name, weights in CALLS:
                 only = "%s:%s:%s:%s" % (scene, target, limit_name(limit), "none" if weights is None else "%d,%d,%d" % weights)
                 print("profiling " + only, file=sys.stderr, flush=True)
-                with tempfile.TemporaryDirectory() as d:
-                    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                           "--only", only, "--calls", str(args.calls), "--iso", str(args.iso)]
-                    subprocess.run(cmd, check=True, timeout=300, stdout=subprocess.DEVNULL)
-                    rows = []
-                    for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-                        rows += list(csv.DictReader(open(f)))
+                rows = kernel_stats(__file__, ["--only", only, "--calls", str(args.calls), "--iso", str(args.iso)], 300, quiet=True)
                 lines.append("%s, to the %s, limit %s: %s" % (scene, target, limit_name(limit), name))
                 total = 0.0
                 for r in sorted(rows, key=lambda r: r["Name"]):
                     if "k_edt_" in r["Name"] or "k_env_" in r["Name"]:
-                        kernel = (r["Name"][5:] if r["Name"].startswith("void ") else r["Name"]).split("(")[0]
+                        kernel = kernel_name(r["Name"])
                         mean = float(r["AverageNs"]) / 1e6
                         lines.append("    %-12s %4d dispatches %10.4f ms" % (kernel, int(r["Calls"]), mean))
                         total += mean * (2.0 if kernel.endswith("_axis") else 1.0)
@@ -123,27 +111,19 @@ def main():
     ap.add_argument("--only", default=None, help="scene:target:limit:weights - one case alone, untimed (what --rocprof runs under the profiler)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "distance_weighted_rocprof.txt" if args.rocprof else "distance_weighted_times.txt")
-    if args.only:
+
+    def only(ctx):
         scene, target, limit, weights = args.only.split(":")
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
         one_case(ctx, scene, args.iso, target, None if limit == "none" else int(limit), None if weights == "none" else tuple(int(w) for w in weights.split(",")),
                  args.calls)
-        ctx.close()
-        return
-    if args.rocprof:
-        lines = rocprof(args)
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_distance_weighted.py --iso %s --calls %d --repeats %d on one MI355X (device events; median [min .. max]; x: against" % (
             args.iso, args.calls, args.repeats), "# vkv_distance_transform of the same block)"]
         measure(ctx, args.iso, args.calls, args.repeats, lines)
-        ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), only, times_name="distance_weighted_times.txt", rocprof_name="distance_weighted_rocprof.txt")
 
 
 if __name__ == "__main__":

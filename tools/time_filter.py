@@ -24,39 +24,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from tools.benchmark_sweep import PRESETS, preset_seed  # noqa: E402
-from vkvolume_amd import abi, lib, volume as V  # noqa: E402
+from tools.measure import alternate, fmt, run, stream as st  # noqa: E402
+from tools.scenes import SALT  # noqa: E402
+from vkvolume_amd import abi, volume as V  # noqa: E402
 
 KINDS = (("binomial", abi.FILTER_BINOMIAL3), ("median", abi.FILTER_MEDIAN3))
-SALT = (4, 200, 0, 0.071)  # tools/ess_crossover.py SCATTERED[1]: shells, thickness / 256, noise word, imin
-
-
-def st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def event_ms(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def fmt(runs):
-    return "%9.4f [%9.4f .. %9.4f]" % (statistics.median(runs), min(runs), max(runs))
-
-
-def alternate(kinds, calls, repeats):
-    for fn in kinds.values():
-        fn()
-    torch.cuda.synchronize()
-    runs = {k: [] for k in kinds}
-    for _ in range(repeats):
-        for k, fn in kinds.items():
-            runs[k].append(event_ms(fn, calls))
-    return runs
 
 
 def whole_volume_and_boxes(ctx, calls, repeats, out):
@@ -137,15 +109,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "filter_times.txt"))
     args = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# tools/time_filter.py --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.calls, args.repeats)]
-    whole_volume_and_boxes(ctx, args.calls, args.repeats, lines)
-    salt_scene(ctx, args.calls, args.repeats, lines)
-    ctx.close()
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+
+    def plain(ctx):
+        lines = ["# tools/time_filter.py --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.calls, args.repeats)]
+        whole_volume_and_boxes(ctx, args.calls, args.repeats, lines)
+        salt_scene(ctx, args.calls, args.repeats, lines)
+        return lines
+
+    run(args, plain)
 
 
 if __name__ == "__main__":

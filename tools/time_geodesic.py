@@ -14,21 +14,16 @@ call of every variant; median [min .. max]).
                                         per-kernel times under rocprofv3 --kernel-trace --stats (no counters): one child process per scene
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, event_ms, fmt, st  # noqa: E402
+from tools.measure import alternate, event_ms, fmt, kernel_name, kernel_stats, run, stream as st, wall_ms  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
 from vkvolume_amd import abi, geodesic, lib, volume as V  # noqa: E402
 
 
@@ -64,17 +59,6 @@ class Propagation:
             self.call(n, True)
             asked += n
         return asked
-
-
-def wall_ms(fn, repeats):
-    runs = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        runs.append((time.perf_counter() - t0) * 1e3)
-    return runs
 
 
 def split_case(ctx, v, iso):
@@ -146,9 +130,9 @@ def time_scene(ctx, v, iso, calls, repeats, out):
     torch.cuda.synchronize()
     body = int((cc_labels == cc_labels.view(-1)[first]).sum().item())
     assert body == reached, (body, reached)
-    lab = wall_ms(label, repeats)
+    lab = wall_ms(label, 1, repeats)
     asked = p.to_the_fixed_point()
-    geo = wall_ms(p.to_the_fixed_point, max(1, repeats // 2))
+    geo = wall_ms(p.to_the_fixed_point, 1, max(1, repeats // 2))
     out.append("  2. reachability from the first inside voxel: its body has %d voxels (both calls agree); settled within %d rounds (to 16)" % (body, rounds))
     out.append("    %-44s %s ms (wall clock)" % ("vkv_label_components, 26-connected", fmt(lab)))
     out.append("    %-44s %s ms (wall clock, %d rounds asked for in calls of 64, 128, ...)  x %5.2f" % (
@@ -179,18 +163,12 @@ def rocprof(args):
              "# Mean ms per dispatch; k_geo_round's mean is over full, partial and empty rounds alike."]
     for name in args.scenes.split(","):
         print("profiling " + name, file=sys.stderr, flush=True)
-        with tempfile.TemporaryDirectory() as d:
-            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--only", name,
-                   "--iso", str(args.iso)]
-            done = subprocess.run(cmd, check=True, timeout=600, stdout=subprocess.PIPE, text=True)
-            rows = []
-            for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-                rows += list(csv.DictReader(open(f)))
-        lines.append("%s (%s)" % (name, ", ".join(x for x in done.stdout.splitlines() if x.startswith("ROUNDS"))))
+        said = []
+        rows = kernel_stats(__file__, ["--only", name, "--iso", str(args.iso)], 600, said=said)
+        lines.append("%s (%s)" % (name, ", ".join(x for x in said if x.startswith("ROUNDS"))))
         for r in sorted(rows, key=lambda r: r["Name"]):
             if "k_geo_" in r["Name"]:
-                kernel = (r["Name"][5:] if r["Name"].startswith("void ") else r["Name"]).split("(")[0]
-                lines.append("    %-16s %5d dispatches %10.4f ms  [%10.4f .. %10.4f]" % (kernel, int(r["Calls"]), float(r["AverageNs"]) / 1e6,
+                lines.append("    %-16s %5d dispatches %10.4f ms  [%10.4f .. %10.4f]" % (kernel_name(r["Name"]), int(r["Calls"]), float(r["AverageNs"]) / 1e6,
                                                                                  float(r.get("MinNs", "nan")) / 1e6, float(r.get("MaxNs", "nan")) / 1e6))
     return lines
 
@@ -205,18 +183,8 @@ def main():
     ap.add_argument("--only", default=None, help="scene - one case alone, untimed (what --rocprof runs under the profiler)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "geodesic_rocprof.txt" if args.rocprof else "geodesic_times.txt")
-    if args.only:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
-        one_case(ctx, args.only, args.iso)
-        ctx.close()
-        return
-    if args.rocprof:
-        lines = rocprof(args)
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_geodesic.py --iso %s --calls %d --repeats %d on one MI355X (device events unless marked wall clock; median [min .. max];" % (
             args.iso, args.calls, args.repeats), "# x: against the first call of the same block: the yardstick of the same run)"]
         for k, name in enumerate(args.scenes.split(",")):
@@ -225,10 +193,9 @@ def main():
             time_scene(ctx, v, iso, args.calls, args.repeats, lines)
             del v
             torch.cuda.empty_cache()
-        ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), lambda ctx: one_case(ctx, args.only, args.iso), times_name="geodesic_times.txt", rocprof_name="geodesic_rocprof.txt")
 
 
 if __name__ == "__main__":

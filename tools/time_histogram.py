@@ -11,45 +11,22 @@ with d_occupied_count against the same update without it followed by the histogr
 """
 import argparse
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from tools.measure import blocks_ms, ptr as p, run, spread, stream  # noqa: E402
 from vkvolume_amd import abi, lib  # noqa: E402
 
 
-def timed(fn, warmup, reps, repeats):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        torch.cuda.synchronize()
-        out.append(s.elapsed_time(e) / reps)
-    return statistics.median(out), min(out), max(out)
+def measure(ctx, a):
+    def timed(fn):
+        return spread(blocks_ms(fn, a.warmup, a.reps, a.repeats))
 
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--scenes", default="shells,constant,noise")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
     v, tf, _, _ = bench.build_scene(ctx, "c3")
-    st = torch.cuda.current_stream().cuda_stream
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    st = stream()
     shells = v.volume.clone()
     n_vox = v.volume.numel()
     hist = torch.zeros(abi.HISTOGRAM_BINS, dtype=torch.int64, device="cuda")
@@ -76,8 +53,8 @@ def main():
         ctx.gradient_map(p(v.volume), p(v.gradient), v.extent, tf, st)
         if scene == "noise":  # the gradient of noise is far from uniform: fill it with noise too, so that every bin is hit
             v.gradient.random_(0, 256)
-        t_hist = timed(lambda: ctx.volume_histogram(p(v.volume), p(v.gradient), v.extent, None, abi.HISTOGRAM_SET, p(hist), st), a.warmup, a.reps, a.repeats)
-        t_cnt = timed(lambda: ctx.occupied_voxel_count(p(v.volume), p(v.gradient), tf, v.extent, p(count[0:1]), st), a.warmup, a.reps, a.repeats)
+        t_hist = timed(lambda: ctx.volume_histogram(p(v.volume), p(v.gradient), v.extent, None, abi.HISTOGRAM_SET, p(hist), st))
+        t_cnt = timed(lambda: ctx.occupied_voxel_count(p(v.volume), p(v.gradient), tf, v.extent, p(count[0:1]), st))
         used = int((hist != 0).sum().item())
         for label, t in (("histogram SET, whole volume", t_hist), ("vkv_occupied_voxel_count (yardstick)", t_cnt)):
             gbs = 2.0 * n_vox / (t[0] * 1e-3) / 1e9
@@ -91,10 +68,10 @@ def main():
                 ctx.volume_histogram(p(v.volume), p(v.gradient), v.extent, b, abi.HISTOGRAM_SUBTRACT, p(hist), st)
                 ctx.volume_histogram(p(v.volume), p(v.gradient), v.extent, b, abi.HISTOGRAM_ADD, p(hist), st)
 
-            emit(fmt % ((scene, "SUBTRACT + ADD of a %d^3 box" % n) + timed(sub_add, a.warmup, a.reps, a.repeats)))
+            emit(fmt % ((scene, "SUBTRACT + ADD of a %d^3 box" % n) + timed(sub_add)))
         ctx.volume_histogram(p(v.volume), p(v.gradient), v.extent, None, abi.HISTOGRAM_SET, p(hist), st)
         emit(fmt % ((scene, "vkv_histogram_occupied_count") +
-                    timed(lambda: ctx.histogram_occupied_count(p(hist), tf, p(count[1:2]), st), a.warmup, a.reps, a.repeats)))
+                    timed(lambda: ctx.histogram_occupied_count(p(hist), tf, p(count[1:2]), st))))
         torch.cuda.synchronize()
         assert count[0].item() == count[1].item(), "counts differ: %s" % count.tolist()
         if scene == "shells":  # a counted slider move, both ways (Chebyshev map)
@@ -108,19 +85,27 @@ def main():
                 ctx.update_transfer_function(opt, p(v.volume), p(v.gradient), v.extent, p(v.transfer_function), p(v.transfer_function_bits), maps,
                                              p(v.distance_map_swap), v.map_extent, abi.SKIP_DISTANCE, d_count, st)
 
-            emit(fmt % ((scene, "slider move, uncounted") + timed(lambda: move(None), a.warmup, a.reps, a.repeats)))
-            emit(fmt % ((scene, "slider move, counted by the volume pass") + timed(lambda: move(p(count[0:1])), a.warmup, a.reps, a.repeats)))
+            emit(fmt % ((scene, "slider move, uncounted") + timed(lambda: move(None))))
+            emit(fmt % ((scene, "slider move, counted by the volume pass") + timed(lambda: move(p(count[0:1])))))
 
             def move_hist():
                 move(None)
                 ctx.histogram_occupied_count(p(hist), tf, p(count[1:2]), st)
 
-            emit(fmt % ((scene, "slider move, counted from the histogram") + timed(move_hist, a.warmup, a.reps, a.repeats)))
+            emit(fmt % ((scene, "slider move, counted from the histogram") + timed(move_hist)))
     v.volume.copy_(shells)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    ctx.close()
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--scenes", default="shells,constant,noise")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    run(a, lambda ctx: measure(ctx, a), echo=False)  # the lines are printed as they are measured
 
 
 if __name__ == "__main__":

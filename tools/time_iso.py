@@ -12,36 +12,18 @@ covered pixel and hit pixels (d_out_counts).  Every frame writes RGBA8 only.
                                                                          child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from vkvolume_amd import abi, lib, volume as V  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, run, stats_table  # noqa: E402
+from vkvolume_amd import abi, volume as V  # noqa: E402
 
 MIP_THRESHOLD = 0.2
-
-
-def event_ms(fn, frames):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(frames):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / frames
-
-
-def fmt(runs):
-    return "%8.4f [%8.4f .. %8.4f]" % (statistics.median(runs), min(runs), max(runs))
 
 
 def measure(ctx, name, isos, frames, repeats, out):
@@ -75,38 +57,20 @@ def measure(ctx, name, isos, frames, repeats, out):
     for skip in (False, True):
         kinds["mip %.2f %-6s" % (MIP_THRESHOLD, "maxmap" if skip else "dense")] = (
             lambda c=None, skip=skip: sp.draw_mip(p, MIP_THRESHOLD, 1.0, rgba8=rgba8, counts=c, skip=skip))
-    for fn in kinds.values():
-        fn()
-    torch.cuda.synchronize()
-    runs = {k: [] for k in kinds}
-    for _ in range(repeats):
-        for k, fn in kinds.items():
-            runs[k].append(event_ms(fn, frames))
+    runs = alternate(kinds, frames, repeats)
     for k, fn in kinds.items():
         spp, covered, hits = stats(fn)
-        out.append("  %-18s %s ms/frame   %8.1f samples filtered per covered pixel (%d covered, %d hit)" % (k, fmt(runs[k]), spp, covered, hits))
+        out.append("  %-18s %s ms/frame   %8.1f samples filtered per covered pixel (%d covered, %d hit)" % (k, fmt(runs[k], 8), spp, covered, hits))
     del v
     torch.cuda.empty_cache()
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--scenes", args.scenes, "--isos", args.isos, "--frames", "5", "--repeats", "1", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=1200)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if any(s in r["Name"] for s in ("k_iso", "k_mip"))]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_iso.py --scenes %s --isos %s --frames 5 --repeats 1` on one MI355X, a run of"
-             % (args.scenes, args.isos),
-             "# its own: the isosurface kernels (k_iso<PACKED, SKIP>: SKIP = max map) and the MIP kernels of the same frames, ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--scenes", args.scenes, "--isos", args.isos, "--frames", "5", "--repeats", "1", "--out", os.devnull], 1200)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_iso.py --scenes %s --isos %s --frames 5 --repeats 1` on one MI355X, a run of"
+            % (args.scenes, args.isos),
+            "# its own: the isosurface kernels (k_iso<PACKED, SKIP>: SKIP = max map) and the MIP kernels of the same frames, ms per dispatch"
+            ] + stats_table(rows, ("k_iso", "k_mip"))
 
 
 def main():
@@ -118,22 +82,16 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.rocprof:
-        lines = rocprof(args)
-        out_path = args.out or os.path.join(ROOT, "profiles", "iso_rocprof.txt")
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_iso.py --scenes %s --isos %s --frames %d --repeats %d on one MI355X (device events; median [min .. max])"
                  % (args.scenes, args.isos, args.frames, args.repeats)]
         for name in args.scenes.split(","):
             measure(ctx, name, [float(t) for t in args.isos.split(",")], args.frames, args.repeats, lines)
             print("\n".join(lines), flush=True)
-        ctx.close()
-        out_path = args.out or os.path.join(ROOT, "profiles", "iso_times.txt")
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="iso_times.txt", rocprof_name="iso_rocprof.txt")
 
 
 if __name__ == "__main__":

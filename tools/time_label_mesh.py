@@ -20,26 +20,18 @@ call of every variant; median [min .. max]).
                                                                  --kernel-trace --stats, in a child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, ptr, run, stats_table, stream as st  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
 from vkvolume_amd import labels as LB, lib  # noqa: E402
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class Calls:
@@ -161,22 +153,10 @@ def measure_salt(ctx, calls, repeats, out):
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--isos", args.isos, "--calls", "2", "--repeats", "1", "--no-salt", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=900)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if "k_mesh_" in r["Name"] or "k_lmesh_" in r["Name"]]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_label_mesh.py --isos %s --calls 2 --repeats 1 --no-salt` on one MI355X, a run of its own:" % args.isos,
-             "# the kernels of vkv_label_mesh (k_lmesh_*) and of vkv_isosurface_mesh (k_mesh_*) over all variants and isos of the c3 scene, ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--isos", args.isos, "--calls", "2", "--repeats", "1", "--no-salt", "--out", os.devnull], 900)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_label_mesh.py --isos %s --calls 2 --repeats 1 --no-salt` on one MI355X, a run of its own:" % args.isos,
+            "# the kernels of vkv_label_mesh (k_lmesh_*) and of vkv_isosurface_mesh (k_mesh_*) over all variants and isos of the c3 scene, ms per dispatch"
+            ] + stats_table(rows, ("k_mesh_", "k_lmesh_"))
 
 
 def main():
@@ -188,21 +168,16 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "label_mesh_rocprof.txt" if args.rocprof else "label_mesh_times.txt")
-    if args.rocprof:
-        lines = rocprof(args)
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_label_mesh.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
             args.isos, args.calls, args.repeats)]
         measure_c3(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
         if not args.no_salt:
             measure_salt(ctx, args.calls, args.repeats, lines)
-        ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="label_mesh_times.txt", rocprof_name="label_mesh_rocprof.txt")
 
 
 if __name__ == "__main__":

@@ -17,22 +17,18 @@ samples looked up per covered pixel and hit pixels (d_out_counts).  Every frame 
                                                           --kernel-trace --stats, in a child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
-from vkvolume_amd import abi, labels as LB, lib, volume as V  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, run, stats_table, stream as st  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
+from vkvolume_amd import abi, labels as LB, volume as V  # noqa: E402
 
 C3_ISO = 0.2
 
@@ -116,23 +112,11 @@ def measure(ctx, name, frames, repeats, out):
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--scenes", args.scenes, "--frames", "3", "--repeats", "1", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=360)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if any(s in r["Name"] for s in ("k_labels", "k_label_visibility_map", "k_iso", "k_max_map", "select"))]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_label_render.py --scenes %s --frames 3 --repeats 1` on one MI355X, a run of its own:" % args.scenes,
-             "# the label render's kernels (k_labels<SHADE, SKIP>: SHADE 0 flat, 1 lit from the linear volume, 2 lit from the packed image; SKIP =",
-             "# visibility map), the isosurface kernels of the same frames, and the map and selection passes; ms per dispatch over both scenes",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--scenes", args.scenes, "--frames", "3", "--repeats", "1", "--out", os.devnull], 360)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_label_render.py --scenes %s --frames 3 --repeats 1` on one MI355X, a run of its own:" % args.scenes,
+            "# the label render's kernels (k_labels<SHADE, SKIP>: SHADE 0 flat, 1 lit from the linear volume, 2 lit from the packed image; SKIP =",
+            "# visibility map), the isosurface kernels of the same frames, and the map and selection passes; ms per dispatch over both scenes"
+            ] + stats_table(rows, ("k_labels", "k_label_visibility_map", "k_iso", "k_max_map", "select"))
 
 
 def main():
@@ -143,23 +127,17 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.rocprof:
-        lines = rocprof(args)
-        out_path = args.out or os.path.join(ROOT, "profiles", "label_render_rocprof.txt")
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_label_render.py --scenes %s --frames %d --repeats %d on one MI355X (device events; median [min .. max]);"
                  % (args.scenes, args.frames, args.repeats),
                  "# 'x iso': against vkv_render_isosurface of the same frame and iso in the same run, dense against dense and map against max map"]
         for name in args.scenes.split(","):
             measure(ctx, name, args.frames, args.repeats, lines)
             print("\n".join(lines), flush=True)
-        ctx.close()
-        out_path = args.out or os.path.join(ROOT, "profiles", "label_render_times.txt")
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="label_render_times.txt", rocprof_name="label_render_rocprof.txt")
 
 
 if __name__ == "__main__":

@@ -20,7 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
+from tools.measure import alternate, fmt, run, stream as st  # noqa: E402
 from vkvolume_amd import lib  # noqa: E402
 
 
@@ -71,14 +71,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_times.txt"))
     args = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# tools/time_mesh.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.isos, args.calls, args.repeats)]
-    measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
-    ctx.close()
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+
+    def plain(ctx):
+        lines = ["# tools/time_mesh.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.isos, args.calls, args.repeats)]
+        measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
+        return lines
+
+    run(args, plain)
 
 
 if __name__ == "__main__":

@@ -16,20 +16,16 @@ call of every variant; median [min .. max]).
                                                                  --kernel-trace --stats, in a child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, ptr, run, stats_table, stream as st  # noqa: E402
 from vkvolume_amd import lib  # noqa: E402
 
 
@@ -45,9 +41,6 @@ def measure(ctx, isos, calls, repeats, out):
     counts = torch.zeros((4,), dtype=torch.int64, device="cuda")
     out.append("c3: volume %dx%dx%d (%.3f GB), max map %dx%dx%d; scratch: list %.1f MB, indexed %.1f MB" % (
         e.width, e.height, e.depth, n / 1e9, me.width, me.height, me.depth, list_scratch.numel() * 8 / 1e6, scratch.numel() * 8 / 1e6))
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
 
     def soup(iso, tri, capacity):
         ctx.isosurface_mesh(vol.data_ptr(), e, None, iso, None, None, list_scratch.data_ptr(), ptr(tri), capacity, list_counts.data_ptr(), st())
@@ -93,22 +86,10 @@ def measure(ctx, isos, calls, repeats, out):
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--isos", args.isos, "--calls", "2", "--repeats", "1", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=900)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if "k_mesh" in r["Name"]]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_mesh_indexed.py --isos %s --calls 2 --repeats 1` on one MI355X, a run of its own:" % args.isos,
-             "# the kernels of vkv_isosurface_mesh_indexed (k_meshi_*) and of vkv_isosurface_mesh (k_mesh_*) over all variants and isos, ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--isos", args.isos, "--calls", "2", "--repeats", "1", "--out", os.devnull], 900)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_mesh_indexed.py --isos %s --calls 2 --repeats 1` on one MI355X, a run of its own:" % args.isos,
+            "# the kernels of vkv_isosurface_mesh_indexed (k_meshi_*) and of vkv_isosurface_mesh (k_mesh_*) over all variants and isos, ms per dispatch"
+            ] + stats_table(rows, ("k_mesh",))
 
 
 def main():
@@ -119,22 +100,14 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "mesh_indexed_rocprof.txt" if args.rocprof else "mesh_indexed_times.txt")
-    if args.rocprof:
-        lines = rocprof(args)
-        with open(out_path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        print("\n".join(lines))
-        return
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# tools/time_mesh_indexed.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
-        args.isos, args.calls, args.repeats)]
-    measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
-    ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+
+    def plain(ctx):
+        lines = ["# tools/time_mesh_indexed.py --isos %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (
+            args.isos, args.calls, args.repeats)]
+        measure(ctx, [float(t) for t in args.isos.split(",")], args.calls, args.repeats, lines)
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="mesh_indexed_times.txt", rocprof_name="mesh_indexed_rocprof.txt")
 
 
 if __name__ == "__main__":

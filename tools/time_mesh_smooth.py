@@ -17,22 +17,18 @@ positions drift from block to block (the extraction in the rotation rewrites the
                                                     --kernel-trace --stats, in a child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from tools.time_components import scene_volume  # noqa: E402
-from tools.time_filter import alternate, fmt, st  # noqa: E402
-from vkvolume_amd import labels as LB, lib, mesh as M  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, run, stats_table, stream as st  # noqa: E402
+from tools.scenes import scene_volume  # noqa: E402
+from vkvolume_amd import labels as LB, mesh as M  # noqa: E402
 
 TAUBIN = [0.5, -0.53] * 10
 
@@ -87,23 +83,11 @@ def measure(ctx, v, labels, vol, iso, name, calls, repeats, out):
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--iso", str(args.iso), "--calls", "1", "--repeats", "1", "--no-salt", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=900)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if any(k in r["Name"] for k in ("k_madj_", "k_msmooth_", "k_mnormals", "k_lmeshi_"))]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_mesh_smooth.py --iso %s --calls 1 --repeats 1 --no-salt` on one MI355X, a run of its own:" % args.iso,
-             "# the kernels of vkv_mesh_adjacency (k_madj_*), vkv_mesh_smooth (k_msmooth_*), vkv_mesh_vertex_normals (k_mnormals) and of the extraction",
-             "# (k_lmeshi_*) over both C3 meshes (the 14-components' and the split bodies'), ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--iso", str(args.iso), "--calls", "1", "--repeats", "1", "--no-salt", "--out", os.devnull], 900)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_mesh_smooth.py --iso %s --calls 1 --repeats 1 --no-salt` on one MI355X, a run of its own:" % args.iso,
+            "# the kernels of vkv_mesh_adjacency (k_madj_*), vkv_mesh_smooth (k_msmooth_*), vkv_mesh_vertex_normals (k_mnormals) and of the extraction",
+            "# (k_lmeshi_*) over both C3 meshes (the 14-components' and the split bodies'), ms per dispatch"
+            ] + stats_table(rows, ("k_madj_", "k_msmooth_", "k_mnormals", "k_lmeshi_"))
 
 
 def main():
@@ -115,33 +99,25 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    out_path = args.out or os.path.join(ROOT, "profiles", "mesh_smooth_rocprof.txt" if args.rocprof else "mesh_smooth_times.txt")
-    if args.rocprof:
-        lines = rocprof(args)
-        with open(out_path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        print("\n".join(lines))
-        return
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# tools/time_mesh_smooth.py --iso %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.iso, args.calls, args.repeats)]
-    v, _, _, _ = bench.build_scene(ctx, "c3")
-    labels = v.label_components(args.iso, connectivity=14, sizes=False)[0]
-    measure(ctx, v, labels, v.volume, args.iso, "c3, label_components(14), vertices from the volume", args.calls, args.repeats, lines)
-    del labels
-    torch.cuda.empty_cache()
-    labels, _ = v.split_bodies(args.iso, radius2=4)
-    measure(ctx, v, labels, None, 0.0, "c3, split_bodies(radius2=4), midpoints", args.calls, args.repeats, lines)
-    del v, labels
-    torch.cuda.empty_cache()
-    if not args.no_salt:
-        v, iso = scene_volume(ctx, "salt")
-        labels = v.label_components(iso, connectivity=14, sizes=False)[0]
-        measure(ctx, v, labels, v.volume, iso, "salt, label_components(14), vertices from the volume", args.calls, args.repeats, lines)
-    ctx.close()
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+
+    def plain(ctx):
+        lines = ["# tools/time_mesh_smooth.py --iso %s --calls %d --repeats %d on one MI355X (device events; median [min .. max])" % (args.iso, args.calls, args.repeats)]
+        v, _, _, _ = bench.build_scene(ctx, "c3")
+        labels = v.label_components(args.iso, connectivity=14, sizes=False)[0]
+        measure(ctx, v, labels, v.volume, args.iso, "c3, label_components(14), vertices from the volume", args.calls, args.repeats, lines)
+        del labels
+        torch.cuda.empty_cache()
+        labels, _ = v.split_bodies(args.iso, radius2=4)
+        measure(ctx, v, labels, None, 0.0, "c3, split_bodies(radius2=4), midpoints", args.calls, args.repeats, lines)
+        del v, labels
+        torch.cuda.empty_cache()
+        if not args.no_salt:
+            v, iso = scene_volume(ctx, "salt")
+            labels = v.label_components(iso, connectivity=14, sizes=False)[0]
+            measure(ctx, v, labels, v.volume, iso, "salt, label_components(14), vertices from the volume", args.calls, args.repeats, lines)
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="mesh_smooth_times.txt", rocprof_name="mesh_smooth_rocprof.txt")
 
 
 if __name__ == "__main__":

@@ -13,49 +13,25 @@ whole-volume vkv_max_map.  Every frame writes RGBA8 only.
                                                                          child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
-import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from vkvolume_amd import abi, lib, volume as V  # noqa: E402
-
-
-def st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def event_ms(fn, frames):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(frames):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / frames
-
-
-def fmt(runs):
-    return "%8.4f [%8.4f .. %8.4f]" % (statistics.median(runs), min(runs), max(runs))
+from tools.measure import alternate, blocks_ms, fmt, kernel_stats, run, stats_table, stream as st  # noqa: E402
+from vkvolume_amd import abi, volume as V  # noqa: E402
 
 
 def measure(ctx, name, thresholds, frames, repeats, out):
     v, tf, (w, h), _ = bench.build_scene(ctx, name)
     view, proj = bench.cameras(v, w / h)[0]
-    v.build_max_map()
-    torch.cuda.synchronize()
-    mm = [event_ms(lambda: v.build_max_map(), 3) for _ in range(repeats)]
+    mm = blocks_ms(lambda: v.build_max_map(), 1, 3, repeats)
     me = v.map_extent
     out.append("%s: volume %dx%dx%d, frame %dx%d, max map %dx%dx%d (block 4)  vkv_max_map %s ms" % (
-        name, v.extent.width, v.extent.height, v.extent.depth, w, h, me.width, me.height, me.depth, fmt(mm)))
+        name, v.extent.width, v.extent.height, v.extent.depth, w, h, me.width, me.height, me.depth, fmt(mm, 8)))
     mip = V.VolumeRenderSubpass(ctx, v, abi.RenderOptions(skipping_type=abi.SKIP_NONE, early_ray_termination=0), (w, h))
     p = mip.make_params(view, proj)
     rgba8 = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
@@ -83,40 +59,22 @@ def measure(ctx, name, thresholds, frames, repeats, out):
     for thr in thresholds:
         kinds = {"dense": lambda: mip.draw_mip(p, thr, 1.0, rgba8=rgba8, skip=False),
                  "maxmap": lambda: mip.draw_mip(p, thr, 1.0, rgba8=rgba8, skip=True), "render": render}
-        for fn in kinds.values():
-            fn()
-        torch.cuda.synchronize()
-        runs = {k: [] for k in kinds}
-        for _ in range(repeats):
-            for k, fn in kinds.items():
-                runs[k].append(event_ms(fn, frames))
+        runs = alternate(kinds, frames, repeats)
         for k in kinds:
             spp, covered = samples(k, thr)
             label = "render SKIP_NONE ERT off" if k == "render" else "mip %-6s" % k
             out.append("  threshold %.2f  %-24s %s ms/frame   %8.1f samples filtered per covered pixel (%d covered)" % (
-                thr, label, fmt(runs[k]), spp, covered))
+                thr, label, fmt(runs[k], 8), spp, covered))
     del v
     torch.cuda.empty_cache()
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--scenes", args.scenes, "--thresholds", args.thresholds, "--frames", "5", "--repeats", "1", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=1200)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if any(s in r["Name"] for s in ("k_mip", "k_max_map", "k_raymarch"))]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_mip.py --scenes %s --thresholds %s --frames 5 --repeats 1` on one MI355X, a run of"
-             % (args.scenes, args.thresholds),
-             "# its own: the MIP kernels (k_mip<PACKED, SKIP>: SKIP = max map), the max map and the integrator's kernels, ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--scenes", args.scenes, "--thresholds", args.thresholds, "--frames", "5", "--repeats", "1", "--out", os.devnull], 1200)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_mip.py --scenes %s --thresholds %s --frames 5 --repeats 1` on one MI355X, a run of"
+            % (args.scenes, args.thresholds),
+            "# its own: the MIP kernels (k_mip<PACKED, SKIP>: SKIP = max map), the max map and the integrator's kernels, ms per dispatch"
+            ] + stats_table(rows, ("k_mip", "k_max_map", "k_raymarch"))
 
 
 def main():
@@ -128,22 +86,16 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.rocprof:
-        lines = rocprof(args)
-        out_path = args.out or os.path.join(ROOT, "profiles", "mip_rocprof.txt")
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_mip.py --scenes %s --thresholds %s --frames %d --repeats %d on one MI355X (device events; median [min .. max])"
                  % (args.scenes, args.thresholds, args.frames, args.repeats)]
         for name in args.scenes.split(","):
             measure(ctx, name, [float(t) for t in args.thresholds.split(",")], args.frames, args.repeats, lines)
             print("\n".join(lines), flush=True)
-        ctx.close()
-        out_path = args.out or os.path.join(ROOT, "profiles", "mip_times.txt")
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="mip_times.txt", rocprof_name="mip_rocprof.txt")
 
 
 if __name__ == "__main__":

@@ -15,38 +15,21 @@ RGBA8 only.
                                                                            a child process of its own, summarised per kernel
 """
 import argparse
-import csv
-import glob
 import os
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from vkvolume_amd import abi, camera, lib, volume as V  # noqa: E402
+from tools.measure import alternate, fmt, kernel_stats, run, stats_table  # noqa: E402
+from vkvolume_amd import abi, camera, volume as V  # noqa: E402
 
 MIP_THRESHOLD = 0.2
 OBLIQUE = (1.0, 2.0, 3.0)
 MODE_NAMES = {abi.SLAB_MAX: "max", abi.SLAB_MIN: "min", abi.SLAB_MEAN: "mean"}
-
-
-def event_ms(fn, frames):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(frames):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / frames
-
-
-def fmt(runs):
-    return "%8.4f [%8.4f .. %8.4f]" % (statistics.median(runs), min(runs), max(runs))
 
 
 def measure(ctx, samples, frames, repeats, out):
@@ -89,40 +72,21 @@ def measure(ctx, samples, frames, repeats, out):
                                                                                         rgba8=rgba8, counts=c))
         kinds["%-20s %-6s" % ("mip %.2f dense" % MIP_THRESHOLD, "packed" if packed else "linear")] = (
             lambda c=None, packed=packed: sp.draw_mip(params[packed], MIP_THRESHOLD, 1.0, rgba8=rgba8, counts=c, skip=False))
-    for fn in kinds.values():
-        fn()
-    torch.cuda.synchronize()
-    runs = {k: [] for k in kinds}
-    for _ in range(repeats):
-        for k, fn in kinds.items():
-            runs[k].append(event_ms(fn, frames))
+    runs = alternate(kinds, frames, repeats)
     mip = {k.split()[-1]: statistics.median(r) for k, r in runs.items() if k.startswith("mip")}
     for k, fn in kinds.items():
         spp, covered = stats(fn)
         out.append("  %s %s ms/frame  (%5.3f of the dense MIP's %7.4f)  %7.1f samples filtered per covered pixel (%d covered)" % (
-            k, fmt(runs[k]), statistics.median(runs[k]) / mip[k.split()[-1]], mip[k.split()[-1]], spp, covered))
+            k, fmt(runs[k], 8), statistics.median(runs[k]) / mip[k.split()[-1]], mip[k.split()[-1]], spp, covered))
     del v
     torch.cuda.empty_cache()
 
 
 def rocprof(args):
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--samples", args.samples, "--frames", "5", "--repeats", "1", "--out", os.path.join(d, "times.txt")]
-        subprocess.run(cmd, check=True, timeout=1100)
-        rows = []
-        for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            rows += list(csv.DictReader(open(f)))
-    keep = [r for r in rows if any(s in r["Name"] for s in ("k_slab", "k_mip"))]
-    lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_slab.py --samples %s --frames 5 --repeats 1` on one MI355X, a run of its own:" % args.samples,
-             "# the slab kernels (k_slab<PACKED, MODE, SKIP>: MODE 0 max, 1 min, 2 mean; SKIP = max map; each kernel serves the slice and both slab",
-             "# thicknesses of its mode) and the dense MIP kernels of the same frame size, ms per dispatch",
-             "%-60s %6s %10s %10s" % ("kernel", "calls", "total ms", "mean ms")]
-    for r in sorted(keep, key=lambda r: -float(r["TotalDurationNs"])):
-        name = r["Name"].replace("(anonymous namespace)::", "")
-        name = (name[5:] if name.startswith("void ") else name).split("(")[0]
-        lines.append("%-60s %6s %10.3f %10.4f" % (name[:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6, float(r["AverageNs"]) / 1e6))
-    return lines
+    rows = kernel_stats(__file__, ["--samples", args.samples, "--frames", "5", "--repeats", "1", "--out", os.devnull], 1100)
+    return ["# rocprofv3 --kernel-trace --stats of `tools/time_slab.py --samples %s --frames 5 --repeats 1` on one MI355X, a run of its own:" % args.samples,
+            "# the slab kernels (k_slab<PACKED, MODE, SKIP>: MODE 0 max, 1 min, 2 mean; SKIP = max map; each kernel serves the slice and both slab",
+            "# thicknesses of its mode) and the dense MIP kernels of the same frame size, ms per dispatch"] + stats_table(rows, ("k_slab", "k_mip"))
 
 
 def main():
@@ -133,20 +97,14 @@ def main():
     ap.add_argument("--rocprof", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.rocprof:
-        lines = rocprof(args)
-        out_path = args.out or os.path.join(ROOT, "profiles", "slab_rocprof.txt")
-    else:
-        torch.cuda.set_device(0)
-        ctx = lib.Context(0)
+
+    def plain(ctx):
         lines = ["# tools/time_slab.py --samples %s --frames %d --repeats %d on one MI355X (device events; median [min .. max])"
                  % (args.samples, args.frames, args.repeats)]
         measure(ctx, [int(t) for t in args.samples.split(",")], args.frames, args.repeats, lines)
-        ctx.close()
-        out_path = args.out or os.path.join(ROOT, "profiles", "slab_times.txt")
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+        return lines
+
+    run(args, plain, lambda: rocprof(args), times_name="slab_times.txt", rocprof_name="slab_rocprof.txt")
 
 
 if __name__ == "__main__":

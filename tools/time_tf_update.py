@@ -19,12 +19,12 @@ import math
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools.measure import run, wall_ms  # noqa: E402
 from vkvolume_amd import abi, camera, lib, volume as V  # noqa: E402
 
 # name: (extent, seed, voxel size, axis-angle, frame, skipping type) - the C3 / C4 scenes of bench.py
@@ -54,15 +54,6 @@ def build(ctx, name):
     ctx.prepare_render([params], torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return v, sp, params, rgba8, skip
-
-
-def timed_block(fn, moves):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for k in range(moves):
-        fn(k)
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / moves
 
 
 def measure(ctx, name, moves, repeats, warmup, paths):
@@ -104,9 +95,12 @@ def measure(ctx, name, moves, repeats, warmup, paths):
             continue
         res = {}
         for frame in (True, False):
-            timed_block(lambda k: fn(k, frame), warmup)
-            runs = [timed_block(lambda k: fn(k, frame), moves) for _ in range(repeats)]
-            res[frame] = runs
+            def block(n):  # moves 0 .. n-1: every block starts from the same setting
+                for k in range(n):
+                    fn(k, frame)
+
+            wall_ms(lambda: block(warmup), 1, 1)
+            res[frame] = [t / moves for t in wall_ms(lambda: block(moves), 1, repeats)]
         rows.append((label, res))
     del graphs
     ctx.release_stream(s.cuda_stream)
@@ -128,27 +122,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
-    lines = ["# ms per slider move: median [min .. max] of %d blocks of %d moves (wall clock, device synchronised around each block)" % (a.repeats, a.moves),
-             "# %s, %s" % (torch.cuda.get_device_name(0), lib.load().vkv_version().decode()),
-             "%-9s %-7s %-30s %-30s" % ("scene", "path", "update + frame (ms)", "update alone (ms)")]
-    for name in a.scenes.split(","):
-        try:
-            rows = measure(ctx, name, a.moves, a.repeats, a.warmup, a.paths.split(","))
-        except torch.cuda.OutOfMemoryError as e:
-            lines.append("%-9s skipped: %s" % (name, str(e).splitlines()[0]))
-            torch.cuda.empty_cache()
-            continue
-        for label, res in rows:
-            lines.append("%-9s %-7s %-30s %-30s" % (name, label, fmt(res[True]), fmt(res[False])))
-        print("\n".join(lines[-len(rows):]), flush=True)
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(text)
-    ctx.close()
+
+    def plain(ctx):
+        lines = ["# ms per slider move: median [min .. max] of %d blocks of %d moves (wall clock, device synchronised around each block)" % (a.repeats, a.moves),
+                 "# %s, %s" % (torch.cuda.get_device_name(0), lib.load().vkv_version().decode()),
+                 "%-9s %-7s %-30s %-30s" % ("scene", "path", "update + frame (ms)", "update alone (ms)")]
+        for name in a.scenes.split(","):
+            try:
+                rows = measure(ctx, name, a.moves, a.repeats, a.warmup, a.paths.split(","))
+            except torch.cuda.OutOfMemoryError as e:
+                lines.append("%-9s skipped: %s" % (name, str(e).splitlines()[0]))
+                torch.cuda.empty_cache()
+                continue
+            for label, res in rows:
+                lines.append("%-9s %-7s %-30s %-30s" % (name, label, fmt(res[True]), fmt(res[False])))
+            print("\n".join(lines[-len(rows):]), flush=True)
+        return lines
+
+    run(a, plain)
+    print()  # the report has always ended on an empty line
 
 
 if __name__ == "__main__":

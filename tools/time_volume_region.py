@@ -12,13 +12,11 @@ Under `rocprofv3 --kernel-trace --stats` every region update starts with one k_c
 """
 import argparse
 import os
-import statistics
 import sys
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from tools.measure import blocks_ms, ptr as p, run, spread, stream  # noqa: E402
 from vkvolume_amd import abi, lib, volume as V  # noqa: E402
 
 MAPS = {"cheb": abi.SKIP_DISTANCE, "aniso": abi.SKIP_ANISOTROPIC_DISTANCE}
@@ -34,35 +32,12 @@ def boxes(ext):
     return out
 
 
-def timed(fn, warmup, reps, repeats):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(reps):
-            fn()
-        e.record()
-        torch.cuda.synchronize()
-        out.append(s.elapsed_time(e) / reps)
-    return statistics.median(out), min(out), max(out)
+def measure(ctx, a):
+    def timed(fn):
+        return spread(blocks_ms(fn, a.warmup, a.reps, a.repeats))
 
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--maps", default="cheb,aniso")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    torch.cuda.set_device(0)
-    ctx = lib.Context(0)
     v, tf, _, _ = bench.build_scene(ctx, "c3")
-    st = torch.cuda.current_stream().cuda_stream
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    st = stream()
     lines = ["# ms per region update of the C3 volume (1024x1024x795, block 4, gradient precomputed, packed image, app TF) on one MI355X",
              "# (tools/time_volume_region.py: HIP events, median [min .. max] of %d blocks of %d calls after %d warm-up calls)" % (a.repeats, a.reps, a.warmup),
              "# region = vkv_update_volume_region with a uint8 source on the device; chain = vkv_gradient_map + vkv_pack_volume +",
@@ -81,7 +56,7 @@ def main():
             ctx.pack_volume(p(v.volume), p(v.gradient), v.extent, p(v.packed), st)
             ctx.compute_distance_map(p(v.volume), p(v.gradient), p(v.transfer_function), tf, v.extent, maps, p(v.distance_map_swap), v.map_extent, skip, st)
 
-        t_chain = timed(chain, a.warmup, a.reps, a.repeats)
+        t_chain = timed(chain)
         for label, b in boxes(v.extent):
             src = v.volume[b.z0:b.z0 + b.depth, b.y0:b.y0 + b.height, b.x0:b.x0 + b.width].contiguous()
 
@@ -89,15 +64,23 @@ def main():
                 ctx.update_volume_region(p(src), 0, False, 0.0, 255.0, b, p(v.volume), p(v.gradient), p(v.packed), v.extent, p(v.transfer_function), tf,
                                          maps, p(v.distance_map_swap), v.map_extent, skip, st)
 
-            t = timed(region, a.warmup, a.reps, a.repeats)
+            t = timed(region)
             line = "%-6s %-22s %8.3f  [%8.3f .. %8.3f]      %8.3f  [%8.3f .. %8.3f]" % ((name, label) + t + t_chain)
             lines.append(line)
             print(line, flush=True)
             del src
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    ctx.close()
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--maps", default="cheb,aniso")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    run(a, lambda ctx: measure(ctx, a), echo=False)  # the lines are printed as they are measured
 
 
 if __name__ == "__main__":
