@@ -11,7 +11,9 @@ Here, without a GPU and without a large allocation:
   (b) every reference on the real contents differs from the reference on a window that holds the surround fill everywhere - what a kernel
       whose address wrapped to the start of the buffer would read: a wrap is visible.  (vkv_propagate_labels without a mask and
       vkv_label_visibility_map read no voxel of the volume: they form no volume address, and their references are asserted to be the same);
-  (c) every *_scratch_bytes function gives, for each large extent and box, what it gives for the box in its window volume."""
+  (c) every *_scratch_bytes function gives, for each large extent and box, what it gives for the box in its window volume;
+  (d) the references and make_aux take the parameters that tests/box_ops_fuzz.py draws as keywords; with the defaults every reference of a
+      large case has the bytes it had before they did (a table of digests)."""
 import functools
 
 import numpy as np
@@ -96,147 +98,203 @@ def crop(vol, box):
 
 
 # ---- the inputs an operation takes besides the volume: made from the box's contents, the same whatever surrounds the box ------------------
-def make_aux(contents, seed):
+def keep_table(rng, k, mode="some"):
+    """one byte per label: which labels a table keeps (or shows): "some" of them at random, "all" or "none" of them"""
+    n = max(k, 1)
+    return {"some": rng.integers(0, 2, size=n), "all": np.ones(n, np.int64), "none": np.zeros(n, np.int64)}[mode].astype(np.uint8)
+
+
+def make_aux(contents, seed, iso=ISO, connectivity=6, weights=WEIGHTS, target=TO_INSIDE, limit=None, dist_limit=10, keep="some", colors="some",
+             seed_density=0.03):
+    """the keywords are tests/box_ops_fuzz.py's drawn parameters; their defaults are what the large cases use"""
     rng = np.random.default_rng(seed + 50000)
-    labels, sizes, counts = components_np(contents, ISO, 6)
+    labels, sizes, counts = components_np(contents, iso, connectivity)
     k = int(counts[0])
-    nearest, _ = nearest_separable_np(contents, ISO, WEIGHTS, TO_INSIDE, None)
+    nearest, _ = nearest_separable_np(contents, iso, weights, target, limit)
     return dict(
         labels=labels, sizes=sizes, counts=counts,
-        keep=rng.integers(0, 2, size=max(k, 1)).astype(np.uint8),
-        colors=(rng.integers(0, 2, size=max(k, 1)).astype(np.uint32) * np.uint32(0xFF000000)) | np.uint32(0x00C08040),
-        dist2=edt2_np(contents, ISO, TO_INSIDE, 10),
+        keep=keep_table(rng, k, keep),
+        colors=(keep_table(rng, k, colors).astype(np.uint32) * np.uint32(0xFF000000)) | np.uint32(0x00C08040),
+        dist2=edt2_np(contents, iso, target, dist_limit),
         nearest=nearest,
         plabels=rng.integers(1, 2 ** 32, size=contents.shape, dtype=np.uint64).astype(np.uint32),
-        seeds=np.where(rng.random(contents.shape) < 0.03, rng.integers(1, 6, size=contents.shape), 0).astype(np.uint32))
+        seeds=np.where(rng.random(contents.shape) < seed_density, rng.integers(1, 6, size=contents.shape), 0).astype(np.uint32))
 
 
-# ---- the references: f(vol, box, origin, aux, blocks) -> {name: array}; vol holds the box at `box` and lies at `origin` in the real volume ----------
-# (a name that starts with "_" says where the arrays lie in the real volume's map, in cells (z, y, x))
-def _map_extent(vol, blocks):
-    return tuple(e // b for e, b in zip(vol.shape[::-1], blocks))
+# ---- the references: f(vol, box, origin, aux, blocks, **parameters) -> {name: array}; vol holds the box at `box` and lies at `origin` in the real
+# volume.  The parameters are keywords whose defaults are the large cases' constants; tests/box_ops_fuzz.py draws them, and gives every
+# reference the whole drawn set, so each takes what it knows and ignores the rest (**_).
+# (a name that starts with "_" is not an output: "_at" says where the arrays lie in the real volume's map, in cells (z, y, x); "_cap*" is the
+# capacity the call is to be given, where the parameters set one)
+def _map_extent(vol, blocks, me=None):
+    return tuple(e // b for e, b in zip(vol.shape[::-1], blocks)) if me is None else tuple(me)
 
 
-def _cells(vol, box, origin, b, lo_hi):
-    """the slices (z, y, x) into vol's own map of the cells lo_hi(x0, n, b) names per axis, in the real volume's map, and their first cell"""
+def _cells(vol, box, origin, b, lo_hi, me=None):
+    """the slices (z, y, x) into vol's own map of the cells lo_hi(x0, n, b) names per axis, in the real volume's map, and their first cell.
+    me: the map extent of a volume that is its own window (origin 0), whose last cells need not be whole"""
     d, h, w = vol.shape
     extent = (w, h, d)
-    assert all(e % k == 0 and o % k == 0 for e, k, o in zip(extent, b, origin)), "the window is made of whole cells"
+    if me is None:
+        assert all(e % k == 0 and o % k == 0 for e, k, o in zip(extent, b, origin)), "the window is made of whole cells"
+        me = tuple(e // k for e, k in zip(extent, b))
+    else:
+        assert tuple(origin) == (0, 0, 0) and all(-(-e // m) == k for e, m, k in zip(extent, me, b)), "blocks are ceil(extent / map extent)"
     sl, at = [], []
     for axis in range(3):
         first, last = lo_hi(box[axis] + origin[axis], box[3 + axis], b[axis])        # in the real map; the window ends where the map does, or later
-        first, last = max(first, origin[axis] // b[axis]), min(last, (origin[axis] + extent[axis]) // b[axis] - 1)
+        first, last = max(first, origin[axis] // b[axis]), min(last, origin[axis] // b[axis] + me[axis] - 1)
         sl.append(slice(first - origin[axis] // b[axis], last + 1 - origin[axis] // b[axis]))
         at.append(first)
     return tuple(sl[::-1]), np.array(at[::-1], np.int64)
 
 
-def ref_max_map_box(vol, box, origin, aux, blocks):
+def capacity_of(cap, total):
+    """a capacity parameter: None (the large cases: nothing is cut, and the call gets total + 5), a number, or a function of the total"""
+    return None if cap is None else int(cap(total) if callable(cap) else cap)
+
+
+def cut(want, counts, pairs):
+    """cuts the lists of a reference at their capacities: pairs of (capacity parameter, index of the total in counts, the lists' names); the
+    element of counts after a total is what is written"""
+    for n, (cap, at, names) in enumerate(pairs):
+        c = capacity_of(cap, int(counts[at]))
+        if c is not None:
+            counts[at + 1] = min(int(counts[at]), c)
+            want["_cap%d" % n] = c
+            for name in names:
+                want[name] = want[name][:c]
+    want["counts"] = counts
+    return want
+
+
+def ref_max_map_box(vol, box, origin, aux, blocks, me=None, **_):
     """vkv_max_map(box): the cells whose voxel box grown by one voxel meets the box: ceil(x0 / b) - 1 .. (x0 + n) / b, clamped to the map"""
-    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (max(-(-x0 // b) - 1, 0), (x0 + n) // b))
-    return {"cells": np.ascontiguousarray(max_map_np(vol, _map_extent(vol, blocks))[sl]), "_at": at}
+    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (max(-(-x0 // b) - 1, 0), (x0 + n) // b), me)
+    return {"cells": np.ascontiguousarray(max_map_np(vol, _map_extent(vol, blocks, me))[sl]), "_at": at}
 
 
-def ref_max_map_whole(vol, box, origin, aux, blocks):
+def ref_max_map_whole(vol, box, origin, aux, blocks, me=None, **_):
     """vkv_max_map of the whole volume, around the box: the cells of the box and one more per side"""
-    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (max(x0 // b - 1, 0), (x0 + n - 1) // b + 1))
-    return {"cells": np.ascontiguousarray(max_map_np(vol, _map_extent(vol, blocks))[sl]), "_at": at}
+    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (max(x0 // b - 1, 0), (x0 + n - 1) // b + 1), me)
+    return {"cells": np.ascontiguousarray(max_map_np(vol, _map_extent(vol, blocks, me))[sl]), "_at": at}
 
 
-def ref_cell_summary(vol, box, origin, aux, blocks):
+def ref_cell_summary(vol, box, origin, aux, blocks, me=None, **_):
     """vkv_cell_summary(box), no gradient: the cells that hold a voxel of the box"""
-    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (x0 // b, (x0 + n - 1) // b))
-    mw, mh, md = me = _map_extent(vol, blocks)
+    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (x0 // b, (x0 + n - 1) // b), me)
+    mw, mh, md = me = _map_extent(vol, blocks, me)
     return {"cells": np.ascontiguousarray(summary_np(vol, None, me).reshape(md, mh, mw, 16)[sl]), "_at": at}
 
 
-def ref_visibility_map(vol, box, origin, aux, blocks):
+def ref_visibility_map(vol, box, origin, aux, blocks, me=None, **_):
     """vkv_label_visibility_map writes the whole map: here the window's cells; every other cell sees no voxel of the box and holds 0"""
-    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (x0 // b - 2, (x0 + n) // b + 2))
-    vis = visibility_map_np(aux["labels"], box, vol.shape, aux["colors"], _map_extent(vol, blocks))
+    sl, at = _cells(vol, box, origin, blocks, lambda x0, n, b: (x0 // b - 2, (x0 + n) // b + 2), me)
+    vis = visibility_map_np(aux["labels"], box, vol.shape, aux["colors"], _map_extent(vol, blocks, me))
     return {"cells": np.ascontiguousarray(vis[sl]), "_at": at}
 
 
-def ref_histogram(vol, box, origin, aux, blocks):
-    return {"hist": np.bincount(crop(vol, box).reshape(-1).astype(np.int64), minlength=65536).astype(np.int64)}
+def ref_histogram(vol, box, origin, aux, blocks, mode=0, before=0, **_):
+    """mode: abi.HISTOGRAM_SET, _ADD or _SUBTRACT (0, 1, 2); before: what every bin held"""
+    counts = np.bincount(crop(vol, box).reshape(-1).astype(np.int64), minlength=65536).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        hist = {0: counts, 1: np.uint64(before) + counts, 2: np.uint64(before) - counts}[mode]
+    return {"hist": hist.view(np.int64)}
 
 
 def ref_filter(statement):
-    return lambda vol, box, origin, aux, blocks: {"dst": crop(statement(vol), box)}
+    return lambda vol, box, origin, aux, blocks, **_: {"dst": crop(statement(vol), box)}
 
 
-def ref_mesh(vol, box, origin, aux, blocks):
-    tri = mesh_np(vol, ISO, box, origin)
-    return {"triangles": tri, "counts": np.array([len(tri), len(tri)], np.uint64)}
+def ref_mesh(vol, box, origin, aux, blocks, iso=ISO, cap=None, **_):
+    tri = mesh_np(vol, iso, box, origin)
+    return cut({"triangles": tri}, np.array([len(tri), len(tri)], np.uint64), [(cap, 0, ("triangles",))])
 
 
-def ref_mesh_indexed(vol, box, origin, aux, blocks):
-    v, n, f = indexed_np(vol, ISO, box, origin)
-    return {"vertices": v, "normals": n, "indices": f.astype(np.uint32), "counts": np.array([len(f), len(f), len(v), len(v)], np.uint64)}
+def ref_mesh_indexed(vol, box, origin, aux, blocks, iso=ISO, cap=None, cap_vertices=None, **_):
+    v, n, f = indexed_np(vol, iso, box, origin)
+    return cut({"vertices": v, "normals": n, "indices": f.astype(np.uint32)}, np.array([len(f), len(f), len(v), len(v)], np.uint64),
+               [(cap, 0, ("indices",)), (cap_vertices, 2, ("vertices", "normals"))])
 
 
 def ref_components(connectivity):
-    def ref(vol, box, origin, aux, blocks):
-        labels, sizes, counts = components_np(vol, ISO, connectivity, box)
-        return {"labels": labels, "sizes": sizes, "counts": counts}
+    def ref(vol, box, origin, aux, blocks, iso=ISO, connectivity=connectivity, cap=None, **_):
+        labels, sizes, counts = components_np(vol, iso, connectivity, box)
+        return cut({"labels": labels, "sizes": sizes}, counts, [(cap, 0, ("sizes",))])
     return ref
 
 
-def ref_select_components(vol, box, origin, aux, blocks):
-    k = int(aux["counts"][0])
-    return {"dst": select_np(crop(vol, box), aux["labels"], aux["sizes"], k, 3, EVERYTHING, 9)}
+def ref_select_components(vol, box, origin, aux, blocks, lo=3, hi=EVERYTHING, fill=9, **_):
+    return {"dst": select_np(crop(vol, box), aux["labels"], aux["sizes"], int(aux["counts"][1]), lo, hi, fill)}
 
 
-def ref_component_stats(vol, box, origin, aux, blocks):
+def ref_component_stats(vol, box, origin, aux, blocks, cap=None, **_):
     """the records as bytes; the statement's coordinates are the array's, the call's the real volume's: exact integers, moved by `origin`"""
     k = int(aux["counts"][0])
-    rec = component_stats_np(vol, aux["labels"], k, k + 5, box)
+    c = capacity_of(cap, k)
+    rec = component_stats_np(vol, aux["labels"], k, k + 5 if c is None else c, box)
     some = rec["voxels"] > 0
     for axis, o in zip("xyz", origin):
         for f in ("min_", "max_"):
             rec[f + axis][some] += np.uint32(o)
         rec["sum_" + axis] += rec["voxels"] * np.uint64(o)
-    return {"records": np.frombuffer(rec.tobytes(), np.uint8).copy()}
+    want = {"records": np.frombuffer(rec.tobytes(), np.uint8).copy()}
+    if c is not None:
+        want["_cap0"] = c
+    return want
 
 
-def ref_select_by_table(vol, box, origin, aux, blocks):
-    return {"dst": select_by_table_np(crop(vol, box), aux["labels"], aux["keep"], 7)}
+def ref_select_by_table(vol, box, origin, aux, blocks, fill=7, **_):
+    return {"dst": select_by_table_np(crop(vol, box), aux["labels"], aux["keep"], fill)}
 
 
 DISTANCE_CALLS = tuple((target, limit) for target in (TO_INSIDE, TO_OUTSIDE) for limit in (None, 10))
 
 
-def ref_distance(vol, box, origin, aux, blocks):
-    return {"to %d limit %s" % (t, l): edt2_np(vol, ISO, t, l, box) for t, l in DISTANCE_CALLS}
+def rejected(shape, names):
+    """the reference of a call that the header rejects (a limit of 0): nothing of any output is written"""
+    return {name: np.zeros((0,) + tuple(shape[1:]), np.uint32) for name in names}
 
 
-def ref_select_by_distance(vol, box, origin, aux, blocks):
-    return {"dst": select_by_distance_np(crop(vol, box), aux["dist2"], 1, 9, 255)}
+def ref_distance(vol, box, origin, aux, blocks, iso=ISO, calls=DISTANCE_CALLS, **_):
+    shape = box[:2:-1]
+    return {"to %d limit %s" % (t, l): rejected(shape, "d")["d"] if l == 0 else edt2_np(vol, iso, t, l, box) for t, l in calls}
 
 
-def ref_distance_weighted(vol, box, origin, aux, blocks):
-    return {"to %d" % t: edt2_weighted_np(vol, ISO, WEIGHTS, t, None, box) for t in (TO_INSIDE, TO_OUTSIDE)}
+def ref_select_by_distance(vol, box, origin, aux, blocks, lo=1, hi=9, fill=255, **_):
+    return {"dst": select_by_distance_np(crop(vol, box), aux["dist2"], lo, hi, fill)}
 
 
-def ref_nearest(vol, box, origin, aux, blocks):
-    nearest, dist2 = nearest_separable_np(vol, ISO, WEIGHTS, TO_INSIDE, None, box)
+def ref_distance_weighted(vol, box, origin, aux, blocks, iso=ISO, weights=WEIGHTS, limit=None, **_):
+    if limit == 0:
+        return rejected(box[:2:-1], ["to %d" % t for t in (TO_INSIDE, TO_OUTSIDE)])
+    return {"to %d" % t: edt2_weighted_np(vol, iso, weights, t, limit, box) for t in (TO_INSIDE, TO_OUTSIDE)}
+
+
+def ref_nearest(vol, box, origin, aux, blocks, iso=ISO, weights=WEIGHTS, target=TO_INSIDE, limit=None, **_):
+    if limit == 0:
+        return rejected(box[:2:-1], ("nearest", "dist2"))
+    nearest, dist2 = nearest_separable_np(vol, iso, weights, target, limit, box)
     return {"nearest": nearest, "dist2": dist2}
 
 
 def ref_propagate(masked):
-    def ref(vol, box, origin, aux, blocks):
-        return {"out": propagate_labels_np(aux["nearest"], aux["plabels"], inside_np(vol, ISO, box) if masked else None)}
+    def ref(vol, box, origin, aux, blocks, iso=ISO, **_):
+        return {"out": propagate_labels_np(aux["nearest"], aux["plabels"], inside_np(vol, iso, box) if masked else None)}
     return ref
 
 
-def ref_geodesic(vol, box, origin, aux, blocks):
-    dist, labels = geodesic_sweeps_np(vol, ISO, aux["seeds"], CHAMFER, None, box)
+def ref_geodesic(vol, box, origin, aux, blocks, iso=ISO, steps=CHAMFER, limit=None, **_):
+    if limit == 0:
+        return dict(rejected(box[:2:-1], ("dist", "labels")), counts=np.zeros(0, np.uint64))
+    dist, labels = geodesic_sweeps_np(vol, iso, aux["seeds"], steps, limit, box)
     return {"dist": dist, "labels": labels, "counts": np.array([1, int((dist != GEO_NONE).sum())], np.uint64)}
 
 
-def ref_label_mesh(vol, box, origin, aux, blocks):
-    tri, lab = label_mesh_np(aux["labels"], None, vol, ISO, box, origin)
-    return {"triangles": tri, "triangle_labels": lab, "counts": np.array([len(tri), len(tri)], np.uint64)}
+def ref_label_mesh(vol, box, origin, aux, blocks, iso=ISO, cap=None, table=False, **_):
+    """table: with aux["colors"] as the colour table (else every label is shown)"""
+    tri, lab = label_mesh_np(aux["labels"], aux["colors"] if table else None, vol, iso, box, origin)
+    return cut({"triangles": tri, "triangle_labels": lab}, np.array([len(tri), len(tri)], np.uint64), [(cap, 0, ("triangles", "triangle_labels"))])
 
 
 # name: (halo, reference, the operation reads voxels of the volume)
@@ -365,3 +423,45 @@ def test_scratch_sizes_are_those_of_the_box_in_its_window(name):
             assert big > 0 and big == scratch_bytes(abi.Extent3D(*size), abi.Box(*wbox)), (what, name, kind)
             assert big == scratch_bytes(abi.Extent3D(*box[3:]), None), (what, name, "the box as a volume of its own")
     assert lib.distance_transform_scratch_bytes(abi.Extent3D(*EXTENTS[extent]), abi.Box(*box)) == 4 * n + 8 * ((n + 63) // 64)
+
+
+# ---- (d) the references are those of the commit before the keywords came ----------------------------------------------------------------------
+# sha256 (16 hex digits) over every large case and both fills of the reference's arrays (name, type, shape, bytes, names sorted), taken before
+# ref_* and make_aux got keyword parameters: with the defaults nothing of what tests/test_gpu_far_boxes.py compares with has moved
+DIGESTS = {
+    "max_map_box": "14ce6904bbcba3d9",
+    "max_map_whole": "ef9aa2acb85d09cd",
+    "cell_summary": "c928f8533700b31a",
+    "histogram": "1f670722138d722e",
+    "filter_binomial": "1265231a39e7d6d8",
+    "filter_median": "6e6ff7264509b838",
+    "mesh": "f278bb0da90f7b92",
+    "mesh_indexed": "7c17677b02139fb0",
+    "components_6": "7ce96b4340f47260",
+    "components_26": "55cbf1f64e7e0717",
+    "select_components": "867f61501ef83f82",
+    "component_stats": "8023391245e45684",
+    "select_by_table": "c710ee5e05ad6df2",
+    "distance": "22b4809379b93dc4",
+    "select_by_distance": "e6e40738efe0e979",
+    "distance_weighted": "c5ba6f2ca456f35e",
+    "nearest": "5dc60b4eb8785eb4",
+    "propagate": "3ecfd87c5fcd317f",
+    "propagate_masked": "e0b11f1a4e611713",
+    "geodesic": "b5636e19cbfa3cc0",
+    "visibility_map": "47d46dcc8baf1130",
+    "label_mesh": "633f6683f22425a2",
+}
+
+
+@pytest.mark.parametrize("op", sorted(REFERENCES))
+def test_the_references_of_the_large_cases_keep_their_bytes(op):
+    import hashlib
+    h = hashlib.sha256()
+    for name, _, _, _ in CASES:
+        for fill in FILLS:
+            r = reference(name, op, fill)
+            for k in sorted(r):
+                h.update(("%s|%s|%s|" % (k, r[k].dtype.str, r[k].shape)).encode())
+                h.update(r[k].tobytes())
+    assert h.hexdigest()[:16] == DIGESTS[op], op

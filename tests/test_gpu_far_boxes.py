@@ -66,29 +66,53 @@ def count_not(t, value):
 
 
 class Buffers:
-    """the small guarded buffers of one call: outputs pre-filled with FILL, inputs copied in; check(): every guard intact, the inputs unchanged"""
+    """the small guarded buffers of one call: outputs pre-filled with `prefill`, inputs copied in; check(): every guard intact, the inputs
+    unchanged.  guard: the byte of the guards (None: the pre-fill's); offsets(name): by how many times its alignment the buffer `name` starts
+    past a 256-byte boundary (None: 0).  After again() the same names give the same buffers once more, the outputs pre-filled anew and the
+    scratch block as the call before left it."""
 
-    def __init__(self):
-        self.handles, self.inputs, self.tail = [], [], None
+    def __init__(self, prefill=FILL, guard=None, offsets=None):
+        self.prefill, self.guard, self.offsets = prefill, prefill if guard is None else guard, offsets or (lambda name: 0)
+        self.handles, self.inputs, self.tail, self.made, self.second = [], [], None, {}, False
 
-    def out(self, name, shape, dtype=np.uint8):
-        t, h = T.guarded(tuple(shape), 0, FILL, "cuda", dtype=dtype)
+    def alloc(self, name, what, dtype=np.uint8, align=None):
+        """(tensor, handle) of a guarded buffer that this object does not keep: `what` is a shape (pre-filled) or an array (copied in)"""
+        item = what.dtype.itemsize if isinstance(what, np.ndarray) else np.dtype(dtype).itemsize
+        if not isinstance(what, np.ndarray) and what[0] == 0:        # a capacity of 0: one element that has to keep its pre-fill (an empty tensor has no address)
+            what = (1,) + tuple(what[1:])
+        t, h = T.guarded(what, self.offsets(name) * (align or item), self.guard, "cuda", dtype=dtype)
+        if not isinstance(what, np.ndarray) and self.prefill != self.guard:
+            h.buf[h.start:h.stop].fill_(self.prefill)
+        return t, h
+
+    def out(self, name, shape, dtype=np.uint8, align=None):
+        if self.second:
+            t, h = self.made[name]
+            if not name.startswith("d_scratch"):
+                h.buf[h.start:h.stop].fill_(self.prefill)
+            return t
+        t, h = self.made[name] = self.alloc(name, tuple(shape), dtype, align)
         self.handles.append((name, h))
         return t
 
-    def inp(self, name, array):
+    def inp(self, name, array, align=None):
+        if self.second:
+            return self.made[name][0]
         a = np.ascontiguousarray(array)
         a = a.view({np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype, a.dtype))
-        t, h = T.guarded(a, 0, FILL, "cuda")
+        t, h = self.made[name] = self.alloc(name, a, align=align)
         self.handles.append((name, h))
         self.inputs.append((name, t, a))
         return t
 
-    def scratch(self, nbytes):
+    def scratch(self, nbytes, name="d_scratch"):
         """exactly nbytes of scratch: the allocation's payload is whole 8-byte words, the bytes past nbytes are not the call's to write"""
-        t = self.out("d_scratch", ((nbytes + 7) // 8,), np.int64)
+        t = self.out(name, ((nbytes + 7) // 8,), np.int64)
         self.tail = (t, nbytes)
         return t
+
+    def again(self):
+        self.second = True
 
     def check(self, what):
         for name, h in self.handles:
@@ -97,7 +121,7 @@ class Buffers:
         for name, t, a in self.inputs:
             assert np.array_equal(t.cpu().numpy(), a), "%s: the input %s changed" % (what, name)
         if self.tail is not None and self.tail[1] % 8:
-            assert (self.tail[0].view(torch.uint8)[self.tail[1]:].cpu().numpy() == FILL).all(), "%s: bytes past the scratch block changed" % what
+            assert (self.tail[0].view(torch.uint8)[self.tail[1]:].cpu().numpy() == self.prefill).all(), "%s: bytes past the scratch block changed" % what
 
 
 # ---- the large volume of a case ---------------------------------------------------------------------------------------------------------------
@@ -153,6 +177,38 @@ def scene(name, fill):
     return _held[(name, fill)]
 
 
+class SmallScene:
+    """Scene's sibling for a volume small enough to come from the host (tests/test_gpu_box_ops_fuzz.py): it is its own window, with origin
+    (0, 0, 0).  vol: the host array [d, h, w]; box: (x0, y0, z0, w, h, d) or None, the whole volume; me: the map extent (w, h, d) of the calls
+    that take a map; B: the Buffers whose guard byte, pre-fill and offsets the volume and the map take"""
+
+    def __init__(self, vol, box, aux, me, B):
+        d, h, w = vol.shape
+        self.extent, self.vol, self.aux, self.me, self.fill = (w, h, d), vol, aux, tuple(me), 0
+        self.box = (0, 0, 0, w, h, d) if box is None else tuple(box)
+        self.e, self.abox, self.ame = abi.Extent3D(w, h, d), None if box is None else abi.Box(*box), abi.Extent3D(*me)
+        self.d_vol, self.h_vol = B.alloc("d_volume", vol)
+        self.contents = np.ascontiguousarray(self.region(vol))
+        self.d_contents = torch.from_numpy(self.contents).cuda()
+        self.shape, self.whole_map, self.B = self.contents.shape, None, B
+
+    region = Scene.region
+
+    def check_volume(self, what):
+        bad = guard_damage(self.h_vol)
+        assert not bad, "%s: d_volume: guard bytes %s changed (payload is bytes %d .. %d)" % (what, bad[:8], self.h_vol.start, self.h_vol.stop - 1)
+        assert np.array_equal(self.d_vol.cpu().numpy(), self.vol), "%s: the volume changed" % what
+
+    def max_map(self, ctx):
+        """vkv_max_map of the whole volume, built once on the device"""
+        if self.whole_map is None:
+            mw, mh, md = self.me
+            self.whole_map = self.B.alloc("d_whole_map", (md, mh, mw))
+            ctx.max_map(self.d_vol.data_ptr(), self.e, self.ame, None, self.whole_map[0].data_ptr(), st())
+            torch.cuda.synchronize()
+        return self.whole_map[0]
+
+
 def cells_of(d_map, want):
     """the view of the map's cells that the reference names"""
     z, y, x = (int(v) for v in want["_at"])
@@ -173,25 +229,26 @@ def cells_and_rest(d_map, want, rest, what, restore=False):
     return got
 
 
-def volume_shaped(S, what, call, in_place=False):
-    """the box of the output of call(d_dst), d_dst of the volume's shape: a second guarded allocation pre-filled with FILL, every byte of which
-    outside the box must keep the pre-fill; in place: the volume itself, whose box is put back"""
+def volume_shaped(S, what, call, in_place=False, B=None):
+    """the box of the output of call(d_dst), d_dst of the volume's shape: a second guarded allocation pre-filled with B's pre-fill, every byte
+    of which outside the box must keep it; in place: the volume itself, whose box is put back"""
     if in_place:
         call(S.d_vol)
         torch.cuda.synchronize()
         got = S.region(S.d_vol).cpu().numpy()
         S.region(S.d_vol).copy_(S.d_contents)
         return got
+    B = B or Buffers()
     w, h, d = S.extent
-    d_dst, h_dst = T.guarded((d, h, w), 0, FILL, "cuda")
+    d_dst, h_dst = B.alloc("d_dst", (d, h, w))
     try:
         call(d_dst)
         torch.cuda.synchronize()
         got = S.region(d_dst).cpu().numpy()
         bad = guard_damage(h_dst)
         assert not bad, "%s: d_dst: guard bytes %s changed" % (what, bad[:8])
-        S.region(d_dst).fill_(FILL)
-        changed = count_not(d_dst, FILL)
+        S.region(d_dst).fill_(B.prefill)
+        changed = count_not(d_dst, B.prefill)
         assert changed == 0, "%s: %d bytes of d_dst outside the box changed" % (what, changed)
         return got
     finally:
@@ -199,43 +256,46 @@ def volume_shaped(S, what, call, in_place=False):
         torch.cuda.empty_cache()
 
 
-# ---- one call of each operation: f(ctx, S, want, B, what) -> {name: whole output buffer} -------------------------------------------------------
-def run_max_map_box(ctx, S, want, B, what):
+# ---- one call of each operation: f(ctx, S, want, B, what, **parameters) -> {name: whole output buffer} ----------------------------------------
+# The parameters are the keywords of the references of tests/test_far_boxes_cpu.py, with the same defaults (the large cases' constants), and
+# every call takes the whole drawn set of tests/box_ops_fuzz.py and ignores what it does not know (**_).  A capacity comes from the reference
+# ("_cap0", "_cap1": what the parameters set), else it is the total + 5.
+def run_max_map_box(ctx, S, want, B, what, **_):
     mw, mh, md = S.me
     d_map = B.out("d_max_map", (md, mh, mw))
     ctx.max_map(S.d_vol.data_ptr(), S.e, S.ame, S.abox, d_map.data_ptr(), st())
     torch.cuda.synchronize()
-    return {"cells": cells_and_rest(d_map, want, FILL, what)}
+    return {"cells": cells_and_rest(d_map, want, B.prefill, what)}
 
 
-def run_max_map_whole(ctx, S, want, B, what):
+def run_max_map_whole(ctx, S, want, B, what, **_):
     """every cell outside those around the box sees the surround fill alone"""
     return {"cells": cells_and_rest(S.max_map(ctx), want, S.fill, what, restore=True)}
 
 
-def run_cell_summary(ctx, S, want, B, what):
+def run_cell_summary(ctx, S, want, B, what, **_):
     mw, mh, md = S.me
-    d_summary, h = T.guarded((md, mh, mw, abi.CELL_SUMMARY_BYTES), 0, FILL, "cuda")
+    d_summary, h = B.alloc("d_summary", (md, mh, mw, abi.CELL_SUMMARY_BYTES), align=16)
     try:
         ctx.cell_summary(S.d_vol.data_ptr(), None, S.e, S.ame, S.abox, d_summary.data_ptr(), st())
         torch.cuda.synchronize()
         bad = guard_damage(h)
         assert not bad, "%s: d_summary: guard bytes %s changed" % (what, bad[:8])
-        return {"cells": cells_and_rest(d_summary, want, FILL, what)}
+        return {"cells": cells_and_rest(d_summary, want, B.prefill, what)}
     finally:
         del d_summary, h
         torch.cuda.empty_cache()
 
 
-def run_histogram(ctx, S, want, B, what):
+def run_histogram(ctx, S, want, B, what, mode=abi.HISTOGRAM_SET, **_):
     d_hist = B.out("d_histogram", (65536,), np.int64)
-    ctx.volume_histogram(S.d_vol.data_ptr(), None, S.e, S.abox, abi.HISTOGRAM_SET, d_hist.data_ptr(), st())
+    ctx.volume_histogram(S.d_vol.data_ptr(), None, S.e, S.abox, mode, d_hist.data_ptr(), st())
     return {"hist": d_hist}
 
 
 def run_filter(kind):
-    def run(ctx, S, want, B, what):
-        return {"dst": volume_shaped(S, what, lambda d_dst: ctx.filter_volume(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, kind, st()))}
+    def run(ctx, S, want, B, what, **_):
+        return {"dst": volume_shaped(S, what, lambda d_dst: ctx.filter_volume(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, kind, st()), B=B)}
     return run
 
 
@@ -244,70 +304,70 @@ def map_args(ctx, S, use_map):
 
 
 def run_mesh(use_map):
-    def run(ctx, S, want, B, what):
-        cap = len(want["triangles"]) + 5
+    def run(ctx, S, want, B, what, iso=ISO, use_map=use_map, **_):
+        cap = want.get("_cap0", len(want["triangles"]) + 5)
         nbytes = lib.mesh_scratch_bytes(S.e, S.abox)
         assert nbytes >= 16 and nbytes % 8 == 0, (what, nbytes)
         d_scratch, d_counts, d_tri = B.scratch(nbytes), B.out("d_counts", (2,), np.int64), B.out("d_triangles", (cap, 3, 3), np.float32)
-        ctx.isosurface_mesh(S.d_vol.data_ptr(), S.e, S.abox, ISO, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_tri.data_ptr(), cap, d_counts.data_ptr(),
+        ctx.isosurface_mesh(S.d_vol.data_ptr(), S.e, S.abox, iso, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_tri.data_ptr(), cap, d_counts.data_ptr(),
                             st())
         return {"triangles": d_tri, "counts": d_counts}
     return run
 
 
 def run_mesh_indexed(use_map):
-    def run(ctx, S, want, B, what):
-        cap_v, cap_t = len(want["vertices"]) + 5, len(want["indices"]) + 5
+    def run(ctx, S, want, B, what, iso=ISO, use_map=use_map, **_):
+        cap_v, cap_t = want.get("_cap1", len(want["vertices"]) + 5), want.get("_cap0", len(want["indices"]) + 5)
         nbytes = lib.mesh_indexed_scratch_bytes(S.e, S.abox)
         assert nbytes >= 16 and nbytes % 8 == 0, (what, nbytes)
         d_scratch, d_counts = B.scratch(nbytes), B.out("d_counts", (4,), np.int64)
         d_vert, d_norm = B.out("d_vertices", (cap_v, 3), np.float32), B.out("d_normals", (cap_v, 3), np.float32)
         d_idx = B.out("d_indices", (cap_t, 3), np.int32)
-        ctx.isosurface_mesh_indexed(S.d_vol.data_ptr(), S.e, S.abox, ISO, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_vert.data_ptr(),
-                                    d_norm.data_ptr(), cap_v, d_idx.data_ptr(), cap_t, d_counts.data_ptr(), st())
+        ctx.isosurface_mesh_indexed(S.d_vol.data_ptr(), S.e, S.abox, iso, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_vert.data_ptr(),
+                                    d_norm.data_ptr() if cap_v else None, cap_v, d_idx.data_ptr(), cap_t, d_counts.data_ptr(), st())
         return {"vertices": d_vert, "normals": d_norm, "indices": d_idx, "counts": d_counts}
     return run
 
 
 def run_components(connectivity, use_map):
-    def run(ctx, S, want, B, what):
-        cap = int(want["counts"][0]) + 5
+    def run(ctx, S, want, B, what, iso=ISO, connectivity=connectivity, use_map=use_map, **_):
+        cap = want.get("_cap0", int(want["counts"][0]) + 5)
         nbytes = lib.components_scratch_bytes(S.e, S.abox)
         assert nbytes >= 40 and nbytes % 8 == 0, (what, nbytes)
         d_scratch, d_counts = B.scratch(nbytes), B.out("d_counts", (3,), np.int64)
         d_labels, d_sizes = B.out("d_labels", S.shape, np.int32), B.out("d_sizes", (cap,), np.int32)
-        ctx.label_components(S.d_vol.data_ptr(), S.e, S.abox, ISO, connectivity, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_labels.data_ptr(),
+        ctx.label_components(S.d_vol.data_ptr(), S.e, S.abox, iso, connectivity, *map_args(ctx, S, use_map), d_scratch.data_ptr(), d_labels.data_ptr(),
                              d_sizes.data_ptr(), cap, d_counts.data_ptr(), st())
         return {"labels": d_labels, "sizes": d_sizes, "counts": d_counts}
     return run
 
 
 def run_select_components(in_place):
-    def run(ctx, S, want, B, what):
+    def run(ctx, S, want, B, what, lo=3, hi=F.EVERYTHING, fill=9, in_place=in_place, **_):
         a = S.aux
         d_labels, d_counts = B.inp("d_labels", a["labels"]), B.inp("d_counts", a["counts"])
         d_sizes = B.inp("d_sizes", a["sizes"] if len(a["sizes"]) else np.zeros(1, np.uint32))
         call = lambda d_dst: ctx.select_components(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, d_labels.data_ptr(), d_sizes.data_ptr(),  # noqa: E731
-                                                   d_counts.data_ptr(), 3, F.EVERYTHING, 9, st())
-        return {"dst": volume_shaped(S, what, call, in_place)}
+                                                   d_counts.data_ptr(), lo, hi, fill, st())
+        return {"dst": volume_shaped(S, what, call, in_place, B)}
     return run
 
 
-def run_component_stats(ctx, S, want, B, what):
+def run_component_stats(ctx, S, want, B, what, **_):
     k = int(S.aux["counts"][0])
-    cap = k + 5
+    cap = want.get("_cap0", k + 5)
     d_labels = B.inp("d_labels", S.aux["labels"])
     d_counts = B.inp("d_counts", np.array([k, GARBAGE, GARBAGE], np.uint64))
-    d_stats = B.out("d_stats", ((cap + 3) * STATS_DTYPE.itemsize,))
+    d_stats = B.out("d_stats", ((cap + 3) * STATS_DTYPE.itemsize,), align=8)
     ctx.component_stats(S.d_vol.data_ptr(), S.e, S.abox, d_labels.data_ptr(), d_counts.data_ptr(), d_stats.data_ptr(), cap, st())
     return {"records": d_stats}
 
 
-def run_select_by_table(ctx, S, want, B, what):
+def run_select_by_table(ctx, S, want, B, what, fill=7, in_place=False, **_):
     d_labels, d_keep = B.inp("d_labels", S.aux["labels"]), B.inp("d_keep", S.aux["keep"])
     call = lambda d_dst: ctx.select_components_by_table(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, d_labels.data_ptr(), d_keep.data_ptr(),  # noqa: E731
-                                                        len(S.aux["keep"]), 7, st())
-    return {"dst": volume_shaped(S, what, call)}
+                                                        len(S.aux["keep"]), fill, st())
+    return {"dst": volume_shaped(S, what, call, in_place, B)}
 
 
 def distance_scratch(S, B, what):
@@ -317,46 +377,55 @@ def distance_scratch(S, B, what):
     return B.scratch(nbytes)
 
 
-def run_distance(ctx, S, want, B, what):
+def accepted(ctx, rc, limit, what):
+    """a limit of 0 is what the header rejects, before anything is enqueued; every other status is the context's error"""
+    if limit == 0:
+        assert rc == abi.VKV_E_INVALID_ARGUMENT, "%s: status %d for a limit of 0" % (what, rc)
+    else:
+        ctx.check(rc)
+
+
+def run_distance(ctx, S, want, B, what, iso=ISO, calls=F.DISTANCE_CALLS, **_):
     d_scratch, got = distance_scratch(S, B, what), {}
-    for target, limit in F.DISTANCE_CALLS:
+    for target, limit in calls:
         key = "to %d limit %s" % (target, limit)
         got[key] = B.out("d_dist2 " + key, S.shape, np.int32)
-        ctx.distance_transform(S.d_vol.data_ptr(), S.e, S.abox, ISO, target, limit, d_scratch.data_ptr(), got[key].data_ptr(), st())
+        accepted(ctx, ctx.distance_transform_rc(S.d_vol.data_ptr(), S.e, S.abox, iso, target, limit, d_scratch.data_ptr(), got[key].data_ptr(), st()), limit, what)
     return got
 
 
-def run_select_by_distance(ctx, S, want, B, what):
+def run_select_by_distance(ctx, S, want, B, what, lo=1, hi=9, fill=255, in_place=False, **_):
     d_dist = B.inp("d_dist2", S.aux["dist2"])
-    call = lambda d_dst: ctx.select_by_distance(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, d_dist.data_ptr(), 1, 9, 255, st())  # noqa: E731
-    return {"dst": volume_shaped(S, what, call)}
+    call = lambda d_dst: ctx.select_by_distance(S.d_vol.data_ptr(), d_dst.data_ptr(), S.e, S.abox, d_dist.data_ptr(), lo, hi, fill, st())  # noqa: E731
+    return {"dst": volume_shaped(S, what, call, in_place, B)}
 
 
-def run_distance_weighted(ctx, S, want, B, what):
+def run_distance_weighted(ctx, S, want, B, what, iso=ISO, weights=F.WEIGHTS, limit=None, **_):
     d_scratch, got = distance_scratch(S, B, what), {}
     for target in (TO_INSIDE, TO_OUTSIDE):
         got["to %d" % target] = d_dist = B.out("d_dist2 to %d" % target, S.shape, np.int32)
-        ctx.check(ctx.distance_transform_weighted_rc(S.d_vol.data_ptr(), S.e, S.abox, ISO, target, F.WEIGHTS, None, d_scratch.data_ptr(), d_dist.data_ptr(), st()))
+        accepted(ctx, ctx.distance_transform_weighted_rc(S.d_vol.data_ptr(), S.e, S.abox, iso, target, weights, limit, d_scratch.data_ptr(), d_dist.data_ptr(),
+                                                         st()), limit, what)
     return got
 
 
-def run_nearest(ctx, S, want, B, what):
+def run_nearest(ctx, S, want, B, what, iso=ISO, weights=F.WEIGHTS, target=TO_INSIDE, limit=None, **_):
     d_scratch, d_near, d_dist = distance_scratch(S, B, what), B.out("d_nearest", S.shape, np.int32), B.out("d_dist2", S.shape, np.int32)
-    ctx.check(ctx.nearest_target_rc(S.d_vol.data_ptr(), S.e, S.abox, ISO, TO_INSIDE, F.WEIGHTS, None, d_scratch.data_ptr(), d_near.data_ptr(), d_dist.data_ptr(),
-                                    st()))
+    accepted(ctx, ctx.nearest_target_rc(S.d_vol.data_ptr(), S.e, S.abox, iso, target, weights, limit, d_scratch.data_ptr(), d_near.data_ptr(), d_dist.data_ptr(),
+                                        st()), limit, what)
     return {"nearest": d_near, "dist2": d_dist}
 
 
 def run_propagate(masked):
-    def run(ctx, S, want, B, what):
+    def run(ctx, S, want, B, what, iso=ISO, **_):
         d_near, d_labels, d_out = B.inp("d_nearest", S.aux["nearest"]), B.inp("d_labels", S.aux["plabels"]), B.out("d_out", S.shape, np.int32)
         ctx.check(ctx.propagate_labels_rc(d_near.data_ptr(), d_labels.data_ptr(), d_out.data_ptr(), S.e, S.abox, S.d_vol.data_ptr() if masked else None,
-                                          ISO if masked else 0.0, st()))
+                                          iso if masked else 0.0, st()))
         return {"out": d_out}
     return run
 
 
-def run_geodesic(ctx, S, want, B, what, rounds=16, max_calls=40):
+def run_geodesic(ctx, S, want, B, what, rounds=16, max_calls=40, iso=ISO, steps=CHAMFER, limit=None, **_):
     """`rounds` rounds from the seeds, then resumed calls of as many until d_counts[0] says that the state is the fixed point"""
     n = int(np.prod(S.shape))
     nbytes = geodesic.scratch_bytes(S.e, S.abox)
@@ -365,8 +434,11 @@ def run_geodesic(ctx, S, want, B, what, rounds=16, max_calls=40):
     d_dist, d_labels = B.out("d_dist", S.shape, np.int32), B.out("d_labels", S.shape, np.int32)
     trace = []
     for call in range(max_calls):
-        ctx.check(ctx.geodesic_propagate_rc(S.d_vol.data_ptr(), S.e, S.abox, ISO, None if call else d_seeds.data_ptr(), CHAMFER, None, rounds, call > 0,
-                                            d_scratch.data_ptr(), d_dist.data_ptr(), d_labels.data_ptr(), d_counts.data_ptr(), st()))
+        rc = ctx.geodesic_propagate_rc(S.d_vol.data_ptr(), S.e, S.abox, iso, None if call else d_seeds.data_ptr(), steps, limit, rounds, call > 0,
+                                       d_scratch.data_ptr(), d_dist.data_ptr(), d_labels.data_ptr(), d_counts.data_ptr(), st())
+        accepted(ctx, rc, limit, what)
+        if limit == 0:
+            return {"dist": d_dist, "labels": d_labels, "counts": d_counts}
         torch.cuda.synchronize()
         trace.append(int(d_counts[0].item()))
         assert trace[-1] in (0, 1), (what, trace)
@@ -376,7 +448,7 @@ def run_geodesic(ctx, S, want, B, what, rounds=16, max_calls=40):
     return {"dist": d_dist, "labels": d_labels, "counts": d_counts}
 
 
-def run_visibility_map(ctx, S, want, B, what):
+def run_visibility_map(ctx, S, want, B, what, **_):
     mw, mh, md = S.me
     d_labels, d_colors, d_map = B.inp("d_labels", S.aux["labels"]), B.inp("d_colors", S.aux["colors"]), B.out("d_map", (md, mh, mw))
     ctx.check(ctx.label_visibility_map_rc(d_labels.data_ptr(), S.e, S.abox, d_colors.data_ptr(), len(S.aux["colors"]), S.ame, d_map.data_ptr(), st()))
@@ -384,14 +456,33 @@ def run_visibility_map(ctx, S, want, B, what):
     return {"cells": cells_and_rest(d_map, want, 0, what)}
 
 
-def run_label_mesh(ctx, S, want, B, what):
-    cap = len(want["triangles"]) + 5
+def label_table(ctx, S, B, table, use_map):
+    """(d_labels, d_colors or None, table entries, d_visibility_map or None, its extent or None): with a table its colour words, and with a
+    map vkv_label_visibility_map of the same labels, box and table, built on the device"""
+    d_labels = B.inp("d_labels", S.aux["labels"])
+    if not table:
+        return d_labels, None, 0, None, None
+    d_colors, n = B.inp("d_colors", S.aux["colors"]), len(S.aux["colors"])
+    if not use_map:
+        return d_labels, d_colors.data_ptr(), n, None, None
+    mw, mh, md = S.me
+    d_map = B.inp("d_visibility_map", np.full((md, mh, mw), B.prefill, np.uint8))
+    if not B.second:
+        ctx.check(ctx.label_visibility_map_rc(d_labels.data_ptr(), S.e, S.abox, d_colors.data_ptr(), n, S.ame, d_map.data_ptr(), st()))
+        torch.cuda.synchronize()
+        B.inputs[-1] = ("d_visibility_map", d_map, d_map.cpu().numpy())        # from here on an input that has to stay as it is
+    return d_labels, d_colors.data_ptr(), n, d_map.data_ptr(), S.ame
+
+
+def run_label_mesh(ctx, S, want, B, what, iso=ISO, table=False, use_map=False, **_):
+    cap = want.get("_cap0", len(want["triangles"]) + 5)
     nbytes = LB.mesh_scratch_bytes(S.e, S.abox)
     assert nbytes >= 16 and nbytes % 8 == 0, (what, nbytes)
-    d_labels, d_scratch, d_counts = B.inp("d_labels", S.aux["labels"]), B.scratch(nbytes), B.out("d_counts", (2,), np.int64)
+    d_labels, d_colors, entries, d_map, map_extent = label_table(ctx, S, B, table, use_map)
+    d_scratch, d_counts = B.scratch(nbytes), B.out("d_counts", (2,), np.int64)
     d_tri, d_tl = B.out("d_triangles", (cap, 3, 3), np.float32), B.out("d_triangle_labels", (cap,), np.int32)
-    ctx.check(ctx.label_mesh_rc(d_labels.data_ptr(), S.e, S.abox, None, 0, S.d_vol.data_ptr(), ISO, None, None, d_scratch.data_ptr(), d_tri.data_ptr(),
-                                d_tl.data_ptr(), cap, d_counts.data_ptr(), st()))
+    ctx.check(ctx.label_mesh_rc(d_labels.data_ptr(), S.e, S.abox, d_colors, entries, S.d_vol.data_ptr(), iso, d_map, map_extent, d_scratch.data_ptr(),
+                                d_tri.data_ptr(), d_tl.data_ptr(), cap, d_counts.data_ptr(), st()))
     return {"triangles": d_tri, "triangle_labels": d_tl, "counts": d_counts}
 
 
@@ -428,7 +519,7 @@ OPERATIONS = {
 assert {r for r, _ in OPERATIONS.values()} == set(F.REFERENCES)
 
 
-def compare(got, want, what):
+def compare(got, want, what, fill=FILL):
     """every output buffer as a whole: the reference, then the pre-fill up to the buffer's end; to the bit"""
     for name, w in want.items():
         if name.startswith("_"):
@@ -437,7 +528,7 @@ def compare(got, want, what):
         g = np.ascontiguousarray(g.cpu().numpy() if isinstance(g, torch.Tensor) else g)
         assert g.dtype.itemsize == w.dtype.itemsize and g.shape[1:] == w.shape[1:] and len(g) >= len(w), (what, name, g.dtype, g.shape, w.dtype, w.shape)
         expect = np.empty(g.shape, w.dtype)
-        expect.view(np.uint8)[...] = FILL
+        expect.view(np.uint8)[...] = fill
         expect[:len(w)] = w
         g = g.view(w.dtype)
         bad = g.view(np.uint8).reshape(g.shape + (-1,)) != expect.view(np.uint8).reshape(g.shape + (-1,))
