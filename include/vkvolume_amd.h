@@ -809,8 +809,8 @@ int vkv_isosurface_mesh(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D exten
  * a non-zero capacity_vertices with a NULL d_vertices or capacity_triangles with a NULL d_indices, d_normals with capacity_vertices == 0, a
  * d_vertices, d_normals or d_indices that is not 4-byte aligned, a d_counts or d_scratch that is not 8-byte aligned.  VKV_E_UNSUPPORTED: a
  * volume too large for the launches.
- * Not here: nothing is decimated.  Smoothing, and normals from the faces instead of the volume, are vkv_mesh_smooth and
- * vkv_mesh_vertex_normals: they take this call's buffers and d_counts as they are. */
+ * Not here: smoothing, and normals from the faces instead of the volume, are vkv_mesh_smooth and vkv_mesh_vertex_normals (DESIGN.md
+ * §5.24); decimation is vkv_mesh_decimate.  They take this call's buffers and d_counts as they are. */
 size_t vkv_isosurface_mesh_indexed_scratch_bytes(VkvExtent3D extent, const VkvBox *box);
 int vkv_isosurface_mesh_indexed(vkv_ctx *ctx, const uint8_t *d_volume, VkvExtent3D extent, const VkvBox *box, float iso, const uint8_t *d_max_map,
                                 VkvExtent3D map_extent, void *d_scratch, float *d_vertices, float *d_normals, uint64_t capacity_vertices,
@@ -1251,7 +1251,7 @@ int vkv_label_mesh_indexed(vkv_ctx *ctx, const uint32_t *d_labels, VkvExtent3D e
  * d_adjacency, d_vertices, d_swap or d_normals where the call takes one; a d_vertices, d_swap, d_indices, d_triangle_labels or d_normals that
  * is not 4-byte aligned, a d_counts or d_adjacency that is not 8-byte aligned; d_swap or d_normals equal to d_vertices; n_passes != 0 with
  * NULL factors; a non-finite factor.  VKV_E_UNSUPPORTED: a capacity above 0xffffffff.
- * Not here: decimation, cotangent or feature-preserving weights, smoothing during extraction. */
+ * Not here: cotangent or feature-preserving weights, smoothing during extraction.  Decimation is vkv_mesh_decimate below. */
 size_t vkv_mesh_adjacency_scratch_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles);
 int vkv_mesh_adjacency(vkv_ctx *ctx, const uint32_t *d_indices, uint64_t capacity_triangles, uint64_t capacity_vertices, const uint64_t *d_counts,
                        void *d_adjacency, void *stream);
@@ -1260,6 +1260,54 @@ int vkv_mesh_smooth(vkv_ctx *ctx, float *d_vertices, float *d_swap, uint64_t cap
 int vkv_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint32_t label,
                             uint64_t capacity_vertices, uint64_t capacity_triangles, const uint64_t *d_counts, const void *d_adjacency,
                             float *d_normals, void *stream);
+
+/* ---- indexed meshes decimated by vertex clustering ------------------------------------------------------------------------
+ * Rossignac-Borrel clustering on a regular grid: every vertex falls into a cell, a cell's vertices become one vertex at their mean, and a
+ * triangle survives if and only if its three cells differ.  The answer is unique and the same bytes come back twice.
+ * Input: a MESH as above (d_vertices, d_indices, the four d_counts read ON THE DEVICE, the two capacities; nt, nv and USED FACES as above; a
+ * truncated extraction is a valid input), and optionally d_triangle_labels (one uint32 per triangle; NULL: none).
+ * Grid: grid_origin and grid_cell are 3 HOST floats each, read during the call; grid_extent holds the cell counts n_x, n_y, n_z.
+ * Cell of a vertex at p, per axis a, in fp32: u = (p_a - origin_a) / cell_a, one subtraction and one correctly rounded division; c_a = u >= 0 ?
+ * (u < (float) n_a ? (uint32) u : n_a - 1) : 0.  Positions outside the grid fall into its border cells, NaN falls to 0 by that comparison, and
+ * nothing indexes out of range.  Cell id = c_x + n_x (c_y + n_y c_z).
+ * Output faces: the used faces whose three cells are pairwise distinct, in input order, 3 x uint32 each: the new numbers of the three cells.
+ * d_out_triangle_labels receives their labels in parallel when d_triangle_labels is given (else it is not touched).  Faces that become
+ * duplicates of one another are kept: the interface faces of a label mesh come in opposite pairs and stay so.
+ * Output vertices: one per cell that at least one surviving face names, in rising cell id; no output vertex is an orphan.  A cell's new number
+ * is its position in that FULL list, reduced mod 2^32 in the faces; it depends on neither output capacity.  Position, per component:
+ * (float) ((double) S / (double) k * 2^-24), where S is the int64 sum of q(p) (q as above: rint(x * 2^24)) over ALL of the first nv input
+ * vertices in the cell, used by a face or not, and k is their number.  The sums are integer atomics, no floating-point atomic is used; they
+ * are defined while they stay below 2^63: positions up to 2^20 in magnitude with up to 2^18 vertices in one cell at the least.  Non-finite
+ * positions give unspecified values in their cell, but never an access outside a buffer.
+ * Closedness.  If over the used input faces every directed edge a -> b occurs as often as b -> a, the same holds for the output faces: bodies
+ * of a label mesh stay closed, also against each other, since the vertex they share is one vertex afterwards.
+ * d_vertex_map (NULL: none): one uint32 per input vertex v < nv, the new number of v's cell, or 0xffffffff where no surviving face names that
+ * cell; rows past nv are not written.  It carries per-vertex attributes such as label pairs over.
+ * d_out_counts: [0] = the surviving faces, [1] = min([0], out_capacity_triangles), [2] = the output vertices, [3] = min([2],
+ * out_capacity_vertices): the output is again a MESH for the calls above and for another vkv_mesh_decimate.  Exactly the first [1] faces (and
+ * labels) and the first [3] vertices are written, and not one element beyond them.  A capacity of zero for either list enqueues no emit for that
+ * list; both zero is the counting call.
+ * d_scratch: vkv_mesh_decimate_scratch_bytes(capacity_vertices, capacity_triangles, grid_extent) bytes of caller memory, 8-byte aligned: with C
+ * = n_x n_y n_z cells and B = ceil(capacity_triangles / 256), 32 * C + 8 * ceil(C / 4096) + 8 * B + 8 * ceil(B / 4096) + roundup8(4 *
+ * capacity_vertices); 0 for what the call rejects.  Per cell three int64 sums, a count and a mark that becomes the number; per input vertex
+ * its cell; the scan blocks.  Its contents mean nothing between calls.
+ * Kernels only (a clear kernel; no allocation, no memset or copy node, no host wait; the kernels use no scratch memory): after one direct call
+ * on `stream` it can be captured into a hipGraph (the grid is then the capture's).  Two runs give the same bytes in every output.  Nothing in
+ * the context is written.  Every argument is checked before anything is enqueued, and a rejected call writes nothing.
+ * VKV_E_INVALID_ARGUMENT: a null ctx, d_vertices, d_indices, d_counts, grid_origin, grid_cell, d_scratch or d_out_counts; a d_vertices,
+ * d_indices, d_triangle_labels, d_out_vertices, d_out_indices, d_out_triangle_labels or d_vertex_map that is not 4-byte aligned, a d_counts,
+ * d_scratch or d_out_counts that is not 8-byte aligned; a zero grid axis; a cell size that is not finite and positive; a non-finite origin;
+ * an output (d_out_vertices, d_out_indices, d_out_triangle_labels, d_vertex_map, d_out_counts) equal to an input (d_vertices, d_indices,
+ * d_triangle_labels, d_counts), to d_scratch or to another output; a non-zero
+ * out_capacity_vertices with a NULL d_out_vertices, a non-zero out_capacity_triangles with a NULL d_out_indices or, with labels, a NULL
+ * d_out_triangle_labels.  VKV_E_UNSUPPORTED: one of the four capacities above 0xffffffff; more than 0xffffffff cells.
+ * Not here: quadric error metrics, edge collapse, removal of duplicate faces on the device (vkvolume_amd.mesh.drop_duplicate_faces does it
+ * on the host), feature preservation. */
+size_t vkv_mesh_decimate_scratch_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles, VkvExtent3D grid_extent);
+int vkv_mesh_decimate(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint64_t capacity_vertices,
+                      uint64_t capacity_triangles, const uint64_t *d_counts, const float *grid_origin, const float *grid_cell, VkvExtent3D grid_extent,
+                      void *d_scratch, float *d_out_vertices, uint64_t out_capacity_vertices, uint32_t *d_out_indices, uint32_t *d_out_triangle_labels,
+                      uint64_t out_capacity_triangles, uint32_t *d_vertex_map, uint64_t *d_out_counts, void *stream);
 
 /* Deterministic synthetic uint8 volume, generated on the device. kind 0 = soft
  * sphere (config C1), kind 1 = ellipsoid shells + hash noise (configs C2..C5).  The shells take three knobs in the upper bits of `kind`

@@ -605,6 +605,65 @@ int vkv_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint32_
 	                                  d_normals, (hipStream_t) stream);
 }
 
+size_t vkv_mesh_decimate_scratch_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles, VkvExtent3D grid_extent)
+{
+	return mesh_decimate_bytes(capacity_vertices, capacity_triangles, grid_extent);
+}
+
+// every argument is checked before the first launch (and before the device is touched); nothing in the context is written
+int vkv_mesh_decimate(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint64_t capacity_vertices,
+                      uint64_t capacity_triangles, const uint64_t *d_counts, const float *grid_origin, const float *grid_cell, VkvExtent3D grid_extent,
+                      void *d_scratch, float *d_out_vertices, uint64_t out_capacity_vertices, uint32_t *d_out_indices, uint32_t *d_out_triangle_labels,
+                      uint64_t out_capacity_triangles, uint32_t *d_vertex_map, uint64_t *d_out_counts, void *stream)
+{
+	const char *what = "mesh_decimate";
+	if (!ctx)
+		return VKV_E_INVALID_ARGUMENT;
+	if (!d_vertices || !d_indices || !d_counts || !grid_origin || !grid_cell || !d_scratch || !d_out_counts)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: null pointer", what);
+	if (((uintptr_t) d_vertices | (uintptr_t) d_indices | (uintptr_t) d_triangle_labels | (uintptr_t) d_out_vertices | (uintptr_t) d_out_indices |
+	     (uintptr_t) d_out_triangle_labels | (uintptr_t) d_vertex_map) &
+	    3u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT,
+		                 "%s: d_vertices, d_indices, d_triangle_labels, d_out_vertices, d_out_indices, d_out_triangle_labels and d_vertex_map must be 4-byte aligned",
+		                 what);
+	if (((uintptr_t) d_counts | (uintptr_t) d_scratch | (uintptr_t) d_out_counts) & 7u)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: d_counts, d_scratch and d_out_counts must be 8-byte aligned", what);
+	if (grid_extent.width == 0 || grid_extent.height == 0 || grid_extent.depth == 0)
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: a grid of %u x %u x %u cells", what, grid_extent.width, grid_extent.height, grid_extent.depth);
+	for (int a = 0; a < 3; ++a)
+	{
+		if (!std::isfinite(grid_cell[a]) || !(grid_cell[a] > 0.0f))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: grid_cell[%d] must be finite and positive", what, a);
+		if (!std::isfinite(grid_origin[a]))
+			return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: grid_origin[%d] is not finite", what, a);
+	}
+	// every output that is given against every input, the scratch block and every other output
+	const void *const inputs[]  = {d_vertices, d_indices, d_triangle_labels, d_counts, d_scratch};
+	const void *const outputs[] = {d_out_vertices, d_out_indices, d_out_triangle_labels, d_vertex_map, d_out_counts};
+	for (size_t o = 0; o < 5; ++o)
+	{
+		if (!outputs[o])
+			continue;
+		for (size_t i = 0; i < 5; ++i)
+			if (outputs[o] == inputs[i])
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: every output must be a buffer of its own, not an input or the scratch block", what);
+		for (size_t p = o + 1; p < 5; ++p)
+			if (outputs[o] == outputs[p])
+				return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: every output must be a buffer of its own, not another output", what);
+	}
+	if ((out_capacity_vertices != 0 && !d_out_vertices) || (out_capacity_triangles != 0 && (!d_out_indices || (d_triangle_labels && !d_out_triangle_labels))))
+		return set_error(ctx, VKV_E_INVALID_ARGUMENT, "%s: an output capacity without its buffer", what);
+	if (capacity_vertices > 0xffffffffull || capacity_triangles > 0xffffffffull || out_capacity_vertices > 0xffffffffull || out_capacity_triangles > 0xffffffffull)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: a capacity above 2^32 - 1 (indices are 32-bit)", what);
+	if (mesh_decimate_cells(grid_extent) == 0)
+		return set_error(ctx, VKV_E_UNSUPPORTED, "%s: a grid of more than 2^32 - 1 cells", what);
+	DeviceGuard guard(ctx->device);
+	return launch_mesh_decimate(ctx, d_vertices, d_indices, d_triangle_labels, capacity_vertices, capacity_triangles, d_counts, grid_origin, grid_cell,
+	                            grid_extent, d_scratch, d_out_vertices, out_capacity_vertices, d_out_indices, d_out_triangle_labels, out_capacity_triangles,
+	                            d_vertex_map, d_out_counts, (hipStream_t) stream);
+}
+
 size_t vkv_label_components_scratch_bytes(VkvExtent3D extent, const VkvBox *box) { return components_scratch_bytes(extent, box); }
 
 // every argument is checked before the first launch (and before the device is touched); nothing in the context is written

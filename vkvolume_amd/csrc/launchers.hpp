@@ -149,6 +149,17 @@ int launch_mesh_vertex_normals(vkv_ctx *ctx, const float *d_vertices, const uint
                                uint64_t capacity_vertices, uint64_t capacity_triangles, const uint64_t *d_counts, const void *d_adjacency, float *d_normals,
                                hipStream_t s);
 
+// ---- mesh_decimate.hip
+// the cells of a clustering grid (0 for a zero axis or more than 2^32 - 1 cells), vkv_mesh_decimate_scratch_bytes (0 for such a grid or a
+// capacity above 2^32 - 1), and vkv_mesh_decimate after the entry point's argument checks (grid_origin, grid_cell: 3 host floats each, read
+// now; d_triangle_labels, d_vertex_map may be null; an output capacity of 0 enqueues no emit of its list)
+uint64_t mesh_decimate_cells(VkvExtent3D grid);
+size_t   mesh_decimate_bytes(uint64_t capacity_vertices, uint64_t capacity_triangles, VkvExtent3D grid);
+int launch_mesh_decimate(vkv_ctx *ctx, const float *d_vertices, const uint32_t *d_indices, const uint32_t *d_triangle_labels, uint64_t capacity_vertices,
+                         uint64_t capacity_triangles, const uint64_t *d_counts, const float *grid_origin, const float *grid_cell, VkvExtent3D grid,
+                         void *d_scratch, float *d_out_vertices, uint64_t out_capacity_vertices, uint32_t *d_out_indices, uint32_t *d_out_triangle_labels,
+                         uint64_t out_capacity_triangles, uint32_t *d_vertex_map, uint64_t *d_out_counts, hipStream_t s);
+
 // ---- components.hip
 // vkv_label_components_scratch_bytes (0 for an extent or box that is not accepted), what the launches can take (box_linear_plan: at most
 // 2^32 - 1 voxels in the box), and vkv_label_components / vkv_select_components after the entry points' argument checks (b inside e)

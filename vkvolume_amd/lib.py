@@ -103,6 +103,8 @@ def _signatures():
         row(INT, "vkv_mesh_adjacency", vp, vp, u64, u64, vp, vp, vp),
         row(INT, "vkv_mesh_smooth", vp, vp, vp, u64, vp, vp, vp, P(f32), u32, vp),
         row(INT, "vkv_mesh_vertex_normals", vp, vp, vp, vp, u32, u64, u64, vp, vp, vp, vp),
+        row(size, "vkv_mesh_decimate_scratch_bytes", u64, u64, abi.Extent3D),
+        row(INT, "vkv_mesh_decimate", vp, vp, vp, vp, u64, u64, vp, P(f32), P(f32), abi.Extent3D, vp, vp, u64, vp, vp, u64, vp, vp, vp),
         # include/vkvolume_amd_debug.h (diagnostics: tools/ and the exhaustive numerics tests)
         row(INT, "vkv_debug_trace", vp, vp, debug=True),
         row(INT, "vkv_debug_tile_orders", vp, vp, u32, u32, debug=True),
@@ -534,6 +536,20 @@ class Context:
         same mesh.  Returns the status code, as label_visibility_map_rc()."""
         return self._lib.vkv_mesh_vertex_normals(self.handle, d_vertices, d_indices, d_triangle_labels, int(label), int(capacity_vertices),
                                                  int(capacity_triangles), d_counts, d_adjacency, d_normals, stream)
+
+    def mesh_decimate_rc(self, d_vertices, d_indices, d_triangle_labels, capacity_vertices, capacity_triangles, d_counts, grid_origin, grid_cell,
+                         grid_extent, d_scratch, d_out_vertices, out_capacity_vertices, d_out_indices, d_out_triangle_labels, out_capacity_triangles,
+                         d_vertex_map, d_out_counts, stream=0):
+        """vkv_mesh_decimate: the indexed mesh (d_counts: the 4 x uint64 of the indexed extractors, read on the device) clustered on the grid
+        of grid_extent cells of size grid_cell from grid_origin (three host floats each; None passes NULL): one output vertex per cell that a
+        surviving face names, the faces whose three cells differ, their labels when d_triangle_labels is given, d_vertex_map (None or one
+        uint32 per input vertex) and the four d_out_counts.  d_scratch: mesh_decimate_scratch_bytes() bytes.  Returns the status code, as
+        label_visibility_map_rc()."""
+        origin = None if grid_origin is None else (C.c_float * 3)(*(float(x) for x in grid_origin))
+        cell = None if grid_cell is None else (C.c_float * 3)(*(float(x) for x in grid_cell))
+        return self._lib.vkv_mesh_decimate(self.handle, d_vertices, d_indices, d_triangle_labels, int(capacity_vertices), int(capacity_triangles), d_counts,
+                                           origin, cell, grid_extent, d_scratch, d_out_vertices, int(out_capacity_vertices), d_out_indices,
+                                           d_out_triangle_labels, int(out_capacity_triangles), d_vertex_map, d_out_counts, stream)
 
     def filter_volume_rc(self, d_src, d_dst, extent, box, kind, stream=0):
         """vkv_filter_volume: the voxels of `box` (None: every voxel) of d_dst = the 3x3x3 filter `kind` (abi.FILTER_*) of d_src"""

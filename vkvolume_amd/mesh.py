@@ -13,6 +13,8 @@ oriented_corner_normals() turns the normals to each face's side, contact_areas()
 Three functions work ON THE DEVICE and ARE pinned to the bit (vkv_mesh_adjacency, vkv_mesh_smooth, vkv_mesh_vertex_normals):
 build_adjacency(), smooth() and vertex_normals() take an indexed mesh as torch device tensors, with the extraction's ``counts`` tensor if its
 capacities were given, and never wait for the host.  boundary_vertices() is the host helper that finds what callers will want pinned.
+decimate() (vkv_mesh_decimate) clusters such a mesh's vertices on a regular grid, cluster_grid() lays that grid over a box
+of voxels, and drop_duplicate_faces() is the host helper for the duplicates that clustering keeps.
 """
 import struct
 
@@ -350,6 +352,111 @@ def vertex_normals(ctx, vertices, faces, counts=None, face_labels=None, label=0,
         ctx.check(ctx.mesh_vertex_normals_rc(vertices.data_ptr(), _ptr(faces) if ct else adjacency.block.data_ptr(), _ptr(face_labels) if ct else None,
                                              label, cv, ct, adjacency.counts.data_ptr(), adjacency.block.data_ptr(), normals.data_ptr(), stream))
     return normals
+
+
+# ---- on the device: decimation by vertex clustering ---------------------------------------------------------------------------
+
+def decimate_scratch_bytes(capacity_vertices, capacity_triangles, grid):
+    """vkv_mesh_decimate_scratch_bytes, and the header's formula: with C = nx * ny * nz cells and B = ceil(triangles / 256), 32 per cell + 8
+    per 4096 cells + 8 per B + 8 per 4096 B + (4 per vertex, rounded up to 8); 0 for a capacity or a cell count above 2^32 - 1 or a zero axis.
+    ``grid``: (nx, ny, nz) or an abi.Extent3D."""
+    cv, ct = int(capacity_vertices), int(capacity_triangles)
+    nx, ny, nz = (grid.width, grid.height, grid.depth) if hasattr(grid, "width") else (int(n) for n in grid)
+    cells = nx * ny * nz
+    if cv > 0xffffffff or ct > 0xffffffff or cells == 0 or cells > 0xffffffff:
+        return 0
+    blocks = (ct + 255) // 256
+    return 32 * cells + 8 * ((cells + 4095) // 4096) + 8 * blocks + 8 * ((blocks + 4095) // 4096) + ((4 * cv + 7) & ~7)
+
+
+def cluster_grid(extent_or_box, cell=2.0):
+    """``(origin, cell, counts)`` of a clustering grid that covers a box of voxels: three float32 each for origin and cell size, three ints for
+    the cells per axis.  ``extent_or_box``: (W, H, D), an abi.Extent3D (the whole volume) or an abi.Box; ``cell``: one number or three, in
+    voxels.  The origin is ``lo - 0.25`` per axis: with integer cell sizes neither integer coordinates (voxel centres) nor half-integers (where
+    the vertices of a label mesh without a volume sit) lie on a cell boundary.  The cells reach to ``lo + length - 0.75`` at the least, past
+    the last voxel centre at ``lo + length - 1``."""
+    if hasattr(extent_or_box, "x0"):
+        b = extent_or_box
+        lo, length = (b.x0, b.y0, b.z0), (b.width, b.height, b.depth)
+    else:
+        lo, length = (0, 0, 0), tuple(int(n) for n in _whd(extent_or_box))
+    return _cluster_grid(lo, length, cell)
+
+
+def _cluster_grid(lo, length, cell):
+    size = np.broadcast_to(np.asarray(cell, np.float32), (3,)).copy()
+    if not (np.isfinite(size).all() and (size > 0).all()):
+        raise ValueError("mesh.cluster_grid: cell sizes must be finite and positive, not %s" % (cell,))
+    origin = np.asarray(lo, np.float32) - np.float32(0.25)
+    counts = tuple(max(1, int(np.ceil((n - 0.75) / float(s)))) for n, s in zip(length, size))
+    return origin, size, counts
+
+
+def decimate(ctx, vertices, faces, counts=None, face_labels=None, cell=2.0, origin=None, grid=None, capacity=None):
+    """vkv_mesh_decimate on the current stream: vertex clustering.  Every vertex falls into a cell of a regular grid, a cell's vertices become
+    their mean, a face survives iff its three cells differ; pinned to the bit, no host wait.  ``vertices``, ``faces``, ``counts`` as for
+    smooth(); ``face_labels``: None or the [n] torch.uint32 labels.  The grid: ``cell`` (one number or three), ``origin`` (three numbers) and
+    ``grid`` (the cells per axis), as cluster_grid(volume.extent, cell) returns them: with them the call never waits for the host.  With
+    ``grid`` None, ``origin`` and ``counts`` must be None too (every row is then meant, so every row is a position), and the grid is
+    cluster_grid's for the integer box about the vertices, which reads their range on the host and so WAITS for it.
+    ``capacity``: None sizes the outputs by the inputs (they can only shrink), or (vertices, triangles).  Returns ``(vertices, faces,
+    face_labels or None, counts, vertex_map)``: new device tensors; ``counts`` the four int64 counts of the result, which with the first
+    three is a mesh for build_adjacency(), smooth(), vertex_normals() and decimate(); ``vertex_map`` [v] torch.uint32, per input vertex the
+    new number of its cell, 0xffffffff where no surviving face names it (and past the counts' vertices)."""
+    import torch
+    from . import abi
+    if grid is None and (origin is not None or counts is not None):        # rows past the counts hold no positions to take a range of
+        raise ValueError("mesh.decimate: an origin, or a mesh with counts, needs the grid's cell counts (mesh.cluster_grid)")
+    cv, ct, counts, stream = _device_mesh("decimate", vertices, faces, counts)
+    if face_labels is not None and not (isinstance(face_labels, torch.Tensor) and face_labels.device == vertices.device and face_labels.shape == (ct,)
+                                        and face_labels.dtype in (torch.uint32, torch.int32) and face_labels.is_contiguous()):
+        raise ValueError("mesh.decimate: face_labels must be a contiguous [n] uint32 tensor on the vertices' device")
+    if grid is None:
+        if cv:
+            lo = np.floor(vertices.min(dim=0).values.cpu().numpy()).astype(np.int64)
+            hi = np.ceil(vertices.max(dim=0).values.cpu().numpy()).astype(np.int64)
+        else:
+            lo = hi = np.zeros(3, np.int64)
+        origin, cell, grid = _cluster_grid(lo, hi - lo + 1, cell)        # lo may be negative, which a box cannot be
+    else:
+        cell = np.broadcast_to(np.asarray(cell, np.float32), (3,))
+        origin = np.zeros(3, np.float32) if origin is None else np.asarray(origin, np.float32).reshape(3)
+    nx, ny, nz = (grid.width, grid.height, grid.depth) if hasattr(grid, "width") else (int(n) for n in grid)
+    extent = abi.Extent3D(nx, ny, nz)
+    out_cv, out_ct = (cv, ct) if capacity is None else (int(capacity[0]), int(capacity[1]))
+    nbytes = decimate_scratch_bytes(cv, ct, (nx, ny, nz))
+    if nbytes == 0:
+        raise ValueError("mesh.decimate: a grid of %d x %d x %d cells" % (nx, ny, nz))
+    dev = vertices.device
+    scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    out_vertices = torch.zeros((out_cv, 3), dtype=torch.float32, device=dev)
+    out_faces = torch.zeros((out_ct, 3), dtype=torch.int32, device=dev).view(torch.uint32)
+    out_labels = None if face_labels is None else torch.zeros((out_ct,), dtype=torch.int32, device=dev).view(torch.uint32)
+    vertex_map = torch.full((cv,), -1, dtype=torch.int32, device=dev).view(torch.uint32)
+    out_counts = torch.zeros((4,), dtype=torch.int64, device=dev)
+    # empty lists still get a pointer: the call reads nothing through it
+    ctx.check(ctx.mesh_decimate_rc(_ptr(vertices) or scratch.data_ptr(), _ptr(faces) or scratch.data_ptr(), _ptr(face_labels), cv, ct, counts.data_ptr(),
+                                   origin, cell, extent, scratch.data_ptr(), _ptr(out_vertices), out_cv, _ptr(out_faces), _ptr(out_labels), out_ct,
+                                   _ptr(vertex_map), out_counts.data_ptr(), stream))
+    return out_vertices, out_faces, out_labels, out_counts, vertex_map
+
+
+def drop_duplicate_faces(faces, face_labels=None):
+    """On the host: the faces without those that repeat an earlier one, up to rotation of the three vertex numbers and with the same label;
+    the first of each stays, in order.  A face with the opposite winding is another face: the opposite pairs of a label mesh's interfaces
+    stay.  Returns ``faces`` (int64), or ``(faces, face_labels)`` with labels.  decimate() keeps duplicates; this removes them."""
+    f = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    key = f
+    for r in (f[:, [1, 2, 0]], f[:, [2, 0, 1]]):        # the least of the three rotations, as a triple
+        less = (r[:, 0] < key[:, 0]) | ((r[:, 0] == key[:, 0]) & ((r[:, 1] < key[:, 1]) | ((r[:, 1] == key[:, 1]) & (r[:, 2] < key[:, 2]))))
+        key = np.where(less[:, None], r, key)
+    if face_labels is not None:
+        face_labels = np.asarray(face_labels).reshape(-1)
+        if len(face_labels) != len(f):
+            raise ValueError("%d labels for %d faces" % (len(face_labels), len(f)))
+        key = np.concatenate([key, face_labels.astype(np.int64)[:, None]], axis=1)
+    keep = np.sort(np.unique(key, axis=0, return_index=True)[1]) if len(f) else np.zeros(0, np.int64)
+    return f[keep] if face_labels is None else (f[keep], face_labels[keep])
 
 
 def boundary_vertices(faces, n_vertices):
